@@ -18,10 +18,20 @@ Multi-GPU (`--gpus N`, launched by torch.distributed.run): streams are independe
 streams with no data-path collective; RCCL carries the barriers around the timed region, the MAX all-reduce of the
 elapsed time and the tiny end-of-run gather of per-rank frame and parity counts.
 
-Timed region: exactly `--steps` steps, repeated back to back until at least `--min-seconds` have passed (repetitions
-are whole multiples of `--steps`; `timed_steps` in the output says how many steps were timed in total).  The default, 7 s
-(the repetition count comes from a short probe, so the region ends up a few per cent either side of it), is long enough
-for an outside sampler (amd-smi every 5 s) to land inside it.
+Timed region: exactly `--steps` steps (`ms_per_step` = its length / `--steps`), after `--warmup` steps with one batch in
+flight and a short pipelined probe.  `--min-seconds S` (opt-in; 0 by default) repeats the `--steps` steps back to back until
+at least S seconds have passed (repetitions are whole multiples of `--steps`, counted from the probe's step time, so the
+region ends up a few per cent either side of S; `timed_steps` in the output says how many steps were timed in total): 7 s,
+for example, is long enough for an outside sampler (amd-smi every 5 s) to land inside it.
+
+`--dump-outputs DIR` writes what the timed path returned for its last step -- the masked depth planes and the masks of rank 0's
+streams -- as float32 `DIR/masked_depth.npy` and `DIR/mask.npy` ([streams, H, W]), with `DIR/streams.npy` (float64) naming
+the streams they hold: all of them, or a fixed seeded sample where all would exceed 64 MB (where one frame alone would, a
+seeded sample of one stream's pixels, indexed by `DIR/pixels.npy`).  Unfiltered pixels carry the sensor's value, NaN and inf
+included: `masked_depth.npy` holds 0 there and `DIR/masked_depth_nonfinite.npy` (float32: 0 finite, 1 NaN, 2 +inf, 3 -inf;
+not written for 16UC1 output, which has none) says which, so every file is finite.  The inputs are seeded, and a few pipelined steps before the timed region
+give its last step the same joint states and sensor planes whatever the repetition count, so the same arguments give the same
+inputs on every run and build.
 
 `value` comes from ONE default-configured context: three raster lanes, a batch split into three launch groups whose kernels
 overlap (rtuf_params.raster_lanes).  Overlapping kernels share the GPU, so their per-launch times describe no single
@@ -67,6 +77,58 @@ def pin_to_numa_node_of_gpu(local_rank):
     except Exception:
         pass
     return None
+
+
+DUMP_BYTES = 64_000_000        # --dump-outputs: at most this much in all (arrays + .npy headers)
+DUMP_SEED = 20261015           # seed of the stream sample taken where all streams would not fit
+
+
+def dump_outputs(out_dir, masked, mask):
+    """--dump-outputs: the last timed step's outputs as float32 arrays [streams, H, W] -- masked depth (16UC1: the uint16
+    millimetres' values) and, unless there is none, the mask -- plus the float64 indices of the streams they hold.  Every
+    file is finite: float masked depth holds 0 where the output is NaN or inf (a sensor value passed through), and
+    masked_depth_nonfinite the class of those pixels (0 finite, 1 NaN, 2 +inf, 3 -inf; 16UC1 output has none, so no such
+    file).  Every stream where that fits in DUMP_BYTES, otherwise a sample of streams drawn with DUMP_SEED (the same for the
+    same batch size and frame size); where one frame alone does not fit, a seeded sample of one stream's pixels: arrays
+    [1, pixels] and the float64 flat pixel indices in pixels.npy.  Returns the file names written."""
+    n, H, W = masked.shape
+    floating = np.issubdtype(masked.dtype, np.floating)
+    planes = (2 if floating else 1) + (0 if mask is None else 1)      # float32 arrays per pixel
+    budget = DUMP_BYTES - 5 * 4096                                     # (the .npy headers)
+    rng = np.random.default_rng(DUMP_SEED)
+    fit = min(n, budget // (4 * planes * H * W + 8))
+    pixels = None
+    if fit == n:
+        streams = np.arange(n)
+    elif fit >= 1:
+        streams = np.sort(rng.choice(n, size=fit, replace=False))
+    else:
+        streams = rng.choice(n, size=1)
+        pixels = np.sort(rng.choice(H * W, size=(budget - 8) // (4 * planes + 8), replace=False))
+
+    def take(a):
+        a = a[streams]
+        return a if pixels is None else a.reshape(len(streams), H * W)[:, pixels]
+
+    depth = take(masked).astype(np.float32)
+    arrays = {"masked_depth": depth, "streams": streams.astype(np.float64)}
+    if floating:
+        nonfinite = np.zeros(depth.shape, np.float32)
+        nonfinite[np.isnan(depth)] = 1
+        nonfinite[np.isposinf(depth)] = 2
+        nonfinite[np.isneginf(depth)] = 3
+        depth[nonfinite != 0] = 0
+        arrays["masked_depth_nonfinite"] = nonfinite
+    if mask is not None:
+        arrays["mask"] = take(mask).astype(np.float32)
+    if pixels is not None:
+        arrays["pixels"] = pixels.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        names.append(name + ".npy")
+    return sorted(names)
 
 
 def side_leg(label, workload, job_world, near_arm, streams, seconds, local_rank, triangles, reuse_planes=None):
@@ -181,7 +243,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--min-seconds", type=float, default=7.0, help="the timed region repeats the --steps steps until it is at least this long")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="opt-in floor: the timed region repeats the --steps steps until it is at least this long (0, the default: exactly --steps timed steps)")
     ap.add_argument("--workload", choices=["c3", "c4", "c5"], default="c3", help="BASELINE.json config: c3 (headline, weak scaling), c4, c5 (fixed totals, sharded)")
     ap.add_argument("--streams", type=int, default=None, help="c3: concurrent camera streams per GPU (256); c4: streams in total (512); c5: cameras per URDF (128)")
     ap.add_argument("--urdfs", type=int, default=64, help="c5: distinct URDFs in total")
@@ -208,6 +270,7 @@ def main():
     ap.add_argument("--debug-flags", type=lambda x: int(x, 0), default=0, help="timing experiments only (needs the RTUF_ABLATE build; results are wrong)")
     ap.add_argument("--near-arm", action="store_true", help="c3 / c4: every stream poses the robot's right forearm 0.1-0.35 m in front of the lens (exact-z pass, near-plane clipping, whole-tile occluders)")
     ap.add_argument("--check-frames", type=int, default=-1, help="frames of the last step verified against the oracle, per rank (-1 = every stream; the oracle runs on all host cores)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (rank 0's streams, float32; a fixed seeded sample of them beyond 64 MB) as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -327,11 +390,12 @@ def main():
         ctx.sync()
     torch.cuda.synchronize()
     # how often the --steps steps are repeated so that the timed region is at least --min-seconds long: from the
-    # time of a few pipelined steps after the warm-up (agreed between the ranks: the slowest decides)
+    # time of a few pipelined steps after the warm-up (agreed between the ranks: the slowest decides).  Without a floor
+    # the probe is eight steps exactly.
     stage_into(k0)
     t_p = time.perf_counter()
     probe = 0
-    while probe < 8 or (time.perf_counter() - t_p < 0.05 and probe < 4096):
+    while probe < 8 or (args.min_seconds > 0 and time.perf_counter() - t_p < 0.05 and probe < 4096):
         enqueue(k0 + probe)
         probe += 1
     for c in ctxs:
@@ -344,6 +408,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         reps = int(t.item())
     timed_steps = args.steps * reps
+    # Step k poses joint state k % V on sensor planes k % VD.  However long the probe ran and however many repetitions
+    # follow, a few more pipelined steps (fewer than lcm(V, VD)) give the last timed step the inputs it has after the
+    # eight-step probe without repetitions -- the same inputs on every run with the same arguments.
+    pad = ((args.warmup * P + 8 + args.steps - 1) - (k0 + timed_steps - 1)) % int(np.lcm(V, VD))
+    for k in range(k0, k0 + pad):
+        enqueue(k)
+    k0 += pad
     for c in ctxs:
         c.sync()
     torch.cuda.synchronize()
@@ -444,6 +515,10 @@ def main():
         checked_total = sum(x["frames_checked"] for x in per_rank)
 
     if rank == 0:
+        dumped = None
+        if args.dump_outputs:
+            dump_masked = h_masked_all.view(np.uint16) if args.u16 else h_masked_all
+            dumped = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, dump_masked, h_mask_all), "step": k_last}
         value = frames_total / elapsed
         # pace of the timed region, step by step, on rank 0's host clock: the time between two returns of the enqueue call (which
         # returns when the context has room again: steady state = one GPU step).  The first steps fill the two in-flight slots.
@@ -705,6 +780,8 @@ def main():
         }
         if fk_err is not None:
             out["fk"] = {"on_device": True, "max_abs_diff_vs_host_fk": fk_err}
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         # the whole path against the HBM roofline: algorithmic bytes of a frame (fused: sensor read + masked write + mask write;
         # two-kernel: + the z-surface written and read) x frames/s over all GPUs / (GPUs x 8 TB/s)
         bytes_per_frame = (((4 if args.u16 else 8) + mask_b) + (8 if two else 0)) * px

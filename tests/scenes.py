@@ -88,3 +88,30 @@ def sensor_depth(W, H, phase=0.0, specials=True):
         d[(h & np.uint64(1023)) == 3] = np.inf
         d[(h & np.uint64(255)) == 4] = 7.9
     return d
+
+
+def llvmpipe_scene(seed, W=320, H=240):
+    """The seeded random scene of tests/test_oracle_vs_llvmpipe.py: a soup of links in front of the camera (near and far
+    planes crossed depending on the seed), a random camera and a sensor plane with NaN / inf pixels.  Returns the projection,
+    sensor depth, camera matrices, the harness's renderables and the oracle's draws."""
+    rng = np.random.default_rng(seed)
+    P = projection(262.5, 262.5, 159.5, 119.5, W, H)
+    geo = soup_geometry(rng, n_links=7, tris_per_link=50)
+    tfs = random_link_poses(rng, len(geo), near=bool(seed & 1), far=(seed % 3 == 0))
+    offinv, camtf = random_camera(rng, small=bool(seed & 2))
+    depth = sensor_depth(W, H, 0.21 * seed)
+    rend = [(tfs[i], [("mesh", geo[i][0], geo[i][1], geo[i][2], geo[i][3])]) for i in range(len(geo))]
+    draws = [(tfs[i],) + geo[i] for i in range(len(geo))]
+    return P, depth, offinv, camtf, rend, draws
+
+
+def scene_digest(P, depth, offinv, camtf, draws):
+    """sha256 over every input of a scene: a stored result names the inputs it was rendered from."""
+    import hashlib
+    h = hashlib.sha256()
+    for a in (depth, P, offinv, camtf):
+        h.update(np.ascontiguousarray(a).tobytes())
+    for d in draws:
+        for a in d:
+            h.update(np.ascontiguousarray(a).tobytes())
+    return h.digest()

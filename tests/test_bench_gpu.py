@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -160,6 +161,35 @@ def test_bench_min_seconds_floor_and_per_gpu_share_flag():
     assert d["timed_steps"] * d["ms_per_step"] * 1e-3 >= 0.1           # the floor held (within the error of the step-time estimate)
     assert d["config"]["streams_total"] == 2 and "8-GPU job" in d["config"]["parallelism"]
     assert d["parity"]["mismatching_values"] == 0 and "cpu_baseline" not in d
+
+
+def test_bench_dump_outputs_same_on_every_run(tmp_path):
+    """--dump-outputs: what the timed path returned for its last step (masked depth + its NaN / inf classes + mask of every
+    stream, finite float32) is the same, bit for bit, whether the --steps steps run once -- the default: a command line
+    without --min-seconds times exactly --steps steps -- or are repeated to fill --min-seconds: the last step's inputs do
+    not depend on the repetitions."""
+    base = ["--steps", "5", "--warmup", "1", "--streams", "8", "--triangles", "8000", "--width", "320", "--height", "192", "--cpu-seconds", "0",
+            "--isolated-seconds", "0", "--host-copy-seconds", "0"]
+    files = ["mask.npy", "masked_depth.npy", "masked_depth_nonfinite.npy", "streams.npy"]
+    dumps = []
+    for name, floor in (("once", []), ("repeated", ["--min-seconds", "0.3"])):
+        out_dir = str(tmp_path / name)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + base + floor + ["--dump-outputs", out_dir],
+                           capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = last_json(r.stdout)
+        assert d["steps"] == 5 and d["parity"]["frames_checked"] == 8 and d["parity"]["mismatching_values"] == 0
+        assert d["timed_steps"] == 5 if not floor else (d["timed_steps"] % 5 == 0 and d["timed_steps"] > 5)
+        assert abs(d["ms_per_step"] - d["timed_seconds"] / d["timed_steps"] * 1e3) < 1e-9 * d["ms_per_step"]
+        assert d["dumped_outputs"]["files"] == files
+        dumps.append({f[:-len(".npy")]: np.load(os.path.join(out_dir, f)) for f in files})
+    a, b = dumps
+    assert a["masked_depth"].shape == a["masked_depth_nonfinite"].shape == a["mask"].shape == (8, 192, 320)
+    assert np.array_equal(a["streams"], np.arange(8))
+    assert (a["masked_depth_nonfinite"] == 1).any()          # the sensor planes' NaN pixels that no link covers
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.isfinite(a[f]).all(), f
+        assert np.array_equal(a[f].view(np.uint8), b[f].view(np.uint8)), f
 
 
 # Launches of fewer than 2,048 tile workgroups -- every small scene of the tests -- take the tile kernels of 1,024 threads, larger ones

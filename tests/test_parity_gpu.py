@@ -3,6 +3,7 @@
 Bar: bit-exact masks and bit-exact float depth (north_star tolerance for depth is 1e-4; the
 implementation is exact, so the tests demand equality)."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -1560,6 +1561,11 @@ def test_stl_facets_are_welded_at_load_and_the_image_does_not_change():
 
 
 # ---- raster lanes (ABI 5) -----------------------------------------------------------------------------------------
+def hw_queues():
+    """Hardware queues the HIP runtime spreads a process's streams over: GPU_MAX_HW_QUEUES, 4 where it is not set."""
+    return int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
+
+
 @pytest.mark.parametrize("lanes,group,want_groups", [(0, 0, 3), (3, 8, 8), (3, 6, 11), (2, 0, 2), (2, 24, 4), (2, 8, 8), (1, 0, 1), (1, 24, 3)])
 def test_raster_lanes_split_a_batch_into_launch_groups(lanes, group, want_groups):
     """64 streams.  With several raster lanes (own HIP stream + own tile bins each; 0 = the default, three) the batch is
@@ -1572,7 +1578,9 @@ def test_raster_lanes_split_a_batch_into_launch_groups(lanes, group, want_groups
     masked, mask = ctx.filter_batch(depth)
     check_vs_oracle(masked, mask, P, geo, depth, per)
     st = ctx.stats()
-    assert st["raster_lanes"] == (lanes or 3) and st["groups_last_batch"] == want_groups and st["regrowths"] >= 1 and st["lanes_side_by_side"] == 1, st
+    # the lanes and the pose stage's stream run side by side when the runtime has a hardware queue for each of them
+    side_by_side = 1 if (lanes or 3) + 1 <= hw_queues() else 0
+    assert st["raster_lanes"] == (lanes or 3) and st["groups_last_batch"] == want_groups and st["regrowths"] >= 1 and st["lanes_side_by_side"] == side_by_side, st
     assert st["work_items"] > 0 and st["triangles_submitted"] == n * 350
     assert (ctx.stream_handle() is None) == (lanes != 1)
     # three device batches back to back (two in flight): the lanes run ahead of each other across batch boundaries
