@@ -19,6 +19,7 @@
 
 #include "rtuf.h"
 #include "rtuf_device.h"
+#include "rtuf_numerics.h"
 
 
 using namespace rtuf;
@@ -976,13 +977,7 @@ int rtuf_finalize_models(rtuf_context* c)
   c->n_draws = (int)draws.size();
   c->n_tris = tri_seq;
   if (tri_seq >= (int64_t)kMaxOrder) return c->fail(RTUF_ERR_CAPACITY, "%lld triangles: draw-order keys are limited to %u", (long long)tri_seq, kMaxOrder);
-  {
-    // draw orders are 1 .. tri_seq (0 = background quad): the key's low word keeps the bits above them for the float z's
-    // low bits (at most 16: by then the exact-z pass is needed only within nanometres of the near plane)
-    int order_bits = 1;
-    while (((int64_t)1 << order_bits) <= tri_seq) order_bits++;
-    c->key_shift = std::min(32 - order_bits, 16);
-  }
+  c->key_shift = key_shift_for((uint32_t)tri_seq);
   // background quad as the hidden last draw (used only when a stream's projection does not make
   // it a constant full-screen plane): GL_QUADS -> (0,1,3), (1,2,3); both get order 0
   {
@@ -1364,9 +1359,6 @@ struct BatchPlan {
   }
 };
 
-#ifndef RTUF_CULL_ON_LANE
-#define RTUF_CULL_ON_LANE 0        // (1: A/B switch -- only the first group of a one-lane batch culls in the pose stage, as before)
-#endif
 static constexpr int kGraphMaxStreams = 32;     // batches up to this size replay a captured hipGraph (timing off)
 
 // Timing events of a batch: start and end of the pose stage, the end of every lane's part, and five per launch group --
@@ -1393,7 +1385,6 @@ static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& 
   // +1.4 %).  Later groups of a lane reuse that array and cull in turn.  (Moving the other small kernel of a lane's chain --
   // the copy of the counters -- to a stream of its own behind an event was measured as well: -0.5 %, one camera -12 %.)
   auto cull_in_pose = [&](size_t g) {
-    if (RTUF_CULL_ON_LANE) return c->n_lanes == 1 && g == 0;
     return g < (size_t)c->n_lanes && (g == 0 || plan.groups[g].lane != plan.groups[g - 1].lane);
   };
   for (size_t g = 0; g < plan.groups.size() && g < (size_t)c->n_lanes; g++)
@@ -1535,16 +1526,10 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   PoseArgs& pa = plan.pa;
   memset(&pa, 0, sizeof pa);
   pa.cams = b.d_cams; pa.link_tf = b.d_link_tf; pa.draws = c->d_draws; pa.mvp = b.d_mvp;
-  // to_linear_depth's constants exactly as the shader evaluates them (include/shaders/urdf_filter.frag:14-17), in float
-  const float zn = c->params.near_plane, zf = c->params.far_plane;
-  const float sc_num = (zn * zf) / (zn - zf), sc_off = zf / (zf - zn);
-  // The per-pixel division num / (z - off) needs neither the operand scaling nor the special-case fix-up of the IEEE expansion
-  // when no operand or intermediate can leave the normal range: |num| within 2^+-40, off in [1 + 2^-10, 2^20] (every z the
-  // kernels hand to it lies in [-1, 1 + 2^-11]: |z - off| >= 2^-11).  The kernels then run its eight-instruction core
-  // (shade_threshold; scripts/fdiv_check.hip compares the two forms over every float z of that range); anything else -- a far
-  // plane more than a thousand times the near plane, non-finite parameters -- keeps the full expansion.
-  const float sc_abs = std::fabs(sc_num);
-  const int fast_div = std::isfinite(sc_num) && std::isfinite(sc_off) && sc_abs >= 0x1p-40f && sc_abs <= 0x1p40f && sc_off >= 1.0f + 0x1p-10f && sc_off <= 0x1p20f;
+  // to_linear_depth's constants exactly as the shader evaluates them (include/shaders/urdf_filter.frag:14-17), in float, and
+  // whether the kernels' per-pixel division by z - off may run as its eight-instruction core (div_core)
+  const float sc_num = shade_num(c->params.near_plane, c->params.far_plane), sc_off = shade_off(c->params.near_plane, c->params.far_plane);
+  const int fast_div = fast_div_admitted(sc_num, sc_off);
   pa.bg = b.d_bg; pa.counters = b.d_counters; pa.n_counters = n_groups; pa.status = b.d_status;
   pa.sc_num = sc_num; pa.sc_off = sc_off; pa.max_diff = c->params.depth_distance_threshold;
   pa.n_streams = n; pa.n_draws = c->n_draws; pa.n_links = (int)L; pa.z_far = c->params.far_plane;

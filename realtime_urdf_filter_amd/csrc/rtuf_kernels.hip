@@ -28,6 +28,7 @@
 #include <stdlib.h>
 
 #include "rtuf_device.h"
+#include "rtuf_numerics.h"
 
 namespace rtuf {
 
@@ -245,7 +246,7 @@ __global__ void pose_kernel(PoseArgs a)
     bi.z = zw;
     bi.mode = ok ? 1u : 0u;
     bi.thr = __fsub_rn(__fdiv_rn(a.sc_num, __fsub_rn(zw, a.sc_off)), a.max_diff);                  // shade_threshold(zw)
-    bi.z24 = (uint32_t)__float2int_rn(__fmul_rn(fminf(fmaxf(zw, 0.0f), 1.0f), 16777215.0f));       // z24_of(zw)
+    bi.z24 = z24_of(zw);
     a.bg[s] = bi;
     return;
   }
@@ -463,20 +464,6 @@ __global__ __launch_bounds__(kFkMaxFrames) void fk_tree_kernel(FkArgs a)
 // ---------------------------------------------------------------------------------------
 // triangle set-up
 // ---------------------------------------------------------------------------------------
-// (issue classes: see depth_test below)
-#ifndef RTUF_FAST_CLASS
-#define RTUF_FAST_CLASS 1
-#endif
-#ifndef RTUF_FAST_COVER
-#define RTUF_FAST_COVER RTUF_FAST_CLASS        // (A/B switch: cover-only tiles compare 24-bit depths instead of composing keys)
-#endif
-#ifndef RTUF_FAST_RESOLVE
-#define RTUF_FAST_RESOLVE RTUF_FAST_CLASS      // (A/B switch of the second batch: no exact-z look in tiles without near geometry, z of a winner by one add)
-#endif
-#ifndef RTUF_SMALL_FRAGS
-#define RTUF_SMALL_FRAGS 1      // resolve <= 4x4 single-tile boxes to fragments in the set-up kernel
-#endif
-
 __device__ __forceinline__ int snap(float v)
 {
   return __float2int_rn(__fmul_rn(__fsub_rn(v, 0.5f), 256.0f));
@@ -499,26 +486,7 @@ __device__ __forceinline__ void edges_from_snapped(int x0, int y0, int x1, int y
     const int dcdy = xs[i] - xs[j];
     r.A[i] = -dcdx;
     r.B[i] = dcdy;
-#if RTUF_FAST_CLASS
-    // The same C without 64-bit arithmetic (two 24-bit multiplies with their high halves, four carry operations, a 64-bit
-    // shift and a branch for the bias, all in the 4-cycle class): with x = 256 X + xf, y = 256 Y + yf
-    //   c = 256 (dcdx X - dcdy Y) + t,   t = dcdx xf - dcdy yf + bias   (|t| < 2^29: exact in 32 bits)
-    //   ceil(c / 256) = (dcdx X - dcdy Y) + ceil(t / 256)
-    // and only C's low 32 bits were ever used (the edge value at a pixel of the tile is small; A px + B py + C is evaluated
-    // modulo 2^32).  bias = dcdx < 0 || (dcdx == 0 && dcdy > 0)  <=>  2 dcdx - (dcdy > 0) < 0, as shifts and subtractions.
-    // (400 M random vertex pairs, incl. coincident and nearly coincident ones, against the 64-bit form on the CPU: identical.)
-    {
-      const int X = xs[i] >> 8, Y = ys[i] >> 8, xf = xs[i] & 255, yf = ys[i] & 255;
-      const uint32_t bias = ((uint32_t)(dcdx + dcdx) - ((uint32_t)(0 - dcdy) >> 31)) >> 31;
-      const int t = __mul24(dcdx, xf) - __mul24(dcdy, yf) + (int)bias;
-      r.C[i] = (int)((uint32_t)__mul24(dcdx, X) - (uint32_t)__mul24(dcdy, Y) + (uint32_t)(-((-t) >> 8)));
-    }
-#else
-    long long c = (long long)dcdx * xs[i] - (long long)dcdy * ys[i];
-    if (dcdx < 0 || (dcdx == 0 && dcdy > 0)) c += 1;   // inclusive on low-x / low-row edges
-    // inside <=> c - dcdx*256*px + dcdy*256*py > 0  <=>  ceil(c/256) - dcdx*px + dcdy*py > 0
-    r.C[i] = (int)(-((-c) >> 8));
-#endif
+    r.C[i] = edge_constant(dcdx, dcdy, xs[i], ys[i]);
   }
   r.bbx = (uint32_t)bx0 | ((uint32_t)bx1 << 16);
   r.bby = (uint32_t)by0 | ((uint32_t)by1 << 16);
@@ -750,23 +718,6 @@ __device__ __forceinline__ uint32_t emit_record_wave(const SetupArgs& a, int sha
   return n;
 }
 
-// 24-bit depth-buffer value of a window z: round(clamp(z, 0, 1) * (2^24 - 1)), half to even (llvmpipe Z24)
-__device__ __forceinline__ uint32_t z24_of(float z)
-{
-  const float zc = fminf(fmaxf(z, 0.0f), 1.0f);
-  return (uint32_t)__float2int_rn(__fmul_rn(zc, 16777215.0f));
-}
-
-// 24-bit depth of a window z that is KNOWN to be above 0.5 (tiles without near geometry: every record and fragment there has
-// z >= 0.51 over its whole box, that is what kNearBit / the bin's near flag say): p = clamp(z) * 16777215 then lies in
-// [2^23, 2^24), where a float IS an integer (ulp 1: the product's rounding is the rounding to integer, half to even, that
-// v_rndne_f32 would repeat), and its bit pattern is 0x4B000000 + (p - 2^23): one integer add instead of v_rndne + v_cvt.
-__device__ __forceinline__ uint32_t z24_of_upper_half(float z)
-{
-  const float zc = fminf(fmaxf(z, 0.0f), 1.0f);
-  return __float_as_uint(__fmul_rn(zc, 16777215.0f)) - 0x4A800000u;
-}
-
 // Set-up + coverage of a triangle (snapped coordinates x0..y2 from phase 1) whose pixel-centre bounding box
 // is at most N x N (N <= 4): returns
 // the covered box positions (bit dy*4+dx, origin bx0,by0) and orients v0/v1 like orient_and_bound.
@@ -881,7 +832,7 @@ __device__ __forceinline__ uint32_t emit_fragments_wave(const SetupArgs& a, int 
         if (pos < a.fcapacity) {
           const float z = __fmaf_rn(dzdy, (float)py, __fmaf_rn(dzdx, (float)px, a0));
           // (a triangle that may reach z <= 0.51 anywhere in its box never gets here: it was handed to the record pass)
-          const unsigned long long f = ((unsigned long long)(RTUF_FAST_CLASS ? z24_of_upper_half(z) : z24_of(z)) << 40) | ((unsigned long long)order << kFragPosBits) |
+          const unsigned long long f = ((unsigned long long)z24_of_upper_half(z) << 40) | ((unsigned long long)order << kFragPosBits) |
                                        (unsigned long long)(lbase + (k >> 2) * kTileW + (k & 3));
           dst[pos] = f;
         }
@@ -899,7 +850,7 @@ __device__ __forceinline__ uint32_t emit_fragments_wave(const SetupArgs& a, int 
       const uint32_t pos = atomicAdd(&a.fbin_count[bin], 1u) & 0x7fffffffu;
       if (pos < a.fcapacity) {
         const float z = __fmaf_rn(dzdy, (float)py, __fmaf_rn(dzdx, (float)px, a0));
-        const unsigned long long f = ((unsigned long long)(RTUF_FAST_CLASS ? z24_of_upper_half(z) : z24_of(z)) << 40) | ((unsigned long long)order << kFragPosBits) |
+        const unsigned long long f = ((unsigned long long)z24_of_upper_half(z) << 40) | ((unsigned long long)order << kFragPosBits) |
                                      (unsigned long long)((py % kTileH) * kTileW + (px % kTileW));
         reinterpret_cast<unsigned long long*>(a.fbins)[(size_t)bin * a.fcapacity + pos] = f;
       }
@@ -1123,7 +1074,7 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
           tiny = survive && (bx1 - bx0) <= 1 && (by1 - by0) <= 1;
           // up to 4x4 candidates inside ONE tile: also resolved to fragments here (boxes that straddle
           // a tile boundary stay records)
-          small = survive && !tiny && (bx1 - bx0) <= 3 && (by1 - by0) <= 3 && RTUF_SMALL_FRAGS &&
+          small = survive && !tiny && (bx1 - bx0) <= 3 && (by1 - by0) <= 3 &&
                   (bx0 / kTileW) == (bx1 / kTileW) && (by0 / kTileH) == (by1 / kTileH);
         }
       }
@@ -1587,12 +1538,7 @@ constexpr unsigned long long kNoFragment = 0x00ffffff00000000ull;   // cleared d
 constexpr unsigned long long kResolvedBit = 1ull << 63;
 
 
-// The key tile's rows may be padded in LDS (RTUF_KEY_PAD keys per row: an A/B switch, 0 in the product -- 2 moves vertically
-// adjacent pixels four banks apart; measured).
-#ifndef RTUF_KEY_PAD
-#define RTUF_KEY_PAD 0
-#endif
-constexpr int kKeyStride = kTileW + RTUF_KEY_PAD, kKeyCount = kKeyStride * kTileH;
+constexpr int kKeyStride = kTileW, kKeyCount = kKeyStride * kTileH;      // the key tile in LDS: one row per pixel row
 // MODE 0: depth test (atomicMin of {z24, order});  MODE 1: write the exact float z of the
 // fragment that won (needed only for window z <= 0.5, where float z is finer than 24 bits).
 // Instrumented builds (-DRTUF_COUNT, scripts/overdraw.sh; never the product): every depth test the tile kernel issues and
@@ -1621,30 +1567,17 @@ struct KeyFmt {
   uint32_t abl;         // RTUF_ABLATE builds: the launch's timing-experiment bits (0x4000: depth tests without their LDS atomic, 0x2000000: strips fetched but not walked)
 };
 
-// float z of a fragment from its 24-bit depth (zexact <= z24 <= 2^23) and the low `shift` bits of its float
-__device__ __forceinline__ float near_z_from_key(uint32_t z24, uint32_t low, int shift)
-{
-  const uint32_t cb = __float_as_uint(__fmul_rn((float)z24, 5.9604648328104515e-08f));      // about the middle of z24's interval
-  const uint32_t span = 1u << shift;
-  uint32_t cand = (cb & ~(span - 1u)) | low;
-  const int d = (int)(cand - cb);
-  const int half = (int)(span >> 1);
-  cand = d > half ? cand - span : (d < -half ? cand + span : cand);
-  return __uint_as_float(cand);
-}
-
 // One depth test of a fragment whose window z is already evaluated (`order`: the draw order shifted into place).
 // Issue classes (profiles/valu_peak.json: gfx950 issues v_fma/mul/add_f32, v_add/sub_u32, v_and/or/xor_b32 and the right shifts
 // in 2 cycles per wave64, everything else -- conversions, v_rndne, min/max, compares, selects, 24-bit multiplies, left shifts --
-// in 4): RTUF_FAST_CLASS = 1 takes the 4-cycle instructions out of the hot walks where a 2-cycle one computes the same number
-// (0: A/B switch, the code of rounds 1-5).
+// in 4): the hot walks use 2-cycle ones wherever they compute the same number (z24_of_upper_half, rtuf_numerics.h).
 template <int MODE, bool LOW>
 __device__ __forceinline__ void depth_test(unsigned long long* keys, uint32_t order, float z, int lidx, const KeyFmt& kf, int lc)
 {
   if (MODE == 0) RTUF_COUNT_TEST();
   if (MODE == 0) RTUF_LANES(lc, true);
   const uint32_t lo = LOW ? (order | (__float_as_uint(z) & kf.lowmask)) : order;
-  const unsigned long long key = ((unsigned long long)((RTUF_FAST_CLASS && !LOW && MODE == 0) ? z24_of_upper_half(z) : z24_of(z)) << 32) | lo;
+  const unsigned long long key = ((unsigned long long)((!LOW && MODE == 0) ? z24_of_upper_half(z) : z24_of(z)) << 32) | lo;
   if (RTUF_ABL(kf.abl, 0x4000u)) { if (key == 0x0123456789abcdefull) keys[lidx] = key; return; }      // timing experiment: everything but the atomic
   if (MODE == 0) {
     atomicMin(&keys[lidx], key);
@@ -1736,9 +1669,6 @@ __device__ __forceinline__ void raster_pair(unsigned long long* keys, const TriR
 // integers: exact), so fma(dzdy, py, .) sees the operands fragment() gives it.  A trip costs 16 VALU instructions for 2 x 2^team_log
 // candidates where the linear run of pairs it replaces (raster_pair: index -> column / row by a reciprocal multiply, six 24-bit
 // multiplies per pair) took 42.  EDGES = false: the caller knows that every candidate is covered (classify_box == 2).
-#ifndef RTUF_STRIP_WALK
-#define RTUF_STRIP_WALK 2          // (A/B switch -- 0: quarter-wave and whole-wave walks as linear runs of candidate pairs, as up to round 4; 2: strips only in tiles with near geometry)
-#endif
 template <int MODE, bool LOW, bool EDGES>
 __device__ __forceinline__ void strip_walk(unsigned long long* keys, const TriRec& q, int x_base, int y_base, int qx0, int wc, int qy0, int h,
                                            int team_log, int sub, bool on, const KeyFmt& kf, int lc_trip, int lc_frag)
@@ -1851,11 +1781,11 @@ __device__ __forceinline__ void raster_bin(unsigned long long* keys, const Packe
     // different step at the end of a quad row); the other three pixels' are those plus A, B, A + B -- the
     // same integer arithmetic as evaluating A*px + B*py + C at every candidate, at about half the
     // instructions per candidate and a quarter of the loop trips.
-    if constexpr (RTUF_FAST_CLASS != 0) {
-      // The same walk with the pixel position kept as two floats (small integers: every add is exact) -- the plane wants them
-      // as floats, and four conversions per trip were 4-cycle instructions; the key's LDS address is stepped in bytes (no
-      // left shift per trip); the right-hand pixels of a quad lie outside the box only in the last quad column of a box of odd
-      // width, which the wrap test already knows (one compare less).  Same integers, same floats, same order of depth tests.
+    {
+      // The pixel position is kept as two floats (small integers: every add is exact) -- the plane wants them as floats, and
+      // four conversions per trip would be 4-cycle instructions; the key's LDS address is stepped in bytes (no left shift per
+      // trip); the right-hand pixels of a quad lie outside the box only in the last quad column of a box of odd width, which
+      // the wrap test already knows (one compare less: tests/fast_class_check.cpp).
       const int qcols = (lx1 - lx0 + 2) >> 1;                              // quads per quad row
       const int back = 2 * (qcols - 1);                                    // x distance from the last quad of a row to the first
       const float fpx0 = (float)(x_base + lx0), fpy_last = (float)(y_base + ly1), fpx_lastq = (float)(x_base + lx0 + back);
@@ -1899,39 +1829,6 @@ __device__ __forceinline__ void raster_bin(unsigned long long* keys, const Packe
           }
         }
       }
-    } else
-    {
-      const int px0 = x_base + lx0, px1 = x_base + lx1, py_last = y_base + ly1;
-      int px = px0, py = y_base + ly0, lidx = ly0 * kKeyStride + lx0;
-      int e0 = __mul24(r.A[0], px) + __mul24(r.B[0], py) + r.C[0];
-      int e1 = __mul24(r.A[1], px) + __mul24(r.B[1], py) + r.C[1];
-      int e2 = __mul24(r.A[2], px) + __mul24(r.B[2], py) + r.C[2];
-      const int qcols = (lx1 - lx0 + 2) >> 1;                              // quads per quad row
-      const int back = 2 * (qcols - 1);                                    // x distance from the last quad of a row to the first
-      const int s0 = 2 * r.B[0] - __mul24(back, r.A[0]), s1 = 2 * r.B[1] - __mul24(back, r.A[1]), s2 = 2 * r.B[2] - __mul24(back, r.A[2]);
-      const int a0x2 = 2 * r.A[0], a1x2 = 2 * r.A[1], a2x2 = 2 * r.A[2];
-      const int row_step = 2 * kKeyStride - back;
-      const int px_lastq = px0 + back;
-      int todo = small ? __mul24(qcols, (ly1 - ly0 + 2) >> 1) : 0;
-      while (__ballot(todo > 0)) {
-        if (MODE == 0) RTUF_LANES(kLaneWalkTrip, todo > 0);
-        if (todo > 0) {
-          const bool right = px < px1, below = py < py_last;
-          const int f0 = e0 + r.B[0], f1 = e1 + r.B[1], f2 = e2 + r.B[2];
-          if (min(e0, min(e1, e2)) > 0) fragment<MODE, LOW>(keys, r, px, py, lidx, kf);
-          if (min(e0 + r.A[0], min(e1 + r.A[1], e2 + r.A[2])) > 0 && right) fragment<MODE, LOW>(keys, r, px + 1, py, lidx + 1, kf);
-          if (min(f0, min(f1, f2)) > 0 && below) fragment<MODE, LOW>(keys, r, px, py + 1, lidx + kKeyStride, kf);
-          if (min(f0 + r.A[0], min(f1 + r.A[1], f2 + r.A[2])) > 0 && right && below) fragment<MODE, LOW>(keys, r, px + 1, py + 1, lidx + kKeyStride + 1, kf);
-          const bool wrap = px == px_lastq;
-          e0 += wrap ? s0 : a0x2;
-          e1 += wrap ? s1 : a1x2;
-          e2 += wrap ? s2 : a2x2;
-          lidx += wrap ? row_step : 2;
-          py += wrap ? 2 : 0;
-          px = wrap ? px0 : px + 2;
-          todo--;
-        }
-      }
     }
     // quarter-wave cooperative: four triangles at a time, 16 lanes each, one vertical candidate pair per
     // lane and step (the bounding box is walked as a linear run of pairs, so slivers waste little)
@@ -1958,13 +1855,13 @@ __device__ __forceinline__ void raster_bin(unsigned long long* keys, const Packe
       if (parked) s_huge[1 + hs] = ri;
       huge &= ~__ballot(parked);
     }
-    if constexpr (RTUF_STRIP_WALK == 1 || (RTUF_STRIP_WALK == 2 && (LOW || MODE == 1))) {
+    if constexpr (LOW || MODE == 1) {
     // Everything beyond the lane-per-triangle class that stays with this wave: STRIPS, one per team of lanes.  A strip is up to
     // 16 columns of a record's part of the tile over all its rows (a wider record is dealt out as two to four strips, to
     // neighbouring teams or successive rounds); its lanes step down the rows (strip_walk).  With three and more records waiting
     // a round deals four strips to the four quarters of the wave; the last two share the wave half and half, a single one gets
     // all 64 lanes (16 columns x 4 rows per step).  The record travels from the lane that loaded it with 15 shuffles.
-    // Taken in tiles with near geometry only (RTUF_STRIP_WALK = 2: the LOW instance and the exact-z pass), where such records
+    // Taken in tiles with near geometry only (the LOW instance and the exact-z pass), where such records
     // come by the dozen per wave-load and the rounds are full: tile kernel 1.117 -> 1.07 ms with the arm in front of the lens.
     // Elsewhere a wave-load holds one such record in four, a round is one strip, and the pair runs below measure the same or
     // better (C3 +0.5 %, C4 / C5 shares +-0.5 %: profiles/r05_experiment_strips.txt).
@@ -2135,7 +2032,7 @@ __device__ __forceinline__ void raster_bin(unsigned long long* keys, const Packe
         for (int ly = qy0 + (tid >> 6); ly <= qy1; ly += NT / 64) {
           if (MODE == 0) { RTUF_LANES(kLaneParkTrip, true); RTUF_LANES(kLaneParkFrag, true); }
           const float z = __fmaf_rn(q.dzdy, (float)(y_base + ly), zc);
-          const unsigned long long key = ((unsigned long long)((RTUF_FAST_CLASS && !LOW && MODE == 0) ? z24_of_upper_half(z) : z24_of(z)) << 32) | (LOW ? (q.order | (__float_as_uint(z) & kf.lowmask)) : q.order);
+          const unsigned long long key = ((unsigned long long)((!LOW && MODE == 0) ? z24_of_upper_half(z) : z24_of(z)) << 32) | (LOW ? (q.order | (__float_as_uint(z) & kf.lowmask)) : q.order);
           const int lidx = ly * kKeyStride + lane;
           if (MODE == 0) {
             RTUF_COUNT_TEST();
@@ -2165,9 +2062,6 @@ __device__ __forceinline__ void raster_bin(unsigned long long* keys, const Packe
   }
 }
 
-#ifndef RTUF_COVER_ONLY
-#define RTUF_COVER_ONLY 1          // (A/B switch -- 0: tiles that hold nothing but their cover take the key tile like every other raster tile, as up to round 5)
-#endif
 #ifndef RTUF_FRAG_UNROLL
 #define RTUF_FRAG_UNROLL 4
 #endif
@@ -2192,12 +2086,11 @@ __device__ __forceinline__ void apply_frags(unsigned long long* keys, const unsi
 #pragma unroll
   for (int u = 0; u < kFragUnroll; u++) {
     const uint32_t i = base + (uint32_t)u * NT + (uint32_t)tid;
-    const int fpos = (int)((uint32_t)f[u] & ((1u << kFragPosBits) - 1u));      // row * kTileW + column, as the set-up kernel wrote it
-    const int lidx = RTUF_KEY_PAD ? fpos + (fpos / kTileW) * RTUF_KEY_PAD : fpos;
+    const int fpos = (int)((uint32_t)f[u] & ((1u << kFragPosBits) - 1u));      // row * kTileW + column: the key's index
     const unsigned long long key = ((f[u] >> 40) << 32) | (((uint32_t)(f[u] >> kFragPosBits) & kMaxOrder) << shift);
     // (zcover == 0xffffffff: no cover, every fragment passes; behind the tile's cover: cannot win)
     RTUF_LANES(kLaneFragList, i < nf && (uint32_t)(f[u] >> 40) <= zcover);
-    if (i < nf && (uint32_t)(f[u] >> 40) <= zcover) { RTUF_COUNT_TEST(); atomicMin(&keys[lidx], key); }
+    if (i < nf && (uint32_t)(f[u] >> 40) <= zcover) { RTUF_COUNT_TEST(); atomicMin(&keys[fpos], key); }
   }
 }
 
@@ -2233,41 +2126,16 @@ __device__ __forceinline__ uint32_t metres_to_u16(float m)
   return (uint32_t)min(max(i, 0), 65535);
 }
 
-// urdf_filter.frag:14-35.  num = z_near*z_far/(z_near-z_far) and off = z_far/(z_far-z_near)
-// depend on uniforms only and are evaluated once per thread (same float operations).
-// num = z_near*z_far/(z_near-z_far), off = z_far/(z_far-z_near): evaluated once per batch on the host, in float,
-// exactly as the shader's to_linear_depth does (rtuf_api.cpp, enqueue_batch)
+// urdf_filter.frag:14-35.  num = z_near*z_far/(z_near-z_far), off = z_far/(z_far-z_near): evaluated once per batch on the
+// host, in float, exactly as the shader's to_linear_depth does (shade_num / shade_off, rtuf_numerics.h).  core: the host
+// admits div_core for the two constants (fast_div_admitted).
 struct ShadeConsts { float num, off, max_diff, replace_value; bool core; };
-
-// The IEEE division without the instructions that only matter for operands near the ends of the exponent range: the compiler
-// expands a correctly rounded a / b into v_div_scale_f32 twice (operand pre-scaling), v_rcp_f32, one Newton step, the quotient
-// with two residual corrections (the last as v_div_fmas_f32, which undoes the scaling) and v_div_fixup_f32 (zero / infinite /
-// NaN / denormal operands).  With both operands and the quotient far inside the normal range the scalings are identities and
-// the fix-up returns its input, and what is left is this: one v_rcp_f32 and seven 2-cycle instructions instead of eleven, four
-// of them in the 4-cycle class.  The host admits it per batch (TileArgs::fast_div, rtuf_api.cpp) from the two constants;
-// scripts/fdiv_check.hip compares it with __fdiv_rn for every float z in [-1, 1 + 2^-11] on the GPU: 0 of 5.75e10 quotients differ
-// inside the admitted domain, and the two pairs outside it (z_far 10,000 x z_near) show what the rule is for -- there z - off
-// passes through zero and the fix-up's infinity is not what the core returns (profiles/r06_experiment_fast_class_batches_2_3.txt).
-#ifndef RTUF_FAST_DIV
-#define RTUF_FAST_DIV RTUF_FAST_CLASS
-#endif
-__device__ __forceinline__ float div_core(float n, float d)
-{
-  float r = __builtin_amdgcn_rcpf(d);
-  const float e = __fmaf_rn(-d, r, 1.0f);
-  r = __fmaf_rn(e, r, r);
-  float q = __fmul_rn(n, r);
-  float res = __fmaf_rn(-d, q, n);
-  q = __fmaf_rn(res, r, q);
-  res = __fmaf_rn(-d, q, n);
-  return __fmaf_rn(res, r, q);
-}
 
 // sensor > shade_threshold(z)  <=>  should_filter of include/shaders/urdf_filter.frag:22-23
 __device__ __forceinline__ float shade_threshold(float z, const ShadeConsts& k)
 {
   const float d = __fsub_rn(z, k.off);
-  const float virt = (RTUF_FAST_DIV && k.core) ? div_core(k.num, d) : __fdiv_rn(k.num, d);
+  const float virt = k.core ? div_core(k.num, d) : __fdiv_rn(k.num, d);
   return __fsub_rn(virt, k.max_diff);
 }
 
@@ -2315,7 +2183,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   kf.shift = a.key_shift;
   kf.abl = a.flags;
   kf.lowmask = near_tile ? (1u << a.key_shift) - 1u : 0u;
-  kf.zexact = near_tile ? 1u << (26 - a.key_shift) : 8388609u;
+  kf.zexact = near_tile ? exact_z_floor(a.key_shift) : 8388609u;
   const uint32_t count = count_front + count_back;
   // (the stream's background entry after the bin's header in program order: the compiler then issues the three scalar loads
   // together -- with the background first it waited for it before it even computed the header's address)
@@ -2372,8 +2240,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   // common path cost the headline workload 20 % when this was first written for all variants).
   bool cover_only = false;
   float cov_a0 = 0.0f, cov_dzdx = 0.0f, cov_dzdy = 0.0f;
-  uint32_t cov_order = 0u;
-  if constexpr (COVER && RTUF_COVER_ONLY != 0) {
+  if constexpr (COVER) {
     cover_only = has_cover && n == 0 && nf == 0 && !empty;
     if (cover_only) {
       request_sensor();
@@ -2381,7 +2248,6 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
       cov_a0 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.x));
       cov_dzdx = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.y));
       cov_dzdy = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.z));
-      cov_order = (uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask;
 #ifdef RTUF_COUNT
       if (tid < 2) count_words()[tid] = 0u;
 #endif
@@ -2411,22 +2277,19 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
     };
     // Ask for the first things this lane will need from the bins BEFORE the key tile is initialised: its first record and
     // its first fragments (their latency then passes under the initialisation and the barrier instead of after it).
-#ifndef RTUF_PRELOAD
-#define RTUF_PRELOAD 1           // (0: A/B switch -- first record and first fragments are requested after the barrier, as before)
-#endif
     uint4 first_rec0 = make_uint4(0u, 0u, 0u, 0u), first_rec1 = make_uint4(0u, 0u, 0u, 0u);
-    if (RTUF_PRELOAD && (uint32_t)tid < n) {
+    if ((uint32_t)tid < n) {
       const uint4* src = reinterpret_cast<const uint4*>(recs + ((uint32_t)tid < n_front ? (uint32_t)tid : a.capacity - 1u - ((uint32_t)tid - n_front)));
       first_rec0 = src[0]; first_rec1 = src[1];
     }
     unsigned long long first_frags[kFragUnroll];
-    if (RTUF_PRELOAD) load_frags<NT>(first_frags, frags, nf, 0u, tid);
+    load_frags<NT>(first_frags, frags, nf, 0u, tid);
     if (has_cover) {
       const CoverPlane c = cover_plane();
-      for (int i = tid; i < kKeyCount; i += NT) {        // (padding columns, if any, hold the background key: the scans below skip them like any pixel nothing was drawn to)
+      for (int i = tid; i < kKeyCount; i += NT) {
         const float z = __fmaf_rn(c.dzdy, (float)(y_base + i / kKeyStride), __fmaf_rn(c.dzdx, (float)(x_base + i % kKeyStride), c.a0));
         const unsigned long long key = ((unsigned long long)z24_of(z) << 32) | (c.order << kf.shift) | (__float_as_uint(z) & kf.lowmask);
-        keys[i] = (RTUF_KEY_PAD == 0 || i % kKeyStride < kTileW) ? min(key, bgkey) : bgkey;
+        keys[i] = min(key, bgkey);
       }
     } else {
       for (int i = tid; i < kKeyCount; i += NT) keys[i] = bgkey;
@@ -2461,7 +2324,6 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
       do_frags = !(a.flags & 0x400u); do_records = !(a.flags & 0x800u); load_only = (a.flags & 0x200u) != 0; skip = (int)((a.flags >> 12) & 3u);
 #endif
       if (do_frags) {
-        if (!RTUF_PRELOAD) load_frags<NT>(first_frags, frags, nf, 0u, tid);
         apply_frags<NT>(keys, first_frags, nf, 0u, tid, zcover, kf.shift);
         for (uint32_t base = kFragUnroll * NT; base < nf; base += kFragUnroll * NT) {
           unsigned long long f[kFragUnroll];
@@ -2470,8 +2332,8 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
         }
       }
       if (do_records) {
-        if (near_tile) raster_bin<0, true, NT>(keys, recs, n, x_base, y_base, tid, load_only, a.width, a.height, n_front, a.capacity, s_huge, s_prec, s_pmeta, zcover, s_winners, kf, first_rec0, first_rec1, RTUF_PRELOAD != 0, skip);
-        else raster_bin<0, false, NT>(keys, recs, n, x_base, y_base, tid, load_only, a.width, a.height, n_front, a.capacity, s_huge, s_prec, s_pmeta, zcover, s_winners, kf, first_rec0, first_rec1, RTUF_PRELOAD != 0, skip);
+        if (near_tile) raster_bin<0, true, NT>(keys, recs, n, x_base, y_base, tid, load_only, a.width, a.height, n_front, a.capacity, s_huge, s_prec, s_pmeta, zcover, s_winners, kf, first_rec0, first_rec1, true, skip);
+        else raster_bin<0, false, NT>(keys, recs, n, x_base, y_base, tid, load_only, a.width, a.height, n_front, a.capacity, s_huge, s_prec, s_pmeta, zcover, s_winners, kf, first_rec0, first_rec1, true, skip);
       }
     }
     __syncthreads();
@@ -2484,7 +2346,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
     // (round 6: a tile without near geometry does not look -- no record, fragment or cover of it can produce z < 0.51, which is
     // what its depth tests already rely on (z24_of_upper_half) -- and is spared eight key reads per lane and a barrier)
     bool need = false;
-    if (near_tile || !RTUF_FAST_RESOLVE) {
+    if (near_tile) {
       for (int i = tid; i < kKeyCount; i += NT) {
         const unsigned long long k = keys[i];
         if (k != bgkey && (uint32_t)(k >> 32) < kf.zexact) need = true;
@@ -2584,30 +2446,25 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
     RTUF_LANES(kLaneResolve, valid);
     if (valid) {
       if (empty) {                                   // tile without geometry: a streaming compare against the plane
-        if (RTUF_FAST_RESOLVE && analytic_bg) {          // (uniform: with the flags known to be set the four selects on them fall away)
+        if (analytic_bg) {          // (uniform: with the flags known to be set the four selects on them fall away)
           const bool all4[4] = {true, true, true, true};
           flags4 = finish(ps, bg_z4, bg_thr4, all4);
         } else {
           flags4 = finish(ps, bg_z4, bg_thr4, bg_frag4);
         }
-      } else if (COVER && RTUF_COVER_ONLY != 0 && cover_only) {      // nothing but a triangle over the whole tile: its fragment or the background's, from registers
+      } else if (COVER && cover_only) {      // nothing but a triangle over the whole tile: its fragment or the background's, from registers
         float z[4], thr[4];
         bool frag[4];
         const float zrow = (float)(y_base + r_ly);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           const float zf = __fmaf_rn(cov_dzdy, zrow, __fmaf_rn(cov_dzdx, (float)(r_px + j), cov_a0));
-#if RTUF_FAST_COVER
           // what atomicMin on a key tile initialised with the background would keep: the cover's key {z24, order << shift | low
           // bits} against the background's (or "no fragment"'s) {z24, 0} -- its draw order is at least 1, so it is below exactly
           // when its 24-bit depth is: one 32-bit compare, no key to put together; without near geometry (a near cover marks its
           // tile) the depth comes from the product's bit pattern like everywhere else
           const uint32_t cz24 = near_tile ? z24_of(zf) : z24_of_upper_half(zf);
           const bool drawn = cz24 < (uint32_t)(bgkey >> 32);
-#else
-          const unsigned long long key = ((unsigned long long)z24_of(zf) << 32) | (cov_order << kf.shift) | (__float_as_uint(zf) & kf.lowmask);
-          const bool drawn = key < bgkey;            // (what atomicMin on a key tile initialised with the background would keep)
-#endif
           z[j] = drawn ? zf : bgz;
           frag[j] = drawn ? true : analytic_bg;
           thr[j] = thr_bg;
@@ -2634,16 +2491,14 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
             // range, or -- only in tiles with near geometry (uniform test: the headline workload never gets there) -- from
             // z24 and the low bits of the float the key carries
             const uint32_t khi = (uint32_t)(k >> 32);
-            if (RTUF_FAST_RESOLVE && !near_tile) {          // (uniform) no exact-z pass ran here, no depth below 0.51 exists
-              z[j] = __uint_as_float(khi + 0x3E800001u);
+            if (!near_tile) {          // (uniform) no exact-z pass ran here, no depth below 0.51 exists
+              z[j] = z_of_upper_half_z24(khi);
             } else if (k & kResolvedBit) {
               z[j] = __uint_as_float((uint32_t)k);
             } else {
-              // (z24 + 1) * 2^-24.  For z24 >= 2^23 - 1 that float's bit pattern is z24 + 0x3E800001 (the integer is its own
-              // mantissa, the power of two an exponent offset, and 2^24 carries into the exponent: checked for all 2^23 values
-              // on the CPU) -- one 2-cycle add instead of a conversion and a multiply; smaller depths exist only in tiles
-              // with near geometry and take near_z_from_key below.
-              z[j] = RTUF_FAST_RESOLVE ? __uint_as_float(khi + 0x3E800001u) : __fmul_rn((float)(khi + 1u), 5.9604644775390625e-08f);
+              // (z24 + 1) * 2^-24 for z24 >= 2^23 - 1; smaller depths exist only in tiles with near geometry and take
+              // near_z_from_key below.
+              z[j] = z_of_upper_half_z24(khi);
               if (near_tile) {
                 if (khi <= 8388608u) z[j] = near_z_from_key(khi, (uint32_t)k & kf.lowmask, kf.shift);
               }

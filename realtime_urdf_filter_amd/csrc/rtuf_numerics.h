@@ -1,0 +1,165 @@
+// rtuf_numerics.h -- the arithmetic whose exact bits the results depend on and that something besides the kernels checks or
+// shares: the 24-bit depth and its bit-pattern forms, the depth keys' encoding of a near fragment's float z, the set-up's
+// 32-bit edge constants, the key format's host-side rules, and the compare threshold's constants, division core and the rule
+// that admits that core.
+//
+// Included by the kernels (rtuf_kernels.hip, device and host pass), the host API (rtuf_api.cpp), scripts/fdiv_check.hip (which
+// holds div_core against the IEEE division on the GPU) and the CPU checks (tests/fast_class_check.cpp, tests/near_key_check.cpp:
+// plain g++, no ROCm headers), which hold every function here against a reference form of their own.  Every function has ONE
+// body, written with the HIP intrinsics the kernels use; only where HIP is absent (the CPU checks) does this file define the
+// handful of them it needs, as portable forms with the same results.  No product here feeds an addition, so the includer's
+// -ffp-contract has nothing to fuse.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <cmath>
+
+#ifdef __HIP__
+#include <hip/hip_runtime.h>
+#define RTUF_NUMERIC __device__ __forceinline__
+#else
+#define RTUF_NUMERIC inline
+#endif
+
+namespace rtuf {
+
+#ifndef __HIP__
+// Without HIP: the intrinsics used below, with the same results.  (The bodies call the intrinsics by name, not through wrappers
+// of our own: a wrapper around __mul24 alone changes the instruction schedule of the tile kernel.)
+inline float __fmul_rn(float a, float b) { return a * b; }
+inline int __float2int_rn(float x) { return (int)rintf(x); }      // (round half to even: the default rounding mode)
+inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+inline int __mul24(int a, int b)      // v_mul_i32_i24: the low 32 bits of the product of the sign-extended low 24 bits
+{
+  const int64_t x = (int32_t)((uint32_t)a << 8) >> 8, y = (int32_t)((uint32_t)b << 8) >> 8;
+  return (int)(uint32_t)(uint64_t)(x * y);
+}
+#endif
+
+// ---------------------------------------------------------------------------------------
+// depths
+// ---------------------------------------------------------------------------------------
+
+// 24-bit depth-buffer value of a window z: round(clamp(z, 0, 1) * (2^24 - 1)), half to even (llvmpipe Z24)
+RTUF_NUMERIC uint32_t z24_of(float z)
+{
+  const float zc = fminf(fmaxf(z, 0.0f), 1.0f);
+  return (uint32_t)__float2int_rn(__fmul_rn(zc, 16777215.0f));
+}
+
+// 24-bit depth of a window z that is KNOWN to be above 0.5 (tiles without near geometry: every record and fragment there has
+// z >= 0.51 over its whole box, that is what kNearBit / the bin's near flag say): p = clamp(z) * 16777215 then lies in
+// [2^23, 2^24), where a float IS an integer (ulp 1: the product's rounding is the rounding to integer, half to even, that
+// v_rndne_f32 would repeat), and its bit pattern is 0x4B000000 + (p - 2^23): one integer add instead of v_rndne + v_cvt.
+// (Equal to z24_of for every float z > 0.5: tests/fast_class_check.cpp.)
+RTUF_NUMERIC uint32_t z24_of_upper_half(float z)
+{
+  const float zc = fminf(fmaxf(z, 0.0f), 1.0f);
+  return __float_as_uint(__fmul_rn(zc, 16777215.0f)) - 0x4A800000u;
+}
+
+// The float z of a winner with 24-bit depth z24 >= 2^23 - 1: (z24 + 1) * 2^-24, whose bit pattern is z24 + 0x3E800001 (the
+// integer is its own mantissa, the power of two an exponent offset, and 2^24 carries into the exponent) -- one 2-cycle add
+// instead of a conversion and a multiply.  (Every such z24: tests/fast_class_check.cpp.)
+RTUF_NUMERIC float z_of_upper_half_z24(uint32_t z24) { return __uint_as_float(z24 + 0x3E800001u); }
+
+// ---------------------------------------------------------------------------------------
+// depth keys: {z24, draw order << shift | low `shift` bits of the fragment's float z} (KeyFmt, rtuf_kernels.hip)
+// ---------------------------------------------------------------------------------------
+
+// The key's shift for a context of n_tris triangles: draw orders 1 .. n_tris (0 = background quad) take the word's top bits,
+// the rest carries the float z's low bits -- at most 16: by then the exact-z pass is needed only within nanometres of the
+// near plane.
+inline int key_shift_for(uint32_t n_tris)
+{
+  int order_bits = 1;
+  while (((uint64_t)1 << order_bits) <= n_tris) order_bits++;
+  return 32 - order_bits < 16 ? 32 - order_bits : 16;
+}
+
+// In a tile with near geometry, winners with z24 below this need the exact-z pass: z24 and the float's low `shift` bits pin
+// the float down as long as z24's interval of 2^-24 holds fewer than 2^(shift-1) floats, i.e. for z24 >= 2^(26-shift)
+// (near_z_from_key).
+RTUF_NUMERIC uint32_t exact_z_floor(int shift) { return 1u << (26 - shift); }
+
+// float z of a fragment from its 24-bit depth (exact_z_floor <= z24 <= 2^23) and the low `shift` bits of its float
+// (every such float, every shift key_shift_for returns: tests/near_key_check.cpp)
+RTUF_NUMERIC float near_z_from_key(uint32_t z24, uint32_t low, int shift)
+{
+  const uint32_t cb = __float_as_uint(__fmul_rn((float)z24, 5.9604648328104515e-08f));      // about the middle of z24's interval
+  const uint32_t span = 1u << shift;
+  uint32_t cand = (cb & ~(span - 1u)) | low;
+  const int d = (int)(cand - cb);
+  const int half = (int)(span >> 1);
+  cand = d > half ? cand - span : (d < -half ? cand + span : cand);
+  return __uint_as_float(cand);
+}
+
+// ---------------------------------------------------------------------------------------
+// edge functions of a snapped triangle (1/256 px): inside <=> A px + B py + C > 0, A = -dcdx, B = dcdy
+// ---------------------------------------------------------------------------------------
+
+// Inclusive on low-x / low-row edges: dcdx < 0 || (dcdx == 0 && dcdy > 0)  <=>  2 dcdx - (dcdy > 0) < 0, as shifts and
+// subtractions (2-cycle instructions instead of compares and selects).
+RTUF_NUMERIC uint32_t inclusive_edge_bias(int dcdx, int dcdy) { return ((uint32_t)(dcdx + dcdx) - ((uint32_t)(0 - dcdy) >> 31)) >> 31; }
+
+// C = ceil((dcdx x - dcdy y + bias) / 256) for the edge from vertex (x, y), without 64-bit arithmetic (two 24-bit multiplies
+// with their high halves, four carry operations, a 64-bit shift and a branch for the bias, all in the 4-cycle class): with
+// x = 256 X + xf, y = 256 Y + yf
+//   c = 256 (dcdx X - dcdy Y) + t,   t = dcdx xf - dcdy yf + bias   (|t| < 2^29: exact in 32 bits)
+//   ceil(c / 256) = (dcdx X - dcdy Y) + ceil(t / 256)
+// and only C's low 32 bits are ever used (the edge value at a pixel of the tile is small; A px + B py + C is evaluated
+// modulo 2^32).  (The 64-bit form's low 32 bits for 120 M vertex pairs: tests/fast_class_check.cpp.)
+RTUF_NUMERIC int edge_constant(int dcdx, int dcdy, int x, int y)
+{
+  const int X = x >> 8, Y = y >> 8, xf = x & 255, yf = y & 255;
+  const uint32_t bias = inclusive_edge_bias(dcdx, dcdy);
+  const int t = __mul24(dcdx, xf) - __mul24(dcdy, yf) + (int)bias;
+  return (int)((uint32_t)__mul24(dcdx, X) - (uint32_t)__mul24(dcdy, Y) + (uint32_t)(-((-t) >> 8)));
+}
+
+// ---------------------------------------------------------------------------------------
+// compare threshold: sensor > num / (z - off) - max_diff  (include/shaders/urdf_filter.frag:14-23)
+// ---------------------------------------------------------------------------------------
+
+// to_linear_depth's constants exactly as the shader evaluates them, in float (host only: once per batch)
+inline float shade_num(float z_near, float z_far) { return (z_near * z_far) / (z_near - z_far); }
+inline float shade_off(float z_near, float z_far) { return z_far / (z_far - z_near); }
+
+// May the per-pixel division num / (z - off) run as div_core?  It needs neither the operand scaling nor the special-case
+// fix-up of the IEEE expansion when no operand or intermediate can leave the normal range: |num| within 2^+-40, off in
+// [1 + 2^-10, 2^20] (every z the kernels hand to it lies in [-1, 1 + 2^-11]: |z - off| >= 2^-11).  Anything else -- a far
+// plane more than a thousand times the near plane, non-finite parameters -- keeps the full expansion.
+inline bool fast_div_admitted(float num, float off)
+{
+  const float a = std::fabs(num);
+  return std::isfinite(num) && std::isfinite(off) && a >= 0x1p-40f && a <= 0x1p40f && off >= 1.0f + 0x1p-10f && off <= 0x1p20f;
+}
+
+#ifdef __HIP__
+// The IEEE division without the instructions that only matter for operands near the ends of the exponent range: the compiler
+// expands a correctly rounded a / b into v_div_scale_f32 twice (operand pre-scaling), v_rcp_f32, one Newton step, the quotient
+// with two residual corrections (the last as v_div_fmas_f32, which undoes the scaling) and v_div_fixup_f32 (zero / infinite /
+// NaN / denormal operands).  With both operands and the quotient far inside the normal range the scalings are identities and
+// the fix-up returns its input, and what is left is this: one v_rcp_f32 and seven 2-cycle instructions instead of eleven, four
+// of them in the 4-cycle class.  scripts/fdiv_check.hip compares it with __fdiv_rn for every float z in [-1, 1 + 2^-11] on the
+// GPU: 0 of 5.75e10 quotients differ inside the domain fast_div_admitted admits, and the two pairs outside it (z_far 10,000 x
+// z_near) show what the rule is for -- there z - off passes through zero and the fix-up's infinity is not what the core
+// returns (profiles/r06_experiment_fast_class_batches_2_3.txt).
+__device__ __forceinline__ float div_core(float n, float d)
+{
+  float r = __builtin_amdgcn_rcpf(d);
+  const float e = __fmaf_rn(-d, r, 1.0f);
+  r = __fmaf_rn(e, r, r);
+  float q = __fmul_rn(n, r);
+  float res = __fmaf_rn(-d, q, n);
+  q = __fmaf_rn(res, r, q);
+  res = __fmaf_rn(-d, q, n);
+  return __fmaf_rn(res, r, q);
+}
+#endif
+
+}  // namespace rtuf

@@ -1,5 +1,7 @@
 // fdiv_check: is the division core WITHOUT its scaling / fix-up instructions the IEEE quotient on the operands the compare
-// threshold sees?  (GPU box:  scripts/bin/fdiv_check [n_random_pairs]  -- built by __graft_entry__.build().)
+// threshold sees?  (GPU box:  scripts/bin/fdiv_check [n_random_pairs]  -- built by __graft_entry__.build(), run by
+// tests/test_fdiv_check_gpu.py.)  div_core, the rule that admits it and the shade constants are the library's own
+// (realtime_urdf_filter_amd/csrc/rtuf_numerics.h); the reference is __fdiv_rn.
 //
 // include/shaders/urdf_filter.frag:14-17 divides num = z_near z_far / (z_near - z_far) by d = z - z_far / (z_far - z_near) for
 // every drawn pixel.  The compiler expands a correctly rounded f32 division into eleven instructions: v_div_scale_f32 twice
@@ -16,17 +18,9 @@
 #include <math.h>
 #include <vector>
 
-__device__ __forceinline__ float div_core(float n, float d)
-{
-  float r = __builtin_amdgcn_rcpf(d);
-  const float e = __fmaf_rn(-d, r, 1.0f);
-  r = __fmaf_rn(e, r, r);
-  float q = __fmul_rn(n, r);
-  float res = __fmaf_rn(-d, q, n);
-  q = __fmaf_rn(res, r, q);
-  res = __fmaf_rn(-d, q, n);
-  return __fmaf_rn(res, r, q);
-}
+#include "../realtime_urdf_filter_amd/csrc/rtuf_numerics.h"
+
+using rtuf::div_core;
 
 __global__ void check_kernel(float num, float off, uint32_t first_bits, uint32_t count, unsigned long long* bad, uint32_t* first_bad)
 {
@@ -53,10 +47,13 @@ int main(int argc, char** argv)
   (void)hipMalloc(&d_bad, 8); (void)hipMalloc(&d_first, 4);
   struct Pair { float num, off; const char* what; bool admitted; };
   std::vector<Pair> pairs;
-  // (the host's rule, rtuf_api.cpp: |num| within 2^+-40, off in [1 + 2^-10, 2^20]; pairs outside it are checked as well, to show
-  // what the rule is for -- with off closer to 1 than the z range reaches, z - off passes through zero and the fix-up matters)
-  auto admitted = [](float num, float off) { return fabsf(num) >= 0x1p-40f && fabsf(num) <= 0x1p40f && off >= 1.0f + 0x1p-10f && off <= 0x1p20f; };
-  auto consts = [&](float zn, float zf, const char* what) { Pair p; p.num = (zn * zf) / (zn - zf); p.off = zf / (zf - zn); p.what = what; p.admitted = admitted(p.num, p.off); return p; };
+  // (the library's rule, rtuf::fast_div_admitted: |num| within 2^+-40, off in [1 + 2^-10, 2^20]; pairs outside it are checked as
+  // well, to show what the rule is for -- with off closer to 1 than the z range reaches, z - off passes through zero and the
+  // fix-up matters)
+  auto consts = [&](float zn, float zf, const char* what) {
+    Pair p; p.num = rtuf::shade_num(zn, zf); p.off = rtuf::shade_off(zn, zf); p.what = what; p.admitted = rtuf::fast_div_admitted(p.num, p.off);
+    return p;
+  };
   pairs.push_back(consts(0.1f, 10.0f, "library default z_near 0.1 z_far 10"));
   pairs.push_back(consts(0.01f, 100.0f, "z_near 0.01 z_far 100"));
   pairs.push_back(consts(0.3f, 5.0f, "z_near 0.3 z_far 5"));
@@ -69,7 +66,7 @@ int main(int argc, char** argv)
     p.off = i % 3 == 0 ? 1.0f + ldexpf(1.0f + rnd01(s), -10 + (int)(rnd01(s) * 9.0f)) : ldexpf(1.0f + rnd01(s), (int)(rnd01(s) * 20.0f));
     if (p.off < 1.0f + 0.0009765625f) p.off = 1.0f + 0.0009765625f;
     p.what = "random";
-    p.admitted = admitted(p.num, p.off);
+    p.admitted = rtuf::fast_div_admitted(p.num, p.off);
     pairs.push_back(p);
   }
   unsigned long long total_bad = 0, total = 0, outside_bad = 0;
