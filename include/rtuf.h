@@ -358,7 +358,9 @@ typedef struct {
   uint32_t zero_survivor_items;     /* ... of which no triangle survived the clip / sub-pixel culls                    */
   uint32_t cover_pass;              /* 1: the last batch ran the cover pass (on while scenes have whole-tile triangles,
                                        switched off after three batches without one, probed again every 64th batch)     */
-  uint32_t reserved0;
+  uint32_t counter_blocks;          /* counter blocks of each batch slot: the most launch groups any batch of 1 .. max_streams
+                                       streams can be split into at the present launch group (was reserved0; a batch of fewer
+                                       streams than max_streams can need more groups than a full one)                    */
   uint64_t raster_atomics;          /* instrumented builds (-DRTUF_COUNT) only: depth tests the tile kernel issued      */
   uint64_t drawn_pixels;            /* instrumented builds only: pixels whose final depth key is not the background's   */
   /* ABI 5 */

@@ -57,7 +57,7 @@ class Stats(ctypes.Structure):
                 ("device_bytes", ctypes.c_uint64), ("occluded_entries", ctypes.c_uint64),
                 ("cover_tiles", ctypes.c_uint32), ("exact_tiles", ctypes.c_uint32),
                 ("work_items", ctypes.c_uint32), ("zero_survivor_items", ctypes.c_uint32),
-                ("cover_pass", ctypes.c_uint32), ("reserved0", ctypes.c_uint32),
+                ("cover_pass", ctypes.c_uint32), ("counter_blocks", ctypes.c_uint32),
                 ("raster_atomics", ctypes.c_uint64), ("drawn_pixels", ctypes.c_uint64),
                 ("raster_lanes", ctypes.c_uint32), ("launch_group", ctypes.c_uint32), ("groups_last_batch", ctypes.c_uint32),
                 ("graphs_enabled", ctypes.c_uint32), ("graph_hits", ctypes.c_uint64), ("graph_misses", ctypes.c_uint64),

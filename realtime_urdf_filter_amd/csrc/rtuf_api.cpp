@@ -19,6 +19,7 @@
 
 #include "rtuf.h"
 #include "rtuf_device.h"
+#include "rtuf_groups.h"
 #include "rtuf_numerics.h"
 
 
@@ -39,8 +40,6 @@ static constexpr int kMaxInflight = 2;      // device batches that may be in fli
 #endif
 static constexpr int kMaxLanes = RTUF_MAX_LANES;         // raster lanes a context can have (rtuf_params.raster_lanes; the default is kDefaultLanes)
 static constexpr int kDefaultLanes = 3;     // (three lanes + the pose stage's stream = the HIP runtime's four hardware queues)
-static constexpr int kSplitMin = 32;        // batches of at least this many streams are split over the lanes; smaller ones
-                                            // take one lane each, in turn (their cost is launches, not kernel time)
 
 struct Kinematics {               // on-device forward kinematics of one model
   int n_frames = 0, camera_frame = -1, max_depth = 0;
@@ -140,7 +139,7 @@ struct rtuf_context {
   int next_lane = 0;                   // lane of the next batch that is not split
   int last_lane = 0;                   // lane of the newest batch's last group (debug read-back of the z-surface)
   int group = 0;                       // streams per launch group at most (= streams a lane's bins are sized for)
-  int max_groups = 1;                  // launch groups a batch of max_streams streams is split into (sizes the counter blocks)
+  int max_groups = 1;                  // counter blocks of a batch slot: launch groups of any batch up to max_streams at most
   uint32_t capacity = 0, fcapacity = 0, clip_capacity = 0;
   uint32_t big_capacity = 0;           // many-tile list, per counter shard
   uint32_t items_hint = 0; int items_hint_streams = 0;      // longest work list of the last batch's groups, and their size
@@ -279,19 +278,8 @@ static void dev_free(rtuf_context* c, T*& p)
   p = nullptr;
 }
 
-// Launch groups a batch of n streams is split into: as many as the lanes' bins need (c->group streams each at most), and,
-// with several lanes, a multiple of the lanes for batches worth splitting, so that every lane gets the same amount of work.
-static int groups_for(const rtuf_context* c, int n)
-{
-  int k = (n + c->group - 1) / std::max(c->group, 1);
-  if (c->n_lanes > 1 && n >= kSplitMin) k = ((std::max(k, 1) + c->n_lanes - 1) / c->n_lanes) * c->n_lanes;      // a multiple of the lanes
-  k = std::max(k, 1);
-  // ... of ceil(n / k) streams each, which can come to FEWER than k groups (100 streams in 16 groups of 7 are 15): the number
-  // returned is the number enqueue_batch makes -- the batch's status word starts at it and every group takes one off
-  // (round 5 returned k: the word of such a batch never reached 0)
-  const int per_group = (std::max(n, 1) + k - 1) / k;
-  return (std::max(n, 1) + per_group - 1) / per_group;
-}
+// Launch groups a batch of n streams is split into (rtuf_groups.h)
+static int groups_for(const rtuf_context* c, int n) { return rtuf::groups_for(n, c->group, c->n_lanes); }
 
 static void sync_lanes(rtuf_context* c)
 {
@@ -334,10 +322,11 @@ static size_t lane_bins_bytes(const rtuf_context* c, int G, uint32_t cap, uint32
   return (size_t)G * (size_t)c->tiles_x * c->tiles_y * ((size_t)cap * sizeof(PackedTri) + (size_t)fcap * sizeof(Frag));
 }
 
-// The per-batch counter blocks (one per launch group) follow the number of groups a full batch is split into.
+// The per-batch counter blocks (one per launch group): enough for the groups of every batch of 1 .. max_streams streams
+// (rtuf_groups.h: a full batch can make fewer groups than a partial one).
 static int alloc_counter_blocks(rtuf_context* c)
 {
-  c->max_groups = groups_for(c, c->max_streams);
+  c->max_groups = rtuf::counter_blocks_for(c->max_streams, c->group, c->n_lanes);
   for (auto& b : c->batch) {
     dev_free(c, b.d_counters);
     if (b.h_counters) { (void)hipHostFree(b.h_counters); b.h_counters = nullptr; }
@@ -1447,6 +1436,11 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   // lane, the next such batch the other.
   const int n_groups = groups_for(c, n);
   const int per_group = (n + n_groups - 1) / n_groups;
+  // (checked before anything in the context or the slot changes: a refused batch leaves both as they were)
+  if (n_groups > c->max_groups)
+    return c->fail(RTUF_ERR_STATE, "internal: %d launch groups for %d streams, but counter blocks for %d", n_groups, n, c->max_groups);
+  if ((n + per_group - 1) / per_group != n_groups)
+    return c->fail(RTUF_ERR_STATE, "internal: %d launch groups planned, %d made (the status word counts the former down)", n_groups, (n + per_group - 1) / per_group);
   if (!rerun) {
     b.lanes_used = 0;
     if (n_groups == 1) { b.lanes_used = 1u << c->next_lane; c->next_lane = (c->next_lane + 1) % c->n_lanes; }
@@ -1575,8 +1569,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
       ca.sc_num = sc_num; ca.sc_off = sc_off; ca.fast_div = fast_div;
     }
   }
-  b.n_groups = (int)plan.groups.size();
-  if (b.n_groups != n_groups) return c->fail(RTUF_ERR_STATE, "internal: %d launch groups planned, %d made (the status word counts the former down)", n_groups, b.n_groups);
+  b.n_groups = (int)plan.groups.size();          // (= n_groups: the loop makes ceil(n / per_group) groups, checked above)
   b.setup_grid.assign(plan.groups.size(), 0xffffffffu);
   c->last_lane = plan.groups.back().lane;
   // host-plane batches: the lanes' first kernels wait for the upload of the planes
@@ -2185,6 +2178,7 @@ int rtuf_get_stats(rtuf_context* c, rtuf_stats* out)
     *out = c->kids[c->last_kid]->stats;
     out->bin_capacity = c->kids[c->last_kid]->capacity;
     out->raster_lanes = (uint32_t)c->kids[c->last_kid]->n_lanes; out->launch_group = (uint32_t)c->kids[c->last_kid]->group;
+    out->counter_blocks = (uint32_t)c->kids[c->last_kid]->max_groups;
     out->regrowths = 0; out->timed_batches = 0; out->device_bytes = 0;
     out->graphs_enabled = 1u; out->graph_hits = out->graph_misses = 0; out->lanes_side_by_side = c->lanes_share_queue ? 0u : 1u;
     for (const rtuf_context* k : c->kids) { out->device_bytes += k->device_bytes; out->graphs_enabled &= k->graphs_ok ? 1u : 0u; out->graph_hits += k->graph_hits; out->graph_misses += k->graph_misses; }
@@ -2200,6 +2194,7 @@ int rtuf_get_stats(rtuf_context* c, rtuf_stats* out)
   out->bin_capacity = c->capacity;
   out->device_bytes = c->device_bytes;
   out->raster_lanes = (uint32_t)c->n_lanes; out->launch_group = (uint32_t)c->group;
+  out->counter_blocks = (uint32_t)c->max_groups;
   out->graphs_enabled = c->graphs_ok ? 1u : 0u; out->graph_hits = c->graph_hits; out->graph_misses = c->graph_misses;
   out->lanes_side_by_side = c->lanes_share_queue ? 0u : 1u;
   return RTUF_OK;

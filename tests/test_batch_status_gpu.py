@@ -9,6 +9,7 @@ when the planes are not the oracle's, (b) after the host has retired the batch t
 import numpy as np
 import pytest
 
+import launch_groups as LG
 import scenes as S
 import realtime_urdf_filter_amd as R
 from bench_support import workloads as WL
@@ -197,11 +198,12 @@ def test_status_word_reaches_zero_when_the_groups_do_not_divide_the_batch(n, gro
     user = Consumer(ctx)
     ctx.filter_batch_device(n, d.data_ptr(), masked.data_ptr(), mask.data_ptr())
     word, early_m, early_k, word_t = user.read(masked, mask)
-    st_groups = -(-n // -(-n // (-(-(-(-n // group)) // lanes) * lanes)))      # ceil(n / ceil(n / (ceil(n / group) rounded up to the lanes)))
+    st_groups = LG.groups_for(n, group, lanes)      # ceil(n / ceil(n / (ceil(n / group) rounded up to the lanes)))
     assert word == 0, "status word %#x behind the batch's kernels (%d launch groups expected)" % (word, st_groups)
     ctx.sync()
     st = ctx.stats()
     assert st["groups_last_batch"] == st_groups and st["batch_status"] == 0 and st["batch_reruns"] == 0, st
+    assert st["counter_blocks"] == LG.counter_blocks_for(n, st["launch_group"], lanes) >= st_groups, st
     torch.cuda.synchronize()
     assert int(word_t.cpu().numpy()[0]) == 0
     for s in (0, n // 2, n - 1):
