@@ -6,7 +6,8 @@ oracle/ref_gl (development container only).  A fixture is data: the inputs of on
 sha256 of the masked depth, which is fully determined by mask, sensor depth and replace value --
 the generator asserts that identity on the llvmpipe output).
 
-Run:  python tests/golden/generate_golden.py        (rewrites every fixture)
+Run:  python tests/golden/generate_golden.py                (rewrites every fixture)
+      python tests/golden/generate_golden.py --only NAME...    (rewrites the named fixtures only)
 """
 import hashlib
 import os
@@ -45,7 +46,7 @@ def dequantise_depth(q):
 
 class Case:
     def __init__(self, name, W, H, depth, projection, renderables, offset_inv=None, cam_tf=None, max_diff=0.05, replace=5.0,
-                 depth_exact=None):
+                 depth_exact=None, z_near=0.1, z_far=8.0):
         self.name, self.W, self.H = name, W, H
         self.depth_q = quantise_depth(depth) if depth_exact is None else None
         self.depth = dequantise_depth(self.depth_q) if depth_exact is None else np.ascontiguousarray(depth_exact, np.float32)
@@ -55,6 +56,7 @@ class Case:
         self.offset_inv = I.copy() if offset_inv is None else np.asarray(offset_inv, np.float64)
         self.cam_tf = I.copy() if cam_tf is None else np.asarray(cam_tf, np.float64)
         self.max_diff, self.replace = max_diff, replace
+        self.z_near, self.z_far = z_near, z_far          # the shader's planes (and the background quad's 0.99 z_far)
 
     def flat_draws(self):
         """Triangle draw list for the oracle / HIP path: matrix ops inside one renderable accumulate
@@ -223,9 +225,68 @@ def threshold_case(hn):
     return Case("threshold_ulps_160x120", W, H, None, P, rend, depth_exact=d)
 
 
+def on_threshold(c, seed=0):
+    """Case c with its sensor ON the shader's threshold of the winners (one ulp above / below in a third of the pixels each),
+    the usual sensor plane where nothing but the background quad (or nothing at all) is drawn."""
+    _, _, zwin, prim, _ = O.filter_frame(np.full((c.H, c.W), 3.0, np.float32), c.projection, c.flat_draws(), c.offset_inv, c.cam_tf,
+                                         z_near=c.z_near, z_far=c.z_far, want_debug=True)
+    n, f = np.float32(c.z_near), np.float32(c.z_far)
+    with np.errstate(all="ignore"):
+        num = np.float32(np.float32(n * f) / np.float32(n - f))
+        off = np.float32(f / np.float32(f - n))
+        thr = ((num / (zwin - off).astype(np.float32)).astype(np.float32) - np.float32(c.max_diff)).astype(np.float32)
+    sel = np.random.default_rng(seed).integers(0, 3, thr.shape)
+    d = thr.copy()
+    d[sel == 1] = np.nextafter(thr[sel == 1], np.float32(np.inf))
+    d[sel == 2] = np.nextafter(thr[sel == 2], np.float32(-np.inf))
+    d = np.where(prim >= 0, d, S.sensor_depth(c.W, c.H, 0.9)).astype(np.float32)
+    c.depth_q, c.depth = None, d
+    return c
+
+
+def plane_cases():
+    """Fixtures at planes other than 0.1 / 8: walls tilted through the far plane over whole tiles, with the background quad
+    clipped away (shader far plane above the projection's far / 0.99) and with it; and uniforms the reference accepts but
+    nothing sensible sets: near 0, near = far, NaN threshold."""
+    W, H = 160, 120
+    fx, cx, cy = 131.25, 79.5, 59.5
+    P = S.projection(fx, fx, cx, cy, W, H)
+    I = np.eye(4).T.reshape(16)
+
+    def obj(x, y, zw, near=0.1, far=8.0):
+        m22, m23 = -(far + near) / (far - near), -2.0 * far * near / (far - near)
+        d = m23 / ((2.0 * zw - 1.0) + m22)
+        return [(x - cx) / fx * d, (y - (H - cy)) / fx * d, d]
+
+    rng = np.random.default_rng(77)
+    tris = []
+    for x0, x1 in ((-300.0, W / 2), (W / 2, W + 300.0)):
+        zf = lambda x, y: 0.97 + 0.06 * (x / W) + 0.004 * (y / H)
+        tris += [[obj(x0, -50, zf(x0, -50)), obj(x1, -50, zf(x1, -50)), obj(x0, H + 400, zf(x0, H + 400))],
+                 [obj(x1, -50, zf(x1, -50)), obj(x1, H + 400, zf(x1, H + 400)), obj(x0, H + 400, zf(x0, H + 400))]]
+    for _ in range(30):
+        px, py, zz = rng.uniform(0, W), rng.uniform(0, H / 2), rng.uniform(0.6, 0.95)
+        tris.append([obj(px + rng.uniform(-4, 4), py + rng.uniform(-4, 4), zz) for _ in range(3)])
+    v = np.asarray(tris, np.float32).reshape(-1, 3)
+    rend = [(I, [("mesh", 0, (0, 0, 0), v, np.arange(len(v), dtype=np.uint32).reshape(-1, 3))])]
+    out = [on_threshold(Case("far_plane_covers_160x120", W, H, None, P, rend, depth_exact=np.zeros((H, W), np.float32),
+                             z_far=8.0 / 0.99 * 1.01)),
+           on_threshold(Case("far_plane_covers_background_160x120", W, H, None, P, rend, depth_exact=np.zeros((H, W), np.float32)))]
+    rng = np.random.default_rng(13)
+    geo = S.soup_geometry(rng, n_links=6, tris_per_link=30)
+    tfs = S.random_link_poses(rng, len(geo), near=True, far=True)
+    offinv, camtf = S.random_camera(rng)
+    rend = [(tfs[i], [("mesh", geo[i][0], geo[i][1], geo[i][2], geo[i][3])]) for i in range(len(geo))]
+    depth = S.sensor_depth(W, H, 1.3)
+    out.append(Case("uniforms_near_zero_160x120", W, H, depth, P, rend, offinv, camtf, z_near=0.0))
+    out.append(Case("uniforms_near_at_far_160x120", W, H, depth, P, rend, offinv, camtf, z_near=8.0))
+    out.append(Case("uniforms_nan_threshold_160x120", W, H, depth, P, rend, offinv, camtf, max_diff=float("nan")))
+    return out
+
+
 def main():
     harn = {}
-    allc = cases()
+    allc = cases() + plane_cases()
     for c in allc + [None]:
         if c is None:
             c = threshold_case(harn.get((160, 120)))
@@ -234,21 +295,29 @@ def main():
         if key not in harn:
             harn[key] = None
     by_size = {}
+    only = sys.argv[sys.argv.index("--only") + 1:] if "--only" in sys.argv else None
     for c in allc + [threshold_case(None)]:
-        by_size.setdefault((c.W, c.H), []).append(c)
+        if only is None or c.name in only:
+            by_size.setdefault((c.W, c.H), []).append(c)
     import subprocess
     if len(sys.argv) > 1 and sys.argv[1] == "--size":
         W, H = int(sys.argv[2]), int(sys.argv[3])
         hn = HN.Harness(W, H)
         print("renderer:", hn.renderer())
         for c in by_size[(W, H)]:
-            masked, mask = hn.frame(c.depth, c.projection, c.renderables, c.offset_inv, c.cam_tf, max_diff=c.max_diff, replace_value=c.replace)
-            # the reference's output is a pure function of mask / sensor / replace value
-            recon = np.where(mask > 0, np.float32(c.replace), c.depth).astype(np.float32)
+            masked, mask = hn.frame(c.depth, c.projection, c.renderables, c.offset_inv, c.cam_tf, z_near=c.z_near, z_far=c.z_far,
+                                    max_diff=c.max_diff, replace_value=c.replace)
+            # the reference's output is a pure function of mask / sensor / replace value -- and, where the background quad
+            # lies beyond the far plane, of the pixels nothing was drawn on (the clear colour: 0)
+            _, _, _, prim, _ = O.filter_frame(c.depth, c.projection, c.flat_draws(), c.offset_inv, c.cam_tf, z_near=c.z_near,
+                                              z_far=c.z_far, max_diff=c.max_diff, replace_value=c.replace, want_debug=True)
+            undrawn = prim == -1
+            recon = np.where(mask > 0, np.float32(c.replace), np.where(undrawn, np.float32(0), c.depth)).astype(np.float32)
             assert np.array_equal(recon.view(np.uint32), masked.view(np.uint32)), c.name
             assert set(np.unique(mask)) <= {0, 255}
             # the CPU oracle must agree with llvmpipe before a fixture is written
-            om, ok = O.filter_frame(c.depth, c.projection, c.flat_draws(), c.offset_inv, c.cam_tf, max_diff=c.max_diff, replace_value=c.replace)
+            om, ok = O.filter_frame(c.depth, c.projection, c.flat_draws(), c.offset_inv, c.cam_tf, z_near=c.z_near, z_far=c.z_far,
+                                    max_diff=c.max_diff, replace_value=c.replace)
             assert np.array_equal(ok, mask), "%s: oracle mask differs from llvmpipe in %d px" % (c.name, int((ok != mask).sum()))
             assert np.array_equal(om.view(np.uint32), masked.view(np.uint32)), c.name
             draws = c.flat_draws()
@@ -266,6 +335,10 @@ def main():
                 "masked_sha256": np.frombuffer(hashlib.sha256(masked.tobytes()).digest(), np.uint8),
                 "renderer": np.frombuffer(hn.renderer().encode(), np.uint8),
             }
+            if undrawn.any():
+                fx["undrawn_bits"] = np.packbits(undrawn)
+            if (c.z_near, c.z_far) != (0.1, 8.0):
+                fx["z_near"], fx["z_far"] = np.float32(c.z_near), np.float32(c.z_far)
             if c.depth_q is not None:
                 fx["depth_q"] = c.depth_q
             else:
@@ -275,7 +348,7 @@ def main():
             print("%-34s masked_px=%6d  %6.1f KiB" % (c.name, int((mask > 0).sum()), os.path.getsize(path) / 1024))
         return
     for (W, H) in by_size:
-        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--size", str(W), str(H)])
+        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--size", str(W), str(H)] + (["--only"] + only if only else []))
 
 
 if __name__ == "__main__":

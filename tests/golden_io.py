@@ -58,6 +58,9 @@ class Fixture:
     def __init__(self, name):
         z = np.load(os.path.join(HERE, "golden", name + ".npz"))
         self.name = name
+        # the shader's planes (the background quad sits at 0.99 z_far); fixtures without them were rendered at 0.1 / 8
+        self.z_near = float(z["z_near"]) if "z_near" in z.files else 0.1
+        self.z_far = float(z["z_far"]) if "z_far" in z.files else 8.0
         if "recipe" in z.files:          # inputs addressed by seed (BASELINE-size frames): rebuilt, and checked against the hash taken when the reference rendered them
             import json
             fi = SeededInputs(json.loads(z["recipe"].tobytes().decode()))
@@ -71,6 +74,7 @@ class Fixture:
             self.mask = (np.unpackbits(z["mask_bits"])[: self.width * self.height].reshape(self.height, self.width) * 255).astype(np.uint8)
             self.masked_sha256 = bytes(z["masked_sha256"].tobytes())
             self.renderer = z["renderer"].tobytes().decode()
+            self.undrawn = np.zeros((self.height, self.width), bool)
             return
         self.width, self.height = int(z["width"]), int(z["height"])
         self.max_diff, self.replace_value = float(z["max_diff"]), float(z["replace_value"])
@@ -94,10 +98,14 @@ class Fixture:
         self.mask = (np.unpackbits(z["mask_bits"])[: self.width * self.height].reshape(self.height, self.width) * 255).astype(np.uint8)
         self.masked_sha256 = bytes(z["masked_sha256"].tobytes())
         self.renderer = z["renderer"].tobytes().decode()
+        # pixels nothing was drawn on, not even the background quad (it lies beyond the far plane): they keep the clear colour
+        self.undrawn = (np.unpackbits(z["undrawn_bits"])[: self.width * self.height].reshape(self.height, self.width) > 0
+                        if "undrawn_bits" in z.files else np.zeros((self.height, self.width), bool))
 
     def expected_masked(self):
-        """The reference's colour attachment 1: replace value where filtered, the sensor value elsewhere."""
-        m = np.where(self.mask > 0, np.float32(self.replace_value), self.depth).astype(np.float32)
+        """The reference's colour attachment 1: replace value where filtered, the sensor value elsewhere (0, the clear
+        colour, where nothing was drawn)."""
+        m = np.where(self.mask > 0, np.float32(self.replace_value), np.where(self.undrawn, np.float32(0), self.depth)).astype(np.float32)
         assert hashlib.sha256(m.tobytes()).digest() == self.masked_sha256
         return m
 

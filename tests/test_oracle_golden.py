@@ -11,7 +11,7 @@ from oracle import bindings as O
 def test_oracle_reproduces_reference_output(name):
     fx = golden_io.Fixture(name)
     assert "llvmpipe" in fx.renderer
-    masked, mask = O.filter_frame(fx.depth, fx.projection, fx.draws, fx.offset_inv, fx.cam_tf,
+    masked, mask = O.filter_frame(fx.depth, fx.projection, fx.draws, fx.offset_inv, fx.cam_tf, z_near=fx.z_near, z_far=fx.z_far,
                                   max_diff=fx.max_diff, replace_value=fx.replace_value)
     fx.check(masked, mask)
     assert np.array_equal(masked.view(np.uint32), fx.expected_masked().view(np.uint32))

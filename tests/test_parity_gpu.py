@@ -39,7 +39,7 @@ def bits_equal(a, b):
 @pytest.mark.parametrize("name", golden_io.fixture_names())
 def test_golden_fixture(name, two_kernel):
     fx = golden_io.Fixture(name)
-    ctx = R.Context(fx.width, fx.height, 1, 0, params(fx.replace_value, fx.max_diff, two_kernel))
+    ctx = R.Context(fx.width, fx.height, 1, 0, params(fx.replace_value, fx.max_diff, two_kernel, near_plane=fx.z_near, far_plane=fx.z_far))
     m, tfs = fx.load_into(ctx)
     ctx.set_camera(0, fx.projection, fx.offset_inv, fx.cam_tf)
     if len(tfs):
