@@ -166,6 +166,8 @@ struct FilterParameters {
   // -- the reference's hard-coded Kinect values by default -- and leaves camera_tx_ / camera_ty_ alone, as the #ifdef does.
   bool use_own_calibration = false;
   double own_calibration[4] = {585.260, 585.028, 317.387, 239.264};      // fx fy cx cy
+  // New, beyond the reference: widen the rendered robot by this many pixels, 0 .. 16 (rtuf_params.silhouette_dilation_px)
+  unsigned silhouette_dilation_px = 0;
 };
 
 // ---- urdf_filter.h --------------------------------------------------------------------------
@@ -175,6 +177,7 @@ class RealtimeURDFFilter {
                      std::map<std::string, std::string> param_server, int device = 0, MeshResolver resolve = nullptr, void* resolve_user = nullptr)
       : tf_(tf), fixed_frame_(params.fixed_frame), cam_frame_(params.camera_frame), show_gui_(params.show_gui),
         depth_distance_threshold_(params.depth_distance_threshold), filter_replace_value_(params.filter_replace_value),
+        silhouette_dilation_px_(params.silhouette_dilation_px),
         params_(params), param_server_(std::move(param_server)), device_(device), resolve_(resolve), resolve_user_(resolve_user)
   {
   }
@@ -218,6 +221,7 @@ class RealtimeURDFFilter {
     p.far_plane = (float)far_plane_;
     p.depth_distance_threshold = (float)depth_distance_threshold_;
     p.filter_replace_value = (float)filter_replace_value_;
+    p.silhouette_dilation_px = silhouette_dilation_px_;
     if (ctx_) { rtuf_destroy(ctx_); ctx_ = nullptr; }
     if (rtuf_create(&ctx_, device_, width_, height_, 1, &p) != RTUF_OK) throw std::runtime_error(std::string("ERROR: could not initialize the GPU context: ") + rtuf_last_error(nullptr));
     this->loadModels();
@@ -352,6 +356,7 @@ class RealtimeURDFFilter {
       p.far_plane = (float)far_plane_;
       p.depth_distance_threshold = (float)depth_distance_threshold_;
       p.filter_replace_value = (float)filter_replace_value_;
+      p.silhouette_dilation_px = silhouette_dilation_px_;
       check(rtuf_set_params(ctx_, &p));
     }
     return true;
@@ -374,6 +379,7 @@ class RealtimeURDFFilter {
   double camera_tx_ = 0, camera_ty_ = 0;
   double far_plane_ = 8, near_plane_ = 0.1;        // src/urdf_filter.cpp:53-54
   double depth_distance_threshold_, filter_replace_value_;
+  unsigned silhouette_dilation_px_;                // re-read every frame like the thresholds
   // output from rendering (library-owned, valid until the next filter())
   const float* masked_depth_ = nullptr;
   const uint8_t* mask_ = nullptr;

@@ -106,7 +106,22 @@ typedef struct {
                                        the launch groups shrink (more, smaller launches) instead of the call failing; when even
                                        one stream's bins are larger the bins are grown all the same (up to what the device has)
                                        and rtuf_stats.over_memory_limit says so. */
-  uint32_t reserved[2];
+  uint32_t silhouette_dilation_px;  /* 0 .. 16 (was reserved[0], same offset; 0 = off, the reference's behaviour).  New, beyond the
+                                       reference, like the batch and lane entries: widens the rendered robot by r pixels to cover
+                                       mixed depth pixels at the sensor's edges, camera_offset calibration error and TF latency.
+                                       For r > 0 every pixel p of a stream is shaded with z'(p) instead of its own window z: the
+                                       smallest drawn z in the (2r+1) x (2r+1) square around p, clipped to that stream's image
+                                       (never padded, never reaching into another stream), and "nothing drawn" when the square
+                                       holds nothing drawn.  The outputs are then exactly the shader's for z': filtered where
+                                       sensor > to_linear_depth(z') - depth_distance_threshold, masked 0 / mask 0 (the GL clear
+                                       colour) where nothing is drawn.  z' is always one of the square's own values, so the depth
+                                       test still decides: a foreground object in front of the widened silhouette is kept.  The
+                                       background quad is drawn, so away from the robot nothing changes; a pixel the background does
+                                       not cover (a non-standard projection) with a drawn pixel within r becomes drawn.  Batches
+                                       run the z-surface route (tile kernel writes the window z, a dilate-and-compare kernel makes
+                                       every output form, mask bits included) whatever RTUF_FLAG_TWO_KERNEL says, one batch in
+                                       flight at a time.  Larger values fail with RTUF_ERR_INVALID. */
+  uint32_t reserved[1];
 } rtuf_params;
 
 void rtuf_default_params(rtuf_params *p);
@@ -258,7 +273,7 @@ int rtuf_filter_batch_u16_async(rtuf_context *ctx, int n_streams, const uint16_t
  * 32-bit word y * ceil(width / 32) + x / 32 (rtuf_mask_bits_words() words per stream).  Device-to-host traffic per
  * VGA frame drops from 1.54 MB to 38 KB, which turns the PCIe-bound host-plane path from download-bound into
  * upload-bound; rtuf_expand_mask_bits() rebuilds masked depth and/or the byte mask of a frame on the host where and
- * when a consumer needs them.  Fused mode only; width must be a multiple of 4.  Exactness: the identity above holds
+ * when a consumer needs them.  Not with RTUF_FLAG_TWO_KERNEL (silhouette dilation is fine); width must be a multiple of 4.  Exactness: the identity above holds
  * wherever the background quad covers the image -- every getProjectionMatrix() camera.  For a projection where it
  * does not (pixels the reference leaves at the GL clear colour 0), retiring the batch fails with RTUF_ERR_STATE
  * instead of returning bits that would expand to something else. */

@@ -41,7 +41,8 @@ class Params(ctypes.Structure):
                 ("depth_distance_threshold", ctypes.c_float), ("filter_replace_value", ctypes.c_float),
                 ("flags", ctypes.c_uint32), ("bin_capacity", ctypes.c_uint32),
                 ("max_inflight_streams", ctypes.c_uint32), ("pipelines", ctypes.c_uint32),
-                ("raster_lanes", ctypes.c_uint32), ("memory_limit_mb", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+                ("raster_lanes", ctypes.c_uint32), ("memory_limit_mb", ctypes.c_uint32),
+                ("silhouette_dilation_px", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 1)]
 
 
 class Stats(ctypes.Structure):

@@ -63,6 +63,7 @@ struct HostModel { std::vector<HostLink> links; int link_base = 0; Kinematics ki
 char g_create_error[512] = "";
 
 constexpr uint32_t kKnownFlags = RTUF_FLAG_TWO_KERNEL | RTUF_FLAG_STRICT_GRID;
+static bool dilation_valid(const rtuf_params* p) { return p->silhouette_dilation_px <= (uint32_t)kMaxDilation; }
 inline bool flags_valid(uint32_t flags)
 {
 #ifdef RTUF_ABLATE
@@ -189,6 +190,7 @@ struct rtuf_context {
     int graph_next = 0;
     std::vector<uint32_t> setup_grid;        // per launch group: work items its set-up launch covered (0xffffffff = the worst case)
     bool cover_pass = true;                  // this batch runs the cover pass (decided when it is first enqueued, kept for re-runs)
+    int dilation = 0;                        // silhouette dilation radius of this batch (set when it is first enqueued, kept for re-runs)
     int timing = 0;                          // event timing of this batch: 0 none, 1 every stage, 2 tile/compare kernel only
     // Host-plane batches (rtuf_filter_batch*): device staging of this slot, the caller's planes, and the
     // events that order upload -> kernels -> download across the copy streams.
@@ -534,6 +536,10 @@ int rtuf_create(rtuf_context** out, int device_id, int width, int height, int ma
     snprintf(g_create_error, sizeof g_create_error, "unknown rtuf_params.flags bits 0x%x", params->flags & ~kKnownFlags);
     return RTUF_ERR_INVALID;
   }
+  if (params && !dilation_valid(params)) {
+    snprintf(g_create_error, sizeof g_create_error, "silhouette_dilation_px = %u: at most %d", params->silhouette_dilation_px, kMaxDilation);
+    return RTUF_ERR_INVALID;
+  }
   if (params && params->raster_lanes > (uint32_t)kMaxLanes) {
     snprintf(g_create_error, sizeof g_create_error, "raster_lanes = %u: at most %d", params->raster_lanes, kMaxLanes);
     return RTUF_ERR_INVALID;
@@ -672,6 +678,7 @@ int rtuf_set_params(rtuf_context* c, const rtuf_params* p)
 {
   if (!c || !p) return RTUF_ERR_INVALID;
   if (!flags_valid(p->flags)) return c->fail(RTUF_ERR_INVALID, "unknown rtuf_params.flags bits 0x%x", p->flags & ~kKnownFlags);
+  if (!dilation_valid(p)) return c->fail(RTUF_ERR_INVALID, "silhouette_dilation_px = %u: at most %d", p->silhouette_dilation_px, kMaxDilation);
   if (!c->kids.empty()) {
     rtuf_params kp = *p;
     kp.pipelines = 0;
@@ -1334,17 +1341,21 @@ static hipEvent_t get_event(rtuf_context::Batch& b, size_t i)
 struct BatchPlan {
   std::vector<FkArgs> fks;
   PoseArgs pa{};
-  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; bool compare = false; int lane = 0; };
+  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; bool compare = false, dilate = false; int lane = 0; };
   std::vector<Group> groups;
   bool cover_pass = true;
+  bool zroute = false;          // the tile kernel writes the z-surface (two-kernel mode, or silhouette dilation)
   uint64_t hash() const
   {
     uint64_t h = 1469598103934665603ull;
     auto mix = [&h](const void* p, size_t n) { const unsigned char* q = static_cast<const unsigned char*>(p); for (size_t i = 0; i < n; i++) { h ^= q[i]; h *= 1099511628211ull; } };
     for (const FkArgs& f : fks) mix(&f, sizeof f);
     mix(&pa, sizeof pa);
-    for (const Group& g : groups) { mix(&g.sa, sizeof g.sa); mix(&g.ta, sizeof g.ta); if (g.compare) mix(&g.ca, sizeof g.ca); mix(&g.lane, sizeof g.lane); }
-    return h ^ (uint64_t)fks.size() << 56 ^ (uint64_t)groups.size() << 48 ^ (uint64_t)cover_pass << 47;
+    for (const Group& g : groups) {
+      mix(&g.sa, sizeof g.sa); mix(&g.ta, sizeof g.ta); if (g.compare) mix(&g.ca, sizeof g.ca); if (g.dilate) mix(&g.da, sizeof g.da);
+      mix(&g.lane, sizeof g.lane);
+    }
+    return h ^ (uint64_t)fks.size() << 56 ^ (uint64_t)groups.size() << 48 ^ (uint64_t)cover_pass << 47 ^ (uint64_t)zroute << 46;
   }
 };
 
@@ -1360,7 +1371,7 @@ enum { kEvStart = 0, kEvPoseEnd = 1, kEvLaneEnd = 2, kEvGroup0 = 2 + kMaxLanes, 
 // group still belongs to the pose stage (it then runs under the previous batch's raster kernels).
 static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& plan, hipStream_t sp, bool worst_case_grid)
 {
-  const bool two = (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0;
+  const bool two = plan.zroute;
   worst_case_grid = worst_case_grid || c->force_worst_grid || (c->params.flags & RTUF_FLAG_STRICT_GRID) != 0;
   auto mark = [&](size_t i, hipStream_t s) { hipEventRecord(get_event(b, i), s); };
   if (b.timing) (void)get_event(b, kEvGroup0 + kEvPerGroup * plan.groups.size() - 1);      // (all of the batch's events exist)
@@ -1412,6 +1423,7 @@ static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& 
     launch_tile(gr.ta, two, plan.cover_pass, st);
     if (b.timing) mark(e0 + 3, st);
     if (gr.compare) { launch_compare(gr.ca, st); if (b.timing) mark(e0 + 4, st); }
+    if (gr.dilate) { launch_dilate_compare(gr.da, st); if (b.timing) mark(e0 + 4, st); }
   }
   // every lane publishes the counter blocks of its own groups
   const int ng = (int)plan.groups.size();
@@ -1485,6 +1497,11 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   BatchPlan plan;
   if (!rerun) b.cover_pass = c->cover_on;
   plan.cover_pass = b.cover_pass;
+  // silhouette dilation: the tile kernel writes the z-surface and dilate_compare_kernel makes every output form from it (the
+  // mask bits included); without it nothing here differs from before
+  if (!rerun) b.dilation = (int)c->params.silhouette_dilation_px;
+  const int dil = b.dilation;
+  plan.zroute = dil > 0 || (two && !b.bits);
   // on-device forward kinematics overwrites the link matrices (and camera) of the streams that use it
   for (HostModel& m : c->models) {
     Kinematics& k = m.kin;
@@ -1532,7 +1549,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     const int gs = std::min(per_group, n - base);
     plan.groups.emplace_back();
     BatchPlan::Group& gr = plan.groups.back();
-    memset(&gr.sa, 0, sizeof gr.sa); memset(&gr.ta, 0, sizeof gr.ta); memset(&gr.ca, 0, sizeof gr.ca);
+    memset(&gr.sa, 0, sizeof gr.sa); memset(&gr.ta, 0, sizeof gr.ta); memset(&gr.ca, 0, sizeof gr.ca); memset(&gr.da, 0, sizeof gr.da);
     gr.lane = n_groups == 1 ? lane0 : g % c->n_lanes;
     const rtuf_context::Lane& ln = c->lane[gr.lane];
     Counters* const d_counters = b.d_counters + g;
@@ -1557,8 +1574,16 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     ta.io_u16 = io_u16 ? 1 : 0;
     ta.key_shift = c->key_shift;
     ta.fast_div = fast_div;
-    ta.bits = b.bits;
-    gr.compare = two && !b.bits;
+    ta.bits = dil ? nullptr : b.bits;
+    gr.compare = two && !b.bits && !dil;
+    gr.dilate = dil > 0;
+    if (gr.dilate) {
+      DilateArgs& da = gr.da;
+      da.depth = d_depth; da.zsurface = ln.d_zsurface; da.masked = d_masked; da.mask = d_mask; da.bits = b.bits; da.counters = d_counters;
+      da.group_base = base; da.group_size = gs; da.width = c->width; da.height = c->height; da.radius = dil;
+      da.max_diff = ta.max_diff; da.replace_value = ta.replace_value; da.sc_num = sc_num; da.sc_off = sc_off;
+      da.io_u16 = io_u16 ? 1 : 0; da.fast_div = fast_div;
+    }
     if (gr.compare) {
       CompareArgs& ca = gr.ca;
       ca.depth = reinterpret_cast<const float*>(reinterpret_cast<const char*>(d_depth) + (size_t)base * plane * esz); ca.zsurface = ln.d_zsurface;
@@ -1748,7 +1773,7 @@ static int retire_oldest(rtuf_context* c)
       if (b.timing && b.events.size() >= (size_t)(kEvGroup0 + kEvPerGroup * b.n_groups)) {
         // per launch group E0 .. E4 (see issue_plan).  With several lanes the kernels of different groups overlap: the sums
         // below add up per-launch durations, they are not wall time.
-        const bool two = (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.bits;
+        const bool two = ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.bits) || b.dilation > 0;
         auto el = [&](size_t i, size_t j) { float ms = 0; hipEventElapsedTime(&ms, b.events[i], b.events[j]); return ms; };
         c->stats.ms_pose = c->stats.ms_setup = c->stats.ms_clip = c->stats.ms_raster = c->stats.ms_compare = c->stats.ms_total = 0;
         for (int g = 0; g < b.n_groups; g++) {
@@ -1837,16 +1862,19 @@ static int retire_oldest(rtuf_context* c)
   return c->fail(RTUF_ERR_CAPACITY, "tile bins still overflow after regrowth");
 }
 
+// the batches of this context write the z-surface: two-kernel mode, or a silhouette dilation radius
+static bool uses_zsurface(const rtuf_context* c) { return (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 || c->params.silhouette_dilation_px > 0; }
+
 static int submit_batch(rtuf_context* c, int n, const float* d_depth, float* d_masked, uint8_t* d_mask, bool u16, uint32_t* d_bits = nullptr,
                         bool wait_upload = false)
 {
   if (c->broken) return c->fail(RTUF_ERR_STATE, "context unusable: a bin regrowth failed (%s)", c->error.c_str());
   hipSetDevice(c->device);
-  if (c->params.flags & RTUF_FLAG_TWO_KERNEL)
+  if (uses_zsurface(c))
     for (int l = 0; l < c->n_lanes; l++)
       if (!c->lane[l].d_zsurface) HIP_TRY(c, dev_alloc(c, &c->lane[l].d_zsurface, (size_t)c->group * c->width * c->height * sizeof(float)));
-  // two-kernel mode keeps one z-surface per lane: its batches do not overlap
-  const int limit = (c->params.flags & RTUF_FLAG_TWO_KERNEL) ? 1 : kMaxInflight;
+  // two-kernel mode and silhouette dilation keep one z-surface per lane: their batches do not overlap
+  const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
   while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
   rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];
   b.n = n; b.depth = d_depth; b.masked = d_masked; b.mask = d_mask; b.u16 = u16; b.host_io = false; b.bits = d_bits;
@@ -2009,7 +2037,7 @@ static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in
     if (!c->d2h) HIP_TRY(c, create_stream_beside(lane_streams(c), &c->d2h, &beside));
     c->stats.copy_streams_side_by_side = (beside && beside_up) ? 1u : 0u;
   }
-  const int limit = (c->params.flags & RTUF_FLAG_TWO_KERNEL) ? 1 : kMaxInflight;
+  const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
   while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
   rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];     // the slot submit_batch takes next
   const size_t plane = (size_t)c->width * c->height;

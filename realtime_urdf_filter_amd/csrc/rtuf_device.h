@@ -23,7 +23,7 @@
 //                                                                    record bin holds a near record, see KeyFmt)
 //     clip_list ClipItem[shards][clip_capacity]   triangles that cross a frustum plane (set-up kernel -> clip kernel)
 //     big_list  BigRec[shards][big_capacity]      records over more than 4 tiles (set-up / clip kernel -> bigrec_kernel)
-//     zsurface  f32[G][H][W]                       two-kernel mode only
+//     zsurface  f32[G][H][W]                       two-kernel mode and silhouette dilation only
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -334,6 +334,25 @@ struct CompareArgs {
   int fast_div;
 };
 
+// Silhouette dilation (rtuf_params.silhouette_dilation_px > 0): dilate_compare_kernel takes the place of compare_kernel.  Per
+// pixel it shades with z' = the smallest non-NaN z-surface value of the (2r+1)^2 window around it, clipped to the stream's
+// image (NaN when the window holds none), and writes the same outputs the compare kernel or the bit-packed tile kernel would.
+constexpr int kMaxDilation = 16;
+struct DilateArgs {
+  const float* depth;     // [n][H][W] sensor planes (f32 metres or, with io_u16, uint16 millimetres): the whole batch
+  const float* zsurface;  // [G][H][W] the lane's z-surface (slot 0 = stream group_base)
+  float* masked;          // [n][H][W] same element type as depth; unused with bits
+  uint8_t* mask;          // [n][H][W] or nullptr; unused with bits
+  uint32_t* bits;         // mask-only output (rtuf_mask_bits_words layout) or nullptr
+  Counters* counters;     // the launch group's block: BITS sets a shard's `uncovered`
+  int group_base, group_size;
+  int width, height;
+  int radius;             // 1 .. kMaxDilation
+  float max_diff, replace_value;
+  float sc_num, sc_off;
+  int io_u16;
+  int fast_div;
+};
 
 struct FkArgs {
   const int32_t* parent;        // [F]
@@ -364,6 +383,7 @@ struct PublishLimits { uint32_t capacity, fcapacity, big_capacity; };
 void launch_publish_counters(const Counters* src, Counters* host_dst, int first, int stride, int count, uint32_t* status, PublishLimits lim, hipStream_t st);
 void launch_tile(const TileArgs& a, bool two_kernel, bool cover_pass, hipStream_t st);   // a.io_u16 selects the 16UC1 variant
 void launch_compare(const CompareArgs& a, hipStream_t st);
+void launch_dilate_compare(const DilateArgs& a, hipStream_t st);     // a.bits selects the mask-only variant, a.io_u16 the 16UC1 one
 void launch_spin(unsigned long long ticks, hipStream_t st);      // a one-wave kernel that idles for `ticks` of the 100 MHz clock
 
 }  // namespace rtuf

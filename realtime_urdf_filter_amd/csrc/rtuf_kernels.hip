@@ -19,6 +19,9 @@
 //                   64-bit LDS atomicMin, then the per-pixel compare      + glGetTexImage conversions
 //                   is done in place (fused) or the z-surface is written
 //   compare_kernel  two-kernel mode only: z-surface + sensor -> outputs   replaces urdf_filter.frag:19-36
+//   dilate_compare_kernel  silhouette dilation only (new, beyond the       (none: the reference has no dilation)
+//                   reference): (2r+1)^2 window minimum of the z-surface,
+//                   then compare_kernel's shading (or the mask bits)
 //
 // Exactness: results must equal the reference's GLSL running on Mesa llvmpipe bit for bit
 // (see oracle/rtuf_oracle.c for what that pins).  Every float operation whose rounding matters
@@ -2629,6 +2632,156 @@ __global__ __launch_bounds__(kBlock) void compare_kernel(CompareArgs a)
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// dilate_compare_kernel (silhouette dilation, rtuf_params.silhouette_dilation_px = r > 0): z-surface -> minimum over the
+// (2r+1)^2 window of every pixel -> the compare kernel's outputs, or the bit-packed mask
+// ---------------------------------------------------------------------------------------
+// One workgroup per (64x32 output tile, stream of the launch group).  LDS holds the tile's z-surface with an r-pixel halo --
+// columns from x0 - R4 (R4 = r rounded up to a multiple of 4, so every float4 of it is aligned), NaN outside the stream's
+// image -- and then the row minima of the halo rows.  Both passes give a lane four outputs: the 2r - 2 inputs all four windows
+// share are folded once, then the three each has of its own: (2r + 10) / 4 minimum instructions per output and pass instead of
+// 2r + 1.  fminf returns the other operand when one is NaN, so NaN (nothing drawn, outside the image) is the identity and an
+// all-NaN window gives NaN; the result is always one of the window's own values.  (r >= 1: at r = 0 the shared edges overlap.)
+constexpr int kDilW = 64, kDilH = 32, kDilThreads = 256;
+static_assert(kDilThreads == (kDilW / 4) * (kDilH / 2), "column pass and output: one lane per 4 x 2 pixels of the tile");
+static_assert(kDilW % 32 == 0, "a tile row is whole mask-bit words");
+__host__ __device__ constexpr int dilate_r4(int r) { return (r + 3) & ~3; }
+static size_t dilate_lds_bytes(int r) { return (size_t)(kDilH + 2 * r) * (size_t)(kDilW + 2 * dilate_r4(r) + kDilW) * sizeof(float); }
+static_assert((kDilH + 2 * kMaxDilation) * (kDilW + 2 * dilate_r4(kMaxDilation) + kDilW) * 4 <= 65536, "LDS of the largest radius");
+
+__device__ __forceinline__ float4 fmin4(float4 a, float4 b) { return make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z), fminf(a.w, b.w)); }
+
+template <bool U16, bool BITS>
+__global__ __launch_bounds__(kDilThreads) void dilate_compare_kernel(DilateArgs a)
+{
+  extern __shared__ float dil_lds[];
+  const int r = a.radius, R4 = dilate_r4(r);
+  const int in_w = kDilW + 2 * R4;            // halo tile columns: image x = x0 - R4 + column
+  const int rows = kDilH + 2 * r;             // halo tile rows:    image y = y0 - r + row
+  float* zin = dil_lds;                       // [rows][in_w]
+  float* rmin = dil_lds + rows * in_w;        // [rows][kDilW]  minimum over the row window of every output column
+  const int tid = threadIdx.x;
+  const int slot = blockIdx.z, stream = a.group_base + slot;
+  const int x0 = blockIdx.x * kDilW, y0 = blockIdx.y * kDilH;
+  const int W = a.width, H = a.height;
+  const float nan = __uint_as_float(0x7fc00000u);
+  const float* zs = a.zsurface + (size_t)slot * ((size_t)H * W);
+
+  // 1. the halo tile (the window is clipped to the image, never padded: NaN is what the minimum ignores)
+  if ((W & 3) == 0) {
+    const int in_w4 = in_w >> 2;
+    for (int i = tid; i < rows * in_w4; i += kDilThreads) {
+      const int row = i / in_w4, c4 = i - row * in_w4;
+      const int y = y0 - r + row, x = x0 - R4 + 4 * c4;
+      float4 v = make_float4(nan, nan, nan, nan);
+      if (y >= 0 && y < H && x >= 0 && x < W) v = *reinterpret_cast<const float4*>(zs + (size_t)y * W + x);      // (x < W: x + 3 < W)
+      *reinterpret_cast<float4*>(zin + row * in_w + 4 * c4) = v;
+    }
+  } else {
+    for (int i = tid; i < rows * in_w; i += kDilThreads) {
+      const int row = i / in_w, c = i - row * in_w;
+      const int y = y0 - r + row, x = x0 - R4 + c;
+      float v = nan;
+      if (y >= 0 && y < H && x >= 0 && x < W) v = zs[(size_t)y * W + x];
+      zin[i] = v;
+    }
+  }
+  __syncthreads();
+
+  // 2. rows: outputs c .. c + 3 of a halo row; output c + j's window is p[j .. j + 2r]
+  for (int i = tid; i < rows * (kDilW / 4); i += kDilThreads) {
+    const int row = i >> 4, c = (i & 15) * 4;
+    const float* p = zin + row * in_w + c + R4 - r;
+    float core = nan;
+    for (int k = 3; k <= 2 * r; k++) core = fminf(core, p[k]);
+    const float e0 = p[0], e1 = p[1], e2 = p[2], f0 = p[2 * r + 1], f1 = p[2 * r + 2], f2 = p[2 * r + 3];
+    *reinterpret_cast<float4*>(rmin + row * kDilW + c) =
+        make_float4(fminf(core, fminf(e0, fminf(e1, e2))), fminf(core, fminf(e1, fminf(e2, f0))),
+                    fminf(core, fminf(e2, fminf(f0, f1))), fminf(core, fminf(f0, fminf(f1, f2))));
+  }
+  __syncthreads();
+
+  // 3. columns: tile rows ly and ly + 1, columns lx .. lx + 3; tile row y's window is halo rows y .. y + 2r
+  const int lx = (tid & 15) * 4, ly = (tid >> 4) * 2;
+  float4 zd[2];
+  {
+    const float* q = rmin + ly * kDilW + lx;
+    float4 core = make_float4(nan, nan, nan, nan);
+    for (int k = 1; k <= 2 * r; k++) core = fmin4(core, *reinterpret_cast<const float4*>(q + k * kDilW));
+    zd[0] = fmin4(core, *reinterpret_cast<const float4*>(q));
+    zd[1] = fmin4(core, *reinterpret_cast<const float4*>(q + (2 * r + 1) * kDilW));
+  }
+
+  // 4. shade exactly as compare_kernel does, with the window's z in place of the pixel's own
+  ShadeConsts sc;
+  sc.num = a.sc_num; sc.off = a.sc_off; sc.max_diff = a.max_diff; sc.replace_value = a.replace_value; sc.core = a.fast_div != 0;
+  const bool vec = (W & 3) == 0;
+  bool uncovered = false;                    // BITS: a pixel whose window holds nothing drawn
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    const int py = y0 + ly + i, px = x0 + lx;
+    const bool valid = py < H && px < W;
+    const float zz[4] = {zd[i].x, zd[i].y, zd[i].z, zd[i].w};
+    uint32_t flags4 = 0;
+    if (valid) {
+      const size_t gofs = (size_t)stream * ((size_t)H * W) + (size_t)py * W + px;
+      const int nvalid = min(4, W - px);
+      float s[4];
+      if (vec) {
+        if (U16) {
+          const ushort4 q = *reinterpret_cast<const ushort4*>(reinterpret_cast<const uint16_t*>(a.depth) + gofs);
+          s[0] = u16_to_metres(q.x); s[1] = u16_to_metres(q.y); s[2] = u16_to_metres(q.z); s[3] = u16_to_metres(q.w);
+        } else {
+          const float4 v = load_stream4(a.depth + gofs);
+          s[0] = v.x; s[1] = v.y; s[2] = v.z; s[3] = v.w;
+        }
+      } else {
+        for (int j = 0; j < 4; j++)
+          s[j] = j < nvalid ? (U16 ? u16_to_metres(reinterpret_cast<const uint16_t*>(a.depth)[gofs + j]) : a.depth[gofs + j]) : 0.0f;
+      }
+      float o[4];
+      uint32_t mbits = 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        bool f;
+        o[j] = shade(s[j], zz[j], sc, f);
+        if (zz[j] != zz[j]) { o[j] = 0.0f; f = false; if (BITS && j < nvalid) uncovered = true; }     // GL clear colour
+        if (f) mbits |= (BITS ? 1u : 0xffu) << ((BITS ? 1 : 8) * j);
+      }
+      flags4 = mbits;
+      if (!BITS) {
+        if (vec) {
+          if (U16) store_stream4(reinterpret_cast<uint16_t*>(a.masked) + gofs, metres_to_u16(o[0]), metres_to_u16(o[1]), metres_to_u16(o[2]), metres_to_u16(o[3]));
+          else store_stream4(a.masked + gofs, o[0], o[1], o[2], o[3]);
+          if (a.mask) __builtin_nontemporal_store(mbits, reinterpret_cast<uint32_t*>(a.mask + gofs));
+        } else {
+          for (int j = 0; j < nvalid; j++) {
+            if (U16) reinterpret_cast<uint16_t*>(a.masked)[gofs + j] = (uint16_t)metres_to_u16(o[j]);
+            else a.masked[gofs + j] = o[j];
+            if (a.mask) a.mask[gofs + j] = (uint8_t)(mbits >> (8 * j));
+          }
+        }
+      }
+    }
+    if (BITS) {
+      // as tile_body: 8 neighbouring lanes hold the 32 pixels of one output word; OR their nibbles, the group's first lane stores
+      uint32_t word = flags4 << (4 * (tid & 7));
+      word |= (uint32_t)__shfl_xor((int)word, 1);
+      word |= (uint32_t)__shfl_xor((int)word, 2);
+      word |= (uint32_t)__shfl_xor((int)word, 4);
+      if (valid && (tid & 7) == 0) {
+        const int row_words = (W + 31) >> 5;
+        const size_t wofs = ((size_t)stream * H + (size_t)py) * (size_t)row_words + (size_t)(px >> 5);
+        __builtin_nontemporal_store(word, a.bits + wofs);
+      }
+    }
+  }
+  if (BITS) {
+    const int bin = ((int)blockIdx.z * (int)gridDim.y + (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x;
+    if (__syncthreads_or(uncovered) && tid == 0) a.counters->shard[bin % kCounterShards].uncovered = 1u;
+  }
+}
+
 // A batch's counters (one block per launch group) go to pinned host memory with plain stores from a tiny kernel, one
 // workgroup per block: a hipMemcpyAsync of 8 KB costs a blit launch plus ~10 us of copy-engine set-up on the stream.
 // Every raster lane publishes the blocks of its own groups (first, first + stride, ...) at the end of its part of the batch.
@@ -2775,6 +2928,16 @@ void launch_compare(const CompareArgs& a, hipStream_t st)
   if (blocks == 0) blocks = 1;
   if (a.io_u16) hipLaunchKernelGGL(compare_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
   else hipLaunchKernelGGL(compare_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
+}
+void launch_dilate_compare(const DilateArgs& a, hipStream_t st)
+{
+  const dim3 grid((unsigned)((a.width + kDilW - 1) / kDilW), (unsigned)((a.height + kDilH - 1) / kDilH), (unsigned)a.group_size);
+  const size_t lds = dilate_lds_bytes(a.radius);
+  if (a.bits) {
+    if (a.io_u16) hipLaunchKernelGGL((dilate_compare_kernel<true, true>), grid, dim3(kDilThreads), lds, st, a);
+    else hipLaunchKernelGGL((dilate_compare_kernel<false, true>), grid, dim3(kDilThreads), lds, st, a);
+  } else if (a.io_u16) hipLaunchKernelGGL((dilate_compare_kernel<true, false>), grid, dim3(kDilThreads), lds, st, a);
+  else hipLaunchKernelGGL((dilate_compare_kernel<false, false>), grid, dim3(kDilThreads), lds, st, a);
 }
 
 }  // namespace rtuf

@@ -164,7 +164,7 @@ class FilterParameters:
     def __init__(self, fixed_frame, camera_frame, models, depth_distance_threshold,
                  camera_offset_translation=(0.0, 0.0, 0.0), camera_offset_rotation=(0.0, 0.0, 0.0, 1.0),
                  show_gui=False, filter_replace_value=0.0, use_own_calibration=False,
-                 own_calibration=(585.260, 585.028, 317.387, 239.264)):
+                 own_calibration=(585.260, 585.028, 317.387, 239.264), silhouette_dilation_px=0):
         self.fixed_frame = fixed_frame
         self.camera_frame = camera_frame
         self.models = models                 # list of dicts: model, tf_prefix, geometry_type, [scale], [ignore]
@@ -177,6 +177,8 @@ class FilterParameters:
         # instead of the CameraInfo's P (the reference's hard-coded values by default; they pass through float there)
         self.use_own_calibration = bool(use_own_calibration)
         self.own_calibration = tuple(float(np.float32(v)) for v in own_calibration)
+        # new, beyond the reference: widen the rendered robot by this many pixels, 0 .. 16 (rtuf_params.silhouette_dilation_px)
+        self.silhouette_dilation_px = int(silhouette_dilation_px)
 
     @staticmethod
     def from_dict(d):
@@ -184,7 +186,8 @@ class FilterParameters:
         return FilterParameters(d["fixed_frame"], d["camera_frame"], d.get("models", []), d["depth_distance_threshold"],
                                 off.get("translation", (0.0, 0.0, 0.0)), off.get("rotation", (0.0, 0.0, 0.0, 1.0)),
                                 d.get("show_gui", False), d.get("filter_replace_value", 0.0),
-                                d.get("use_own_calibration", False), d.get("own_calibration", (585.260, 585.028, 317.387, 239.264)))
+                                d.get("use_own_calibration", False), d.get("own_calibration", (585.260, 585.028, 317.387, 239.264)),
+                                d.get("silhouette_dilation_px", 0))
 
 
 class RealtimeURDFFilter:
@@ -205,6 +208,7 @@ class RealtimeURDFFilter:
         self.camera_offset_q_ = tuple(params.camera_offset_rotation)
         self.depth_distance_threshold_ = params.depth_distance_threshold
         self.filter_replace_value_ = params.filter_replace_value
+        self.silhouette_dilation_px_ = params.silhouette_dilation_px
         self.show_gui_ = params.show_gui
         self.far_plane_, self.near_plane_ = 8.0, 0.1         # src/urdf_filter.cpp:53-54
         self.width_ = self.height_ = 0
@@ -248,6 +252,7 @@ class RealtimeURDFFilter:
         p.near_plane, p.far_plane = self.near_plane_, self.far_plane_
         p.depth_distance_threshold = self.depth_distance_threshold_
         p.filter_replace_value = self.filter_replace_value_
+        p.silhouette_dilation_px = self.silhouette_dilation_px_
         if self.two_kernel:
             p.flags |= _capi.FLAG_TWO_KERNEL
         if self._ctx is not None:

@@ -62,6 +62,7 @@ struct RosFilterConfig {
   double depth_distance_threshold = 0.05, filter_replace_value = 0.0;
   bool show_gui = false;               // accepted, ignored: there is no window system behind this back end
   int device = 0;                      // which GPU
+  int silhouette_dilation_px = 0;      // widen the rendered robot by this many pixels, 0 .. 16 (new, beyond the reference)
 };
 // (pointers to members, one per parameter type: RosFilterConfig holds std::strings, so it is not standard-layout and
 // offsetof on it would only be conditionally supported)
@@ -82,6 +83,7 @@ inline const std::vector<RosParamSpec>& ros_param_table()
       {"filter_replace_value", false, nullptr, &RosFilterConfig::filter_replace_value, nullptr, nullptr},
       {"show_gui", false, nullptr, nullptr, &RosFilterConfig::show_gui, nullptr},
       {"device", false, nullptr, nullptr, nullptr, &RosFilterConfig::device},
+      {"silhouette_dilation_px", false, nullptr, nullptr, nullptr, &RosFilterConfig::silhouette_dilation_px},
   };
   return table;
 }
@@ -103,6 +105,7 @@ class RosFilter {
     prm.fixed_frame = cfg.fixed_frame; prm.camera_frame = cfg.camera_frame;
     prm.depth_distance_threshold = cfg.depth_distance_threshold; prm.filter_replace_value = cfg.filter_replace_value;
     prm.show_gui = cfg.show_gui;
+    prm.silhouette_dilation_px = (unsigned)cfg.silhouette_dilation_px;     // (a negative value is out of range like 17: the context refuses it)
     read_camera_offset(prm);
     std::map<std::string, std::string> urdf_by_param;
     read_models(prm, urdf_by_param);
