@@ -40,6 +40,11 @@ alone on the GPU, the whole batch per launch, HIP events over its own timed regi
 carries the per-launch figures of the two-lane run beside it.  `with_host_copies` (never `value`) is the same workload
 with the planes in pinned host memory (upload + kernels + read-back, what the reference's own timer wraps).
 
+A plain run does only what `value` needs: set-up, warm-up, the timed steps, `--dump-outputs`, the line (`value`, `ms_per_step`,
+`step_ms`, `config`, `hbm_frac_end_to_end`).  `--full` adds, after the timed region, everything else the line can carry: `parity`
+and `fk` (the last timed step against the oracle), the one-lane leg and the extra steps behind `roofline`, `kernel_ms_per_step`
+and `rasteriser`, `with_host_copies`, `other_configs` and `cpu_baseline`.  The timed steps and their outputs are the same either way.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -271,6 +276,9 @@ def main():
     ap.add_argument("--near-arm", action="store_true", help="c3 / c4: every stream poses the robot's right forearm 0.1-0.35 m in front of the lens (exact-z pass, near-plane clipping, whole-tile occluders)")
     ap.add_argument("--check-frames", type=int, default=-1, help="frames of the last step verified against the oracle, per rank (-1 = every stream; the oracle runs on all host cores)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (rank 0's streams, float32; a fixed seeded sample of them beyond 64 MB) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run the oracle check, the one-lane roofline leg and stage breakdown, the host-copy "
+                    "legs, the other configs and the CPU baseline (--check-frames, --isolated-seconds, --host-copy-seconds, --other-configs*, --cpu-seconds "
+                    "apply only with --full); off by default: a plain run measures `value` alone")
     args = ap.parse_args()
 
     import torch
@@ -449,7 +457,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- parity on every rank: by default EVERY stream of the last timed step (oracle = checker only) ----------------
+    # ---- parity on every rank (--full): by default EVERY stream of the last timed step (oracle = checker only) ----------
     from oracle import bindings as O
     from realtime_urdf_filter_amd.filter import depth_f32_to_u16, depth_u16_to_f32
     host_threads = len(os.sched_getaffinity(0))
@@ -464,15 +472,17 @@ def main():
     d_masked, d_mask = d_masked_set[k_last % n_sets], d_mask_set[k_last % n_sets]
     link_dev = cam_dev = None
     fk_err = None
-    if not args.host_poses:
+    if args.full and not args.host_poses:
         # the oracle is fed the very matrices the GPU's forward kinematics produced
         link_dev, cam_dev = ctx.read_poses(n, share.n_links_total)
         fk_err = share.host_fk_error(k_last, link_dev, cam_dev)
-    n_check = n if args.check_frames < 0 else min(args.check_frames, n)
+    n_check = (n if args.check_frames < 0 else min(args.check_frames, n)) if args.full else 0
     check = sorted(set(int(x) for x in np.linspace(0, n - 1, num=n_check))) if n_check > 0 else []
-    h_masked_all = d_masked.cpu().numpy()
-    h_mask_all = d_mask.cpu().numpy() if d_mask is not None else None
-    h_depth_all = d_depth[v_last].cpu().numpy()
+    # (a plain run reads the outputs back only to dump them)
+    read_back = args.full or (rank == 0 and args.dump_outputs)
+    h_masked_all = d_masked.cpu().numpy() if read_back else None
+    h_mask_all = d_mask.cpu().numpy() if read_back and d_mask is not None else None
+    h_depth_all = d_depth[v_last].cpu().numpy() if args.full else None
 
     def fetch(s):
         hm, hd = h_masked_all[s], h_depth_all[s]
@@ -529,7 +539,36 @@ def main():
         px = W * H
         two = args.two_kernel
         mask_b = 0 if args.no_mask else 1
+        peak = 8000.0
+        out = {
+            "metric": "filtered depth frames/sec (640x480, PR2 URDF)",
+            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "timed_steps": timed_steps, "min_seconds": args.min_seconds, "timed_seconds": elapsed,
+            "ms_per_step": elapsed / max(timed_steps, 1) * 1e3, "higher_is_better": True, "scaling": share.scaling, "vs_baseline": None,
+            "step_ms": step_ms,
+            "dtype": "f32", "data": "synthetic", "depth_format": "16UC1" if args.u16 else "32FC1", "full": args.full,
+            "config": {"workload": share.describe(), "distinct_joint_states_per_stream": V, "distinct_sensor_plane_sets": VD,
+                       "streams_per_gpu": n if share.scaling == "weak" else [x["streams"] for x in per_rank], "streams_total": sum(x["streams"] for x in per_rank),
+                       "poses": "host matrices" if args.host_poses else "joint positions, forward kinematics on the GPU", "mode": "two-kernel" if two else "fused", "mask_output": (not args.no_mask),
+                       "parallelism": ("stream-sharded x%d" % world) + (" (shares of a %d-GPU job)" % job_world if args.shard_of else ""), "pipelines_per_gpu": P,
+                       "raster_lanes": lanes, "lanes_side_by_side": bool(st["lanes_side_by_side"]), "launch_groups_per_batch": groups_per_batch, "streams_per_launch_group": st["launch_group"],
+                       "host_threads_pinned_to_gpu_numa_node": pinned_cpus},
+            "per_stream_fps": value / max(sum(x["streams"] for x in per_rank), 1),
+            "collectives": ({"backend": "rccl (torch.distributed nccl)" if backend == "nccl" else backend, "world": world,
+                             "used_for": "barriers around the timed region, MAX all-reduce of the repetition count and the elapsed time, all-gather of per-rank frame and parity counts; no data-path collective"}
+                            if dist is not None else None),
+            "device_memory_bytes": st["device_bytes"],
+        }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        # the whole path against the HBM roofline: algorithmic bytes of a frame (fused: sensor read + masked write + mask write;
+        # two-kernel: + the z-surface written and read) x frames/s over all GPUs / (GPUs x 8 TB/s)
+        bytes_per_frame = (((4 if args.u16 else 8) + mask_b) + (8 if two else 0)) * px
+        out["hbm_frac_end_to_end"] = {"value": value * bytes_per_frame / (world * peak * 1e9), "bytes_per_frame": bytes_per_frame, "peak_GB_per_s_per_gpu": peak, "n_gpus": world,
+                                      "note": "value x algorithmic bytes per frame / (n_gpus x 8 TB/s): pose, cull, set-up, clip and tile kernels of a step all inside it"}
 
+    # ---- --full: everything else the line carries, after the timed region (rank 0; the other ranks wait at the closing barrier)
+    if rank == 0 and args.full:
         def fresh_share():
             return CF.build(args.workload, job_world, rank, streams=args.streams, triangles=args.triangles, variants=max(1, args.variants),
                             width=args.width, height=args.height, urdfs=args.urdfs, near_arm=args.near_arm, host_fk=False)
@@ -636,7 +675,6 @@ def main():
             kernels["tile_kernel<fused>"] = ("raster", ((4 if args.u16 else 8) + mask_b) * px, "hbm")
         kernels["setup_kernel"] = ("setup", None, "valu-issue (triangle set-up: neither HBM nor MFMA, SURVEY.md 8d); HBM figure for context")
         kernels["clip_kernel"] = ("clip", 0, "latency / divergent scalar code at LDS-limited occupancy; no algorithmic HBM traffic of its own (the time covers clip_kernel and bigrec_kernel, which appends the many-tile records both set-up and clip kernel listed)")
-        peak = 8000.0
         # Off-line counter data of this same command (rocprofv3 --pmc passes cannot run inside the timed region):
         # used only when the committed measurement is of this exact workload AND launch shape, and labelled as such.
         default_cmd = (args.workload == "c3" and n == 256 and (W, H) == (640, 480) and not args.no_mask and not args.u16 and args.triangles == 250000 and not args.near_arm and not args.host_poses)
@@ -745,23 +783,7 @@ def main():
         if iso_leg is not None:
             roof["one_lane_leg"] = {"frames_per_s": iso_leg["frames_per_s"], "steps": iso_leg["steps"], "seconds": iso_leg["seconds"], "device_memory_bytes": iso_leg["device_memory_bytes"],
                                     "note": "the same workload through a context of ONE raster lane (kernels one after the other, bins for the whole batch): what the headline figure would be without the lanes' overlap"}
-        out = {
-            "metric": "filtered depth frames/sec (640x480, PR2 URDF)",
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "timed_steps": timed_steps, "min_seconds": args.min_seconds, "timed_seconds": elapsed,
-            "ms_per_step": elapsed / max(timed_steps, 1) * 1e3, "higher_is_better": True, "scaling": share.scaling, "vs_baseline": None,
-            "step_ms": step_ms,
-            "dtype": "f32", "data": "synthetic", "depth_format": "16UC1" if args.u16 else "32FC1",
-            "config": {"workload": share.describe(), "distinct_joint_states_per_stream": V, "distinct_sensor_plane_sets": VD,
-                       "streams_per_gpu": n if share.scaling == "weak" else [x["streams"] for x in per_rank], "streams_total": sum(x["streams"] for x in per_rank),
-                       "poses": "host matrices" if args.host_poses else "joint positions, forward kinematics on the GPU", "mode": "two-kernel" if two else "fused", "mask_output": (not args.no_mask),
-                       "parallelism": ("stream-sharded x%d" % world) + (" (shares of a %d-GPU job)" % job_world if args.shard_of else ""), "pipelines_per_gpu": P,
-                       "raster_lanes": lanes, "lanes_side_by_side": bool(st["lanes_side_by_side"]), "launch_groups_per_batch": groups_per_batch, "streams_per_launch_group": st["launch_group"],
-                       "host_threads_pinned_to_gpu_numa_node": pinned_cpus},
-            "per_stream_fps": value / max(sum(x["streams"] for x in per_rank), 1),
-            "collectives": ({"backend": "rccl (torch.distributed nccl)" if backend == "nccl" else backend, "world": world,
-                             "used_for": "barriers around the timed region, MAX all-reduce of the repetition count and the elapsed time, all-gather of per-rank frame and parity counts; no data-path collective"}
-                            if dist is not None else None),
+        out.update({
             "kernel_ms_per_step": dict(breakdown, note="stage breakdown from %d extra steps after the timed region on the %s: one batch in flight, every stage bracketed by HIP events (ms_setup there = cull + set-up + clip + many-tile kernels)" % (extra, "one-lane context" if iso_leg is not None else "headline context")),
             "rasteriser": {"triangles_per_s": float(share.triangles_per_stream().sum()) / (src_ms["setup"] * 1e-3) * (launch_streams / n) if src_ms["setup"] > 0 else None,
                            "binned_triangles_per_s": st["triangles_binned"] / (src_ms["raster"] * 1e-3) * (launch_streams / n) if src_ms["raster"] > 0 else None,
@@ -772,21 +794,13 @@ def main():
                                      "note": "work item = one set-up workgroup: a chunk of <= 256 triangles x up to 3 streams whose frustum its box touches; zero-survivor = none of its triangles reached a bin or the clip list's survivors (sub-pixel or outside)"},
                            "tile": {"cover_tiles": st["cover_tiles"], "occluded_entries": st["occluded_entries"], "exact_z_tiles": st["exact_tiles"],
                                     "tiles_per_launch": int(round(n / groups_per_batch)) * ((W + 63) // 64) * ((H + 31) // 32), "overdraw": overdraw}},
-            "device_memory_bytes": st["device_bytes"],
             "roofline": roof,
             "parity": {"frames_checked": checked_total, "mismatching_values": bad_total, "mask_mismatch_pixels": bad_mask, "depth_mismatch_pixels": bad_depth,
                        "per_rank": per_rank, "oracle_threads": threads, "seconds": t_par,
                        "note": "every rank checks --check-frames streams (default: all) of its LAST TIMED step against the oracle, which runs on the host cores; mask/depth split is rank 0's"},
-        }
+        })
         if fk_err is not None:
             out["fk"] = {"on_device": True, "max_abs_diff_vs_host_fk": fk_err}
-        if dumped is not None:
-            out["dumped_outputs"] = dumped
-        # the whole path against the HBM roofline: algorithmic bytes of a frame (fused: sensor read + masked write + mask write;
-        # two-kernel: + the z-surface written and read) x frames/s over all GPUs / (GPUs x 8 TB/s)
-        bytes_per_frame = (((4 if args.u16 else 8) + mask_b) + (8 if two else 0)) * px
-        out["hbm_frac_end_to_end"] = {"value": value * bytes_per_frame / (world * peak * 1e9), "bytes_per_frame": bytes_per_frame, "peak_GB_per_s_per_gpu": peak, "n_gpus": world,
-                                      "note": "value x algorithmic bytes per frame / (n_gpus x 8 TB/s): pose, cull, set-up, clip and tile kernels of a step all inside it"}
         # ---- the whole path with the planes in host memory (the reference's own timer wraps upload + render + read-back,
         # src/urdf_filter.cpp:211-244, :332-353, :729-735).  Never `value`. ----------------------------------------------
         if world == 1 and args.host_copy_seconds > 0 and P == 1 and not two and not args.no_mask:
@@ -932,6 +946,7 @@ def main():
             except Exception as e:      # noqa: BLE001 - a missing Mesa must not cost the bench line
                 cb["reference_llvmpipe_live"] = {"error": repr(e)}
             out["cpu_baseline"] = cb
+    if rank == 0:
         print(json.dumps(out))
     for c in ctxs:
         c.close()

@@ -6,7 +6,7 @@
 here="$(cd "$(dirname "$0")/.." && pwd)"
 src=$here/realtime_urdf_filter_amd/csrc
 mkdir -p $here/realtime_urdf_filter_amd/lib/variants
-Q="--cpu-seconds 0 --host-copy-seconds 0 --min-seconds ${SECONDS_EACH:-2} --check-frames ${CHECK:-8} --isolated-seconds 1.5"
+Q="--full --cpu-seconds 0 --host-copy-seconds 0 --min-seconds ${SECONDS_EACH:-2} --check-frames ${CHECK:-8} --isolated-seconds 1.5"
 [ -n "$LANES" ] && Q="$Q --lanes $LANES"
 line() { python -c "
 import sys,json

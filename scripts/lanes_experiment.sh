@@ -3,7 +3,7 @@ src=$here/realtime_urdf_filter_amd/csrc
 mkdir -p $here/realtime_urdf_filter_amd/lib/variants
 lib=$here/realtime_urdf_filter_amd/lib/variants/librtuf_lanes6.so
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -I$here/include -I$src -Wno-unused-value -Wno-unused-result -DRTUF_MAX_LANES=6 $src/rtuf_kernels.hip $src/rtuf_api.cpp -o $lib || exit 1
-Q="--cpu-seconds 0 --host-copy-seconds 0 --min-seconds 3 --check-frames 8 --isolated-seconds 0 --other-configs off"
+Q="--full --cpu-seconds 0 --host-copy-seconds 0 --min-seconds 3 --check-frames 8 --isolated-seconds 0 --other-configs off"
 line() { python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 root=$PWD
 out=$root/gpurun_out/profiles
 rm -rf $out; mkdir -p $out
-B="python $root/bench.py"
+B="python $root/bench.py --full"     # every line with all its legs; the plain run is timed once below
 # The counters and the per-kernel trace are taken on the ONE-LANE launch shape (--lanes 1: every kernel alone on the GPU, the
 # whole batch per launch): that is what bench.py's `roofline` describes (its one-lane leg); the default context overlaps the
 # kernels of several launch groups, whose per-launch times describe no single kernel (traced too, as *_default_lanes).
@@ -19,8 +19,11 @@ PROF_ARGS="--steps 20 --min-seconds 0 --cpu-seconds 0 --check-frames 0 --lanes 1
 Q="--cpu-seconds 0 --host-copy-seconds 0 --min-seconds 3"       # the side lines: no CPU legs, no host-plane legs, 3 s timed
 $B $Q > /dev/null 2> $out/bench.err      # first run on a fresh box is the slowest: warm-up
 t0=$(date +%s.%N)
-$B > $out/${tag}_bench.json 2>> $out/bench.err                   # THE line: defaults, exactly what the driver runs
-echo "python bench.py (defaults, second run on this box): $(python -c "print(round($(date +%s.%N) - $t0, 1))") s wall" > $out/${tag}_bench_wall_time.txt
+$B > $out/${tag}_bench.json 2>> $out/bench.err                   # THE line: defaults, every leg
+echo "python bench.py --full (defaults, second run in a row): $(python -c "print(round($(date +%s.%N) - $t0, 1))") s wall" > $out/${tag}_bench_wall_time.txt
+t0=$(date +%s.%N)
+python $root/bench.py > $out/${tag}_bench_plain.json 2>> $out/bench.err          # the plain run: the headline alone
+echo "python bench.py (plain, defaults): $(python -c "print(round($(date +%s.%N) - $t0, 1))") s wall" >> $out/${tag}_bench_wall_time.txt
 $B $Q --lanes 1 > $out/${tag}_bench_one_lane.json 2>> $out/bench.err
 $B $Q --lanes 2 > $out/${tag}_bench_two_lanes.json 2>> $out/bench.err
 $B $Q --launch-group 43 > $out/${tag}_bench_groups_of_43.json 2>> $out/bench.err
@@ -37,7 +40,7 @@ $B $Q --host-poses > $out/${tag}_bench_host_poses.json 2>> $out/bench.err
 $B $Q --workload c4 --shard-of 8 --steps 50 > $out/${tag}_bench_c4_share.json 2>> $out/bench.err
 $B $Q --workload c5 --shard-of 8 --steps 30 > $out/${tag}_bench_c5_share.json 2>> $out/bench.err
 $B $Q --near-arm --steps 40 > $out/${tag}_bench_near_arm.json 2>> $out/bench.err      # every stream: forearm 0.1-0.35 m in front of the lens
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29561 $root/bench.py --gpus 1 $Q 2>> $out/bench.err | grep '^{' | tail -1 > $out/${tag}_bench_rccl_world1.json      # (RCCL prints its banner on stdout)
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29561 $root/bench.py --gpus 1 --full $Q 2>> $out/bench.err | grep '^{' | tail -1 > $out/${tag}_bench_rccl_world1.json      # (RCCL prints its banner on stdout)
 python $root/scripts/clip_stress.py > $out/${tag}_clip_stress.txt 2>> $out/bench.err
 bash $root/scripts/overdraw.sh > $out/overdraw.json 2>> $out/bench.err
 python $root/scripts/host_planes_rate.py > $out/${tag}_host_planes.json 2>> $out/bench.err

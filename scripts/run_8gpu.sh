@@ -8,7 +8,7 @@ N=${1:-$(python -c 'import torch; print(torch.cuda.device_count())')}
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 # 1. Python host: one process per GPU over torch.distributed (backend "nccl" = RCCL), the three BASELINE configs
 for wl in c3 c4 c5; do
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus "$N" --workload $wl --cpu-seconds 0
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus "$N" --workload $wl --full --cpu-seconds 0
 done
 # 2. C++ host: one process, one thread + one rtuf_context per GPU (include/realtime_urdf_filter_amd/multi_gpu.hpp), both
 #    partitions, masks gathered peer to peer over xGMI (falls back to RCCL, and says so, where a pair has no peer access)

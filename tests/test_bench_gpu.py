@@ -1,6 +1,7 @@
-"""GPU (-m gpu): bench.py's contract on a small workload -- one JSON line with the fields the driver reads,
-parity reported as zero mismatches, and the multi-rank path (one process per rank, barrier + MAX all-reduce of
-the elapsed time) rehearsed with two ranks sharing the one GPU of the test box over gloo."""
+"""GPU (-m gpu): bench.py's contract on a small workload -- one JSON line with the fields the driver reads (a plain run:
+the headline alone; --full: also parity reported as zero mismatches, roofline, CPU baseline and the other legs), and the
+multi-rank path (one process per rank, barrier + MAX all-reduce of the elapsed time) rehearsed with two ranks sharing the
+one GPU of the test box over gloo."""
 import json
 import os
 import subprocess
@@ -11,10 +12,11 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "3", "--warmup", "1", "--streams", "8", "--triangles", "8000", "--cpu-seconds", "0.5", "--check-frames", "2",
+SMALL = ["--full", "--steps", "3", "--warmup", "1", "--streams", "8", "--triangles", "8000", "--cpu-seconds", "0.5", "--check-frames", "2",
          "--min-seconds", "0.5", "--isolated-seconds", "0.3", "--host-copy-seconds", "0.3"]
 REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config", "roofline", "cpu_baseline"]
+FULL_ONLY = ["parity", "fk", "roofline", "kernel_ms_per_step", "rasteriser", "with_host_copies", "other_configs", "cpu_baseline"]
 
 
 def last_json(out):
@@ -50,12 +52,28 @@ def test_bench_line_contract():
     assert cb["all_cores"]["cores"] >= 1 and cb["all_cores"]["value"] > 0
 
 
+def test_plain_bench_line():
+    """Without --full the run ends with the timed region: the headline's fields and nothing that needs the oracle or a
+    leg of its own, even where the options that size those legs are given."""
+    args = ["--steps", "3", "--warmup", "1", "--streams", "8", "--triangles", "8000", "--cpu-seconds", "0.5", "--isolated-seconds", "0.3",
+            "--host-copy-seconds", "0.3", "--other-configs", "on", "--other-configs-seconds", "0.3"]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = last_json(r.stdout)
+    for k in REQUIRED:
+        assert k in d or k in FULL_ONLY, k
+    assert d["full"] is False and [k for k in FULL_ONLY if k in d] == []
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["timed_steps"] == 3 and d["higher_is_better"] is True and d["unit"] == "frames/s"
+    assert d["value"] > 0 and abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["config"]["raster_lanes"] == 3 and d["step_ms"]["median"] > 0 and 0 < d["hbm_frac_end_to_end"]["value"] < 1
+
+
 def test_bench_line_carries_the_other_baseline_configs():
-    """`other_configs` (the driver's default command runs them at full size; here the same legs at the tests' sizes): BASELINE
+    """`other_configs` (`--full` runs them at full size with the default command; here the same legs at the tests' sizes): BASELINE
     config 2 (one camera: frames/s and the latency of one frame in flight), config 3 with the forearm in front of every lens,
     rank 0's shares of configs 4 (64 x 720p, robot + walls) and 5 (8 URDFs x 128 cameras) -- each with frames/s, memory, the
     tile kernel's launch time on a one-lane context and 8 streams (or all) against the oracle."""
-    args = ["--steps", "3", "--warmup", "1", "--streams", "8", "--triangles", "8000", "--cpu-seconds", "0", "--check-frames", "2", "--min-seconds", "0.2",
+    args = ["--full", "--steps", "3", "--warmup", "1", "--streams", "8", "--triangles", "8000", "--cpu-seconds", "0", "--check-frames", "2", "--min-seconds", "0.2",
             "--isolated-seconds", "0.2", "--host-copy-seconds", "0", "--other-configs", "on", "--other-configs-seconds", "0.3"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -76,7 +94,7 @@ def test_bench_line_carries_the_other_baseline_configs():
 def test_bench_line_with_split_batches_and_every_stream_checked():
     """64 streams: the headline context splits every batch into three launch groups, one per raster lane; by default every
     stream of the last timed step is checked against the oracle."""
-    args = ["--steps", "3", "--warmup", "1", "--streams", "64", "--triangles", "8000", "--width", "320", "--height", "192", "--cpu-seconds", "0",
+    args = ["--full", "--steps", "3", "--warmup", "1", "--streams", "64", "--triangles", "8000", "--width", "320", "--height", "192", "--cpu-seconds", "0",
             "--min-seconds", "0.3", "--isolated-seconds", "0.2", "--host-copy-seconds", "0"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -138,7 +156,7 @@ def test_bench_two_ranks_rehearsal_config4_and_config5():
     """The two 8-GPU configs of BASELINE.json run multi-rank through bench.py: c4 block-partitions a fixed total of
     streams (sharding.shard_range), c5 puts URDF m on rank m % N (sharding.models_for_rank); rank 0 sums the frames,
     MAX-reduces the time and gathers every rank's parity counts."""
-    base = ["--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--check-frames", "2", "--min-seconds", "0"]
+    base = ["--full", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--check-frames", "2", "--min-seconds", "0"]
     d = _two_ranks(base + ["--workload", "c4", "--streams", "7", "--triangles", "8000", "--width", "320", "--height", "192"], 29534)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["streams_per_gpu"] == [4, 3] and d["config"]["streams_total"] == 7
     assert d["config"]["workload"].startswith("C4") and "wall" in d["config"]["workload"]
@@ -152,7 +170,7 @@ def test_bench_two_ranks_rehearsal_config4_and_config5():
 
 def test_bench_min_seconds_floor_and_per_gpu_share_flag():
     """--min-seconds repeats the --steps steps (whole multiples); --shard-of runs rank 0's share of a larger job."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--check-frames", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--check-frames", "1",
                         "--min-seconds", "0.2", "--isolated-seconds", "0", "--host-copy-seconds", "0", "--workload", "c4", "--shard-of", "8", "--streams", "16", "--triangles", "8000", "--width", "320", "--height", "192"],
                        capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -167,18 +185,22 @@ def test_bench_dump_outputs_same_on_every_run(tmp_path):
     """--dump-outputs: what the timed path returned for its last step (masked depth + its NaN / inf classes + mask of every
     stream, finite float32) is the same, bit for bit, whether the --steps steps run once -- the default: a command line
     without --min-seconds times exactly --steps steps -- or are repeated to fill --min-seconds: the last step's inputs do
-    not depend on the repetitions."""
+    not depend on the repetitions.  The plain run's dump is the --full run's, whose every stream matches the oracle."""
     base = ["--steps", "5", "--warmup", "1", "--streams", "8", "--triangles", "8000", "--width", "320", "--height", "192", "--cpu-seconds", "0",
             "--isolated-seconds", "0", "--host-copy-seconds", "0"]
     files = ["mask.npy", "masked_depth.npy", "masked_depth_nonfinite.npy", "streams.npy"]
     dumps = []
-    for name, floor in (("once", []), ("repeated", ["--min-seconds", "0.3"])):
+    for name, floor in (("once", []), ("repeated", ["--min-seconds", "0.3", "--full"])):
         out_dir = str(tmp_path / name)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + base + floor + ["--dump-outputs", out_dir],
                            capture_output=True, text=True, cwd=ROOT, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         d = last_json(r.stdout)
-        assert d["steps"] == 5 and d["parity"]["frames_checked"] == 8 and d["parity"]["mismatching_values"] == 0
+        assert d["steps"] == 5 and d["full"] == bool(floor)
+        if floor:
+            assert d["parity"]["frames_checked"] == 8 and d["parity"]["mismatching_values"] == 0
+        else:
+            assert "parity" not in d
         assert d["timed_steps"] == 5 if not floor else (d["timed_steps"] % 5 == 0 and d["timed_steps"] > 5)
         assert abs(d["ms_per_step"] - d["timed_seconds"] / d["timed_steps"] * 1e3) < 1e-9 * d["ms_per_step"]
         assert d["dumped_outputs"]["files"] == files
