@@ -13,11 +13,13 @@
 #pragma once
 
 #include <cmath>
+#include <map>
 #include <cstdio>
 #include <memory>
 #include <stdexcept>
 #include <string>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "../rtuf.h"
@@ -38,6 +40,7 @@ struct Renderable {
   virtual ~Renderable() = default;
   void setLinkName(std::string n) { name = std::move(n); }
   std::string name;
+  std::string urdf_link;                        // the URDF link's own name (`name` carries the tf prefix): its label's key
   Transform link_offset;
   Transform link_to_fixed;
   std::vector<rtuf_host::DrawCall> draws;       // what render() hands to the GPU
@@ -130,6 +133,7 @@ class URDFRenderer {
           break;
       }
       r->setLinkName(tf_prefix_ + "/" + link.name);
+      r->urdf_link = link.name;
       r->link_offset = rtuf_host::pose_to_transform(it.xyz, it.rpy);
       renderables_.push_back(r);
     }
@@ -168,6 +172,9 @@ struct FilterParameters {
   double own_calibration[4] = {585.260, 585.028, 317.387, 239.264};      // fx fy cx cy
   // New, beyond the reference: widen the rendered robot by this many pixels, 0 .. 16 (rtuf_params.silhouette_dilation_px)
   unsigned silhouette_dilation_px = 0;
+  // New, beyond the reference: also produce the link label plane (include/rtuf.h, LINK LABELS; getLabels(), linkLabels()).
+  // Off by default: filter() then costs what it did.  Not together with silhouette_dilation_px > 0.
+  bool link_labels = false;
 };
 
 // ---- urdf_filter.h --------------------------------------------------------------------------
@@ -178,7 +185,8 @@ class RealtimeURDFFilter {
       : tf_(tf), fixed_frame_(params.fixed_frame), cam_frame_(params.camera_frame), show_gui_(params.show_gui),
         depth_distance_threshold_(params.depth_distance_threshold), filter_replace_value_(params.filter_replace_value),
         silhouette_dilation_px_(params.silhouette_dilation_px),
-        params_(params), param_server_(std::move(param_server)), device_(device), resolve_(resolve), resolve_user_(resolve_user)
+        params_(params), param_server_(std::move(param_server)), device_(device), resolve_(resolve), resolve_user_(resolve_user),
+        want_labels_(params.link_labels)
   {
   }
   ~RealtimeURDFFilter() { if (ctx_) rtuf_destroy(ctx_); }
@@ -237,6 +245,20 @@ class RealtimeURDFFilter {
       model_ids_.push_back(m);
     }
     check(rtuf_finalize_models(ctx_));
+    // one label per URDF link, numbered from 1 over the models in order; every renderable of a link shares it, links on a
+    // model's ignore list have no renderable and no label
+    link_labels_.clear();
+    for (size_t i = 0; i < renderers_.size(); i++) {
+      std::vector<uint16_t> lab;
+      for (const auto& r : renderers_[i]->renderables_) {
+        auto key = std::make_pair((int)i, r->urdf_link);
+        auto it = link_labels_.find(key);
+        if (it == link_labels_.end()) it = link_labels_.emplace(key, (uint16_t)(link_labels_.size() + 1)).first;
+        lab.push_back(it->second);
+      }
+      if (want_labels_ && !lab.empty()) check(rtuf_set_link_labels(ctx_, model_ids_[i], lab.data(), (int)lab.size()));
+    }
+    labels_.assign(want_labels_ ? (size_t)width_ * height_ : 0, 0);
     masked_depth_ = nullptr;
     mask_ = nullptr;
   }
@@ -258,9 +280,64 @@ class RealtimeURDFFilter {
   void render(const double* camera_projection_matrix, double timestamp = 0.0)
   {
     if (!ctx_ || !stage_frame(camera_projection_matrix, timestamp)) return;
+    if (want_labels_) {
+      // the single-stream call has no label form: the same frame through the labelled batch call into the façade's planes
+      const size_t px = (size_t)width_ * height_;
+      own_masked_.resize(px);
+      own_mask_.resize(need_mask_ ? px : 0);
+      const float* in = reinterpret_cast<const float*>(pending_buffer_);
+      float* out = own_masked_.data();
+      uint8_t* km = need_mask_ ? own_mask_.data() : nullptr;
+      uint16_t* lab = labels_.data();
+      check(rtuf_filter_batch_labels(ctx_, 1, &in, &out, need_mask_ ? &km : nullptr, &lab));
+      masked_depth_ = own_masked_.data();
+      if (need_mask_) mask_ = own_mask_.data();
+      return;
+    }
     check(rtuf_filter(ctx_, pending_buffer_, nullptr, width_, height_));
     masked_depth_ = rtuf_get_masked_depth(ctx_);
     if (need_mask_) mask_ = rtuf_get_mask(ctx_);
+  }
+
+  // Link labels (FilterParameters::link_labels): the label plane of the last frame (width x height, row 0 first; 0 = the
+  // background quad or nothing drawn; empty while labels are off), and the label of every (model index, URDF link name).
+  const std::vector<uint16_t>& getLabels() const { return labels_; }
+  const std::map<std::pair<int, std::string>, uint16_t>& linkLabels() const { return link_labels_; }
+
+  // filter_into with the link label plane as well (labels_out: width x height uint16; needs FilterParameters::link_labels and
+  // a masked_out).  The plane is also kept for getLabels().
+  bool filter_into(const void* depth, bool is_16uc1, double* glTf, int width, int height, double timestamp, void* masked_out, uint8_t* mask_out,
+                   uint16_t* labels_out)
+  {
+    prepare(width, height);
+    if (!want_labels_ || !masked_out || !labels_out) throw std::runtime_error("filter_into with labels: needs FilterParameters::link_labels and masked_out");
+    if (renderers_.empty() || !stage_frame(glTf, timestamp)) return false;
+    const size_t px = (size_t)width_ * height_;
+    const void* in = depth;
+    if (is_16uc1 && (width_ & 3) != 0) {
+      // (the 16UC1 kernels need a width that is a multiple of 4: the reference's two conversions on the host, as filter_into does)
+      scratch_in_.resize(px);
+      scratch_out_.resize(px);
+      for (size_t i = 0; i < px; i++) scratch_in_[i] = (float)static_cast<const uint16_t*>(depth)[i] * 0.001f;
+      const float* fin = scratch_in_.data();
+      float* fout = scratch_out_.data();
+      check(rtuf_filter_batch_labels(ctx_, 1, &fin, &fout, mask_out ? &mask_out : nullptr, &labels_out));
+      uint16_t* o = static_cast<uint16_t*>(masked_out);
+      for (size_t i = 0; i < px; i++) {
+        const float v = fout[i] * 1000.0f;
+        long q = 0;
+        if (v >= -2147483648.0f && v < 2147483648.0f) q = std::lrintf(v);
+        o[i] = (uint16_t)(q < 0 ? 0 : (q > 65535 ? 65535 : q));
+      }
+    } else if (is_16uc1) {
+      check(rtuf_filter_batch_u16_labels(ctx_, 1, reinterpret_cast<const uint16_t* const*>(&in), reinterpret_cast<uint16_t* const*>(&masked_out),
+                                         mask_out ? &mask_out : nullptr, &labels_out));
+    } else {
+      check(rtuf_filter_batch_labels(ctx_, 1, reinterpret_cast<const float* const*>(&in), reinterpret_cast<float* const*>(&masked_out),
+                                     mask_out ? &mask_out : nullptr, &labels_out));
+    }
+    labels_.assign(labels_out, labels_out + px);
+    return true;
   }
 
   // ---- beyond the reference's surface: what a ROS adapter needs to leave the CPU out of the pixel path ----------------
@@ -399,6 +476,11 @@ class RealtimeURDFFilter {
   unsigned char* pending_buffer_ = nullptr;
   std::vector<uint32_t> bits_;
   std::vector<float> scratch_in_, scratch_out_;      // filter_into for widths that are not a multiple of 4
+  bool want_labels_;                                 // FilterParameters::link_labels
+  std::vector<uint16_t> labels_;                     // label plane of the last frame (getLabels)
+  std::map<std::pair<int, std::string>, uint16_t> link_labels_;
+  std::vector<float> own_masked_;                    // render() with labels: the outputs the library-owned planes hold otherwise
+  std::vector<uint8_t> own_mask_;
 };
 
 }  // namespace realtime_urdf_filter

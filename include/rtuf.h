@@ -347,6 +347,33 @@ enum {
 };
 int rtuf_batch_status_device(rtuf_context *ctx, const uint32_t **d_status);
 
+/* LINK LABELS.  New, beyond the reference: which robot link every pixel shows, as a uint16_t plane [n][H][W] (row 0 first)
+ * beside the masked depth.  A pixel's label is the label of the link whose fragment won its depth test -- GL_LESS on the
+ * 24-bit depth, ties going to the earlier draw: exactly the winner the planes are shaded with.  Label 0: the background
+ * quad won, or nothing was drawn.  The label does not depend on the sensor plane or the threshold; combine it with the mask
+ * (mask 255 with label 0 = filtered by the background quad, i.e. the sensor reads beyond the far plane).
+ * Default labels: link l of model m is 1 + link_base(m) + l, where link_base(m) counts the links of the models added before m
+ * (the order rtuf_add_model / rtuf_add_link create them in).  A context with more than 65535 links fails the label calls with
+ * RTUF_ERR_CAPACITY unless rtuf_set_link_labels has given labels to the models whose defaults would not fit.
+ * rtuf_set_link_labels overrides the labels of one model's links (n_links = rtuf_num_links(model)): any value, 0 ("do not
+ * label this link") and values shared by several links (grouping) included.  It waits for the batches in flight.
+ * The label calls take the arguments of their counterparts plus the label planes (device: [n][H][W], 8-byte aligned; host:
+ * one width*height plane per stream, never NULL) and write masked / mask bit for bit as the counterparts do, mask may be NULL.
+ * Both RTUF_FLAG_TWO_KERNEL settings, any number of raster lanes and pipelines; re-runs after a bin regrowth rewrite the
+ * labels with the planes, and the status word (rtuf_batch_status_device) covers the label plane with the same meaning.
+ * Not supported yet: silhouette_dilation_px > 0 (RTUF_ERR_INVALID).  There are no label forms of the mask-bits calls or of
+ * the asynchronous host-plane calls; the host-plane label calls are synchronous.  The draw-order -> label table they use
+ * (2 bytes per triangle) is allocated by the first label call or rtuf_set_link_labels. */
+int rtuf_set_link_labels(rtuf_context *ctx, int model, const uint16_t *labels, int n_links);
+int rtuf_filter_batch_device_labels(rtuf_context *ctx, int n_streams, const float *d_depth, float *d_masked, uint8_t *d_mask,
+                                    uint16_t *d_labels);
+int rtuf_filter_batch_device_u16_labels(rtuf_context *ctx, int n_streams, const uint16_t *d_depth_mm, uint16_t *d_masked_mm,
+                                        uint8_t *d_mask, uint16_t *d_labels);
+int rtuf_filter_batch_labels(rtuf_context *ctx, int n_streams, const float *const *depth_in, float *const *masked_out,
+                             uint8_t *const *mask_out, uint16_t *const *labels_out);
+int rtuf_filter_batch_u16_labels(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in,
+                                 uint16_t *const *masked_mm_out, uint8_t *const *mask_out, uint16_t *const *labels_out);
+
 /* Counters of the last batch and kernel timings measured with HIP events on the context's
  * stream (replaces the wall-clock statistics of src/urdf_filter.cpp:239-266). */
 typedef struct {

@@ -33,6 +33,8 @@ SYMBOLS = [
     "rtuf_filter_batch_async", "rtuf_filter_batch_u16_async", "rtuf_wait_oldest", "rtuf_host_alloc", "rtuf_host_free",
     "rtuf_mask_bits_words", "rtuf_filter_batch_bits_async", "rtuf_filter_batch_bits_u16_async", "rtuf_filter_batch_device_bits",
     "rtuf_filter_batch_device_bits_u16", "rtuf_expand_mask_bits", "rtuf_order_stream_after_batches", "rtuf_batch_status_device",
+    "rtuf_set_link_labels", "rtuf_filter_batch_device_labels", "rtuf_filter_batch_device_u16_labels", "rtuf_filter_batch_labels",
+    "rtuf_filter_batch_u16_labels",
 ]
 
 
@@ -171,6 +173,11 @@ def load_library(path=None):
     lib.rtuf_expand_mask_bits.argtypes = [vp, ci, vp, ci, ci, ctypes.c_float, vp, vp]
     lib.rtuf_order_stream_after_batches.argtypes = [vp, vp]
     lib.rtuf_batch_status_device.argtypes = [vp, ctypes.POINTER(vp)]
+    lib.rtuf_set_link_labels.argtypes = [vp, ci, vp, ci]
+    lib.rtuf_filter_batch_device_labels.argtypes = [vp, ci, vp, vp, vp, vp]
+    lib.rtuf_filter_batch_device_u16_labels.argtypes = [vp, ci, vp, vp, vp, vp]
+    lib.rtuf_filter_batch_labels.argtypes = [vp, ci, vp, vp, vp, vp]
+    lib.rtuf_filter_batch_u16_labels.argtypes = [vp, ci, vp, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -241,6 +248,11 @@ class Context:
 
     def finalize_models(self):
         self._check(self._lib.rtuf_finalize_models(self._h))
+
+    def num_links(self, model):
+        n = self._lib.rtuf_num_links(self._h, model)
+        self._check(min(n, 0))
+        return n
 
     def num_triangles(self):
         return int(self._lib.rtuf_num_triangles(self._h))
@@ -331,6 +343,36 @@ class Context:
         kout = PP(*[mask[i].ctypes.data for i in range(n)]) if want_mask else None
         self._check(self._lib.rtuf_filter_batch_u16(self._h, n, din, mout, kout))
         return masked, mask
+
+    # link labels (include/rtuf.h, LINK LABELS)
+    def set_link_labels(self, model, labels):
+        """Labels of model `model`'s links (one uint16 per link, in rtuf_add_link order)."""
+        a = np.ascontiguousarray(labels, np.uint16).reshape(-1)
+        self._check(self._lib.rtuf_set_link_labels(self._h, model, _ptr(a), len(a)))
+
+    def filter_batch_labels(self, depth, want_mask=True):
+        """Like filter_batch (float32 depth) or filter_batch_u16 (uint16 depth), plus the link label plane:
+        -> (masked, mask or None, labels [n,H,W] uint16)."""
+        u16 = np.asarray(depth).dtype == np.uint16
+        d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32).reshape(-1, self.height, self.width)
+        n = d.shape[0]
+        masked = np.empty_like(d)
+        mask = np.empty(d.shape, np.uint8) if want_mask else None
+        labels = np.empty(d.shape, np.uint16)
+        PP = ctypes.c_void_p * n
+        din = PP(*[d[i].ctypes.data for i in range(n)])
+        mout = PP(*[masked[i].ctypes.data for i in range(n)])
+        kout = PP(*[mask[i].ctypes.data for i in range(n)]) if want_mask else None
+        lout = PP(*[labels[i].ctypes.data for i in range(n)])
+        fn = self._lib.rtuf_filter_batch_u16_labels if u16 else self._lib.rtuf_filter_batch_labels
+        self._check(fn(self._h, n, din, mout, kout, lout))
+        return masked, mask, labels
+
+    def filter_batch_device_labels(self, n, d_depth, d_masked, d_mask, d_labels, u16=False):
+        """Device pointers (ints; d_mask may be None): enqueue only; call sync()."""
+        fn = self._lib.rtuf_filter_batch_device_u16_labels if u16 else self._lib.rtuf_filter_batch_device_labels
+        self._check(fn(self._h, n, ctypes.c_void_p(d_depth), ctypes.c_void_p(d_masked), ctypes.c_void_p(d_mask) if d_mask else None,
+                       ctypes.c_void_p(d_labels) if d_labels else None))
 
     # asynchronous host planes
     def host_alloc(self, shape, dtype):

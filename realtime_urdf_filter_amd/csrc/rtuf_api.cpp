@@ -58,7 +58,8 @@ struct Kinematics {               // on-device forward kinematics of one model
   double* h_root = nullptr; double* d_root = nullptr;       // [max_streams][12]
   uint8_t* h_enabled = nullptr; uint8_t* d_enabled = nullptr;
 };
-struct HostModel { std::vector<HostLink> links; int link_base = 0; Kinematics kin; };
+// labels: rtuf_set_link_labels's labels of the model's links (empty: the default, 1 + link_base + link)
+struct HostModel { std::vector<HostLink> links; int link_base = 0; Kinematics kin; std::vector<uint16_t> labels; };
 
 char g_create_error[512] = "";
 
@@ -92,6 +93,13 @@ struct rtuf_context {
 
   // static geometry (device)
   float4* d_cverts = nullptr; uint32_t* d_ctris = nullptr; uint32_t* d_corder = nullptr; Chunk* d_chunks = nullptr; Draw* d_draws = nullptr;
+  // Link labels (rtuf_filter_batch*_labels): every draw's global link and the last draw order it owns (draw orders are assigned
+  // draw by draw, model -> link -> draw order), and the device table draw order -> label, [n_tris + 1] (entry 0 = 0).  The
+  // table is allocated by the first label call or rtuf_set_link_labels and rewritten in place after that (captured graphs
+  // keep its address); contexts that never ask for labels allocate nothing.
+  std::vector<uint32_t> draw_link, draw_last_order;
+  uint16_t* d_order_labels = nullptr;
+  bool labels_dirty = true;
 
   // per-frame pose staging
   // Cameras and link matrices are staged in a ring of kMaxInflight + 1 pinned sets, like the joint positions: every
@@ -167,6 +175,7 @@ struct rtuf_context {
     bool active = false;
     int n = 0; const float* depth = nullptr; float* masked = nullptr; uint8_t* mask = nullptr; bool u16 = false;
     uint32_t* bits = nullptr;                // mask-only output (1 bit per pixel) instead of masked / mask
+    uint16_t* labels = nullptr;              // link label plane beside masked / mask (rtuf_filter_batch*_labels) or nullptr
     Counters* h_counters = nullptr;          // pinned [max_groups]: one block per launch group, filled by the copies that end the batch
     hipEvent_t done[kMaxLanes] = {};         // recorded on each lane after its copy
     uint32_t lanes_used = 0;                 // bit l: the batch has launch groups on lane l
@@ -197,7 +206,8 @@ struct rtuf_context {
     bool host_io = false;
     float* st_depth = nullptr; float* st_masked = nullptr; uint8_t* st_mask = nullptr; size_t st_streams = 0;
     uint32_t* st_bits = nullptr; size_t st_bits_streams = 0;
-    std::vector<void*> h_masked, h_mask, h_bits;
+    uint16_t* st_labels = nullptr; size_t st_labels_streams = 0;
+    std::vector<void*> h_masked, h_mask, h_bits, h_labels;
     hipEvent_t uploaded = nullptr, downloaded = nullptr;
     bool wait_upload = false;                // the lanes wait for `uploaded` before the first kernel that reads the planes
   };
@@ -630,6 +640,7 @@ static void free_frame_buffers(rtuf_context* c)
     for (auto*& it : ln.d_items) dev_free(c, it);
   }
   for (auto& b : c->batch) { dev_free(c, b.st_depth); dev_free(c, b.st_masked); dev_free(c, b.st_mask); b.st_streams = 0; dev_free(c, b.st_bits); b.st_bits_streams = 0; }
+  for (auto& b : c->batch) { dev_free(c, b.st_labels); b.st_labels_streams = 0; }
   for (auto*& p : c->ring_cams) hfree(p);
   for (auto*& p : c->ring_link_tf) hfree(p);
   c->h_cams = nullptr; c->h_link_tf = nullptr;
@@ -657,6 +668,7 @@ void rtuf_destroy(rtuf_context* c)
   }
   free_frame_buffers(c);
   dev_free(c, c->d_cverts); dev_free(c, c->d_ctris); dev_free(c, c->d_corder); dev_free(c, c->d_chunks); dev_free(c, c->d_draws);
+  dev_free(c, c->d_order_labels);
   for (auto& b : c->batch) {
     for (hipEvent_t ev : b.events) hipEventDestroy(ev);
     for (hipEvent_t ev : b.done) if (ev) hipEventDestroy(ev);
@@ -965,6 +977,8 @@ int rtuf_finalize_models(rtuf_context* c)
         const uint32_t draw_id = (uint32_t)draws.size();
         draws.push_back(d);
         add_chunks(hd.verts, hd.tris, draw_id, (uint32_t)mi, false);
+        c->draw_link.push_back(d.link);
+        c->draw_last_order.push_back((uint32_t)tri_seq);
       }
     }
     link_base += (int)m.links.size();
@@ -1575,6 +1589,8 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     ta.key_shift = c->key_shift;
     ta.fast_div = fast_div;
     ta.bits = dil ? nullptr : b.bits;
+    ta.labels = b.labels;                    // (the label calls refuse silhouette dilation and mask bits)
+    ta.order_labels = b.labels ? c->d_order_labels : nullptr;
     gr.compare = two && !b.bits && !dil;
     gr.dilate = dil > 0;
     if (gr.dilate) {
@@ -1697,6 +1713,14 @@ static int enqueue_download(rtuf_context* c, rtuf_context::Batch& b)
     while (e < b.n && b.h_mask[e] && (char*)b.h_mask[e] == (char*)b.h_mask[e - 1] + plane) e++;
     HIP_TRY(c, hipMemcpyAsync(b.h_mask[s], b.st_mask + (size_t)s * plane, (size_t)(e - s) * plane, hipMemcpyDeviceToHost, c->d2h));
     s = e;
+  }
+  if (b.labels) {
+    for (int s = 0; s < b.n;) {
+      int e = s + 1;
+      while (e < b.n && (char*)b.h_labels[e] == (char*)b.h_labels[e - 1] + plane * sizeof(uint16_t)) e++;
+      HIP_TRY(c, hipMemcpyAsync(b.h_labels[s], b.st_labels + (size_t)s * plane, (size_t)(e - s) * plane * sizeof(uint16_t), hipMemcpyDeviceToHost, c->d2h));
+      s = e;
+    }
   }
   HIP_TRY(c, hipEventRecord(b.downloaded, c->d2h));
   return RTUF_OK;
@@ -1866,7 +1890,7 @@ static int retire_oldest(rtuf_context* c)
 static bool uses_zsurface(const rtuf_context* c) { return (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 || c->params.silhouette_dilation_px > 0; }
 
 static int submit_batch(rtuf_context* c, int n, const float* d_depth, float* d_masked, uint8_t* d_mask, bool u16, uint32_t* d_bits = nullptr,
-                        bool wait_upload = false)
+                        bool wait_upload = false, uint16_t* d_labels = nullptr)
 {
   if (c->broken) return c->fail(RTUF_ERR_STATE, "context unusable: a bin regrowth failed (%s)", c->error.c_str());
   hipSetDevice(c->device);
@@ -1877,7 +1901,7 @@ static int submit_batch(rtuf_context* c, int n, const float* d_depth, float* d_m
   const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
   while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
   rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];
-  b.n = n; b.depth = d_depth; b.masked = d_masked; b.mask = d_mask; b.u16 = u16; b.host_io = false; b.bits = d_bits;
+  b.n = n; b.depth = d_depth; b.masked = d_masked; b.mask = d_mask; b.u16 = u16; b.host_io = false; b.bits = d_bits; b.labels = d_labels;
   b.wait_upload = wait_upload;
   const int rc = enqueue_batch(c, b, false);
   if (rc == RTUF_OK) { b.active = true; c->pending++; }
@@ -2019,14 +2043,14 @@ int rtuf_order_stream_after_batches(rtuf_context* c, void* hip_stream)
 // batches in flight the transfers of one overlap the kernels of the other; every slot has its own
 // device staging.
 static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in, void* const* masked_out,
-                             void* const* mask_out, bool u16, uint32_t* const* bits_out = nullptr)
+                             void* const* mask_out, bool u16, uint32_t* const* bits_out = nullptr, uint16_t* const* labels_out = nullptr)
 {
   if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
   if (n <= 0 || n > c->max_streams || !depth_in || (!masked_out && !bits_out)) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
   if (u16 && (c->width & 3)) return c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4");
   if (bits_out) { const int rc = check_bits_call(c, n, depth_in, bits_out); if (rc != RTUF_OK) return rc; }
   for (int s = 0; s < n; s++)
-    if (!depth_in[s] || (bits_out ? !bits_out[s] : !masked_out[s])) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
+    if (!depth_in[s] || (bits_out ? !bits_out[s] : !masked_out[s]) || (labels_out && !labels_out[s])) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
   hipSetDevice(c->device);
   // (copy streams beside the lanes as well: an upload queued behind a lane's kernels would hold up the next batch)
   if (!c->h2d || !c->d2h) {
@@ -2055,6 +2079,12 @@ static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in
     HIP_TRY(c, dev_alloc(c, &b.st_bits, (size_t)n * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
     b.st_bits_streams = (size_t)n;
   }
+  if (labels_out && b.st_labels_streams < (size_t)n) {
+    dev_free(c, b.st_labels);
+    b.st_labels_streams = 0;
+    HIP_TRY(c, dev_alloc(c, &b.st_labels, (size_t)n * plane * sizeof(uint16_t)));
+    b.st_labels_streams = (size_t)n;
+  }
   if (!b.uploaded) HIP_TRY(c, hipEventCreateWithFlags(&b.uploaded, hipEventDisableTiming));
   if (!b.downloaded) HIP_TRY(c, hipEventCreateWithFlags(&b.downloaded, hipEventDisableTiming));
   const size_t esz = u16 ? sizeof(uint16_t) : sizeof(float);
@@ -2067,6 +2097,8 @@ static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in
   HIP_TRY(c, hipEventRecord(b.uploaded, c->h2d));          // (the lanes' first kernels wait for it: enqueue_batch)
   bool any_mask = false;
   b.h_bits.clear();
+  b.h_labels.clear();
+  if (labels_out) b.h_labels.assign(reinterpret_cast<void* const*>(labels_out), reinterpret_cast<void* const*>(labels_out) + n);
   if (bits_out) {
     b.h_bits.assign(reinterpret_cast<void* const*>(bits_out), reinterpret_cast<void* const*>(bits_out) + n);
   } else {
@@ -2074,7 +2106,8 @@ static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in
     b.h_mask.assign((size_t)n, nullptr);
     if (mask_out) for (int s = 0; s < n; s++) { b.h_mask[s] = mask_out[s]; any_mask |= mask_out[s] != nullptr; }
   }
-  int rc = submit_batch(c, n, b.st_depth, b.st_masked, any_mask ? b.st_mask : nullptr, u16, bits_out ? b.st_bits : nullptr, true);
+  int rc = submit_batch(c, n, b.st_depth, b.st_masked, any_mask ? b.st_mask : nullptr, u16, bits_out ? b.st_bits : nullptr, true,
+                        labels_out ? b.st_labels : nullptr);
   if (rc != RTUF_OK) return rc;
   b.host_io = true;
   return enqueue_download(c, b);
@@ -2123,6 +2156,100 @@ int rtuf_filter_batch_u16(rtuf_context* c, int n, const uint16_t* const* depth_i
                           uint8_t* const* mask_out)
 {
   const int rc = rtuf_filter_batch_u16_async(c, n, depth_in, masked_out, mask_out);
+  return rc != RTUF_OK ? rc : rtuf_sync(c);
+}
+
+// ---- link labels -----------------------------------------------------------------------------------
+// The tile kernel's depth keys carry the winning triangle's draw order; the table draw order -> label turns it into the
+// label of the link the triangle belongs to.  Built on the host from every draw's link and the models' labels.
+static int ensure_label_table(rtuf_context* c)
+{
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (c->d_order_labels && !c->labels_dirty) return RTUF_OK;
+  std::vector<uint16_t> link_label((size_t)c->n_links, 0);
+  for (const HostModel& m : c->models)
+    for (size_t l = 0; l < m.links.size(); l++) {
+      if (!m.labels.empty()) { link_label[(size_t)m.link_base + l] = m.labels[l]; continue; }
+      const int def = 1 + m.link_base + (int)l;
+      if (def > 65535) return c->fail(RTUF_ERR_CAPACITY, "link %d: default labels are limited to 65535 links (set them with rtuf_set_link_labels)", def - 1);
+      link_label[(size_t)m.link_base + l] = (uint16_t)def;
+    }
+  std::vector<uint16_t> table((size_t)c->n_tris + 1, 0);
+  for (size_t d = 0, first = 1; d < c->draw_link.size(); d++) {
+    const uint16_t lab = link_label[c->draw_link[d]];
+    for (size_t o = first; o <= c->draw_last_order[d]; o++) table[o] = lab;
+    first = (size_t)c->draw_last_order[d] + 1;
+  }
+  hipSetDevice(c->device);
+  if (!c->d_order_labels) HIP_TRY(c, dev_alloc(c, &c->d_order_labels, table.size() * sizeof(uint16_t)));
+  // (no batch in flight reads the table: rtuf_set_link_labels waits for them, and a new table has never been read)
+  HIP_TRY(c, hipMemcpy(c->d_order_labels, table.data(), table.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  c->labels_dirty = false;
+  return RTUF_OK;
+}
+
+int rtuf_set_link_labels(rtuf_context* c, int model, const uint16_t* labels, int n_links)
+{
+  KIDS_ALL(c, rtuf_set_link_labels(k, model, labels, n_links));
+  if (!c) return RTUF_ERR_INVALID;
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (model < 0 || model >= (int)c->models.size()) return c->fail(RTUF_ERR_INVALID, "bad model id %d", model);
+  HostModel& m = c->models[model];
+  if (!labels || n_links != (int)m.links.size()) return c->fail(RTUF_ERR_INVALID, "model %d has %d links (got %d labels)", model, (int)m.links.size(), n_links);
+  WAIT_IF_PENDING(c);
+  m.labels.assign(labels, labels + n_links);
+  c->labels_dirty = true;
+  return ensure_label_table(c);
+}
+
+static int check_labels_call(rtuf_context* c, int n, const void* in, const void* out, const void* labels)
+{
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (n <= 0 || n > c->max_streams || !in || !out || !labels) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
+  if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "link labels are not supported with silhouette dilation yet");
+  return ensure_label_table(c);
+}
+
+int rtuf_filter_batch_device_labels(rtuf_context* c, int n, const float* d_depth, float* d_masked, uint8_t* d_mask, uint16_t* d_labels)
+{
+  KIDS_NEXT(c, rtuf_filter_batch_device_labels(k, n, d_depth, d_masked, d_mask, d_labels));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_labels_call(c, n, d_depth, d_masked, d_labels);
+  return rc != RTUF_OK ? rc : submit_batch(c, n, d_depth, d_masked, d_mask, false, nullptr, false, d_labels);
+}
+
+int rtuf_filter_batch_device_u16_labels(rtuf_context* c, int n, const uint16_t* d_depth, uint16_t* d_masked, uint8_t* d_mask, uint16_t* d_labels)
+{
+  KIDS_NEXT(c, rtuf_filter_batch_device_u16_labels(k, n, d_depth, d_masked, d_mask, d_labels));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_labels_call(c, n, d_depth, d_masked, d_labels);
+  if (rc != RTUF_OK) return rc;
+  if (c->width & 3) return c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4");
+  return submit_batch(c, n, reinterpret_cast<const float*>(d_depth), reinterpret_cast<float*>(d_masked), d_mask, true, nullptr, false, d_labels);
+}
+
+static int filter_batch_labels_async(rtuf_context* c, int n, const void* const* depth_in, void* const* masked_out, uint8_t* const* mask_out,
+                                     uint16_t* const* labels_out, bool u16)
+{
+  KIDS_NEXT(c, filter_batch_labels_async(k, n, depth_in, masked_out, mask_out, labels_out, u16));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_labels_call(c, n, depth_in, masked_out, labels_out);
+  return rc != RTUF_OK ? rc : submit_host_batch(c, n, depth_in, masked_out, reinterpret_cast<void* const*>(mask_out), u16, nullptr, labels_out);
+}
+
+int rtuf_filter_batch_labels(rtuf_context* c, int n, const float* const* depth_in, float* const* masked_out, uint8_t* const* mask_out,
+                             uint16_t* const* labels_out)
+{
+  const int rc = filter_batch_labels_async(c, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(masked_out),
+                                           mask_out, labels_out, false);
+  return rc != RTUF_OK ? rc : rtuf_sync(c);
+}
+
+int rtuf_filter_batch_u16_labels(rtuf_context* c, int n, const uint16_t* const* depth_in, uint16_t* const* masked_out, uint8_t* const* mask_out,
+                                 uint16_t* const* labels_out)
+{
+  const int rc = filter_batch_labels_async(c, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(masked_out),
+                                           mask_out, labels_out, true);
   return rc != RTUF_OK ? rc : rtuf_sync(c);
 }
 

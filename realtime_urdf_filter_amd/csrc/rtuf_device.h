@@ -320,6 +320,9 @@ struct TileArgs {
   int io_u16;                    // 16UC1 in/out fused into the kernel (src/urdf_filter.cpp:287-288, :309-312)
   int key_shift;                 // depth keys: draw order << key_shift in the low word, the float z's low bits below it (KeyFmt)
   int fast_div;                  // the threshold's division may run without its scaling / fix-up instructions (host: fast_div_admitted, rtuf_numerics.h)
+  // link labels (appended: the fields above keep their kernarg offsets).  labels != nullptr selects tile_labels_kernel.
+  uint16_t* labels;              // [n][H][W] link label of every pixel's winner, 8-byte aligned; nullptr = none
+  const uint16_t* order_labels;  // [n_tris + 1] label of every draw order (entry 0, background / no fragment: 0)
 };
 
 struct CompareArgs {

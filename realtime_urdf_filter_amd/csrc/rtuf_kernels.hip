@@ -1568,7 +1568,19 @@ struct KeyFmt {
   uint32_t lowmask;     // (1 << shift) - 1 in tiles that hold near records (or a near cover), else 0
   uint32_t zexact;      // winners with z24 < zexact need the exact-z pass: 2^(26-shift) in near tiles, else 2^23 + 1
   uint32_t abl;         // RTUF_ABLATE builds: the launch's timing-experiment bits (0x4000: depth tests without their LDS atomic, 0x2000000: strips fetched but not walked)
+  bool keep_order;      // link labels (a compile-time constant of the kernel): resolved keys keep the winner's draw order
 };
+
+// The exact-z pass replaces a winning key by kResolvedBit | float z.  Bits 32-62 of that word are unused; with link labels they
+// keep the winner's draw order (at most 29 bits, kMaxOrder), which the label lookup needs.  (keep_order is false in every
+// kernel without labels, so there this is the same single OR it always was.)
+__device__ __forceinline__ unsigned long long resolved_key(unsigned long long key, float z, const KeyFmt& kf)
+{
+  const unsigned long long ord = kf.keep_order ? (unsigned long long)((uint32_t)key >> kf.shift) << 32 : 0ull;
+  return kResolvedBit | ord | (unsigned long long)__float_as_uint(z);
+}
+// draw order of a resolved key (keep_order)
+__device__ __forceinline__ uint32_t resolved_order(unsigned long long k) { return (uint32_t)(k >> 32) & 0x7fffffffu; }
 
 // One depth test of a fragment whose window z is already evaluated (`order`: the draw order shifted into place).
 // Issue classes (profiles/valu_peak.json: gfx950 issues v_fma/mul/add_f32, v_add/sub_u32, v_and/or/xor_b32 and the right shifts
@@ -1585,7 +1597,7 @@ __device__ __forceinline__ void depth_test(unsigned long long* keys, uint32_t or
   if (MODE == 0) {
     atomicMin(&keys[lidx], key);
   } else {
-    if (keys[lidx] == key) keys[lidx] = kResolvedBit | (unsigned long long)__float_as_uint(z);
+    if (keys[lidx] == key) keys[lidx] = resolved_key(key, z, kf);
   }
 }
 
@@ -2041,7 +2053,7 @@ __device__ __forceinline__ void raster_bin(unsigned long long* keys, const Packe
             RTUF_COUNT_TEST();
             atomicMin(&keys[lidx], key);
           } else {
-            if (keys[lidx] == key) keys[lidx] = kResolvedBit | (unsigned long long)__float_as_uint(z);
+            if (keys[lidx] == key) keys[lidx] = resolved_key(key, z, kf);
           }
         }
       } else if (inside) {
@@ -2110,6 +2122,14 @@ __device__ __forceinline__ void store_stream4(uint16_t* dst, uint32_t a, uint32_
   uint32_t* w = reinterpret_cast<uint32_t*>(dst);
   __builtin_nontemporal_store(a | (b << 16), w); __builtin_nontemporal_store(c | (d << 16), w + 1);
 }
+// four link labels (two per word) as one 8-byte non-temporal store
+__device__ __forceinline__ void store_labels4(uint16_t* dst, uint32_t lo, uint32_t hi)
+{
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  u32x2 v;
+  v.x = lo; v.y = hi;
+  __builtin_nontemporal_store(v, reinterpret_cast<u32x2*>(dst));
+}
 __device__ __forceinline__ float4 load_stream4(const float* src)
 {
   return make_float4(__builtin_nontemporal_load(src), __builtin_nontemporal_load(src + 1),
@@ -2150,7 +2170,8 @@ __device__ __forceinline__ float shade(float sensor, float z, const ShadeConsts&
 
 // COVER: the batch ran the cover pass (bigrec_kernel<0>), so a bin's header may name a cover.  Without it (the host skips the
 // pass while no scene has triangles that cover whole tiles) the cover code is compiled out: it costs the headline workload 3 %.
-template <bool TWO_KERNEL, bool U16, bool BITS, bool COVER, int NT>
+// LABELS: the kernel also writes the link label plane (a.labels, a.order_labels: rtuf_filter_batch*_labels); never with BITS.
+template <bool TWO_KERNEL, bool U16, bool BITS, bool COVER, int NT, bool LABELS = false>
 __device__ __forceinline__ void tile_body(const TileArgs& a)
 {
   __shared__ unsigned long long keys[kKeyCount];
@@ -2187,6 +2208,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   kf.abl = a.flags;
   kf.lowmask = near_tile ? (1u << a.key_shift) - 1u : 0u;
   kf.zexact = near_tile ? exact_z_floor(a.key_shift) : 8388609u;
+  kf.keep_order = LABELS;
   const uint32_t count = count_front + count_back;
   // (the stream's background entry after the bin's header in program order: the compiler then issues the three scalar loads
   // together -- with the background first it waited for it before it even computed the header's address)
@@ -2243,6 +2265,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   // common path cost the headline workload 20 % when this was first written for all variants).
   bool cover_only = false;
   float cov_a0 = 0.0f, cov_dzdx = 0.0f, cov_dzdy = 0.0f;
+  uint32_t cov_label = 0;                    // LABELS: the cover's link label, one lookup per tile
   if constexpr (COVER) {
     cover_only = has_cover && n == 0 && nf == 0 && !empty;
     if (cover_only) {
@@ -2251,6 +2274,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
       cov_a0 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.x));
       cov_dzdx = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.y));
       cov_dzdy = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.z));
+      if (LABELS) cov_label = a.order_labels[(uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask];
 #ifdef RTUF_COUNT
       if (tid < 2) count_words()[tid] = 0u;
 #endif
@@ -2375,7 +2399,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
         for (int i = tid; i < kKeyCount; i += NT) {
           const float z = __fmaf_rn(c.dzdy, (float)(y_base + i / kKeyStride), __fmaf_rn(c.dzdx, (float)(x_base + i % kKeyStride), c.a0));
           const unsigned long long key = ((unsigned long long)z24_of(z) << 32) | (c.order << kf.shift) | (__float_as_uint(z) & kf.lowmask);
-          if (keys[i] == key) keys[i] = kResolvedBit | (unsigned long long)__float_as_uint(z);
+          if (keys[i] == key) keys[i] = resolved_key(key, z, kf);
         }
       }
       __syncthreads();
@@ -2390,10 +2414,15 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   // With BITS the only output is one mask bit per pixel: `finish` returns the lane's four mask flags (bit j = pixel j)
   // and stores nothing; the caller packs the flags of 8 neighbouring lanes into one 32-bit word.
   bool uncovered = false;                              // BITS: a pixel no fragment reached (its masked depth would be the clear colour, not the sensor value)
-  auto finish = [&](int ps, const float (&z)[4], const float (&thr)[4], const bool (&frag)[4]) -> uint32_t {
+  // LABELS: lab = the four pixels' link labels, stored to the stream's label plane in either route
+  auto finish = [&](int ps, const float (&z)[4], const float (&thr)[4], const bool (&frag)[4], const uint32_t (&lab)[4]) -> uint32_t {
     const int r_ly = r_ly0 + ps * kRowsPerPass, py = y_base + r_ly, px = r_px;
     const size_t gofs = (size_t)stream * ((size_t)a.height * a.width) + (uint32_t)(__mul24(py, a.width) + px);
     const int nvalid = min(4, a.width - px);
+    if (LABELS) {
+      if (vec) store_labels4(a.labels + gofs, lab[0] | (lab[1] << 16), lab[2] | (lab[3] << 16));
+      else for (int j = 0; j < nvalid; j++) a.labels[gofs + j] = (uint16_t)lab[j];
+    }
     if (TWO_KERNEL) {
       const size_t zofs = (size_t)slot * ((size_t)a.height * a.width) + (uint32_t)(__mul24(py, a.width) + px);
       // "no fragment" (only without background quad) is encoded as NaN
@@ -2441,6 +2470,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   // threshold (one IEEE division) is computed once per lane.  Same operations on the same values as per pixel.
   const float bg_z4[4] = {bgz, bgz, bgz, bgz}, bg_thr4[4] = {thr_bg, thr_bg, thr_bg, thr_bg};
   const bool bg_frag4[4] = {analytic_bg, analytic_bg, analytic_bg, analytic_bg};
+  const uint32_t no_lab4[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
   for (int ps = 0; ps < kPasses; ps++) {
     const int r_ly = r_ly0 + ps * kRowsPerPass;
@@ -2451,13 +2481,14 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
       if (empty) {                                   // tile without geometry: a streaming compare against the plane
         if (analytic_bg) {          // (uniform: with the flags known to be set the four selects on them fall away)
           const bool all4[4] = {true, true, true, true};
-          flags4 = finish(ps, bg_z4, bg_thr4, all4);
+          flags4 = finish(ps, bg_z4, bg_thr4, all4, no_lab4);
         } else {
-          flags4 = finish(ps, bg_z4, bg_thr4, bg_frag4);
+          flags4 = finish(ps, bg_z4, bg_thr4, bg_frag4, no_lab4);
         }
       } else if (COVER && cover_only) {      // nothing but a triangle over the whole tile: its fragment or the background's, from registers
         float z[4], thr[4];
         bool frag[4];
+        uint32_t lab[4];
         const float zrow = (float)(y_base + r_ly);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -2471,20 +2502,23 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
           z[j] = drawn ? zf : bgz;
           frag[j] = drawn ? true : analytic_bg;
           thr[j] = thr_bg;
+          lab[j] = drawn ? cov_label : 0u;
           if (drawn && !TWO_KERNEL) thr[j] = shade_threshold(zf, sc);
 #ifdef RTUF_COUNT
           if (drawn && r_px + j < a.width) atomicAdd(&count_words()[1], 1u);
 #endif
         }
-        flags4 = finish(ps, z, thr, frag);
+        flags4 = finish(ps, z, thr, frag, lab);
       } else {
         float z[4], thr[4];
         bool frag[4];
+        uint32_t lab[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           const unsigned long long k = keys[r_ly * kKeyStride + r_lx + j];
           frag[j] = true;
           thr[j] = thr_bg;
+          lab[j] = 0u;
           if (k == bgkey) { z[j] = bgz; frag[j] = analytic_bg; }
           else {                                        // the per-pixel division only runs where something was drawn
 #ifdef RTUF_COUNT
@@ -2507,9 +2541,12 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
               }
             }
             if (!TWO_KERNEL) thr[j] = shade_threshold(z[j], sc);
+            // the winner's draw order: the key's (or, after the exact-z pass, kept above the float z: resolved_key); 0 is
+            // "no fragment" (kNoFragment), whose table entry is label 0
+            if (LABELS) lab[j] = a.order_labels[(k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift];
           }
         }
-        flags4 = finish(ps, z, thr, frag);
+        flags4 = finish(ps, z, thr, frag, lab);
       }
     }
     if (BITS) {
@@ -2559,6 +2596,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(COVER ? RTUF
 // mask-only output, one bit per pixel (rtuf_filter_batch_bits*): 4 (2) B/pixel in, 1/8 B/pixel out
 template <bool U16, bool COVER, int NT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(COVER ? RTUF_TILE_WAVES_COVER : RTUF_TILE_WAVES))) void tile_bits_kernel(TileArgs a) { tile_body<false, U16, true, COVER, NT>(a); }
+// link labels beside the planes (rtuf_filter_batch*_labels): the variants of tile_kernel, plus 2 B/pixel out
+#ifndef RTUF_TILE_WAVES_LABELS
+#define RTUF_TILE_WAVES_LABELS 7
+#endif
+template <bool TWO_KERNEL, bool U16, bool COVER, int NT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_LABELS))) void tile_labels_kernel(TileArgs a) { tile_body<TWO_KERNEL, U16, false, COVER, NT, true>(a); }
 
 // ---------------------------------------------------------------------------------------
 // compare_kernel (two-kernel mode): streaming, 13 B/pixel (4 sensor + 4 z + 4 masked + 1 mask)
@@ -2903,7 +2946,11 @@ template <bool COVER, int NT>
 static void launch_tile_variant(const TileArgs& a, bool two_kernel, hipStream_t st)
 {
   const dim3 grid(a.tiles_x, a.tiles_y, a.group_size);
-  if (a.bits) {
+  if (a.labels) {
+    if (two_kernel) hipLaunchKernelGGL((tile_labels_kernel<true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
+    else if (a.io_u16) hipLaunchKernelGGL((tile_labels_kernel<false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((tile_labels_kernel<false, false, COVER, NT>), grid, dim3(NT), 0, st, a);
+  } else if (a.bits) {
     if (a.io_u16) hipLaunchKernelGGL((tile_bits_kernel<true, COVER, NT>), grid, dim3(NT), 0, st, a);
     else hipLaunchKernelGGL((tile_bits_kernel<false, COVER, NT>), grid, dim3(NT), 0, st, a);
   } else if (two_kernel) hipLaunchKernelGGL((tile_kernel<true, false, COVER, NT>), grid, dim3(NT), 0, st, a);

@@ -32,6 +32,7 @@ class Renderable:
 
     def __init__(self):
         self.name = ""
+        self.urdf_link = ""                   # the URDF link's own name (`name` carries the tf prefix): its label's key
         self.link_offset = Transform()
         self.link_to_fixed = Transform()
         self.draws = []
@@ -137,6 +138,7 @@ class URDFRenderer:
             else:
                 raise ValueError("unknown geometry type %r (the reference dereferences a null pointer here)" % g.kind)
             r.setLinkName(self.tf_prefix_ + "/" + link.name)
+            r.urdf_link = link.name
             r.link_offset = urdf.pose_to_transform(it.xyz, it.rpy)
             self.renderables_.append(r)
 
@@ -194,7 +196,7 @@ class RealtimeURDFFilter:
     """urdf_filter.h:51-143.  One instance serves `max_streams` concurrent cameras (stream 0 is the
     reference-shaped single-camera interface); the public attribute names follow the reference."""
 
-    def __init__(self, params, tf, param_server=None, max_streams=1, mesh_loader=None, device=0, two_kernel=False):
+    def __init__(self, params, tf, param_server=None, max_streams=1, mesh_loader=None, device=0, two_kernel=False, labels=False):
         self.params = params
         self.tf_ = tf
         self.param_server = param_server or {}
@@ -221,6 +223,10 @@ class RealtimeURDFFilter:
         self._model_ids = []
         self._batch_masked = None
         self._batch_mask = None
+        # new, beyond the reference: link labels (include/rtuf.h, LINK LABELS), off by default -- filter() costs what it did
+        self.want_labels_ = bool(labels)
+        self.labels_ = None
+        self.link_labels_ = {}                # (model index, URDF link name) -> label
 
     # ---- loading -------------------------------------------------------------------------
     def loadModels(self):
@@ -270,6 +276,15 @@ class RealtimeURDFFilter:
                     self._ctx.add_draw(m, l, d.verts, d.tris, d.pre_op, d.op)
             self._model_ids.append(m)
         self._ctx.finalize_models()
+        # one label per URDF link, numbered from 1 over the models in order (every renderable of a link shares it; links on a
+        # model's `ignore` list have no renderable and so no label)
+        self.link_labels_ = {}
+        for mi, (rd, m) in enumerate(zip(self.renderers_, self._model_ids)):
+            for r in rd.renderables_:
+                self.link_labels_.setdefault((mi, r.urdf_link), len(self.link_labels_) + 1)
+            if rd.renderables_ and self.want_labels_:
+                self._ctx.set_link_labels(m, [self.link_labels_[(mi, r.urdf_link)] for r in rd.renderables_])
+        self.labels_ = np.zeros((self.height_, self.width_), np.uint16) if self.want_labels_ else None
         self.masked_depth_ = np.zeros((self.height_, self.width_), np.float32)
         self.mask_ = np.zeros((self.height_, self.width_), np.uint8)
 
@@ -324,13 +339,26 @@ class RealtimeURDFFilter:
             log.error("%s", e)
             return
         depth = np.frombuffer(buffer, np.float32, width * height) if not isinstance(buffer, np.ndarray) else buffer
-        masked, mask = self._ctx.filter_batch(np.asarray(depth, np.float32).reshape(1, height, width), want_mask=self.need_mask_)
+        d = np.asarray(depth, np.float32).reshape(1, height, width)
+        if self.want_labels_:
+            masked, mask, labels = self._ctx.filter_batch_labels(d, want_mask=self.need_mask_)
+            self.labels_ = labels[0]
+        else:
+            masked, mask = self._ctx.filter_batch(d, want_mask=self.need_mask_)
         self.masked_depth_ = masked[0]
         if self.need_mask_:
             self.mask_ = mask[0]
 
     def getMaskedDepth(self):
         return self.masked_depth_
+
+    def getLabels(self):
+        """Link label plane [H,W] uint16 of the last frame (labels=True), label 0 = background quad or nothing drawn."""
+        return self.labels_
+
+    def getLinkLabels(self):
+        """{(model index, URDF link name): label} of the links the labels plane can show."""
+        return dict(self.link_labels_)
 
     def filter_callback(self, image, encoding, camera_info, stamp=None):
         """src/urdf_filter.cpp:270-330.  image: [H,W] float32 metres ("32FC1") or uint16 millimetres
