@@ -111,6 +111,7 @@ class URDFRenderer {
   }
   void loadURDFModel(const rtuf_host::UrdfModel& model)
   {
+    for (const auto& l : model.links) link_names.insert(l.first);
     for (const auto& l : model.links) process_link(l.second);
   }
   // src/urdf_renderer.cpp:100-169
@@ -143,6 +144,10 @@ class URDFRenderer {
   const std::string geometry_type;
   const double scale;
   const std::unordered_set<std::string> ignore;
+ public:
+  std::unordered_set<std::string> link_names;    // every link of the URDF, ignored ones included
+  std::map<std::string, double> link_thresholds; // URDF link name -> depth threshold of its own (RealtimeURDFFilter::loadModels)
+ protected:
   std::string camera_frame_, fixed_frame_;
   const TransformProvider& tf_;
   MeshResolver resolve_;
@@ -156,6 +161,10 @@ struct ModelParameter {
   std::string geometry_type;    // "visual" | "collision"
   double scale = 1.0;
   std::unordered_set<std::string> ignore;
+  // New, beyond the reference: per-link depth thresholds (include/rtuf.h, PER-LINK DEPTH THRESHOLDS), keyed by URDF link
+  // name.  Every renderable of the link takes the value, the model's other links the global depth_distance_threshold; a name
+  // that is no link of the model's URDF is an error at load, a link on the ignore list is accepted and has no effect.
+  std::vector<std::pair<std::string, double>> link_depth_distance_thresholds;
 };
 struct FilterParameters {
   std::string fixed_frame, camera_frame;
@@ -202,6 +211,11 @@ class RealtimeURDFFilter {
       if (it->second.empty()) { std::fprintf(stderr, "[realtime_urdf_filter] URDF is empty\n"); continue; }
       renderers_.push_back(new URDFRenderer(it->second, elem.tf_prefix, cam_frame_, fixed_frame_, tf_, elem.geometry_type, elem.scale, elem.ignore,
                                             resolve_, resolve_user_));
+      for (const auto& lt : elem.link_depth_distance_thresholds) {
+        if (!renderers_.back()->link_names.count(lt.first))
+          throw std::runtime_error("link_depth_distance_thresholds of model " + elem.model + ": no link '" + lt.first + "' in its URDF");
+        renderers_.back()->link_thresholds[lt.first] = lt.second;
+      }
     }
   }
 
@@ -258,6 +272,8 @@ class RealtimeURDFFilter {
       }
       if (want_labels_ && !lab.empty()) check(rtuf_set_link_labels(ctx_, model_ids_[i], lab.data(), (int)lab.size()));
     }
+    applied_threshold_ = depth_distance_threshold_;
+    apply_link_thresholds();
     labels_.assign(want_labels_ ? (size_t)width_ * height_ : 0, 0);
     masked_depth_ = nullptr;
     mask_ = nullptr;
@@ -435,6 +451,8 @@ class RealtimeURDFFilter {
       p.filter_replace_value = (float)filter_replace_value_;
       p.silhouette_dilation_px = silhouette_dilation_px_;
       check(rtuf_set_params(ctx_, &p));
+      // per-link thresholds: the links of such a model without a value of their own follow the global one
+      if (depth_distance_threshold_ != applied_threshold_) { applied_threshold_ = depth_distance_threshold_; apply_link_thresholds(); }
     }
     return true;
   }
@@ -476,6 +494,22 @@ class RealtimeURDFFilter {
   unsigned char* pending_buffer_ = nullptr;
   std::vector<uint32_t> bits_;
   std::vector<float> scratch_in_, scratch_out_;      // filter_into for widths that are not a multiple of 4
+  // per-link depth thresholds (ModelParameter::link_depth_distance_thresholds): every renderable of a listed URDF link takes
+  // its value, the model's other links the global threshold it was last applied with
+  void apply_link_thresholds()
+  {
+    for (size_t i = 0; i < renderers_.size(); i++) {
+      const URDFRenderer* rd = renderers_[i];
+      if (rd->link_thresholds.empty() || rd->renderables_.empty()) continue;
+      std::vector<float> t;
+      for (const auto& r : rd->renderables_) {
+        auto it = rd->link_thresholds.find(r->urdf_link);
+        t.push_back((float)(it != rd->link_thresholds.end() ? it->second : applied_threshold_));
+      }
+      check(rtuf_set_link_thresholds(ctx_, model_ids_[i], t.data(), (int)t.size()));
+    }
+  }
+  double applied_threshold_ = 0.0;                   // the global threshold apply_link_thresholds last used
   bool want_labels_;                                 // FilterParameters::link_labels
   std::vector<uint16_t> labels_;                     // label plane of the last frame (getLabels)
   std::map<std::pair<int, std::string>, uint16_t> link_labels_;

@@ -374,6 +374,30 @@ int rtuf_filter_batch_labels(rtuf_context *ctx, int n_streams, const float *cons
 int rtuf_filter_batch_u16_labels(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in,
                                  uint16_t *const *masked_mm_out, uint8_t *const *mask_out, uint16_t *const *labels_out);
 
+/* PER-LINK DEPTH THRESHOLDS.  New, beyond the reference: a depth_distance_threshold (the shader's max_diff) of its own for
+ * every link of a model -- a wide margin for a gripper holding an object, a tight one for a wall, none at all for a link a
+ * tracker must still see.  A drawn pixel is compared with the threshold of the link whose fragment won its depth test (GL_LESS
+ * on the 24-bit depth, ties going to the earlier draw: the winner the link labels report): sensor > to_linear_depth(z) - t,
+ * the shader's compare with the same float operations and t in place of max_diff.  Pixels the background quad won keep
+ * rtuf_params.depth_distance_threshold; undrawn pixels stay the GL clear colour.
+ * Any float is legal.  A larger t filters more: -inf and NaN never filter the link (the compare is false), +inf filters every
+ * pixel where it is drawn and the sensor is not NaN; 0 and negative values are ordinary margins.
+ * rtuf_set_link_thresholds sets the thresholds of one model's links (n_links = rtuf_num_links(model)).
+ * rtuf_clear_link_thresholds makes the model's links follow rtuf_params again.  Links without a value -- models never given
+ * thresholds, or cleared -- use the global threshold of every batch, so a later rtuf_set_params that changes it applies to
+ * them and not to links set explicitly.  Both calls wait for the batches in flight; a bad model id, a wrong n_links or a NULL
+ * array fail with RTUF_ERR_INVALID and change nothing.
+ * The thresholds apply to every fused entry point: rtuf_filter, the f32 and 16UC1 device and host-plane calls (synchronous
+ * and asynchronous), the mask-bits calls (the replace value stays global, so rtuf_expand_mask_bits stays exact) and the link
+ * label calls.  Any number of raster lanes and pipelines; re-runs after a bin regrowth keep the thresholds, and the status
+ * word (rtuf_batch_status_device) keeps its meaning.
+ * Not supported yet: while any model of the context has thresholds, a batch with RTUF_FLAG_TWO_KERNEL or
+ * silhouette_dilation_px > 0 fails with RTUF_ERR_INVALID before anything is enqueued (the z-surface does not carry the winning
+ * link).  While no model has thresholds -- after the last rtuf_clear_link_thresholds too -- nothing differs from a context that
+ * never used them.  The draw-order -> threshold table (4 bytes per triangle) is allocated by the first rtuf_set_link_thresholds. */
+int rtuf_set_link_thresholds(rtuf_context *ctx, int model, const float *depth_distance_threshold, int n_links);
+int rtuf_clear_link_thresholds(rtuf_context *ctx, int model);
+
 /* Counters of the last batch and kernel timings measured with HIP events on the context's
  * stream (replaces the wall-clock statistics of src/urdf_filter.cpp:239-266). */
 typedef struct {

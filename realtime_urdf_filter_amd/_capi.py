@@ -34,7 +34,7 @@ SYMBOLS = [
     "rtuf_mask_bits_words", "rtuf_filter_batch_bits_async", "rtuf_filter_batch_bits_u16_async", "rtuf_filter_batch_device_bits",
     "rtuf_filter_batch_device_bits_u16", "rtuf_expand_mask_bits", "rtuf_order_stream_after_batches", "rtuf_batch_status_device",
     "rtuf_set_link_labels", "rtuf_filter_batch_device_labels", "rtuf_filter_batch_device_u16_labels", "rtuf_filter_batch_labels",
-    "rtuf_filter_batch_u16_labels",
+    "rtuf_filter_batch_u16_labels", "rtuf_set_link_thresholds", "rtuf_clear_link_thresholds",
 ]
 
 
@@ -178,6 +178,8 @@ def load_library(path=None):
     lib.rtuf_filter_batch_device_u16_labels.argtypes = [vp, ci, vp, vp, vp, vp]
     lib.rtuf_filter_batch_labels.argtypes = [vp, ci, vp, vp, vp, vp]
     lib.rtuf_filter_batch_u16_labels.argtypes = [vp, ci, vp, vp, vp, vp]
+    lib.rtuf_set_link_thresholds.argtypes = [vp, ci, vp, ci]
+    lib.rtuf_clear_link_thresholds.argtypes = [vp, ci]
     if path is None:
         _lib = lib
     return lib
@@ -373,6 +375,16 @@ class Context:
         fn = self._lib.rtuf_filter_batch_device_u16_labels if u16 else self._lib.rtuf_filter_batch_device_labels
         self._check(fn(self._h, n, ctypes.c_void_p(d_depth), ctypes.c_void_p(d_masked), ctypes.c_void_p(d_mask) if d_mask else None,
                        ctypes.c_void_p(d_labels) if d_labels else None))
+
+    # per-link depth thresholds (include/rtuf.h, PER-LINK DEPTH THRESHOLDS)
+    def set_link_thresholds(self, model, thresholds):
+        """Depth thresholds (metres, any float) of model `model`'s links, one per link in rtuf_add_link order."""
+        a = np.ascontiguousarray(thresholds, np.float32).reshape(-1)
+        self._check(self._lib.rtuf_set_link_thresholds(self._h, model, _ptr(a), len(a)))
+
+    def clear_link_thresholds(self, model):
+        """Model `model`'s links follow params.depth_distance_threshold again."""
+        self._check(self._lib.rtuf_clear_link_thresholds(self._h, model))
 
     # asynchronous host planes
     def host_alloc(self, shape, dtype):

@@ -17,3 +17,5 @@ for f in rtuf_node rtuf_nodelet; do
 done
 g++ -std=c++17 -O2 -Wall -Wextra -I"$mock/include" -I"$root/ros/include" -I"$root/include" "$mock/ros_adapter_harness.cpp" \
   -L"$here/../lib" -lrtuf -Wl,-rpath,'$ORIGIN/../../realtime_urdf_filter_amd/lib' -o "$root/examples/bin/ros_adapter_harness"
+g++ -std=c++17 -O2 -Wall -Wextra -I"$mock/include" -I"$root/ros/include" -I"$root/include" "$mock/ros_link_thresholds_harness.cpp" \
+  -L"$here/../lib" -lrtuf -Wl,-rpath,'$ORIGIN/../../realtime_urdf_filter_amd/lib' -o "$root/examples/bin/ros_link_thresholds_harness"

@@ -59,7 +59,8 @@ struct Kinematics {               // on-device forward kinematics of one model
   uint8_t* h_enabled = nullptr; uint8_t* d_enabled = nullptr;
 };
 // labels: rtuf_set_link_labels's labels of the model's links (empty: the default, 1 + link_base + link)
-struct HostModel { std::vector<HostLink> links; int link_base = 0; Kinematics kin; std::vector<uint16_t> labels; };
+// thresholds: rtuf_set_link_thresholds's depth thresholds of the model's links (empty: rtuf_params.depth_distance_threshold)
+struct HostModel { std::vector<HostLink> links; int link_base = 0; Kinematics kin; std::vector<uint16_t> labels; std::vector<float> thresholds; };
 
 char g_create_error[512] = "";
 
@@ -100,6 +101,11 @@ struct rtuf_context {
   std::vector<uint32_t> draw_link, draw_last_order;
   uint16_t* d_order_labels = nullptr;
   bool labels_dirty = true;
+  // Per-link depth thresholds: the device table draw order -> threshold, [n_tris + 1] (entry 0, the background quad: the
+  // global threshold), allocated by the first rtuf_set_link_thresholds and rewritten in place after that (captured graphs
+  // keep its address).  The tile kernels read it only while thresh_models > 0 (models with thresholds of their own).
+  float* d_order_thr = nullptr;
+  int thresh_models = 0;
 
   // per-frame pose staging
   // Cameras and link matrices are staged in a ring of kMaxInflight + 1 pinned sets, like the joint positions: every
@@ -176,6 +182,7 @@ struct rtuf_context {
     int n = 0; const float* depth = nullptr; float* masked = nullptr; uint8_t* mask = nullptr; bool u16 = false;
     uint32_t* bits = nullptr;                // mask-only output (1 bit per pixel) instead of masked / mask
     uint16_t* labels = nullptr;              // link label plane beside masked / mask (rtuf_filter_batch*_labels) or nullptr
+    const float* order_thr = nullptr;        // per-link thresholds: the draw order -> threshold table, or nullptr (set when first enqueued)
     Counters* h_counters = nullptr;          // pinned [max_groups]: one block per launch group, filled by the copies that end the batch
     hipEvent_t done[kMaxLanes] = {};         // recorded on each lane after its copy
     uint32_t lanes_used = 0;                 // bit l: the batch has launch groups on lane l
@@ -669,6 +676,7 @@ void rtuf_destroy(rtuf_context* c)
   free_frame_buffers(c);
   dev_free(c, c->d_cverts); dev_free(c, c->d_ctris); dev_free(c, c->d_corder); dev_free(c, c->d_chunks); dev_free(c, c->d_draws);
   dev_free(c, c->d_order_labels);
+  dev_free(c, c->d_order_thr);
   for (auto& b : c->batch) {
     for (hipEvent_t ev : b.events) hipEventDestroy(ev);
     for (hipEvent_t ev : b.done) if (ev) hipEventDestroy(ev);
@@ -685,6 +693,8 @@ void rtuf_destroy(rtuf_context* c)
   for (auto& ln : c->lane) if (ln.stream) hipStreamDestroy(ln.stream);
   delete c;
 }
+
+static int build_thresh_table(rtuf_context* c);
 
 int rtuf_set_params(rtuf_context* c, const rtuf_params* p)
 {
@@ -706,12 +716,15 @@ int rtuf_set_params(rtuf_context* c, const rtuf_params* p)
     return c->fail(RTUF_ERR_STATE, "far_plane is fixed once the models are finalized (was %g)", (double)c->params.far_plane);
   const uint32_t keep_cap = c->params.bin_capacity, keep_inf = c->params.max_inflight_streams, keep_pipes = c->params.pipelines;
   const uint32_t keep_lanes = c->params.raster_lanes, keep_limit = c->params.memory_limit_mb;
+  const float keep_thr = c->params.depth_distance_threshold;
   c->params = *p;
   c->params.bin_capacity = keep_cap;
   c->params.max_inflight_streams = keep_inf;
   c->params.pipelines = keep_pipes;
   c->params.raster_lanes = keep_lanes;
   c->params.memory_limit_mb = keep_limit;
+  // links without a threshold of their own (and the background quad drawn as geometry) follow the global one (bitwise: NaN too)
+  if (c->thresh_models > 0 && memcmp(&keep_thr, &c->params.depth_distance_threshold, sizeof(float)) != 0) return build_thresh_table(c);
   return RTUF_OK;      // (two-kernel mode's z-surfaces are allocated by the first batch that needs them)
 }
 
@@ -1514,6 +1527,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   // silhouette dilation: the tile kernel writes the z-surface and dilate_compare_kernel makes every output form from it (the
   // mask bits included); without it nothing here differs from before
   if (!rerun) b.dilation = (int)c->params.silhouette_dilation_px;
+  if (!rerun) b.order_thr = c->thresh_models > 0 ? c->d_order_thr : nullptr;
   const int dil = b.dilation;
   plan.zroute = dil > 0 || (two && !b.bits);
   // on-device forward kinematics overwrites the link matrices (and camera) of the streams that use it
@@ -1591,6 +1605,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     ta.bits = dil ? nullptr : b.bits;
     ta.labels = b.labels;                    // (the label calls refuse silhouette dilation and mask bits)
     ta.order_labels = b.labels ? c->d_order_labels : nullptr;
+    ta.order_thr = b.order_thr;              // (batches with per-link thresholds never take the z-surface route: check_thresh_route)
     gr.compare = two && !b.bits && !dil;
     gr.dilate = dil > 0;
     if (gr.dilate) {
@@ -1889,10 +1904,19 @@ static int retire_oldest(rtuf_context* c)
 // the batches of this context write the z-surface: two-kernel mode, or a silhouette dilation radius
 static bool uses_zsurface(const rtuf_context* c) { return (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 || c->params.silhouette_dilation_px > 0; }
 
+// per-link depth thresholds exist in the fused route only: the z-surface does not carry the winning link
+static int check_thresh_route(rtuf_context* c)
+{
+  if (c->thresh_models > 0 && uses_zsurface(c))
+    return c->fail(RTUF_ERR_INVALID, "per-link depth thresholds are not supported with RTUF_FLAG_TWO_KERNEL or silhouette dilation yet");
+  return RTUF_OK;
+}
+
 static int submit_batch(rtuf_context* c, int n, const float* d_depth, float* d_masked, uint8_t* d_mask, bool u16, uint32_t* d_bits = nullptr,
                         bool wait_upload = false, uint16_t* d_labels = nullptr)
 {
   if (c->broken) return c->fail(RTUF_ERR_STATE, "context unusable: a bin regrowth failed (%s)", c->error.c_str());
+  { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
   hipSetDevice(c->device);
   if (uses_zsurface(c))
     for (int l = 0; l < c->n_lanes; l++)
@@ -2051,6 +2075,7 @@ static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in
   if (bits_out) { const int rc = check_bits_call(c, n, depth_in, bits_out); if (rc != RTUF_OK) return rc; }
   for (int s = 0; s < n; s++)
     if (!depth_in[s] || (bits_out ? !bits_out[s] : !masked_out[s]) || (labels_out && !labels_out[s])) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
+  { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }      // (before the planes are staged)
   hipSetDevice(c->device);
   // (copy streams beside the lanes as well: an upload queued behind a lane's kernels would hold up the next batch)
   if (!c->h2d || !c->d2h) {
@@ -2251,6 +2276,66 @@ int rtuf_filter_batch_u16_labels(rtuf_context* c, int n, const uint16_t* const* 
   const int rc = filter_batch_labels_async(c, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(masked_out),
                                            mask_out, labels_out, true);
   return rc != RTUF_OK ? rc : rtuf_sync(c);
+}
+
+// ---- per-link depth thresholds -----------------------------------------------------------------------
+// The same draw order the labels use, turned into the threshold of the winner's link: the table draw order -> threshold,
+// built on the host from every draw's link and the models' thresholds (the global one where a model has none).
+static int build_thresh_table(rtuf_context* c)
+{
+  std::vector<float> link_thr((size_t)c->n_links, c->params.depth_distance_threshold);
+  int with = 0;
+  for (const HostModel& m : c->models) {
+    if (m.thresholds.empty()) continue;
+    with++;
+    for (size_t l = 0; l < m.links.size(); l++) link_thr[(size_t)m.link_base + l] = m.thresholds[l];
+  }
+  std::vector<float> table((size_t)c->n_tris + 1, c->params.depth_distance_threshold);
+  for (size_t d = 0, first = 1; d < c->draw_link.size(); d++) {
+    const float t = link_thr[c->draw_link[d]];
+    for (size_t o = first; o <= c->draw_last_order[d]; o++) table[o] = t;
+    first = (size_t)c->draw_last_order[d] + 1;
+  }
+  hipSetDevice(c->device);
+  if (!c->d_order_thr) HIP_TRY(c, dev_alloc(c, &c->d_order_thr, table.size() * sizeof(float)));
+  // (no batch in flight reads the table: every caller waited for them, and a new table has never been read)
+  HIP_TRY(c, hipMemcpy(c->d_order_thr, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+  c->thresh_models = with;
+  return RTUF_OK;
+}
+
+int rtuf_set_link_thresholds(rtuf_context* c, int model, const float* depth_distance_threshold, int n_links)
+{
+  KIDS_ALL(c, rtuf_set_link_thresholds(k, model, depth_distance_threshold, n_links));
+  if (!c) return RTUF_ERR_INVALID;
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (model < 0 || model >= (int)c->models.size()) return c->fail(RTUF_ERR_INVALID, "bad model id %d", model);
+  HostModel& m = c->models[model];
+  if (!depth_distance_threshold || n_links != (int)m.links.size())
+    return c->fail(RTUF_ERR_INVALID, "model %d has %d links (got %d thresholds)", model, (int)m.links.size(), n_links);
+  WAIT_IF_PENDING(c);
+  std::vector<float> keep = m.thresholds;
+  m.thresholds.assign(depth_distance_threshold, depth_distance_threshold + n_links);      // (a model without links stays without)
+  const int rc = build_thresh_table(c);
+  if (rc != RTUF_OK) m.thresholds = keep;
+  return rc;
+}
+
+int rtuf_clear_link_thresholds(rtuf_context* c, int model)
+{
+  KIDS_ALL(c, rtuf_clear_link_thresholds(k, model));
+  if (!c) return RTUF_ERR_INVALID;
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (model < 0 || model >= (int)c->models.size()) return c->fail(RTUF_ERR_INVALID, "bad model id %d", model);
+  WAIT_IF_PENDING(c);
+  HostModel& m = c->models[model];
+  if (m.thresholds.empty()) return RTUF_OK;
+  std::vector<float> keep;
+  keep.swap(m.thresholds);
+  if (c->thresh_models == 1) { c->thresh_models = 0; return RTUF_OK; }      // the last one: the plain kernels from here on
+  const int rc = build_thresh_table(c);
+  if (rc != RTUF_OK) m.thresholds.swap(keep);
+  return rc;
 }
 
 int rtuf_wait_oldest(rtuf_context* c)

@@ -323,6 +323,8 @@ struct TileArgs {
   // link labels (appended: the fields above keep their kernarg offsets).  labels != nullptr selects tile_labels_kernel.
   uint16_t* labels;              // [n][H][W] link label of every pixel's winner, 8-byte aligned; nullptr = none
   const uint16_t* order_labels;  // [n_tris + 1] label of every draw order (entry 0, background / no fragment: 0)
+  // per-link depth thresholds (appended).  order_thr != nullptr selects tile_thresh_kernel (fused route only).
+  const float* order_thr;        // [n_tris + 1] threshold of every draw order's link (entry 0, the background quad: max_diff)
 };
 
 struct CompareArgs {

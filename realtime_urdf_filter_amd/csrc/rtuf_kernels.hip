@@ -2161,6 +2161,13 @@ __device__ __forceinline__ float shade_threshold(float z, const ShadeConsts& k)
   const float virt = k.core ? div_core(k.num, d) : __fdiv_rn(k.num, d);
   return __fsub_rn(virt, k.max_diff);
 }
+// the same with a threshold of its own in place of max_diff (per-link depth thresholds)
+__device__ __forceinline__ float shade_threshold(float z, const ShadeConsts& k, float max_diff)
+{
+  const float d = __fsub_rn(z, k.off);
+  const float virt = k.core ? div_core(k.num, d) : __fdiv_rn(k.num, d);
+  return __fsub_rn(virt, max_diff);
+}
 
 __device__ __forceinline__ float shade(float sensor, float z, const ShadeConsts& k, bool& filt)
 {
@@ -2171,7 +2178,9 @@ __device__ __forceinline__ float shade(float sensor, float z, const ShadeConsts&
 // COVER: the batch ran the cover pass (bigrec_kernel<0>), so a bin's header may name a cover.  Without it (the host skips the
 // pass while no scene has triangles that cover whole tiles) the cover code is compiled out: it costs the headline workload 3 %.
 // LABELS: the kernel also writes the link label plane (a.labels, a.order_labels: rtuf_filter_batch*_labels); never with BITS.
-template <bool TWO_KERNEL, bool U16, bool BITS, bool COVER, int NT, bool LABELS = false>
+// THRESH: a drawn pixel is compared with its winner's link threshold (a.order_thr: rtuf_set_link_thresholds) instead of
+// max_diff; the background plane keeps thr_bg.  Fused route only (never with TWO_KERNEL).
+template <bool TWO_KERNEL, bool U16, bool BITS, bool COVER, int NT, bool LABELS = false, bool THRESH = false>
 __device__ __forceinline__ void tile_body(const TileArgs& a)
 {
   __shared__ unsigned long long keys[kKeyCount];
@@ -2208,7 +2217,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   kf.abl = a.flags;
   kf.lowmask = near_tile ? (1u << a.key_shift) - 1u : 0u;
   kf.zexact = near_tile ? exact_z_floor(a.key_shift) : 8388609u;
-  kf.keep_order = LABELS;
+  kf.keep_order = LABELS || THRESH;
   const uint32_t count = count_front + count_back;
   // (the stream's background entry after the bin's header in program order: the compiler then issues the three scalar loads
   // together -- with the background first it waited for it before it even computed the header's address)
@@ -2266,6 +2275,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   bool cover_only = false;
   float cov_a0 = 0.0f, cov_dzdx = 0.0f, cov_dzdy = 0.0f;
   uint32_t cov_label = 0;                    // LABELS: the cover's link label, one lookup per tile
+  float cov_thr = 0.0f;                      // THRESH: the cover's link threshold, one lookup per tile
   if constexpr (COVER) {
     cover_only = has_cover && n == 0 && nf == 0 && !empty;
     if (cover_only) {
@@ -2275,6 +2285,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
       cov_dzdx = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.y));
       cov_dzdy = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.z));
       if (LABELS) cov_label = a.order_labels[(uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask];
+      if (THRESH) cov_thr = a.order_thr[(uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask];
 #ifdef RTUF_COUNT
       if (tid < 2) count_words()[tid] = 0u;
 #endif
@@ -2503,7 +2514,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
           frag[j] = drawn ? true : analytic_bg;
           thr[j] = thr_bg;
           lab[j] = drawn ? cov_label : 0u;
-          if (drawn && !TWO_KERNEL) thr[j] = shade_threshold(zf, sc);
+          if (drawn && !TWO_KERNEL) thr[j] = THRESH ? shade_threshold(zf, sc, cov_thr) : shade_threshold(zf, sc);
 #ifdef RTUF_COUNT
           if (drawn && r_px + j < a.width) atomicAdd(&count_words()[1], 1u);
 #endif
@@ -2540,10 +2551,16 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
                 if (khi <= 8388608u) z[j] = near_z_from_key(khi, (uint32_t)k & kf.lowmask, kf.shift);
               }
             }
-            if (!TWO_KERNEL) thr[j] = shade_threshold(z[j], sc);
+            if (!TWO_KERNEL && !THRESH) thr[j] = shade_threshold(z[j], sc);
             // the winner's draw order: the key's (or, after the exact-z pass, kept above the float z: resolved_key); 0 is
-            // "no fragment" (kNoFragment), whose table entry is label 0
-            if (LABELS) lab[j] = a.order_labels[(k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift];
+            // "no fragment" (kNoFragment), whose table entry is label 0 -- and the background quad drawn as geometry, whose
+            // threshold entry is max_diff
+            if (LABELS && !THRESH) lab[j] = a.order_labels[(k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift];
+            if (THRESH) {
+              const uint32_t ord = (k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift;
+              thr[j] = shade_threshold(z[j], sc, a.order_thr[ord]);
+              if (LABELS) lab[j] = a.order_labels[ord];
+            }
           }
         }
         flags4 = finish(ps, z, thr, frag, lab);
@@ -2602,6 +2619,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(COVER ? RTUF
 #endif
 template <bool TWO_KERNEL, bool U16, bool COVER, int NT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_LABELS))) void tile_labels_kernel(TileArgs a) { tile_body<TWO_KERNEL, U16, false, COVER, NT, true>(a); }
+// per-link depth thresholds (rtuf_set_link_thresholds): the fused tile_kernel, tile_bits_kernel and tile_labels_kernel with
+// one more gather (4 B, from the draw order -> threshold table) per drawn pixel
+#ifndef RTUF_TILE_WAVES_THRESH
+#define RTUF_TILE_WAVES_THRESH 7
+#endif
+template <bool U16, bool BITS, bool LABELS, bool COVER, int NT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_THRESH))) void tile_thresh_kernel(TileArgs a) { tile_body<false, U16, BITS, COVER, NT, LABELS, true>(a); }
 
 // ---------------------------------------------------------------------------------------
 // compare_kernel (two-kernel mode): streaming, 13 B/pixel (4 sensor + 4 z + 4 masked + 1 mask)
@@ -2946,7 +2970,16 @@ template <bool COVER, int NT>
 static void launch_tile_variant(const TileArgs& a, bool two_kernel, hipStream_t st)
 {
   const dim3 grid(a.tiles_x, a.tiles_y, a.group_size);
-  if (a.labels) {
+  if (a.order_thr) {                         // (the host refuses per-link thresholds in two-kernel mode)
+    if (a.labels) {
+      if (a.io_u16) hipLaunchKernelGGL((tile_thresh_kernel<true, false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
+      else hipLaunchKernelGGL((tile_thresh_kernel<false, false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
+    } else if (a.bits) {
+      if (a.io_u16) hipLaunchKernelGGL((tile_thresh_kernel<true, true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
+      else hipLaunchKernelGGL((tile_thresh_kernel<false, true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
+    } else if (a.io_u16) hipLaunchKernelGGL((tile_thresh_kernel<true, false, false, COVER, NT>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((tile_thresh_kernel<false, false, false, COVER, NT>), grid, dim3(NT), 0, st, a);
+  } else if (a.labels) {
     if (two_kernel) hipLaunchKernelGGL((tile_labels_kernel<true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
     else if (a.io_u16) hipLaunchKernelGGL((tile_labels_kernel<false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
     else hipLaunchKernelGGL((tile_labels_kernel<false, false, COVER, NT>), grid, dim3(NT), 0, st, a);

@@ -99,6 +99,8 @@ class URDFRenderer:
         self.tf_ = tf
         self.mesh_loader = mesh_loader
         self.renderables_ = []
+        self.link_names_ = []                     # every link of the URDF, ignored ones included
+        self.link_thresholds_ = {}                # URDF link name -> depth threshold of its own (RealtimeURDFFilter.loadModels)
         self.initURDFModel()
 
     def initURDFModel(self):
@@ -110,6 +112,7 @@ class URDFRenderer:
         self.loadURDFModel(model)
 
     def loadURDFModel(self, model):
+        self.link_names_ = [link.name for link in model.get_links()]
         for link in model.get_links():
             self.process_link(link)
 
@@ -169,7 +172,8 @@ class FilterParameters:
                  own_calibration=(585.260, 585.028, 317.387, 239.264), silhouette_dilation_px=0):
         self.fixed_frame = fixed_frame
         self.camera_frame = camera_frame
-        self.models = models                 # list of dicts: model, tf_prefix, geometry_type, [scale], [ignore]
+        self.models = models                 # list of dicts: model, tf_prefix, geometry_type, [scale], [ignore],
+        #                                      [link_depth_distance_thresholds: [{"link": URDF link name, "threshold": metres}]]
         self.depth_distance_threshold = float(depth_distance_threshold)
         self.camera_offset_translation = tuple(camera_offset_translation)
         self.camera_offset_rotation = tuple(camera_offset_rotation)     # x y z w
@@ -250,6 +254,13 @@ class RealtimeURDFFilter:
             self.renderers_.append(URDFRenderer(content, elem.get("tf_prefix", ""), self.cam_frame_, self.fixed_frame_,
                                                 self.tf_, elem.get("geometry_type", ""), elem.get("scale", 1.0),
                                                 ignore, self.mesh_loader))
+            # new, beyond the reference: per-link depth thresholds [{"link": <URDF link name>, "threshold": <metres>}, ...]
+            rd = self.renderers_[-1]
+            rd.link_thresholds_ = {}
+            for e in elem.get("link_depth_distance_thresholds", []) or []:
+                if e["link"] not in rd.link_names_:
+                    raise ValueError("link_depth_distance_thresholds of model %r: no link %r in its URDF" % (description_param, e["link"]))
+                rd.link_thresholds_[e["link"]] = float(e["threshold"])
 
     def initGL(self):
         """src/urdf_filter.cpp:386-436 without GL: create the device context for width_ x height_,
@@ -285,6 +296,12 @@ class RealtimeURDFFilter:
             if rd.renderables_ and self.want_labels_:
                 self._ctx.set_link_labels(m, [self.link_labels_[(mi, r.urdf_link)] for r in rd.renderables_])
         self.labels_ = np.zeros((self.height_, self.width_), np.uint16) if self.want_labels_ else None
+        # per-link depth thresholds: every renderable of a listed URDF link takes its value, the model's other links the
+        # global threshold (links on the model's `ignore` list have no renderable: their entries have no effect)
+        for rd, m in zip(self.renderers_, self._model_ids):
+            if rd.link_thresholds_ and rd.renderables_:
+                self._ctx.set_link_thresholds(m, [rd.link_thresholds_.get(r.urdf_link, self.depth_distance_threshold_)
+                                                  for r in rd.renderables_])
         self.masked_depth_ = np.zeros((self.height_, self.width_), np.float32)
         self.mask_ = np.zeros((self.height_, self.width_), np.uint8)
 

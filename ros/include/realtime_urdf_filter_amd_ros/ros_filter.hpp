@@ -208,7 +208,7 @@ class RosFilter {
   {
     XmlRpc::XmlRpcValue models;
     if (!nh_.getParam("models", models) || models.getType() != XmlRpc::XmlRpcValue::TypeArray) {
-      ROS_ERROR("~models must be a list of {model, tf_prefix, geometry_type[, scale][, ignore]} entries");
+      ROS_ERROR("~models must be a list of {model, tf_prefix, geometry_type[, scale][, ignore][, link_depth_distance_thresholds]} entries");
       return;
     }
     for (int i = 0; i < models.size(); ++i) {
@@ -224,6 +224,21 @@ class RosFilter {
         if (ig.getType() == XmlRpc::XmlRpcValue::TypeString) mp.ignore.insert(static_cast<std::string>(ig));
         else if (ig.getType() == XmlRpc::XmlRpcValue::TypeArray) for (int k = 0; k < ig.size(); k++) mp.ignore.insert(static_cast<std::string>(ig[k]));
         else ROS_ERROR("~models[%d]/ignore: a link name or a list of link names", i);
+      }
+      // new, beyond the reference: [{link: <URDF link name>, threshold: <metres>}, ...] (per-link depth thresholds)
+      if (e.hasMember("link_depth_distance_thresholds")) {
+        XmlRpc::XmlRpcValue& lt = e["link_depth_distance_thresholds"];
+        if (lt.getType() != XmlRpc::XmlRpcValue::TypeArray) ROS_ERROR("~models[%d]/link_depth_distance_thresholds: a list of {link, threshold}", i);
+        else for (int k = 0; k < lt.size(); k++) {
+          XmlRpc::XmlRpcValue& x = lt[k];
+          if (x.getType() != XmlRpc::XmlRpcValue::TypeStruct || !x.hasMember("link") || !x.hasMember("threshold")) {
+            ROS_ERROR("~models[%d]/link_depth_distance_thresholds[%d] is not a {link, threshold} struct", i, k);
+            continue;
+          }
+          XmlRpc::XmlRpcValue& t = x["threshold"];
+          const double v = t.getType() == XmlRpc::XmlRpcValue::TypeInt ? (double)(int)t : (double)t;
+          mp.link_depth_distance_thresholds.emplace_back(static_cast<std::string>(x["link"]), v);
+        }
       }
       // the URDF itself: the named parameter in this namespace, else wherever searchParam finds it (robot_description usually lives above)
       std::string xml, where;

@@ -1,0 +1,498 @@
+"""GPU (-m gpu): per-link depth thresholds (include/rtuf.h, PER-LINK DEPTH THRESHOLDS; rtuf_set_link_thresholds,
+rtuf_clear_link_thresholds).
+
+The expectation maps the CPU oracle's winning source triangle (`prim`) through the draw list it was given: draw -> link ->
+threshold, the global threshold where the background quad won, and shades the oracle's window z with it in numpy float32
+(bench_support/link_thresholds_check.py).  Every pixel of every stream is compared, 0 mismatches, in every output form of the
+fused route."""
+import numpy as np
+import pytest
+
+import golden_io
+import scenes as S
+import realtime_urdf_filter_amd as R
+from bench_support import configs as CF
+from bench_support import workloads as WL
+from bench_support.link_thresholds_check import (expected_planes, link_values, share_draws, workload_draws,
+                                                 workload_link_base)
+from oracle import bindings as O
+from realtime_urdf_filter_amd.filter import depth_f32_to_u16, depth_u16_to_f32
+from test_batch_status_gpu import params
+from test_silhouette_dilation_gpu import _centred, _quad, soup_scene
+
+pytestmark = pytest.mark.gpu
+INVALID = -1
+F = np.float32
+SPECIAL = [0.0, -0.03, np.nan, np.inf, -np.inf, 0.05, 0.5, 1e-4]
+
+
+def _torch():
+    import torch
+    return torch, torch.device("cuda:0")
+
+
+# ---- expectations -------------------------------------------------------------------------------------------------------
+
+def oracle_planes(frames, depth):
+    """([n,H,W] window z, [n,H,W] prim) of (projection, draws, offset_inv, cam_tf, near, far) frames on all usable host cores."""
+    prep = [O.PreparedFrame(depth[s], P, draws, off, cam, z_near=zn, z_far=zf, want_debug=True)
+            for s, (P, draws, off, cam, zn, zf) in enumerate(frames)]
+    O.run_prepared(prep, O.usable_threads())
+    return np.stack([f.zwin for f in prep]), np.stack([f.prim for f in prep])
+
+
+class Planes:
+    """Oracle planes of a batch and the expected outputs for any link thresholds.  draws(s, link_thr) -> (threshold,
+    triangle count) of every draw stream s was rendered with."""
+
+    def __init__(self, depth, zwin, prim, draws, near, far, replace, global_thr):
+        self.depth = np.ascontiguousarray(depth, np.float32)
+        self.zwin, self.prim, self.draws = zwin, prim, draws
+        self.near, self.far, self.replace, self.global_thr = near, far, replace, global_thr
+        self.n, self.H, self.W = self.depth.shape
+
+    def expected(self, link_thr, u16=False, global_thr=None):
+        g = self.global_thr if global_thr is None else global_thr
+        ms, ks = [], []
+        for s in range(self.n):
+            sensor = depth_u16_to_f32(depth_f32_to_u16(self.depth[s])) if u16 else self.depth[s]
+            m, k = expected_planes(self.zwin[s], self.prim[s], sensor, *self.draws(s, link_thr), g, self.near, self.far, self.replace)
+            ms.append(depth_f32_to_u16(m) if u16 else m)
+            ks.append(k)
+        return np.stack(ms), np.stack(ks)
+
+
+def wl_planes(wl, depth=None):
+    depth = np.ascontiguousarray(wl.depth_batch() if depth is None else depth, np.float32)
+    zwin, prim = oracle_planes([(wl.projection[s], wl.oracle_draws(s), wl.offset_inv[s], wl.cam_tf[s], wl.near, wl.far)
+                                for s in range(wl.n_streams)], depth)
+    return Planes(depth, zwin, prim, lambda s, t: workload_draws(wl, t), wl.near, wl.far, wl.replace_value, wl.max_diff)
+
+
+def wl_context(wl, max_streams=None, n=None, global_thr=None, **kw):
+    p = params(replace=wl.replace_value, max_diff=wl.max_diff if global_thr is None else global_thr, **kw)
+    p.near_plane, p.far_plane = wl.near, wl.far
+    ctx = R.Context(wl.width, wl.height, max_streams or wl.n_streams, 0, p)
+    ids = wl.load_into(ctx)
+    wl.stage(ctx, ids, n=n or min(wl.n_streams, max_streams or wl.n_streams))
+    return ctx, ids
+
+
+# ---- every output form of the fused route --------------------------------------------------------------------------------
+
+def _cmp(got_m, got_k, want_m, want_k, what, u16):
+    if got_k is not None:
+        bad = np.asarray(got_k) != want_k
+        if bad.any():
+            s, y, x = np.argwhere(bad)[0]
+            raise AssertionError("%s: %d mask pixels differ (first: stream %d y %d x %d: %d instead of %d)"
+                                 % (what, int(bad.sum()), s, y, x, int(np.asarray(got_k)[s, y, x]), int(want_k[s, y, x])))
+    if got_m is not None:
+        g = np.asarray(got_m)
+        bad = (g != want_m) if u16 else (np.ascontiguousarray(g, np.float32).view(np.uint32) != want_m.view(np.uint32))
+        assert not bad.any(), "%s: %d masked pixels differ" % (what, int(bad.sum()))
+
+
+def _unpack_bits(bits, n, H, W):
+    b = np.ascontiguousarray(bits).view(np.uint8).reshape(n, H, -1)
+    return (np.unpackbits(b, axis=2, bitorder="little")[:, :, :W] * 255).astype(np.uint8)
+
+
+def run_form(ctx, form, depth, n):
+    """(masked, mask) of one batch through `form` (mask bits come back as a 0 / 255 mask, masked None)."""
+    u16 = form.endswith("u16")
+    d = depth_f32_to_u16(depth[:n]) if u16 else np.ascontiguousarray(depth[:n], np.float32)
+    H, W = d.shape[1:]
+    if form.startswith("host"):
+        return (ctx.filter_batch_u16 if u16 else ctx.filter_batch)(d)
+    if form.startswith("labels_host"):
+        m, k, _ = ctx.filter_batch_labels(d)
+        return m, k
+    if form.startswith("async"):
+        pin_in, pin_out, pin_k = ctx.host_alloc(d.shape, d.dtype), ctx.host_alloc(d.shape, d.dtype), ctx.host_alloc(d.shape, np.uint8)
+        pin_in[:] = d
+        ctx.filter_batch_async(pin_in, pin_out, pin_k)
+        ctx.sync()
+        out = (pin_out.copy(), pin_k.copy())
+        for a in (pin_in, pin_out, pin_k):
+            ctx.host_free(a)
+        return out
+    if form.startswith("bits_async"):
+        pin_in, pin_bits = ctx.host_alloc(d.shape, d.dtype), ctx.host_alloc((n, ctx.mask_bits_words()), np.uint32)
+        pin_in[:] = d
+        ctx.filter_batch_bits_async(pin_in, pin_bits)
+        ctx.sync()
+        k = _unpack_bits(pin_bits.copy(), n, H, W)
+        ctx.host_free(pin_in)
+        ctx.host_free(pin_bits)
+        return None, k
+    torch, dev = _torch()
+    td = torch.from_numpy(d.view(np.int16) if u16 else d).to(dev)
+    if form.startswith("bits_device"):
+        bits = torch.zeros((n, ctx.mask_bits_words()), dtype=torch.int32, device=dev)
+        ctx.filter_batch_device_bits(n, td.data_ptr(), bits.data_ptr(), u16=u16)
+        ctx.sync()
+        return None, _unpack_bits(bits.cpu().numpy(), n, H, W)
+    m = torch.empty_like(td)
+    k = torch.empty(td.shape, dtype=torch.uint8, device=dev)
+    if form.startswith("labels_device"):
+        lab = torch.empty(td.shape, dtype=torch.int16, device=dev)
+        ctx.filter_batch_device_labels(n, td.data_ptr(), m.data_ptr(), k.data_ptr(), lab.data_ptr(), u16=u16)
+    elif u16:
+        ctx.filter_batch_device_u16(n, td.data_ptr(), m.data_ptr(), k.data_ptr())
+    else:
+        ctx.filter_batch_device(n, td.data_ptr(), m.data_ptr(), k.data_ptr())
+    ctx.sync()
+    mm = m.cpu().numpy()
+    return (mm.view(np.uint16) if u16 else mm), k.cpu().numpy()
+
+
+FORMS = ["host", "device", "async", "bits_device", "bits_async", "labels_host", "labels_device"]
+
+
+def check_forms(ctx, pl, link_thr, what, forms=None, n=None, global_thr=None):
+    n = n or pl.n
+    want = {False: None, True: None}
+    for form in (forms or FORMS):
+        for u16 in ((False, True) if pl.W % 4 == 0 else (False,)):
+            # (mask bits need a width that is a multiple of 4 and a background quad over the whole image: the batch fails
+            # with RTUF_ERR_STATE at sync otherwise, thresholds or not)
+            if form.startswith("bits") and (pl.W % 4 or (pl.prim[:n] == -1).any()):
+                continue
+            if want[u16] is None:
+                wm, wk = pl.expected(link_thr, u16, global_thr)
+                want[u16] = (wm[:n], wk[:n])
+            f = form + ("_u16" if u16 else "")
+            got_m, got_k = run_form(ctx, f, pl.depth, n)
+            _cmp(got_m, got_k, want[u16][0], want[u16][1], "%s %s" % (what, f), u16)
+    assert ctx.stats()["batch_status"] == 0
+    return want[False]
+
+
+# ---- 1. two links at one depth ---------------------------------------------------------------------------------------------
+
+def _two_link_workload(W=160, H=128, n=1):
+    wl = WL.Workload("two_links", W, H, n)
+
+    class D:
+        def __init__(self, g):
+            self.pre_op, self.op, self.verts, self.tris = g
+    geo = [_quad(-0.5, -0.05, -0.3, 0.3, 1.0), _quad(0.05, 0.5, -0.3, 0.3, 1.0)]
+    wl.models = [[[D(g)] for g in geo]]
+    wl.link_tf = [np.tile(S.gl(np.eye(4)), (n, len(geo), 1))]
+    wl.projection = np.tile(_centred(W, H), (n, 1))
+    wl.offset_inv = np.tile(S.gl(np.eye(4)), (n, 1))
+    wl.cam_tf = np.tile(S.gl(np.eye(4)), (n, 1))
+    return wl
+
+
+def test_two_links_one_depth_only_the_wide_link_filters():
+    """Two boxes side by side at one depth, the sensor 0.10 m in front of both: the global threshold 0.05 keeps them, link
+    A's 0.20 filters exactly A's pixels -- in every output form, rtuf_filter included."""
+    wl = _two_link_workload()
+    zwin, prim = oracle_planes([(wl.projection[0], wl.oracle_draws(0), wl.offset_inv[0], wl.cam_tf[0], wl.near, wl.far)],
+                               np.zeros((1, wl.height, wl.width), np.float32))
+    drawn = prim[0] >= 0
+    virt = (F(wl.near) * F(wl.far) / (F(wl.near) - F(wl.far))) / (zwin[0] - F(wl.far) / (F(wl.far) - F(wl.near)))
+    depth = np.where(drawn, virt - F(0.10), F(3.0)).astype(np.float32)[None]
+    pl = wl_planes(wl, depth)
+    ctx, ids = wl_context(wl)
+    ctx.set_link_thresholds(ids[0], [0.20, 0.05])
+    m, k = check_forms(ctx, pl, [0.20, 0.05], "two links")
+    a_pixels = (pl.prim[0] >= 0) & (pl.prim[0] < 2)           # link A's two triangles come first in the draw list
+    assert a_pixels.sum() > 500 and ((pl.prim[0] >= 2).sum() > 500)
+    assert np.array_equal(k[0] == 255, a_pixels)
+    mk = ctx.filter(pl.depth[0], wl.projection[0])[1]           # rtuf_filter: the single-stream call
+    assert np.array_equal(mk == 255, a_pixels)
+    ctx.close()
+
+
+# ---- 2. golden fixtures with random thresholds -------------------------------------------------------------------------------
+
+def _fixture_thresholds(rng, n, global_thr):
+    return np.array([SPECIAL[i] if i < len(SPECIAL) and rng.random() < 0.5 else
+                     (global_thr if rng.random() < 0.2 else rng.uniform(-0.2, 0.6)) for i in rng.permutation(max(n, len(SPECIAL)))[:n]],
+                    np.float32)
+
+
+@pytest.mark.parametrize("name", golden_io.fixture_names())
+def test_golden_fixtures_random_thresholds(name):
+    fx = golden_io.Fixture(name)
+    p = params(fx.replace_value, fx.max_diff, near_plane=fx.z_near, far_plane=fx.z_far)
+    ctx = R.Context(fx.width, fx.height, 1, 0, p)
+    m, tfs = fx.load_into(ctx)
+    ctx.set_camera(0, fx.projection, fx.offset_inv, fx.cam_tf)
+    if len(tfs):
+        ctx.set_link_poses(0, m, tfs)
+    zwin, prim = oracle_planes([(fx.projection, fx.draws, fx.offset_inv, fx.cam_tf, fx.z_near, fx.z_far)], fx.depth[None])
+    ntris = [len(d[4]) for d in fx.draws]
+    pl = Planes(fx.depth[None], zwin, prim, lambda s, t: (list(t), ntris), fx.z_near, fx.z_far, fx.replace_value, fx.max_diff)
+    masked, mask = ctx.filter_batch(fx.depth[None])
+    fx.check(masked[0], mask[0])                               # (the plain call, for the record)
+    rng = np.random.default_rng(sum(map(ord, name)))
+    for trial in range(2):
+        t = _fixture_thresholds(rng, len(fx.draws), fx.max_diff)
+        if len(t):
+            ctx.set_link_thresholds(m, t)
+        check_forms(ctx, pl, t, "%s trial %d" % (name, trial), forms=["host", "device", "bits_device", "labels_host"])
+    ctx.close()
+
+
+@pytest.mark.parametrize("lanes,pipelines", [(1, 1), (2, 1), (3, 1), (3, 2)])
+def test_lanes_and_pipelines(lanes, pipelines):
+    sc = soup_scene(3, 320, 240, n=6)
+    pl = wl_planes(sc.wl, sc.depth)
+    ctx, ids = wl_context(sc.wl, raster_lanes=lanes, pipelines=pipelines)
+    rng = np.random.default_rng(lanes * 10 + pipelines)
+    t = _fixture_thresholds(rng, ctx.num_links(ids[0]), sc.wl.max_diff)
+    ctx.set_link_thresholds(ids[0], t)
+    for _ in range(2):
+        check_forms(ctx, pl, t, "lanes %d pipelines %d" % (lanes, pipelines), forms=["device", "host", "bits_device"])
+    ctx.close()
+
+
+# ---- 3. BASELINE sizes ---------------------------------------------------------------------------------------------------
+
+def run_share(share, n, set_thr, link_thr, forms=("device",)):
+    """Loads a RankShare, sets thresholds through set_thr(ctx), filters step 0 and checks against the oracle; returns the
+    expected mask, the same without per-link thresholds, and the stats."""
+    p = params(replace=share.wl0.replace_value, max_diff=share.wl0.max_diff)
+    ctx = R.Context(share.width, share.height, n, 0, p)
+    share.load(ctx)
+    set_thr(ctx)
+    share.stage(ctx, 0)
+    depth = np.ascontiguousarray(share.depth_host(0), np.float32)
+    run_form(ctx, "device", depth, n)                # (the share poses its links on the device: one batch before they are read)
+    link_dev, cam_dev = ctx.read_poses(n, share.n_links_total)
+    frames = []
+    for s in range(n):
+        P, draws, off, cam = share.oracle_frame(0, s, link_dev, cam_dev)
+        frames.append((P, draws, off, cam, share.wl0.near, share.wl0.far))
+    zwin, prim = oracle_planes(frames, depth)
+    pl = Planes(depth, zwin, prim, lambda s, t: share_draws(share, s, t), share.wl0.near, share.wl0.far,
+                share.wl0.replace_value, share.wl0.max_diff)
+    _, k = check_forms(ctx, pl, link_thr, "share", forms=list(forms))
+    _, k0 = pl.expected(np.full(share.n_links_total, share.wl0.max_diff, np.float32))
+    st = ctx.stats()
+    ctx.close()
+    return k, k0, st
+
+
+def _share_thresholds(share, per_model):
+    return link_values(share.n_links_total, share.wl0.max_diff, per_model, share.link_base)
+
+
+def share_links(share):
+    """{context model id: number of links} of a RankShare (from its link_base; needs share.load to have run)."""
+    order = sorted(share.link_base, key=lambda m: share.link_base[m])
+    ends = [share.link_base[m] for m in order[1:]] + [share.n_links_total]
+    return {m: e - share.link_base[m] for m, e in zip(order, ends)}
+
+
+def loaded(share):
+    """The share with its context model ids known (share.load on a throw-away context)."""
+    p = params(replace=share.wl0.replace_value, max_diff=share.wl0.max_diff)
+    ctx = R.Context(share.width, share.height, share.n, 0, p)
+    share.load(ctx)
+    ctx.close()
+    return share_links(share)
+
+
+def _setter(per):
+    return lambda ctx: [ctx.set_link_thresholds(m, t) for m, t in per.items()]
+
+
+def test_config3_256_streams():
+    share = CF.build("c3", 1, 0)
+    rng = np.random.default_rng(7)
+    # (the sensor sees the robot where it is drawn: only links that never filter change much of the mask)
+    per = {m: np.where(rng.random(nl) < 0.5, -np.inf, rng.uniform(-0.02, 0.3, nl)).astype(np.float32) for m, nl in loaded(share).items()}
+    k, k0, _ = run_share(share, share.n, _setter(per), _share_thresholds(share, per), forms=("device", "bits_device"))
+    assert (k != k0).sum() > 1000
+
+
+@pytest.mark.parametrize("forms", [("device", "labels_device"), ("host", "bits_device")])
+def test_config3_near_arm_exact_z_winners_use_their_own_link(forms):
+    share = CF.build("c3", 1, 0, streams=16, near_arm=True)
+    per = {m: np.linspace(0.4, -0.01, nl).astype(np.float32) for m, nl in loaded(share).items()}
+    k, k0, st = run_share(share, share.n, _setter(per), _share_thresholds(share, per), forms)
+    assert st["exact_tiles"] > 0
+    assert (k != k0).any()
+
+
+def test_config4_share_720p_walls_cover_tiles_use_the_cover_link():
+    share = CF.build("c4", 8, 0, streams=64)
+    links = loaded(share)
+    g = share.groups[0]
+    robot, walls = g.model_ids[0], list(g.model_ids[1:])
+    per = {robot: np.full(links[robot], 0.12, np.float32)}
+    for w in walls:
+        per[w] = np.full(links[w], -np.inf if w == walls[0] else 0.9, np.float32)
+    k, k0, st = run_share(share, share.n, _setter(per), _share_thresholds(share, per), forms=("device", "bits_device"))
+    assert st["cover_tiles"] > 0
+    assert (k != k0).sum() > 1000
+
+
+def test_config5_share_some_models_set_some_inherit():
+    share = CF.build("c5", 8, 0, per_urdf=8)
+    links = loaded(share)
+    set_models = [g.model_ids[0] for i, g in enumerate(share.groups) if i % 2 == 0]
+    per = {m: np.where(np.arange(links[m]) % 2, 0.3, np.nan).astype(np.float32) for m in set_models}
+    k, k0, _ = run_share(share, share.n, _setter(per), _share_thresholds(share, per), forms=("device", "host"))
+    assert (k != k0).any()
+    for i, g in enumerate(share.groups):                  # the inheriting robots' streams filter as without thresholds
+        if i % 2:
+            assert np.array_equal(k[g.first:g.first + g.count], k0[g.first:g.first + g.count])
+
+
+# ---- 4. identity and clear -----------------------------------------------------------------------------------------------
+
+def _plain_outputs(ctx, depth, n):
+    return {f: run_form(ctx, f, depth, n) for f in ("device", "device_u16", "bits_device", "host")}
+
+
+def _same(a, b, what):
+    for f in a:
+        for x, y in zip(a[f], b[f]):
+            if x is None:
+                assert y is None
+            else:
+                assert np.array_equal(np.asarray(x).view(np.uint8), np.asarray(y).view(np.uint8)), "%s %s" % (what, f)
+
+
+def test_identity_and_clear_give_the_plain_planes():
+    wl = WL.pr2_workload(3, 640, 480, total_triangles=40000, near_arm=True, walls=True)
+    depth = wl.depth_batch()
+    ctx, ids = wl_context(wl)
+    plain = _plain_outputs(ctx, depth, wl.n_streams)
+    for m in ids:
+        ctx.set_link_thresholds(m, np.full(ctx.num_links(m), wl.max_diff, np.float32))
+    _same(plain, _plain_outputs(ctx, depth, wl.n_streams), "every link at the global value")
+    for m in ids:
+        ctx.set_link_thresholds(m, np.full(ctx.num_links(m), 0.4, np.float32))
+    changed = _plain_outputs(ctx, depth, wl.n_streams)
+    assert not np.array_equal(changed["device"][1], plain["device"][1])
+    ctx.clear_link_thresholds(ids[0])
+    ctx.clear_link_thresholds(ids[0])                         # (clearing twice is harmless)
+    for m in ids[1:]:
+        ctx.clear_link_thresholds(m)
+    _same(plain, _plain_outputs(ctx, depth, wl.n_streams), "after clear")
+    st = ctx.stats()
+    assert st["exact_tiles"] > 0 and st["cover_tiles"] > 0, st
+    ctx.close()
+
+
+# ---- 5. inheritance --------------------------------------------------------------------------------------------------------
+
+def test_inheriting_links_follow_set_params_and_set_links_do_not():
+    wl = WL.pr2_workload(2, 320, 240, total_triangles=20000, walls=True)
+    pl = wl_planes(wl)
+    ctx, ids = wl_context(wl)
+    base = workload_link_base(wl)
+    robot = ids[0]
+    t_robot = np.linspace(0.0, 0.3, ctx.num_links(robot)).astype(np.float32)
+    ctx.set_link_thresholds(robot, t_robot)
+    for g in (wl.max_diff, 0.6, -0.1, np.nan, 0.6):
+        p = params(replace=wl.replace_value, max_diff=g)
+        p.near_plane, p.far_plane = wl.near, wl.far
+        ctx.set_params(p)
+        link_thr = link_values(sum(len(m) for m in wl.models), g, {0: t_robot}, base)
+        check_forms(ctx, pl, link_thr, "global %r" % g, forms=["device", "bits_device"], global_thr=g)
+    ctx.close()
+
+
+# ---- 6. hard cases ---------------------------------------------------------------------------------------------------------
+
+def test_partial_batches():
+    wl = WL.pr2_workload(49, 320, 240, total_triangles=20000, near_arm=True)
+    pl = wl_planes(wl)
+    ctx, ids = wl_context(wl, max_streams=64, n=49, max_inflight_streams=8)
+    t = np.linspace(-0.02, 0.25, ctx.num_links(ids[0])).astype(np.float32)
+    ctx.set_link_thresholds(ids[0], t)
+    check_forms(ctx, pl, t, "n=49 of 64", forms=["device", "host", "bits_device", "labels_device"], n=49)
+    check_forms(ctx, pl, t, "n=17 of 64", forms=["device", "async"], n=17)
+    ctx.close()
+
+
+def test_regrown_bins_rerun_with_the_thresholds():
+    wl = WL.pr2_workload(3, 640, 480, total_triangles=40000, near_arm=True, walls=True)
+    pl = wl_planes(wl)
+    ctx, ids = wl_context(wl, bin_capacity=1)
+    base = workload_link_base(wl)
+    per = {i: np.linspace(0.3, -0.01, ctx.num_links(m)).astype(np.float32) for i, m in enumerate(ids)}
+    for i, m in enumerate(ids):
+        ctx.set_link_thresholds(m, per[i])
+    link_thr = link_values(sum(len(m) for m in wl.models), wl.max_diff, per, base)
+    wm, wk = pl.expected(link_thr)
+    masked, mask = ctx.filter_batch(pl.depth)
+    st = ctx.stats()
+    assert st["regrowths"] >= 1 and st["batch_reruns"] >= 1
+    _cmp(masked, mask, wm, wk, "re-run", False)
+    check_forms(ctx, pl, link_thr, "after the re-run", forms=["device", "bits_device"])
+    ctx.close()
+
+
+def test_graph_replay_picks_up_changed_thresholds():
+    """One raster lane, pipelines = 2, batches of one stream: graph replay is on; the thresholds change between batches."""
+    torch, dev = _torch()
+    wl = WL.example_workload(640, 480)
+    pl = wl_planes(wl)
+    ctx, ids = wl_context(wl, max_streams=1, n=1, raster_lanes=1, pipelines=2)
+    nl = ctx.num_links(ids[0])
+    d = torch.from_numpy(pl.depth[:1]).to(dev)
+    m = torch.empty_like(d)
+    k = torch.empty(d.shape, dtype=torch.uint8, device=dev)
+    tables = [np.full(nl, 0.05, np.float32), np.linspace(0.5, 2.0, nl).astype(np.float32), np.full(nl, -np.inf, np.float32)]
+    seq = [0, 0, 1, 1, 2, 0, 2, 2, 1, 0, 0, 1]
+    for i, j in enumerate(seq):
+        ctx.set_link_thresholds(ids[0], tables[j])
+        ctx.filter_batch_device(1, d.data_ptr(), m.data_ptr(), k.data_ptr())
+        ctx.sync()
+        wm, wk = pl.expected(tables[j])
+        _cmp(m.cpu().numpy(), k.cpu().numpy(), wm[:1], wk[:1], "batch %d table %d" % (i, j), False)
+    st = ctx.stats()
+    assert st["graphs_enabled"] == 1 and st["graph_hits"] > 0
+    assert st["batch_status"] == 0
+    ctx.close()
+
+
+# ---- 7. refusals -----------------------------------------------------------------------------------------------------------
+
+def test_refusals_leave_the_state_unchanged():
+    torch, dev = _torch()
+    wl = WL.example_workload(640, 480)
+    pl = wl_planes(wl)
+    ctx, ids = wl_context(wl)
+    nl = ctx.num_links(ids[0])
+    t = np.linspace(0.3, 1.5, nl).astype(np.float32)
+    ctx.set_link_thresholds(ids[0], t)
+    lib, h = ctx._lib, ctx._h
+    for rc in (lib.rtuf_set_link_thresholds(h, ids[0], None, nl),                                   # NULL
+               lib.rtuf_set_link_thresholds(h, len(ids), np.zeros(nl, np.float32).ctypes.data, nl),  # bad model
+               lib.rtuf_set_link_thresholds(h, -1, np.zeros(nl, np.float32).ctypes.data, nl),
+               lib.rtuf_set_link_thresholds(h, ids[0], np.zeros(nl + 1, np.float32).ctypes.data, nl + 1),   # wrong n_links
+               lib.rtuf_clear_link_thresholds(h, len(ids))):
+        assert rc == INVALID
+    check_forms(ctx, pl, t, "after refused calls", forms=["device"])
+    d = torch.from_numpy(pl.depth).to(dev)
+    mo = torch.empty_like(d)
+    bits = torch.zeros((pl.n, ctx.mask_bits_words()), dtype=torch.int32, device=dev)
+    for kw in ({"flags": R.FLAG_TWO_KERNEL}, {"silhouette_dilation_px": 2}):
+        p = params(replace=wl.replace_value, max_diff=wl.max_diff, **kw)
+        ctx.set_params(p)
+        for call in (lambda: ctx.filter_batch_device(pl.n, d.data_ptr(), mo.data_ptr()),
+                     lambda: ctx.filter_batch(pl.depth),
+                     lambda: ctx.filter_batch_device_bits(pl.n, d.data_ptr(), bits.data_ptr()),
+                     lambda: ctx.filter_batch_labels(pl.depth),
+                     lambda: ctx.filter(pl.depth[0], wl.projection[0])):
+            with pytest.raises(R.RtufError) as e:
+                call()
+            assert e.value.code == INVALID, kw
+        ctx.set_params(params(replace=wl.replace_value, max_diff=wl.max_diff))
+        check_forms(ctx, pl, t, "after the refused %s batches" % kw, forms=["device"])
+    # once the thresholds are cleared the same parameters work again
+    ctx.clear_link_thresholds(ids[0])
+    for kw in ({"flags": R.FLAG_TWO_KERNEL}, {"silhouette_dilation_px": 2}):
+        ctx.set_params(params(replace=wl.replace_value, max_diff=wl.max_diff, **kw))
+        ctx.filter_batch(pl.depth)
+    ctx.close()
