@@ -320,6 +320,28 @@ class RealtimeURDFFilter {
   const std::vector<uint16_t>& getLabels() const { return labels_; }
   const std::map<std::pair<int, std::string>, uint16_t>& linkLabels() const { return link_labels_; }
 
+  // Virtual depth (include/rtuf.h, VIRTUAL DEPTH): the robot's own depth image for the camera and link poses filter_into would
+  // use, no sensor image involved.  virtual_out: width x height float metres, or uint16 millimetres with is_16uc1 (width a
+  // multiple of 4); pixels no link covers hold empty_value.  labels_out: nullptr or width x height uint16 (needs
+  // FilterParameters::link_labels, kept for getLabels()).  The plane is also kept for getVirtualDepth(), in metres.
+  bool render_into(double* glTf, int width, int height, double timestamp, void* virtual_out, bool is_16uc1 = false, float empty_value = 0.0f,
+                   uint16_t* labels_out = nullptr)
+  {
+    prepare(width, height);
+    if (!virtual_out || (labels_out && !want_labels_)) throw std::runtime_error("render_into: needs virtual_out, and FilterParameters::link_labels for labels_out");
+    if (renderers_.empty() || !stage_frame(glTf, timestamp)) return false;
+    const size_t px = (size_t)width_ * height_;
+    if (is_16uc1) check(rtuf_render_batch_u16(ctx_, 1, reinterpret_cast<uint16_t* const*>(&virtual_out), labels_out ? &labels_out : nullptr, empty_value));
+    else check(rtuf_render_batch(ctx_, 1, reinterpret_cast<float* const*>(&virtual_out), labels_out ? &labels_out : nullptr, empty_value));
+    virtual_depth_.resize(px);
+    for (size_t i = 0; i < px; i++)
+      virtual_depth_[i] = is_16uc1 ? (float)static_cast<const uint16_t*>(virtual_out)[i] * 0.001f : static_cast<const float*>(virtual_out)[i];
+    if (labels_out) labels_.assign(labels_out, labels_out + px);
+    return true;
+  }
+  // the virtual depth plane of the last render_into (width x height metres, row 0 first; empty before the first)
+  const std::vector<float>& getVirtualDepth() const { return virtual_depth_; }
+
   // filter_into with the link label plane as well (labels_out: width x height uint16; needs FilterParameters::link_labels and
   // a masked_out).  The plane is also kept for getLabels().
   bool filter_into(const void* depth, bool is_16uc1, double* glTf, int width, int height, double timestamp, void* masked_out, uint8_t* mask_out,
@@ -512,6 +534,7 @@ class RealtimeURDFFilter {
   double applied_threshold_ = 0.0;                   // the global threshold apply_link_thresholds last used
   bool want_labels_;                                 // FilterParameters::link_labels
   std::vector<uint16_t> labels_;                     // label plane of the last frame (getLabels)
+  std::vector<float> virtual_depth_;                 // virtual depth plane of the last render_into (getVirtualDepth)
   std::map<std::pair<int, std::string>, uint16_t> link_labels_;
   std::vector<float> own_masked_;                    // render() with labels: the outputs the library-owned planes hold otherwise
   std::vector<uint8_t> own_mask_;

@@ -398,6 +398,34 @@ int rtuf_filter_batch_u16_labels(rtuf_context *ctx, int n_streams, const uint16_
 int rtuf_set_link_thresholds(rtuf_context *ctx, int model, const float *depth_distance_threshold, int n_links);
 int rtuf_clear_link_thresholds(rtuf_context *ctx, int model);
 
+/* VIRTUAL DEPTH.  New, beyond the reference: the robot's own depth image -- to_linear_depth(gl_FragCoord.z) of
+ * include/shaders/urdf_filter.frag:22, the metric depth at which the model puts the robot in every pixel -- as a plane
+ * [n][H][W] (row 0 first), with no sensor plane read and nothing compared.  Streams 0 .. n-1 are posed by the same setters as
+ * a filter batch.  A pixel's winner is the filter's: GL_LESS on the 24-bit depth, ties going to the earlier draw.
+ * Where a link's fragment won: virtual = num / (z - off), z the float window z the compare uses, num / off the shader's
+ * z_near*z_far/(z_near-z_far) and z_far/(z_far-z_near) in float -- the operations of the compare threshold without its final
+ * subtraction, bit for bit, so sensor > virtual - t reproduces the mask of a filter batch with threshold t.
+ * Where the background quad won, or nothing was drawn: empty_value as given; any float is legal, NaN and +-inf included.
+ * The 16UC1 forms (width a multiple of 4) write uint16 millimetres: every value, empty_value included, goes through the
+ * conversion the masked 16UC1 output applies (round half to even, saturating, NaN and out of int range -> 0).
+ * Labels: d_labels may be NULL; labels_out is NULL or one plane per stream.  When given it is exactly the plane the label
+ * calls write (LINK LABELS: default labels, rtuf_set_link_labels, the > 65535 links rule, the table allocated on first use;
+ * device: [n][H][W], 8-byte aligned).  sensor - virtual where labels > 0 is the calibration residual of the links.
+ * depth_distance_threshold, filter_replace_value, per-link thresholds and RTUF_FLAG_TWO_KERNEL do not enter: a render batch
+ * is always one tile kernel, never touches the z-surface (rtuf_debug_read_zsurface keeps showing the last filter batch), and
+ * is accepted on a context with per-link thresholds or the two-kernel flag set.
+ * Otherwise a render batch is a batch like any other: raster lanes, pipelines, launch groups, as many in flight as the
+ * context's filter batches, partial batches, re-runs after a bin regrowth into the same planes with the same empty_value,
+ * the status word (rtuf_batch_status_device) and rtuf_stats with their meaning (timings: ms_raster),
+ * rtuf_order_stream_after_batches; no order between batches in flight, render or filter.  The host-plane forms are
+ * synchronous.  Not supported yet: silhouette_dilation_px > 0 (RTUF_ERR_INVALID).  A NULL plane, n out of range or an
+ * un-finalized context fail as the filter calls do; a refused call enqueues nothing. */
+int rtuf_render_batch_device(rtuf_context *ctx, int n_streams, float *d_virtual, uint16_t *d_labels, float empty_value);
+int rtuf_render_batch_device_u16(rtuf_context *ctx, int n_streams, uint16_t *d_virtual_mm, uint16_t *d_labels, float empty_value);
+int rtuf_render_batch(rtuf_context *ctx, int n_streams, float *const *virtual_out, uint16_t *const *labels_out, float empty_value);
+int rtuf_render_batch_u16(rtuf_context *ctx, int n_streams, uint16_t *const *virtual_mm_out, uint16_t *const *labels_out,
+                          float empty_value);
+
 /* Counters of the last batch and kernel timings measured with HIP events on the context's
  * stream (replaces the wall-clock statistics of src/urdf_filter.cpp:239-266). */
 typedef struct {

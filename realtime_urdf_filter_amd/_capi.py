@@ -35,6 +35,7 @@ SYMBOLS = [
     "rtuf_filter_batch_device_bits_u16", "rtuf_expand_mask_bits", "rtuf_order_stream_after_batches", "rtuf_batch_status_device",
     "rtuf_set_link_labels", "rtuf_filter_batch_device_labels", "rtuf_filter_batch_device_u16_labels", "rtuf_filter_batch_labels",
     "rtuf_filter_batch_u16_labels", "rtuf_set_link_thresholds", "rtuf_clear_link_thresholds",
+    "rtuf_render_batch_device", "rtuf_render_batch_device_u16", "rtuf_render_batch", "rtuf_render_batch_u16",
 ]
 
 
@@ -178,6 +179,10 @@ def load_library(path=None):
     lib.rtuf_filter_batch_device_u16_labels.argtypes = [vp, ci, vp, vp, vp, vp]
     lib.rtuf_filter_batch_labels.argtypes = [vp, ci, vp, vp, vp, vp]
     lib.rtuf_filter_batch_u16_labels.argtypes = [vp, ci, vp, vp, vp, vp]
+    lib.rtuf_render_batch_device.argtypes = [vp, ci, vp, vp, ctypes.c_float]
+    lib.rtuf_render_batch_device_u16.argtypes = [vp, ci, vp, vp, ctypes.c_float]
+    lib.rtuf_render_batch.argtypes = [vp, ci, vp, vp, ctypes.c_float]
+    lib.rtuf_render_batch_u16.argtypes = [vp, ci, vp, vp, ctypes.c_float]
     lib.rtuf_set_link_thresholds.argtypes = [vp, ci, vp, ci]
     lib.rtuf_clear_link_thresholds.argtypes = [vp, ci]
     if path is None:
@@ -385,6 +390,28 @@ class Context:
     def clear_link_thresholds(self, model):
         """Model `model`'s links follow params.depth_distance_threshold again."""
         self._check(self._lib.rtuf_clear_link_thresholds(self._h, model))
+
+    # virtual depth (include/rtuf.h, VIRTUAL DEPTH)
+    def render_batch(self, n, empty_value=0.0, labels=False, u16=False):
+        """The robot's own depth image of streams 0 .. n-1, no sensor plane involved: -> (virtual [n,H,W] float32 metres, or
+        uint16 millimetres with u16; labels [n,H,W] uint16 or None).  Pixels no link won hold empty_value."""
+        virt = np.empty((n, self.height, self.width), np.uint16 if u16 else np.float32)
+        lab = np.empty(virt.shape, np.uint16) if labels else None
+        PP = ctypes.c_void_p * max(n, 1)
+        vout = PP(*[virt[i].ctypes.data for i in range(n)])
+        lout = PP(*[lab[i].ctypes.data for i in range(n)]) if labels else None
+        fn = self._lib.rtuf_render_batch_u16 if u16 else self._lib.rtuf_render_batch
+        self._check(fn(self._h, n, vout, lout, empty_value))
+        return virt, lab
+
+    def render_batch_device(self, n, d_virtual, d_labels=None, empty_value=0.0):
+        """Device pointers (ints; d_labels may be None): enqueue only; call sync()."""
+        self._check(self._lib.rtuf_render_batch_device(self._h, n, ctypes.c_void_p(d_virtual) if d_virtual else None,
+                                                       ctypes.c_void_p(d_labels) if d_labels else None, empty_value))
+
+    def render_batch_device_u16(self, n, d_virtual_mm, d_labels=None, empty_value=0.0):
+        self._check(self._lib.rtuf_render_batch_device_u16(self._h, n, ctypes.c_void_p(d_virtual_mm) if d_virtual_mm else None,
+                                                           ctypes.c_void_p(d_labels) if d_labels else None, empty_value))
 
     # asynchronous host planes
     def host_alloc(self, shape, dtype):

@@ -183,6 +183,9 @@ struct rtuf_context {
     uint32_t* bits = nullptr;                // mask-only output (1 bit per pixel) instead of masked / mask
     uint16_t* labels = nullptr;              // link label plane beside masked / mask (rtuf_filter_batch*_labels) or nullptr
     const float* order_thr = nullptr;        // per-link thresholds: the draw order -> threshold table, or nullptr (set when first enqueued)
+    // render batch (rtuf_render_batch*): the virtual depth plane (float, or uint16 with u16) and the value of its empty pixels;
+    // depth / masked / mask / bits are unused, labels may be given.  nullptr: a filter batch.
+    float* virt = nullptr; float empty_value = 0.0f;
     Counters* h_counters = nullptr;          // pinned [max_groups]: one block per launch group, filled by the copies that end the batch
     hipEvent_t done[kMaxLanes] = {};         // recorded on each lane after its copy
     uint32_t lanes_used = 0;                 // bit l: the batch has launch groups on lane l
@@ -214,7 +217,8 @@ struct rtuf_context {
     float* st_depth = nullptr; float* st_masked = nullptr; uint8_t* st_mask = nullptr; size_t st_streams = 0;
     uint32_t* st_bits = nullptr; size_t st_bits_streams = 0;
     uint16_t* st_labels = nullptr; size_t st_labels_streams = 0;
-    std::vector<void*> h_masked, h_mask, h_bits, h_labels;
+    float* st_virtual = nullptr; size_t st_virtual_streams = 0;      // (float-sized: large enough for uint16 planes)
+    std::vector<void*> h_masked, h_mask, h_bits, h_labels, h_virtual;
     hipEvent_t uploaded = nullptr, downloaded = nullptr;
     bool wait_upload = false;                // the lanes wait for `uploaded` before the first kernel that reads the planes
   };
@@ -647,7 +651,7 @@ static void free_frame_buffers(rtuf_context* c)
     for (auto*& it : ln.d_items) dev_free(c, it);
   }
   for (auto& b : c->batch) { dev_free(c, b.st_depth); dev_free(c, b.st_masked); dev_free(c, b.st_mask); b.st_streams = 0; dev_free(c, b.st_bits); b.st_bits_streams = 0; }
-  for (auto& b : c->batch) { dev_free(c, b.st_labels); b.st_labels_streams = 0; }
+  for (auto& b : c->batch) { dev_free(c, b.st_labels); b.st_labels_streams = 0; dev_free(c, b.st_virtual); b.st_virtual_streams = 0; }
   for (auto*& p : c->ring_cams) hfree(p);
   for (auto*& p : c->ring_link_tf) hfree(p);
   c->h_cams = nullptr; c->h_link_tf = nullptr;
@@ -1470,7 +1474,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   const float* d_depth = b.depth; float* d_masked = b.masked; uint8_t* d_mask = b.mask;
   const bool io_u16 = b.u16;
   const size_t esz = io_u16 ? sizeof(uint16_t) : sizeof(float);
-  const bool two = (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0;
+  const bool two = (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.virt;      // (a render batch is always one tile kernel)
   // Launch groups: as many as the lanes' bins ask for, alternating between the lanes; a batch that is not split takes one
   // lane, the next such batch the other.
   const int n_groups = groups_for(c, n);
@@ -1526,8 +1530,9 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   plan.cover_pass = b.cover_pass;
   // silhouette dilation: the tile kernel writes the z-surface and dilate_compare_kernel makes every output form from it (the
   // mask bits included); without it nothing here differs from before
-  if (!rerun) b.dilation = (int)c->params.silhouette_dilation_px;
-  if (!rerun) b.order_thr = c->thresh_models > 0 ? c->d_order_thr : nullptr;
+  // (a render batch compares nothing: no thresholds, and the render calls refuse silhouette dilation)
+  if (!rerun) b.dilation = b.virt ? 0 : (int)c->params.silhouette_dilation_px;
+  if (!rerun) b.order_thr = c->thresh_models > 0 && !b.virt ? c->d_order_thr : nullptr;
   const int dil = b.dilation;
   plan.zroute = dil > 0 || (two && !b.bits);
   // on-device forward kinematics overwrites the link matrices (and camera) of the streams that use it
@@ -1606,6 +1611,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     ta.labels = b.labels;                    // (the label calls refuse silhouette dilation and mask bits)
     ta.order_labels = b.labels ? c->d_order_labels : nullptr;
     ta.order_thr = b.order_thr;              // (batches with per-link thresholds never take the z-surface route: check_thresh_route)
+    ta.virtual_out = b.virt; ta.empty_value = b.empty_value;
     gr.compare = two && !b.bits && !dil;
     gr.dilate = dil > 0;
     if (gr.dilate) {
@@ -1627,7 +1633,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   }
   b.n_groups = (int)plan.groups.size();          // (= n_groups: the loop makes ceil(n / per_group) groups, checked above)
   b.setup_grid.assign(plan.groups.size(), 0xffffffffu);
-  c->last_lane = plan.groups.back().lane;
+  if (!b.virt) c->last_lane = plan.groups.back().lane;      // (a render batch leaves the z-surface alone)
   // host-plane batches: the lanes' first kernels wait for the upload of the planes
   if (b.wait_upload)
     for (int l = 0; l < c->n_lanes; l++)
@@ -1716,13 +1722,16 @@ static int enqueue_download(rtuf_context* c, rtuf_context::Batch& b)
     HIP_TRY(c, hipEventRecord(b.downloaded, c->d2h));
     return RTUF_OK;
   }
+  // (a render batch: the virtual depth planes in place of masked / mask)
+  const std::vector<void*>& h_planes = b.virt ? b.h_virtual : b.h_masked;
+  const char* st_planes = b.virt ? (const char*)b.st_virtual : (const char*)b.st_masked;
   for (int s = 0; s < b.n;) {
     int e = s + 1;
-    while (e < b.n && (char*)b.h_masked[e] == (char*)b.h_masked[e - 1] + plane * esz) e++;
-    HIP_TRY(c, hipMemcpyAsync(b.h_masked[s], (char*)b.st_masked + (size_t)s * plane * esz, (size_t)(e - s) * plane * esz, hipMemcpyDeviceToHost, c->d2h));
+    while (e < b.n && (char*)h_planes[e] == (char*)h_planes[e - 1] + plane * esz) e++;
+    HIP_TRY(c, hipMemcpyAsync(h_planes[s], st_planes + (size_t)s * plane * esz, (size_t)(e - s) * plane * esz, hipMemcpyDeviceToHost, c->d2h));
     s = e;
   }
-  for (int s = 0; s < b.n;) {
+  for (int s = 0; s < b.n && !b.virt;) {
     if (!b.h_mask[s]) { s++; continue; }
     int e = s + 1;
     while (e < b.n && b.h_mask[e] && (char*)b.h_mask[e] == (char*)b.h_mask[e - 1] + plane) e++;
@@ -1812,7 +1821,7 @@ static int retire_oldest(rtuf_context* c)
       if (b.timing && b.events.size() >= (size_t)(kEvGroup0 + kEvPerGroup * b.n_groups)) {
         // per launch group E0 .. E4 (see issue_plan).  With several lanes the kernels of different groups overlap: the sums
         // below add up per-launch durations, they are not wall time.
-        const bool two = ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.bits) || b.dilation > 0;
+        const bool two = ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.bits && !b.virt) || b.dilation > 0;
         auto el = [&](size_t i, size_t j) { float ms = 0; hipEventElapsedTime(&ms, b.events[i], b.events[j]); return ms; };
         c->stats.ms_pose = c->stats.ms_setup = c->stats.ms_clip = c->stats.ms_raster = c->stats.ms_compare = c->stats.ms_total = 0;
         for (int g = 0; g < b.n_groups; g++) {
@@ -1912,13 +1921,14 @@ static int check_thresh_route(rtuf_context* c)
   return RTUF_OK;
 }
 
+// d_virtual != nullptr: a render batch (d_depth, d_masked, d_mask, d_bits unused)
 static int submit_batch(rtuf_context* c, int n, const float* d_depth, float* d_masked, uint8_t* d_mask, bool u16, uint32_t* d_bits = nullptr,
-                        bool wait_upload = false, uint16_t* d_labels = nullptr)
+                        bool wait_upload = false, uint16_t* d_labels = nullptr, float* d_virtual = nullptr, float empty_value = 0.0f)
 {
   if (c->broken) return c->fail(RTUF_ERR_STATE, "context unusable: a bin regrowth failed (%s)", c->error.c_str());
-  { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
+  if (!d_virtual) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
   hipSetDevice(c->device);
-  if (uses_zsurface(c))
+  if (uses_zsurface(c) && !d_virtual)
     for (int l = 0; l < c->n_lanes; l++)
       if (!c->lane[l].d_zsurface) HIP_TRY(c, dev_alloc(c, &c->lane[l].d_zsurface, (size_t)c->group * c->width * c->height * sizeof(float)));
   // two-kernel mode and silhouette dilation keep one z-surface per lane: their batches do not overlap
@@ -1926,6 +1936,7 @@ static int submit_batch(rtuf_context* c, int n, const float* d_depth, float* d_m
   while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
   rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];
   b.n = n; b.depth = d_depth; b.masked = d_masked; b.mask = d_mask; b.u16 = u16; b.host_io = false; b.bits = d_bits; b.labels = d_labels;
+  b.virt = d_virtual; b.empty_value = empty_value;
   b.wait_upload = wait_upload;
   const int rc = enqueue_batch(c, b, false);
   if (rc == RTUF_OK) { b.active = true; c->pending++; }
@@ -2066,6 +2077,19 @@ int rtuf_order_stream_after_batches(rtuf_context* c, void* hip_stream)
 // :729-735).  Here the planes of a batch go up on one copy stream and come back on another, so with two
 // batches in flight the transfers of one overlap the kernels of the other; every slot has its own
 // device staging.
+// (copy streams beside the lanes as well: an upload queued behind a lane's kernels would hold up the next batch)
+static int ensure_copy_streams(rtuf_context* c)
+{
+  if (c->h2d && c->d2h) return RTUF_OK;
+  bool beside = true;
+  sync_lanes(c);                      // (the probe times idle kernels: nothing else may be running; first host-plane call only)
+  bool beside_up = true;
+  if (!c->h2d) HIP_TRY(c, create_stream_beside(lane_streams(c), &c->h2d, &beside_up));
+  if (!c->d2h) HIP_TRY(c, create_stream_beside(lane_streams(c), &c->d2h, &beside));
+  c->stats.copy_streams_side_by_side = (beside && beside_up) ? 1u : 0u;
+  return RTUF_OK;
+}
+
 static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in, void* const* masked_out,
                              void* const* mask_out, bool u16, uint32_t* const* bits_out = nullptr, uint16_t* const* labels_out = nullptr)
 {
@@ -2077,15 +2101,7 @@ static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in
     if (!depth_in[s] || (bits_out ? !bits_out[s] : !masked_out[s]) || (labels_out && !labels_out[s])) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
   { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }      // (before the planes are staged)
   hipSetDevice(c->device);
-  // (copy streams beside the lanes as well: an upload queued behind a lane's kernels would hold up the next batch)
-  if (!c->h2d || !c->d2h) {
-    bool beside = true;
-    sync_lanes(c);                      // (the probe times idle kernels: nothing else may be running; first host-plane call only)
-    bool beside_up = true;
-    if (!c->h2d) HIP_TRY(c, create_stream_beside(lane_streams(c), &c->h2d, &beside_up));
-    if (!c->d2h) HIP_TRY(c, create_stream_beside(lane_streams(c), &c->d2h, &beside));
-    c->stats.copy_streams_side_by_side = (beside && beside_up) ? 1u : 0u;
-  }
+  { const int rc = ensure_copy_streams(c); if (rc != RTUF_OK) return rc; }
   const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
   while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
   rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];     // the slot submit_batch takes next
@@ -2336,6 +2352,82 @@ int rtuf_clear_link_thresholds(rtuf_context* c, int model)
   const int rc = build_thresh_table(c);
   if (rc != RTUF_OK) m.thresholds.swap(keep);
   return rc;
+}
+
+// ---- virtual depth ---------------------------------------------------------------------------------
+// A render batch is a batch like any other (submit_batch) whose tile kernel stores the winners' virtual depth instead of
+// comparing a sensor plane with it.  Parameters of the compare do not enter, and the z-surface is never used.
+static int check_render_call(rtuf_context* c, int n, const void* out, bool want_labels, bool u16)
+{
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (n <= 0 || n > c->max_streams || !out) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
+  if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "virtual depth is not supported with silhouette dilation yet");
+  if (u16 && (c->width & 3)) return c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4");
+  return want_labels ? ensure_label_table(c) : RTUF_OK;
+}
+
+int rtuf_render_batch_device(rtuf_context* c, int n, float* d_virtual, uint16_t* d_labels, float empty_value)
+{
+  KIDS_NEXT(c, rtuf_render_batch_device(k, n, d_virtual, d_labels, empty_value));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_render_call(c, n, d_virtual, d_labels != nullptr, false);
+  return rc != RTUF_OK ? rc : submit_batch(c, n, nullptr, nullptr, nullptr, false, nullptr, false, d_labels, d_virtual, empty_value);
+}
+
+int rtuf_render_batch_device_u16(rtuf_context* c, int n, uint16_t* d_virtual, uint16_t* d_labels, float empty_value)
+{
+  KIDS_NEXT(c, rtuf_render_batch_device_u16(k, n, d_virtual, d_labels, empty_value));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_render_call(c, n, d_virtual, d_labels != nullptr, true);
+  return rc != RTUF_OK ? rc : submit_batch(c, n, nullptr, nullptr, nullptr, true, nullptr, false, d_labels, reinterpret_cast<float*>(d_virtual), empty_value);
+}
+
+// host planes: the batch renders into the slot's device staging, the planes come back on the download stream
+static int render_batch_async(rtuf_context* c, int n, void* const* virtual_out, uint16_t* const* labels_out, float empty_value, bool u16)
+{
+  KIDS_NEXT(c, render_batch_async(k, n, virtual_out, labels_out, empty_value, u16));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = check_render_call(c, n, virtual_out, labels_out != nullptr, u16); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; s < n; s++)
+    if (!virtual_out[s] || (labels_out && !labels_out[s])) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
+  hipSetDevice(c->device);
+  { const int rc = ensure_copy_streams(c); if (rc != RTUF_OK) return rc; }
+  const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
+  while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
+  rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];     // the slot submit_batch takes next
+  const size_t plane = (size_t)c->width * c->height;
+  if (b.st_virtual_streams < (size_t)n) {
+    dev_free(c, b.st_virtual);
+    b.st_virtual_streams = 0;
+    HIP_TRY(c, dev_alloc(c, &b.st_virtual, (size_t)n * plane * sizeof(float)));
+    b.st_virtual_streams = (size_t)n;
+  }
+  if (labels_out && b.st_labels_streams < (size_t)n) {
+    dev_free(c, b.st_labels);
+    b.st_labels_streams = 0;
+    HIP_TRY(c, dev_alloc(c, &b.st_labels, (size_t)n * plane * sizeof(uint16_t)));
+    b.st_labels_streams = (size_t)n;
+  }
+  if (!b.downloaded) HIP_TRY(c, hipEventCreateWithFlags(&b.downloaded, hipEventDisableTiming));
+  b.h_virtual.assign(virtual_out, virtual_out + n);
+  b.h_labels.clear();
+  if (labels_out) b.h_labels.assign(reinterpret_cast<void* const*>(labels_out), reinterpret_cast<void* const*>(labels_out) + n);
+  const int rc = submit_batch(c, n, nullptr, nullptr, nullptr, u16, nullptr, false, labels_out ? b.st_labels : nullptr, b.st_virtual, empty_value);
+  if (rc != RTUF_OK) return rc;
+  b.host_io = true;
+  return enqueue_download(c, b);
+}
+
+int rtuf_render_batch(rtuf_context* c, int n, float* const* virtual_out, uint16_t* const* labels_out, float empty_value)
+{
+  const int rc = render_batch_async(c, n, reinterpret_cast<void* const*>(virtual_out), labels_out, empty_value, false);
+  return rc != RTUF_OK ? rc : rtuf_sync(c);
+}
+
+int rtuf_render_batch_u16(rtuf_context* c, int n, uint16_t* const* virtual_out, uint16_t* const* labels_out, float empty_value)
+{
+  const int rc = render_batch_async(c, n, reinterpret_cast<void* const*>(virtual_out), labels_out, empty_value, true);
+  return rc != RTUF_OK ? rc : rtuf_sync(c);
 }
 
 int rtuf_wait_oldest(rtuf_context* c)

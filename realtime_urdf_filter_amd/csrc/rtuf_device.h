@@ -325,6 +325,9 @@ struct TileArgs {
   const uint16_t* order_labels;  // [n_tris + 1] label of every draw order (entry 0, background / no fragment: 0)
   // per-link depth thresholds (appended).  order_thr != nullptr selects tile_thresh_kernel (fused route only).
   const float* order_thr;        // [n_tris + 1] threshold of every draw order's link (entry 0, the background quad: max_diff)
+  // virtual depth planes (appended).  virtual_out != nullptr selects tile_render_kernel: depth, masked, mask, bits unused.
+  float* virtual_out;            // [n][H][W] virtual depth of every pixel's winner (f32 metres or, with io_u16, uint16 millimetres)
+  float empty_value;             // ... and what a pixel holds where the background quad won or nothing was drawn
 };
 
 struct CompareArgs {

@@ -2161,6 +2161,12 @@ __device__ __forceinline__ float shade_threshold(float z, const ShadeConsts& k)
   const float virt = k.core ? div_core(k.num, d) : __fdiv_rn(k.num, d);
   return __fsub_rn(virt, k.max_diff);
 }
+// the virtual depth itself, to_linear_depth(gl_FragCoord.z): shade_threshold without its subtraction (rtuf_render_batch*)
+__device__ __forceinline__ float shade_virtual(float z, const ShadeConsts& k)
+{
+  const float d = __fsub_rn(z, k.off);
+  return k.core ? div_core(k.num, d) : __fdiv_rn(k.num, d);
+}
 // the same with a threshold of its own in place of max_diff (per-link depth thresholds)
 __device__ __forceinline__ float shade_threshold(float z, const ShadeConsts& k, float max_diff)
 {
@@ -2180,7 +2186,10 @@ __device__ __forceinline__ float shade(float sensor, float z, const ShadeConsts&
 // LABELS: the kernel also writes the link label plane (a.labels, a.order_labels: rtuf_filter_batch*_labels); never with BITS.
 // THRESH: a drawn pixel is compared with its winner's link threshold (a.order_thr: rtuf_set_link_thresholds) instead of
 // max_diff; the background plane keeps thr_bg.  Fused route only (never with TWO_KERNEL).
-template <bool TWO_KERNEL, bool U16, bool BITS, bool COVER, int NT, bool LABELS = false, bool THRESH = false>
+// RENDER: no sensor plane, no compare: the only outputs are the virtual depth plane (a.virtual_out: shade_virtual of every
+// winner's z, a.empty_value where the background quad won or nothing was drawn; U16: both through metres_to_u16) and, with
+// LABELS, the label plane (rtuf_render_batch*).  Never with TWO_KERNEL, BITS or THRESH.
+template <bool TWO_KERNEL, bool U16, bool BITS, bool COVER, int NT, bool LABELS = false, bool THRESH = false, bool RENDER = false>
 __device__ __forceinline__ void tile_body(const TileArgs& a)
 {
   __shared__ unsigned long long keys[kKeyCount];
@@ -2217,7 +2226,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   kf.abl = a.flags;
   kf.lowmask = near_tile ? (1u << a.key_shift) - 1u : 0u;
   kf.zexact = near_tile ? exact_z_floor(a.key_shift) : 8388609u;
-  kf.keep_order = LABELS || THRESH;
+  kf.keep_order = LABELS || THRESH || RENDER;      // (RENDER: order 0 is the background quad drawn as geometry)
   const uint32_t count = count_front + count_back;
   // (the stream's background entry after the bin's header in program order: the compiler then issues the three scalar loads
   // together -- with the background first it waited for it before it even computed the header's address)
@@ -2276,16 +2285,18 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   float cov_a0 = 0.0f, cov_dzdx = 0.0f, cov_dzdy = 0.0f;
   uint32_t cov_label = 0;                    // LABELS: the cover's link label, one lookup per tile
   float cov_thr = 0.0f;                      // THRESH: the cover's link threshold, one lookup per tile
+  bool cov_robot = true;                     // RENDER: the cover is a link's triangle, not the background quad drawn as geometry
   if constexpr (COVER) {
     cover_only = has_cover && n == 0 && nf == 0 && !empty;
     if (cover_only) {
-      request_sensor();
+      if (!RENDER) request_sensor();
       const uint4 pl = reinterpret_cast<const uint4*>(a.big_list + cover_idx)[1];       // {a0, dzdx, dzdy, order}: same address in every lane
       cov_a0 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.x));
       cov_dzdx = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.y));
       cov_dzdy = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.z));
       if (LABELS) cov_label = a.order_labels[(uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask];
       if (THRESH) cov_thr = a.order_thr[(uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask];
+      if (RENDER) cov_robot = ((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask) != 0u;
 #ifdef RTUF_COUNT
       if (tid < 2) count_words()[tid] = 0u;
 #endif
@@ -2297,7 +2308,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
       }
     }
   }
-  if (empty) request_sensor();
+  if (empty && !RENDER) request_sensor();
   if (!empty && !cover_only) {
     // Initial depth keys: the background plane and, where a triangle covers the whole tile, that triangle's fragments --
     // evaluated per pixel exactly as fragment() would (same two fused multiply-adds, same 24-bit conversion, its draw
@@ -2417,7 +2428,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
     }
     // (requested here, not before the scan above: with the eight registers live from there the kernel sits at its 80-register
     // limit and the allocation of everything before it suffers -- measured once more in round 4: tile kernel 296 instead of 280 us)
-    request_sensor();
+    if (!RENDER) request_sensor();
   }
 
   // resolve: kLanesPerRow lanes x 4 pixels per tile row, kRowsPerPass rows per pass.  `finish` turns four
@@ -2433,6 +2444,18 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
     if (LABELS) {
       if (vec) store_labels4(a.labels + gofs, lab[0] | (lab[1] << 16), lab[2] | (lab[3] << 16));
       else for (int j = 0; j < nvalid; j++) a.labels[gofs + j] = (uint16_t)lab[j];
+    }
+    if (RENDER) {                            // z = the four virtual depths (or the empty value): the plane's only store
+      if (vec) {
+        if (U16) store_stream4(reinterpret_cast<uint16_t*>(a.virtual_out) + gofs, metres_to_u16(z[0]), metres_to_u16(z[1]), metres_to_u16(z[2]), metres_to_u16(z[3]));
+        else store_stream4(a.virtual_out + gofs, z[0], z[1], z[2], z[3]);
+      } else {
+        for (int j = 0; j < nvalid; j++) {
+          if (U16) reinterpret_cast<uint16_t*>(a.virtual_out)[gofs + j] = (uint16_t)metres_to_u16(z[j]);
+          else a.virtual_out[gofs + j] = z[j];
+        }
+      }
+      return 0u;
     }
     if (TWO_KERNEL) {
       const size_t zofs = (size_t)slot * ((size_t)a.height * a.width) + (uint32_t)(__mul24(py, a.width) + px);
@@ -2482,6 +2505,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   const float bg_z4[4] = {bgz, bgz, bgz, bgz}, bg_thr4[4] = {thr_bg, thr_bg, thr_bg, thr_bg};
   const bool bg_frag4[4] = {analytic_bg, analytic_bg, analytic_bg, analytic_bg};
   const uint32_t no_lab4[4] = {0u, 0u, 0u, 0u};
+  const float empty4[4] = {a.empty_value, a.empty_value, a.empty_value, a.empty_value};      // RENDER
 #pragma unroll
   for (int ps = 0; ps < kPasses; ps++) {
     const int r_ly = r_ly0 + ps * kRowsPerPass;
@@ -2489,7 +2513,9 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
     uint32_t flags4 = 0;
     RTUF_LANES(kLaneResolve, valid);
     if (valid) {
-      if (empty) {                                   // tile without geometry: a streaming compare against the plane
+      if (RENDER && empty) {                         // tile without geometry: a streaming store of the empty value
+        flags4 = finish(ps, empty4, bg_thr4, bg_frag4, no_lab4);
+      } else if (empty) {                            // tile without geometry: a streaming compare against the plane
         if (analytic_bg) {          // (uniform: with the flags known to be set the four selects on them fall away)
           const bool all4[4] = {true, true, true, true};
           flags4 = finish(ps, bg_z4, bg_thr4, all4, no_lab4);
@@ -2514,7 +2540,8 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
           frag[j] = drawn ? true : analytic_bg;
           thr[j] = thr_bg;
           lab[j] = drawn ? cov_label : 0u;
-          if (drawn && !TWO_KERNEL) thr[j] = THRESH ? shade_threshold(zf, sc, cov_thr) : shade_threshold(zf, sc);
+          if (RENDER) z[j] = drawn && cov_robot ? shade_virtual(zf, sc) : a.empty_value;
+          else if (drawn && !TWO_KERNEL) thr[j] = THRESH ? shade_threshold(zf, sc, cov_thr) : shade_threshold(zf, sc);
 #ifdef RTUF_COUNT
           if (drawn && r_px + j < a.width) atomicAdd(&count_words()[1], 1u);
 #endif
@@ -2530,7 +2557,8 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
           frag[j] = true;
           thr[j] = thr_bg;
           lab[j] = 0u;
-          if (k == bgkey) { z[j] = bgz; frag[j] = analytic_bg; }
+          if (RENDER && k == bgkey) z[j] = a.empty_value;
+          else if (k == bgkey) { z[j] = bgz; frag[j] = analytic_bg; }
           else {                                        // the per-pixel division only runs where something was drawn
 #ifdef RTUF_COUNT
             if (r_px + j < a.width) atomicAdd(&count_words()[1], 1u);
@@ -2551,7 +2579,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
                 if (khi <= 8388608u) z[j] = near_z_from_key(khi, (uint32_t)k & kf.lowmask, kf.shift);
               }
             }
-            if (!TWO_KERNEL && !THRESH) thr[j] = shade_threshold(z[j], sc);
+            if (!TWO_KERNEL && !THRESH && !RENDER) thr[j] = shade_threshold(z[j], sc);
             // the winner's draw order: the key's (or, after the exact-z pass, kept above the float z: resolved_key); 0 is
             // "no fragment" (kNoFragment), whose table entry is label 0 -- and the background quad drawn as geometry, whose
             // threshold entry is max_diff
@@ -2560,6 +2588,10 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
               const uint32_t ord = (k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift;
               thr[j] = shade_threshold(z[j], sc, a.order_thr[ord]);
               if (LABELS) lab[j] = a.order_labels[ord];
+            }
+            if (RENDER) {                            // (draw order 0: the background quad drawn as geometry is background too)
+              const uint32_t ord = (k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift;
+              z[j] = ord ? shade_virtual(z[j], sc) : a.empty_value;
             }
           }
         }
@@ -2626,6 +2658,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WA
 #endif
 template <bool U16, bool BITS, bool LABELS, bool COVER, int NT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_THRESH))) void tile_thresh_kernel(TileArgs a) { tile_body<false, U16, BITS, COVER, NT, LABELS, true>(a); }
+// virtual depth planes (rtuf_render_batch*): no sensor plane in, 4 (2) B/pixel out, plus 2 B/pixel with labels.
+// Without the sensor registers the variants take 71 or 72 VGPRs and spill none at 7 waves/SIMD (the label variants' setting).
+// More cannot help the 256-thread kernels: seven key tiles fill the CU's LDS, and seven workgroups of four waves are 7 per SIMD.
+#ifndef RTUF_TILE_WAVES_RENDER
+#define RTUF_TILE_WAVES_RENDER 7
+#endif
+template <bool U16, bool LABELS, bool COVER, int NT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_RENDER))) void tile_render_kernel(TileArgs a) { tile_body<false, U16, false, COVER, NT, LABELS, false, true>(a); }
 
 // ---------------------------------------------------------------------------------------
 // compare_kernel (two-kernel mode): streaming, 13 B/pixel (4 sensor + 4 z + 4 masked + 1 mask)
@@ -2970,7 +3010,13 @@ template <bool COVER, int NT>
 static void launch_tile_variant(const TileArgs& a, bool two_kernel, hipStream_t st)
 {
   const dim3 grid(a.tiles_x, a.tiles_y, a.group_size);
-  if (a.order_thr) {                         // (the host refuses per-link thresholds in two-kernel mode)
+  if (a.virtual_out) {                       // (a render batch has neither thresholds nor a z-surface route)
+    if (a.labels) {
+      if (a.io_u16) hipLaunchKernelGGL((tile_render_kernel<true, true, COVER, NT>), grid, dim3(NT), 0, st, a);
+      else hipLaunchKernelGGL((tile_render_kernel<false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
+    } else if (a.io_u16) hipLaunchKernelGGL((tile_render_kernel<true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((tile_render_kernel<false, false, COVER, NT>), grid, dim3(NT), 0, st, a);
+  } else if (a.order_thr) {                         // (the host refuses per-link thresholds in two-kernel mode)
     if (a.labels) {
       if (a.io_u16) hipLaunchKernelGGL((tile_thresh_kernel<true, false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
       else hipLaunchKernelGGL((tile_thresh_kernel<false, false, true, COVER, NT>), grid, dim3(NT), 0, st, a);

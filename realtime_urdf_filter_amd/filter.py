@@ -230,6 +230,7 @@ class RealtimeURDFFilter:
         # new, beyond the reference: link labels (include/rtuf.h, LINK LABELS), off by default -- filter() costs what it did
         self.want_labels_ = bool(labels)
         self.labels_ = None
+        self.virtual_depth_ = None            # new, beyond the reference: the plane of the last render() (VIRTUAL DEPTH)
         self.link_labels_ = {}                # (model index, URDF link name) -> label
 
     # ---- loading -------------------------------------------------------------------------
@@ -365,6 +366,27 @@ class RealtimeURDFFilter:
         self.masked_depth_ = masked[0]
         if self.need_mask_:
             self.mask_ = mask[0]
+
+    def render(self, projection_matrix, width, height, timestamp=None, empty_value=0.0):
+        """New, beyond the reference: the robot's own depth image (include/rtuf.h, VIRTUAL DEPTH) for the camera and link
+        poses filter() would use, no sensor image involved.  getVirtualDepth() returns the plane; with labels=True the label
+        plane of the same render is in getLabels().  Pixels no link covers hold empty_value."""
+        self._ensure_size(width, height)
+        if not self.renderers_:
+            return
+        try:
+            self._stage_stream(0, projection_matrix, self.tf_, timestamp)
+        except Exception as e:                      # noqa: BLE001 - ROS_ERROR + return (quirk Q6)
+            log.error("%s", e)
+            return
+        virt, labels = self._ctx.render_batch(1, empty_value, labels=self.want_labels_)
+        self.virtual_depth_ = virt[0]
+        if self.want_labels_:
+            self.labels_ = labels[0]
+
+    def getVirtualDepth(self):
+        """Virtual depth plane [H,W] float32 metres of the last render() (None before the first)."""
+        return self.virtual_depth_
 
     def getMaskedDepth(self):
         return self.masked_depth_

@@ -116,6 +116,7 @@ def build(tag):
     text("GPU test suite on the round's tree", ["DESIGN.md 8"], T + "_gpu_tests.txt", "pytest's last line")
     text("fuzz campaigns (fuzz_parity 6,000 + fuzz_features 3,000 + FUZZ_BIG 150 scenes)", ["DESIGN.md 2"], T + "_fuzz.txt", "'streams with mismatches' of each of the three runs")
     text("wall time of the default bench command", ["README.md"], T + "_bench_wall_time.txt", "the line")
+    text("virtual depth planes on c3: render batches beside the plain fused filter", ["README.md", "DESIGN.md 4"], "virtual_rate_c3.txt", "the last line")
     for f, claim, docs in ((T + "_experiment_block_bounds.txt", "block depth bounds (not merged)", ["DESIGN.md 8", "docs/experiments.md R6.1"]),
                            (T + "_experiment_more_lanes.txt", "4-6 raster lanes", ["docs/experiments.md R6.6"]),
                            (T + "_experiment_compiler_flags.txt", "compiler flag sweep", ["docs/experiments.md R6.6"]),
