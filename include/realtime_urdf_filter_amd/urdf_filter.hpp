@@ -342,6 +342,44 @@ class RealtimeURDFFilter {
   // the virtual depth plane of the last render_into (width x height metres, row 0 first; empty before the first)
   const std::vector<float>& getVirtualDepth() const { return virtual_depth_; }
 
+  // Link residual tables (include/rtuf.h, LINK RESIDUAL TABLES): per link label, how the sensor image compares with the model
+  // for the camera and link poses filter_into would use.  depth: width x height float metres, or uint16 millimetres with
+  // is_16uc1; table_out: n_labels rows, at least numLinkResidualRows(); row = label (linkLabels() with
+  // FilterParameters::link_labels, else 1 + the renderable's index over all models; row 0: no link).  No plane is written.
+  bool link_residuals_into(const void* depth, bool is_16uc1, double* glTf, int width, int height, double timestamp, rtuf_link_residuals* table_out,
+                           int n_labels)
+  {
+    prepare(width, height);
+    if (!depth || !table_out) throw std::runtime_error("link_residuals_into: needs depth and table_out");
+    if (renderers_.empty() || !stage_frame(glTf, timestamp)) return false;
+    const void* in = depth;
+    if (is_16uc1 && (width_ & 3) != 0) {
+      // (the 16UC1 kernels need a width that is a multiple of 4: the reference's conversion on the host, as filter_into does)
+      const size_t px = (size_t)width_ * height_;
+      scratch_in_.resize(px);
+      for (size_t i = 0; i < px; i++) scratch_in_[i] = (float)static_cast<const uint16_t*>(depth)[i] * 0.001f;
+      const float* fin = scratch_in_.data();
+      check(rtuf_link_residuals_batch(ctx_, 1, &fin, table_out, n_labels));
+    } else if (is_16uc1) {
+      check(rtuf_link_residuals_batch_u16(ctx_, 1, reinterpret_cast<const uint16_t* const*>(&in), table_out, n_labels));
+    } else {
+      check(rtuf_link_residuals_batch(ctx_, 1, reinterpret_cast<const float* const*>(&in), table_out, n_labels));
+    }
+    return true;
+  }
+  // rows a link_residuals_into table needs: one more than the largest label in effect (0 before the models are loaded)
+  int numLinkResidualRows() const
+  {
+    if (want_labels_) {
+      int largest = 0;
+      for (const auto& kv : link_labels_) largest = std::max(largest, (int)kv.second);
+      return largest + 1;
+    }
+    size_t n = 0;
+    for (const URDFRenderer* rd : renderers_) n += rd->renderables_.size();
+    return (int)n + 1;
+  }
+
   // filter_into with the link label plane as well (labels_out: width x height uint16; needs FilterParameters::link_labels and
   // a masked_out).  The plane is also kept for getLabels().
   bool filter_into(const void* depth, bool is_16uc1, double* glTf, int width, int height, double timestamp, void* masked_out, uint8_t* mask_out,

@@ -426,6 +426,56 @@ int rtuf_render_batch(rtuf_context *ctx, int n_streams, float *const *virtual_ou
 int rtuf_render_batch_u16(rtuf_context *ctx, int n_streams, uint16_t *const *virtual_mm_out, uint16_t *const *labels_out,
                           float empty_value);
 
+/* LINK RESIDUAL TABLES.  New, beyond the reference: per stream and link label, how the sensor plane compares with the model
+ * -- how many pixels the link covers, how many the sensor confirms, how many show something in front of the link or see
+ * through it, how many hold no reading, and the summed residual sensor - virtual of the confirmed ones -- as a table
+ * [n_streams][n_labels] of 64-byte rows, with no plane written at all.  Streams 0 .. n-1 are posed by the same setters as a
+ * filter batch.  Row l of stream s collects the pixels of s whose label is l, the label rtuf_filter_batch*_labels would write
+ * (LINK LABELS: same winner, default labels or rtuf_set_link_labels, the > 65535 links rule, the table allocated on first
+ * use); row 0 covers the background quad, pixels nothing was drawn to, and links labelled 0.  Every call overwrites its
+ * table (rows no pixel reaches are zero); it never accumulates into what was there.  All sums are integers: the table does
+ * not depend on the order of execution.
+ * Per pixel, s = the sensor value (the float as given; 16UC1: uint16 * 0.001f, as every 16UC1 call reads it):
+ *   no fragment reached the pixel:  pixels++, and invalid++ if !(s > 0); nothing else.
+ *   drawn pixel (the background quad included), z the float window z the filter uses, t the threshold the filter would
+ *   use (the winner's link threshold where rtuf_set_link_thresholds gave one, else depth_distance_threshold),
+ *   v = num / (z - off) (VIRTUAL DEPTH), lo = v - t and hi = v + t (one float operation each):
+ *     valid = s > 0;  filtered = s > lo  (the filter's mask, for an invalid s as well);
+ *     in_front = valid && !filtered;  behind = valid && filtered && s > hi;  agree = valid && filtered && !(s > hi);
+ *     agree pixels add q = round_half_even((s - v) * 2^20) (float subtraction and product; saturating to int32, NaN -> 0)
+ *     to sum_residual and |q| to sum_abs_residual: sum_residual / agree * 2^-20 is the mean signed residual in metres.
+ *   For rows without undrawn pixels invalid + in_front + behind + agree == pixels.
+ * With t NaN or -inf every valid pixel of that link counts as in_front; with t = +inf every valid pixel counts as agree, and
+ * q saturates where the residual is 2048 m or more.
+ * Refusals, each enqueuing nothing and leaving the table untouched: a link of the context whose label is >= n_labels, or
+ * n_labels < 1 (RTUF_ERR_INVALID; the label table is checked on the host); silhouette_dilation_px > 0 (RTUF_ERR_INVALID); a
+ * NULL plane or table, n out of range, an un-finalized context, a 16UC1 call with a width that is not a multiple of 4, as
+ * the filter calls.
+ * RTUF_FLAG_TWO_KERNEL and filter_replace_value do not enter: a residual batch is always one tile kernel, never touches the
+ * z-surface, and is accepted on a context with per-link thresholds (honoured) and with the two-kernel flag.  Otherwise it is
+ * a batch like any other: raster lanes, pipelines, launch groups, partial batches, batches in flight (each with a table of
+ * its own), graph replay of small batches, re-runs after a bin regrowth (the table is zeroed again: as if the batch had run
+ * once), the status word and rtuf_stats with their meaning (timings: ms_raster), rtuf_order_stream_after_batches.  The
+ * device forms only enqueue (d_table: [n][n_labels], 8-byte aligned); the host-plane forms are synchronous: planes up,
+ * table down. */
+typedef struct {
+  uint64_t pixels;           /* pixels of the stream whose label is this row's                                      */
+  uint64_t invalid;          /* ... whose sensor value is not > 0 (NaN, 0, negative)                                */
+  uint64_t filtered;         /* ... the filter would mask: exactly the pixels with mask 255                         */
+  uint64_t in_front;         /* valid, not filtered: the sensor sees something nearer than the link by more than t  */
+  uint64_t behind;           /* valid, filtered, sensor > virtual + t: the sensor sees through the link             */
+  uint64_t agree;            /* valid, filtered, not behind: the sensor confirms the link                           */
+  int64_t sum_residual;      /* over the agree pixels: sum of q, q = (sensor - virtual) in units of 2^-20 m         */
+  uint64_t sum_abs_residual; /* over the agree pixels: sum of |q|                                                   */
+} rtuf_link_residuals;       /* 64 bytes */
+
+int rtuf_link_residuals_batch_device(rtuf_context *ctx, int n_streams, const float *d_depth, rtuf_link_residuals *d_table, int n_labels);
+int rtuf_link_residuals_batch_device_u16(rtuf_context *ctx, int n_streams, const uint16_t *d_depth_mm, rtuf_link_residuals *d_table,
+                                         int n_labels);
+int rtuf_link_residuals_batch(rtuf_context *ctx, int n_streams, const float *const *depth_in, rtuf_link_residuals *table_out, int n_labels);
+int rtuf_link_residuals_batch_u16(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in, rtuf_link_residuals *table_out,
+                                  int n_labels);
+
 /* Counters of the last batch and kernel timings measured with HIP events on the context's
  * stream (replaces the wall-clock statistics of src/urdf_filter.cpp:239-266). */
 typedef struct {

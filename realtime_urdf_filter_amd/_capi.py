@@ -36,7 +36,12 @@ SYMBOLS = [
     "rtuf_set_link_labels", "rtuf_filter_batch_device_labels", "rtuf_filter_batch_device_u16_labels", "rtuf_filter_batch_labels",
     "rtuf_filter_batch_u16_labels", "rtuf_set_link_thresholds", "rtuf_clear_link_thresholds",
     "rtuf_render_batch_device", "rtuf_render_batch_device_u16", "rtuf_render_batch", "rtuf_render_batch_u16",
+    "rtuf_link_residuals_batch_device", "rtuf_link_residuals_batch_device_u16", "rtuf_link_residuals_batch", "rtuf_link_residuals_batch_u16",
 ]
+
+# rtuf_link_residuals (include/rtuf.h, LINK RESIDUAL TABLES): one 64-byte row per (stream, label)
+LINK_RESIDUALS_DTYPE = np.dtype([("pixels", "<u8"), ("invalid", "<u8"), ("filtered", "<u8"), ("in_front", "<u8"), ("behind", "<u8"),
+                                 ("agree", "<u8"), ("sum_residual", "<i8"), ("sum_abs_residual", "<u8")])
 
 
 class Params(ctypes.Structure):
@@ -183,6 +188,10 @@ def load_library(path=None):
     lib.rtuf_render_batch_device_u16.argtypes = [vp, ci, vp, vp, ctypes.c_float]
     lib.rtuf_render_batch.argtypes = [vp, ci, vp, vp, ctypes.c_float]
     lib.rtuf_render_batch_u16.argtypes = [vp, ci, vp, vp, ctypes.c_float]
+    lib.rtuf_link_residuals_batch_device.argtypes = [vp, ci, vp, vp, ci]
+    lib.rtuf_link_residuals_batch_device_u16.argtypes = [vp, ci, vp, vp, ci]
+    lib.rtuf_link_residuals_batch.argtypes = [vp, ci, vp, vp, ci]
+    lib.rtuf_link_residuals_batch_u16.argtypes = [vp, ci, vp, vp, ci]
     lib.rtuf_set_link_thresholds.argtypes = [vp, ci, vp, ci]
     lib.rtuf_clear_link_thresholds.argtypes = [vp, ci]
     if path is None:
@@ -412,6 +421,32 @@ class Context:
     def render_batch_device_u16(self, n, d_virtual_mm, d_labels=None, empty_value=0.0):
         self._check(self._lib.rtuf_render_batch_device_u16(self._h, n, ctypes.c_void_p(d_virtual_mm) if d_virtual_mm else None,
                                                            ctypes.c_void_p(d_labels) if d_labels else None, empty_value))
+
+    # link residual tables (include/rtuf.h, LINK RESIDUAL TABLES)
+    def link_residuals_batch(self, depth, n_labels):
+        """Per stream and label, how the sensor planes compare with the model: depth [n,H,W] float32 metres (or uint16
+        millimetres: the 16UC1 form) -> table [n, n_labels] of LINK_RESIDUALS_DTYPE.  Synchronous."""
+        u16 = np.asarray(depth).dtype == np.uint16
+        d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32).reshape(-1, self.height, self.width)
+        n = d.shape[0]
+        table = np.empty((n, max(int(n_labels), 0)), LINK_RESIDUALS_DTYPE)
+        PP = ctypes.c_void_p * max(n, 1)
+        din = PP(*[d[i].ctypes.data for i in range(n)])
+        fn = self._lib.rtuf_link_residuals_batch_u16 if u16 else self._lib.rtuf_link_residuals_batch
+        self._check(fn(self._h, n, din, ctypes.c_void_p(table.ctypes.data), int(n_labels)))
+        return table
+
+    def link_residuals_batch_u16(self, depth_mm, n_labels):
+        return self.link_residuals_batch(np.ascontiguousarray(depth_mm, np.uint16), n_labels)
+
+    def link_residuals_batch_device(self, n, d_depth, d_table, n_labels):
+        """Device pointers (ints): d_depth [n,H,W] float32, d_table [n, n_labels] rows of 64 bytes; enqueue only; call sync()."""
+        self._check(self._lib.rtuf_link_residuals_batch_device(self._h, n, ctypes.c_void_p(d_depth) if d_depth else None,
+                                                               ctypes.c_void_p(d_table) if d_table else None, int(n_labels)))
+
+    def link_residuals_batch_device_u16(self, n, d_depth_mm, d_table, n_labels):
+        self._check(self._lib.rtuf_link_residuals_batch_device_u16(self._h, n, ctypes.c_void_p(d_depth_mm) if d_depth_mm else None,
+                                                                   ctypes.c_void_p(d_table) if d_table else None, int(n_labels)))
 
     # asynchronous host planes
     def host_alloc(self, shape, dtype):

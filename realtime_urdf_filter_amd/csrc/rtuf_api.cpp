@@ -101,6 +101,7 @@ struct rtuf_context {
   std::vector<uint32_t> draw_link, draw_last_order;
   uint16_t* d_order_labels = nullptr;
   bool labels_dirty = true;
+  uint32_t max_label = 0;                    // the largest label of any link (ensure_label_table): what a residual table's n_labels must exceed
   // Per-link depth thresholds: the device table draw order -> threshold, [n_tris + 1] (entry 0, the background quad: the
   // global threshold), allocated by the first rtuf_set_link_thresholds and rewritten in place after that (captured graphs
   // keep its address).  The tile kernels read it only while thresh_models > 0 (models with thresholds of their own).
@@ -186,6 +187,9 @@ struct rtuf_context {
     // render batch (rtuf_render_batch*): the virtual depth plane (float, or uint16 with u16) and the value of its empty pixels;
     // depth / masked / mask / bits are unused, labels may be given.  nullptr: a filter batch.
     float* virt = nullptr; float empty_value = 0.0f;
+    // residual batch (rtuf_link_residuals_batch*): the table [n][n_labels] the tile kernel sums into, zeroed on every run (first
+    // runs and re-runs alike); depth is read, masked / mask / bits / labels / virt are unused.  nullptr: not a residual batch.
+    rtuf_link_residuals* resid = nullptr; int n_labels = 0;
     Counters* h_counters = nullptr;          // pinned [max_groups]: one block per launch group, filled by the copies that end the batch
     hipEvent_t done[kMaxLanes] = {};         // recorded on each lane after its copy
     uint32_t lanes_used = 0;                 // bit l: the batch has launch groups on lane l
@@ -214,11 +218,12 @@ struct rtuf_context {
     // Host-plane batches (rtuf_filter_batch*): device staging of this slot, the caller's planes, and the
     // events that order upload -> kernels -> download across the copy streams.
     bool host_io = false;
-    float* st_depth = nullptr; float* st_masked = nullptr; uint8_t* st_mask = nullptr; size_t st_streams = 0;
+    float* st_depth = nullptr; float* st_masked = nullptr; uint8_t* st_mask = nullptr; size_t st_streams = 0, st_depth_streams = 0;
     uint32_t* st_bits = nullptr; size_t st_bits_streams = 0;
     uint16_t* st_labels = nullptr; size_t st_labels_streams = 0;
     float* st_virtual = nullptr; size_t st_virtual_streams = 0;      // (float-sized: large enough for uint16 planes)
     std::vector<void*> h_masked, h_mask, h_bits, h_labels, h_virtual;
+    rtuf_link_residuals* st_table = nullptr; size_t st_table_rows = 0; rtuf_link_residuals* h_table = nullptr;      // residual batch with host planes
     hipEvent_t uploaded = nullptr, downloaded = nullptr;
     bool wait_upload = false;                // the lanes wait for `uploaded` before the first kernel that reads the planes
   };
@@ -650,8 +655,8 @@ static void free_frame_buffers(rtuf_context* c)
     dev_free(c, ln.d_clip_spill); dev_free(c, ln.d_big_list); dev_free(c, ln.d_zsurface);
     for (auto*& it : ln.d_items) dev_free(c, it);
   }
-  for (auto& b : c->batch) { dev_free(c, b.st_depth); dev_free(c, b.st_masked); dev_free(c, b.st_mask); b.st_streams = 0; dev_free(c, b.st_bits); b.st_bits_streams = 0; }
-  for (auto& b : c->batch) { dev_free(c, b.st_labels); b.st_labels_streams = 0; dev_free(c, b.st_virtual); b.st_virtual_streams = 0; }
+  for (auto& b : c->batch) { dev_free(c, b.st_depth); dev_free(c, b.st_masked); dev_free(c, b.st_mask); b.st_streams = 0; b.st_depth_streams = 0; dev_free(c, b.st_bits); b.st_bits_streams = 0; }
+  for (auto& b : c->batch) { dev_free(c, b.st_labels); b.st_labels_streams = 0; dev_free(c, b.st_virtual); b.st_virtual_streams = 0; dev_free(c, b.st_table); b.st_table_rows = 0; }
   for (auto*& p : c->ring_cams) hfree(p);
   for (auto*& p : c->ring_link_tf) hfree(p);
   c->h_cams = nullptr; c->h_link_tf = nullptr;
@@ -1451,6 +1456,11 @@ static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& 
     launch_clip(gr.sa, st);
     launch_bigrec(gr.sa, plan.cover_pass, st);      // appends the many-tile records the two kernels above listed (after the cover pass, if it is on)
     if (b.timing) mark(e0 + 2, st);
+    // a residual batch: the group's rows of the table are contiguous and start from zero on every run (timed with the tile
+    // kernel: ms_raster)
+    if (gr.ta.resid_table)
+      launch_zero_residual_rows(gr.ta.resid_table + (size_t)gr.ta.group_base * (size_t)gr.ta.n_labels * 8u,
+                                (size_t)gr.ta.group_size * (size_t)gr.ta.n_labels * 8u, st);
     launch_tile(gr.ta, two, plan.cover_pass, st);
     if (b.timing) mark(e0 + 3, st);
     if (gr.compare) { launch_compare(gr.ca, st); if (b.timing) mark(e0 + 4, st); }
@@ -1474,7 +1484,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   const float* d_depth = b.depth; float* d_masked = b.masked; uint8_t* d_mask = b.mask;
   const bool io_u16 = b.u16;
   const size_t esz = io_u16 ? sizeof(uint16_t) : sizeof(float);
-  const bool two = (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.virt;      // (a render batch is always one tile kernel)
+  const bool two = (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.virt && !b.resid;      // (render and residual batches are always one tile kernel)
   // Launch groups: as many as the lanes' bins ask for, alternating between the lanes; a batch that is not split takes one
   // lane, the next such batch the other.
   const int n_groups = groups_for(c, n);
@@ -1531,7 +1541,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   // silhouette dilation: the tile kernel writes the z-surface and dilate_compare_kernel makes every output form from it (the
   // mask bits included); without it nothing here differs from before
   // (a render batch compares nothing: no thresholds, and the render calls refuse silhouette dilation)
-  if (!rerun) b.dilation = b.virt ? 0 : (int)c->params.silhouette_dilation_px;
+  if (!rerun) b.dilation = b.virt || b.resid ? 0 : (int)c->params.silhouette_dilation_px;      // (a residual batch honours the thresholds and refuses dilation too)
   if (!rerun) b.order_thr = c->thresh_models > 0 && !b.virt ? c->d_order_thr : nullptr;
   const int dil = b.dilation;
   plan.zroute = dil > 0 || (two && !b.bits);
@@ -1609,9 +1619,10 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     ta.fast_div = fast_div;
     ta.bits = dil ? nullptr : b.bits;
     ta.labels = b.labels;                    // (the label calls refuse silhouette dilation and mask bits)
-    ta.order_labels = b.labels ? c->d_order_labels : nullptr;
+    ta.order_labels = b.labels || b.resid ? c->d_order_labels : nullptr;
     ta.order_thr = b.order_thr;              // (batches with per-link thresholds never take the z-surface route: check_thresh_route)
     ta.virtual_out = b.virt; ta.empty_value = b.empty_value;
+    ta.resid_table = reinterpret_cast<unsigned long long*>(b.resid); ta.n_labels = b.n_labels;
     gr.compare = two && !b.bits && !dil;
     gr.dilate = dil > 0;
     if (gr.dilate) {
@@ -1633,7 +1644,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   }
   b.n_groups = (int)plan.groups.size();          // (= n_groups: the loop makes ceil(n / per_group) groups, checked above)
   b.setup_grid.assign(plan.groups.size(), 0xffffffffu);
-  if (!b.virt) c->last_lane = plan.groups.back().lane;      // (a render batch leaves the z-surface alone)
+  if (!b.virt && !b.resid) c->last_lane = plan.groups.back().lane;      // (render and residual batches leave the z-surface alone)
   // host-plane batches: the lanes' first kernels wait for the upload of the planes
   if (b.wait_upload)
     for (int l = 0; l < c->n_lanes; l++)
@@ -1711,6 +1722,11 @@ static int enqueue_download(rtuf_context* c, rtuf_context::Batch& b)
   const size_t esz = b.u16 ? sizeof(uint16_t) : sizeof(float);
   for (int l = 0; l < c->n_lanes; l++)
     if (b.lanes_used >> l & 1u) HIP_TRY(c, hipStreamWaitEvent(c->d2h, b.done[l], 0));
+  if (b.resid) {                             // a residual batch: the table is all that comes back
+    HIP_TRY(c, hipMemcpyAsync(b.h_table, b.st_table, (size_t)b.n * (size_t)b.n_labels * sizeof(rtuf_link_residuals), hipMemcpyDeviceToHost, c->d2h));
+    HIP_TRY(c, hipEventRecord(b.downloaded, c->d2h));
+    return RTUF_OK;
+  }
   if (b.bits) {
     const size_t words = (size_t)c->height * (size_t)((c->width + 31) / 32);
     for (int s = 0; s < b.n;) {
@@ -1821,7 +1837,7 @@ static int retire_oldest(rtuf_context* c)
       if (b.timing && b.events.size() >= (size_t)(kEvGroup0 + kEvPerGroup * b.n_groups)) {
         // per launch group E0 .. E4 (see issue_plan).  With several lanes the kernels of different groups overlap: the sums
         // below add up per-launch durations, they are not wall time.
-        const bool two = ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.bits && !b.virt) || b.dilation > 0;
+        const bool two = ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.bits && !b.virt && !b.resid) || b.dilation > 0;
         auto el = [&](size_t i, size_t j) { float ms = 0; hipEventElapsedTime(&ms, b.events[i], b.events[j]); return ms; };
         c->stats.ms_pose = c->stats.ms_setup = c->stats.ms_clip = c->stats.ms_raster = c->stats.ms_compare = c->stats.ms_total = 0;
         for (int g = 0; g < b.n_groups; g++) {
@@ -1922,13 +1938,15 @@ static int check_thresh_route(rtuf_context* c)
 }
 
 // d_virtual != nullptr: a render batch (d_depth, d_masked, d_mask, d_bits unused)
+// d_resid != nullptr: a residual batch (d_masked, d_mask, d_bits, d_labels, d_virtual unused)
 static int submit_batch(rtuf_context* c, int n, const float* d_depth, float* d_masked, uint8_t* d_mask, bool u16, uint32_t* d_bits = nullptr,
-                        bool wait_upload = false, uint16_t* d_labels = nullptr, float* d_virtual = nullptr, float empty_value = 0.0f)
+                        bool wait_upload = false, uint16_t* d_labels = nullptr, float* d_virtual = nullptr, float empty_value = 0.0f,
+                        rtuf_link_residuals* d_resid = nullptr, int n_labels = 0)
 {
   if (c->broken) return c->fail(RTUF_ERR_STATE, "context unusable: a bin regrowth failed (%s)", c->error.c_str());
-  if (!d_virtual) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
+  if (!d_virtual && !d_resid) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
   hipSetDevice(c->device);
-  if (uses_zsurface(c) && !d_virtual)
+  if (uses_zsurface(c) && !d_virtual && !d_resid)
     for (int l = 0; l < c->n_lanes; l++)
       if (!c->lane[l].d_zsurface) HIP_TRY(c, dev_alloc(c, &c->lane[l].d_zsurface, (size_t)c->group * c->width * c->height * sizeof(float)));
   // two-kernel mode and silhouette dilation keep one z-surface per lane: their batches do not overlap
@@ -1937,6 +1955,7 @@ static int submit_batch(rtuf_context* c, int n, const float* d_depth, float* d_m
   rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];
   b.n = n; b.depth = d_depth; b.masked = d_masked; b.mask = d_mask; b.u16 = u16; b.host_io = false; b.bits = d_bits; b.labels = d_labels;
   b.virt = d_virtual; b.empty_value = empty_value;
+  b.resid = d_resid; b.n_labels = n_labels;
   b.wait_upload = wait_upload;
   const int rc = enqueue_batch(c, b, false);
   if (rc == RTUF_OK) { b.active = true; c->pending++; }
@@ -2090,6 +2109,44 @@ static int ensure_copy_streams(rtuf_context* c)
   return RTUF_OK;
 }
 
+// the slot's device staging of the sensor planes and -- with_outputs: not for a residual batch, which writes no plane -- of
+// the filter's outputs, for n streams
+static int ensure_plane_staging(rtuf_context* c, rtuf_context::Batch& b, int n, bool with_outputs)
+{
+  const size_t plane = (size_t)c->width * c->height;
+  if (b.st_depth_streams < (size_t)n) {
+    dev_free(c, b.st_depth);
+    b.st_depth_streams = 0;
+    HIP_TRY(c, dev_alloc(c, &b.st_depth, (size_t)n * plane * sizeof(float)));     // float-sized: large enough for uint16 planes
+    b.st_depth_streams = (size_t)n;
+  }
+  if (with_outputs && b.st_streams < (size_t)n) {
+    dev_free(c, b.st_masked); dev_free(c, b.st_mask);
+    b.st_streams = 0;
+    HIP_TRY(c, dev_alloc(c, &b.st_masked, (size_t)n * plane * sizeof(float)));
+    HIP_TRY(c, dev_alloc(c, &b.st_mask, (size_t)n * plane));
+    b.st_streams = (size_t)n;
+  }
+  return RTUF_OK;
+}
+
+// the sensor planes go up on the upload stream (consecutive planes as one transfer); `uploaded` marks their arrival
+static int upload_planes(rtuf_context* c, rtuf_context::Batch& b, int n, const void* const* depth_in, bool u16)
+{
+  const size_t plane = (size_t)c->width * c->height;
+  if (!b.uploaded) HIP_TRY(c, hipEventCreateWithFlags(&b.uploaded, hipEventDisableTiming));
+  if (!b.downloaded) HIP_TRY(c, hipEventCreateWithFlags(&b.downloaded, hipEventDisableTiming));
+  const size_t esz = u16 ? sizeof(uint16_t) : sizeof(float);
+  for (int s = 0; s < n;) {
+    int e = s + 1;
+    while (e < n && (const char*)depth_in[e] == (const char*)depth_in[e - 1] + plane * esz) e++;
+    HIP_TRY(c, hipMemcpyAsync((char*)b.st_depth + (size_t)s * plane * esz, depth_in[s], (size_t)(e - s) * plane * esz, hipMemcpyHostToDevice, c->h2d));
+    s = e;
+  }
+  HIP_TRY(c, hipEventRecord(b.uploaded, c->h2d));          // (the lanes' first kernels wait for it: enqueue_batch)
+  return RTUF_OK;
+}
+
 static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in, void* const* masked_out,
                              void* const* mask_out, bool u16, uint32_t* const* bits_out = nullptr, uint16_t* const* labels_out = nullptr)
 {
@@ -2106,14 +2163,7 @@ static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in
   while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
   rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];     // the slot submit_batch takes next
   const size_t plane = (size_t)c->width * c->height;
-  if (b.st_streams < (size_t)n) {
-    dev_free(c, b.st_depth); dev_free(c, b.st_masked); dev_free(c, b.st_mask);
-    b.st_streams = 0;
-    HIP_TRY(c, dev_alloc(c, &b.st_depth, (size_t)n * plane * sizeof(float)));     // float-sized: large enough for uint16 planes
-    HIP_TRY(c, dev_alloc(c, &b.st_masked, (size_t)n * plane * sizeof(float)));
-    HIP_TRY(c, dev_alloc(c, &b.st_mask, (size_t)n * plane));
-    b.st_streams = (size_t)n;
-  }
+  { const int rc = ensure_plane_staging(c, b, n, true); if (rc != RTUF_OK) return rc; }
   if (bits_out && b.st_bits_streams < (size_t)n) {
     dev_free(c, b.st_bits);
     b.st_bits_streams = 0;
@@ -2126,16 +2176,7 @@ static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in
     HIP_TRY(c, dev_alloc(c, &b.st_labels, (size_t)n * plane * sizeof(uint16_t)));
     b.st_labels_streams = (size_t)n;
   }
-  if (!b.uploaded) HIP_TRY(c, hipEventCreateWithFlags(&b.uploaded, hipEventDisableTiming));
-  if (!b.downloaded) HIP_TRY(c, hipEventCreateWithFlags(&b.downloaded, hipEventDisableTiming));
-  const size_t esz = u16 ? sizeof(uint16_t) : sizeof(float);
-  for (int s = 0; s < n;) {
-    int e = s + 1;
-    while (e < n && (const char*)depth_in[e] == (const char*)depth_in[e - 1] + plane * esz) e++;
-    HIP_TRY(c, hipMemcpyAsync((char*)b.st_depth + (size_t)s * plane * esz, depth_in[s], (size_t)(e - s) * plane * esz, hipMemcpyHostToDevice, c->h2d));
-    s = e;
-  }
-  HIP_TRY(c, hipEventRecord(b.uploaded, c->h2d));          // (the lanes' first kernels wait for it: enqueue_batch)
+  { const int rc = upload_planes(c, b, n, depth_in, u16); if (rc != RTUF_OK) return rc; }
   bool any_mask = false;
   b.h_bits.clear();
   b.h_labels.clear();
@@ -2215,6 +2256,8 @@ static int ensure_label_table(rtuf_context* c)
       if (def > 65535) return c->fail(RTUF_ERR_CAPACITY, "link %d: default labels are limited to 65535 links (set them with rtuf_set_link_labels)", def - 1);
       link_label[(size_t)m.link_base + l] = (uint16_t)def;
     }
+  c->max_label = 0;
+  for (const uint16_t lab : link_label) c->max_label = std::max(c->max_label, (uint32_t)lab);
   std::vector<uint16_t> table((size_t)c->n_tris + 1, 0);
   for (size_t d = 0, first = 1; d < c->draw_link.size(); d++) {
     const uint16_t lab = link_label[c->draw_link[d]];
@@ -2427,6 +2470,79 @@ int rtuf_render_batch(rtuf_context* c, int n, float* const* virtual_out, uint16_
 int rtuf_render_batch_u16(rtuf_context* c, int n, uint16_t* const* virtual_out, uint16_t* const* labels_out, float empty_value)
 {
   const int rc = render_batch_async(c, n, reinterpret_cast<void* const*>(virtual_out), labels_out, empty_value, true);
+  return rc != RTUF_OK ? rc : rtuf_sync(c);
+}
+
+// ---- link residual tables ----------------------------------------------------------------------------
+// A residual batch is a batch like any other (submit_batch) whose tile kernel stores no plane: it classifies every pixel
+// against the sensor plane and sums the classes per label into the caller's table.  Per-link thresholds are honoured, the
+// two-kernel flag and the replace value do not enter, and the z-surface is never used.
+static int check_residuals_call(rtuf_context* c, int n, const void* in, const void* table, int n_labels, bool u16)
+{
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (n <= 0 || n > c->max_streams || !in || !table) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
+  if (n_labels < 1) return c->fail(RTUF_ERR_INVALID, "a residual table needs at least one row per stream (n_labels=%d)", n_labels);
+  if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "link residual tables are not supported with silhouette dilation yet");
+  if (u16 && (c->width & 3)) return c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4");
+  { const int rc = ensure_label_table(c); if (rc != RTUF_OK) return rc; }
+  if (c->max_label >= (uint32_t)n_labels) return c->fail(RTUF_ERR_INVALID, "a link has label %u: the table needs n_labels > %u (got %d)", c->max_label, c->max_label, n_labels);
+  return RTUF_OK;
+}
+
+int rtuf_link_residuals_batch_device(rtuf_context* c, int n, const float* d_depth, rtuf_link_residuals* d_table, int n_labels)
+{
+  KIDS_NEXT(c, rtuf_link_residuals_batch_device(k, n, d_depth, d_table, n_labels));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_residuals_call(c, n, d_depth, d_table, n_labels, false);
+  return rc != RTUF_OK ? rc : submit_batch(c, n, d_depth, nullptr, nullptr, false, nullptr, false, nullptr, nullptr, 0.0f, d_table, n_labels);
+}
+
+int rtuf_link_residuals_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth, rtuf_link_residuals* d_table, int n_labels)
+{
+  KIDS_NEXT(c, rtuf_link_residuals_batch_device_u16(k, n, d_depth, d_table, n_labels));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_residuals_call(c, n, d_depth, d_table, n_labels, true);
+  return rc != RTUF_OK ? rc : submit_batch(c, n, reinterpret_cast<const float*>(d_depth), nullptr, nullptr, true, nullptr, false, nullptr, nullptr, 0.0f, d_table, n_labels);
+}
+
+// host planes: planes up into the slot's staging, the table back from its device copy on the download stream
+static int link_residuals_batch_async(rtuf_context* c, int n, const void* const* depth_in, rtuf_link_residuals* table_out, int n_labels, bool u16)
+{
+  KIDS_NEXT(c, link_residuals_batch_async(k, n, depth_in, table_out, n_labels, u16));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = check_residuals_call(c, n, depth_in, table_out, n_labels, u16); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; s < n; s++)
+    if (!depth_in[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
+  hipSetDevice(c->device);
+  { const int rc = ensure_copy_streams(c); if (rc != RTUF_OK) return rc; }
+  const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
+  while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
+  rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];     // the slot submit_batch takes next
+  { const int rc = ensure_plane_staging(c, b, n, false); if (rc != RTUF_OK) return rc; }
+  const size_t rows = (size_t)n * (size_t)n_labels;
+  if (b.st_table_rows < rows) {
+    dev_free(c, b.st_table);
+    b.st_table_rows = 0;
+    HIP_TRY(c, dev_alloc(c, &b.st_table, rows * sizeof(rtuf_link_residuals)));
+    b.st_table_rows = rows;
+  }
+  { const int rc = upload_planes(c, b, n, depth_in, u16); if (rc != RTUF_OK) return rc; }
+  b.h_table = table_out;
+  const int rc = submit_batch(c, n, b.st_depth, nullptr, nullptr, u16, nullptr, true, nullptr, nullptr, 0.0f, b.st_table, n_labels);
+  if (rc != RTUF_OK) return rc;
+  b.host_io = true;
+  return enqueue_download(c, b);
+}
+
+int rtuf_link_residuals_batch(rtuf_context* c, int n, const float* const* depth_in, rtuf_link_residuals* table_out, int n_labels)
+{
+  const int rc = link_residuals_batch_async(c, n, reinterpret_cast<const void* const*>(depth_in), table_out, n_labels, false);
+  return rc != RTUF_OK ? rc : rtuf_sync(c);
+}
+
+int rtuf_link_residuals_batch_u16(rtuf_context* c, int n, const uint16_t* const* depth_mm_in, rtuf_link_residuals* table_out, int n_labels)
+{
+  const int rc = link_residuals_batch_async(c, n, reinterpret_cast<const void* const*>(depth_mm_in), table_out, n_labels, true);
   return rc != RTUF_OK ? rc : rtuf_sync(c);
 }
 

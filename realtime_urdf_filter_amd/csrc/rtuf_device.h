@@ -328,6 +328,10 @@ struct TileArgs {
   // virtual depth planes (appended).  virtual_out != nullptr selects tile_render_kernel: depth, masked, mask, bits unused.
   float* virtual_out;            // [n][H][W] virtual depth of every pixel's winner (f32 metres or, with io_u16, uint16 millimetres)
   float empty_value;             // ... and what a pixel holds where the background quad won or nothing was drawn
+  // link residual tables (appended).  resid_table != nullptr selects tile_resid_kernel: masked, mask, bits, labels unused;
+  // order_labels is always set, order_thr as for a filter batch.
+  unsigned long long* resid_table;   // [n][n_labels] rows of eight 64-bit sums (rtuf_link_residuals), zeroed before the kernel
+  int n_labels;
 };
 
 struct CompareArgs {
@@ -389,6 +393,7 @@ void launch_init_headers(BinHeader* hdr, size_t n_bins, hipStream_t st);
 // ... and folds what they say about overflows into the batch's status word (PublishLimits: the capacities they are held against)
 struct PublishLimits { uint32_t capacity, fcapacity, big_capacity; };
 void launch_publish_counters(const Counters* src, Counters* host_dst, int first, int stride, int count, uint32_t* status, PublishLimits lim, hipStream_t st);
+void launch_zero_residual_rows(unsigned long long* rows, size_t n_words, hipStream_t st);      // n_words 64-bit words from rows on
 void launch_tile(const TileArgs& a, bool two_kernel, bool cover_pass, hipStream_t st);   // a.io_u16 selects the 16UC1 variant
 void launch_compare(const CompareArgs& a, hipStream_t st);
 void launch_dilate_compare(const DilateArgs& a, hipStream_t st);     // a.bits selects the mask-only variant, a.io_u16 the 16UC1 one

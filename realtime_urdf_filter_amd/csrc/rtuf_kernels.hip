@@ -2181,6 +2181,74 @@ __device__ __forceinline__ float shade(float sensor, float z, const ShadeConsts&
   return filt ? k.replace_value : sensor;
 }
 
+// Link residual tables (rtuf_link_residuals_batch*): the reduction of a resolve pass.  Every lane brings four pixels' class
+// bits (rtuf_numerics.h, 0: outside the image), labels and quantised residuals.  While pixels remain, the wave takes the first
+// remaining pixel's label, ballots the pixels that share it, popcounts the six class ballots, wave-sums q and |q| of the
+// agree pixels among them, and eight lanes add the row's eight 64-bit values (zero addends skipped) -- not to the table but to
+// the workgroup's copy of the row in LDS: kResidSlots rows in the exact-z pass's record buffer, dead at resolve time, found by
+// linear probing over their label tags; the workgroup's last step adds every used row to the table, one 64-byte line per
+// label.  All waves of a stream's tiles add to the same few rows, and adders of one line are served one after the other; with
+// this a tile has one per (label, field) instead of one per wave and pass (reasoned, not measured against the direct form).  A workgroup that sees more than kResidSlots labels adds the surplus to the table directly.
+constexpr int kResidSlots = 16;
+constexpr uint32_t kResidFree = 0xffffffffu;      // (labels are 16 bits wide)
+__device__ __forceinline__ void resid_reduce(const uint32_t (&cls)[4], const uint32_t (&lab)[4], const int (&q)[4], unsigned long long* rows, uint32_t* tags,
+                                             unsigned long long* table_rows)
+{
+  const int lane = (int)(threadIdx.x & 63u);
+  uint32_t rem = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) rem |= (cls[j] & kResPixel) << j;
+  for (;;) {
+    const unsigned long long live = __ballot(rem != 0u);
+    if (!live) break;
+    uint32_t mine = 0u;                      // the label of the lane's first remaining pixel
+#pragma unroll
+    for (int j = 3; j >= 0; j--) mine = (rem >> j & 1u) != 0u ? lab[j] : mine;
+    const uint32_t label = (uint32_t)__builtin_amdgcn_readlane((int)mine, __ffsll((long long)live) - 1);
+    uint32_t cnt[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    long long sq = 0;
+    unsigned long long sa = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const bool in = (rem >> j & 1u) != 0u && lab[j] == label;
+      const uint32_t c = in ? cls[j] : 0u;
+      if (in) rem &= ~(1u << j);
+#pragma unroll
+      for (int f = 0; f < 6; f++) cnt[f] += (uint32_t)__popcll(__ballot((c >> f & 1u) != 0u));
+      if (c & kResAgree) { sq += (long long)q[j]; sa += (unsigned long long)(q[j] < 0 ? -(long long)q[j] : (long long)q[j]); }
+    }
+    if (cnt[5]) {                            // (uniform) sums over the wave: in 32 bits where 64 lanes' sums cannot leave them
+      if (__ballot(sa >= (1ull << 25)) == 0ull) {
+        int s32 = (int)sq, a32 = (int)sa;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { s32 += __shfl_xor(s32, d); a32 += __shfl_xor(a32, d); }
+        sq = (long long)s32; sa = (unsigned long long)(uint32_t)a32;
+      } else {
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { sq += __shfl_xor(sq, d); sa += __shfl_xor(sa, d); }
+      }
+    }
+    // the row's slot in LDS: the first free or equal tag from the label's home on (-1: every slot holds another label)
+    int slot = -1;
+    for (int i = 0; i < kResidSlots && slot < 0; i++) {
+      const int idx = (int)((label + (uint32_t)i) & (uint32_t)(kResidSlots - 1));
+      uint32_t old = 0u;
+      if (lane == 0) old = atomicCAS(&tags[idx], kResidFree, label);
+      old = (uint32_t)__builtin_amdgcn_readfirstlane((int)old);
+      if (old == kResidFree || old == label) slot = idx;
+    }
+    unsigned long long val = (unsigned long long)cnt[0];
+#pragma unroll
+    for (int f = 1; f < 6; f++) val = lane == f ? (unsigned long long)cnt[f] : val;
+    val = lane == 6 ? (unsigned long long)sq : val;
+    val = lane == 7 ? sa : val;
+    if (lane < 8 && val != 0ull) {
+      if (slot >= 0) atomicAdd(&rows[slot * 8 + lane], val);
+      else atomicAdd(&table_rows[(size_t)label * 8u + (uint32_t)lane], val);
+    }
+  }
+}
+
 // COVER: the batch ran the cover pass (bigrec_kernel<0>), so a bin's header may name a cover.  Without it (the host skips the
 // pass while no scene has triangles that cover whole tiles) the cover code is compiled out: it costs the headline workload 3 %.
 // LABELS: the kernel also writes the link label plane (a.labels, a.order_labels: rtuf_filter_batch*_labels); never with BITS.
@@ -2189,7 +2257,11 @@ __device__ __forceinline__ float shade(float sensor, float z, const ShadeConsts&
 // RENDER: no sensor plane, no compare: the only outputs are the virtual depth plane (a.virtual_out: shade_virtual of every
 // winner's z, a.empty_value where the background quad won or nothing was drawn; U16: both through metres_to_u16) and, with
 // LABELS, the label plane (rtuf_render_batch*).  Never with TWO_KERNEL, BITS or THRESH.
-template <bool TWO_KERNEL, bool U16, bool BITS, bool COVER, int NT, bool LABELS = false, bool THRESH = false, bool RENDER = false>
+// RESID: no output plane at all: every pixel of the image is classified against the sensor plane (link_residual_class:
+// virtual depth, the winner's threshold -- a.order_thr's with THRESH, max_diff without -- and label) and counted in its
+// label's row of the stream's table (a.resid_table: rtuf_link_residuals_batch*; resid_reduce).  Never with TWO_KERNEL, BITS,
+// LABELS or RENDER.
+template <bool TWO_KERNEL, bool U16, bool BITS, bool COVER, int NT, bool LABELS = false, bool THRESH = false, bool RENDER = false, bool RESID = false>
 __device__ __forceinline__ void tile_body(const TileArgs& a)
 {
   __shared__ unsigned long long keys[kKeyCount];
@@ -2226,7 +2298,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   kf.abl = a.flags;
   kf.lowmask = near_tile ? (1u << a.key_shift) - 1u : 0u;
   kf.zexact = near_tile ? exact_z_floor(a.key_shift) : 8388609u;
-  kf.keep_order = LABELS || THRESH || RENDER;      // (RENDER: order 0 is the background quad drawn as geometry)
+  kf.keep_order = LABELS || THRESH || RENDER || RESID;      // (RENDER: order 0 is the background quad drawn as geometry)
   const uint32_t count = count_front + count_back;
   // (the stream's background entry after the bin's header in program order: the compiler then issues the three scalar loads
   // together -- with the background first it waited for it before it even computed the header's address)
@@ -2294,7 +2366,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
       cov_a0 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.x));
       cov_dzdx = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.y));
       cov_dzdy = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.z));
-      if (LABELS) cov_label = a.order_labels[(uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask];
+      if (LABELS || RESID) cov_label = a.order_labels[(uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask];
       if (THRESH) cov_thr = a.order_thr[(uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask];
       if (RENDER) cov_robot = ((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask) != 0u;
 #ifdef RTUF_COUNT
@@ -2436,6 +2508,22 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   // With BITS the only output is one mask bit per pixel: `finish` returns the lane's four mask flags (bit j = pixel j)
   // and stores nothing; the caller packs the flags of 8 neighbouring lanes into one 32-bit word.
   bool uncovered = false;                              // BITS: a pixel no fragment reached (its masked depth would be the clear colour, not the sensor value)
+  // RESID: the workgroup's table rows and their label tags in LDS the rasterisation is done with (every use of it above ends
+  // at a barrier), and what `finish` leaves of a pass for resid_reduce: class bits, label and quantised residual per pixel.
+  // In this mode `finish` takes the virtual depths for z and the thresholds themselves (t, not virtual - t) for thr; the
+  // background plane's virtual depth is the division the pose kernel's thr_bg holds (IEEE, as BgInfo::thr).
+  unsigned long long* const rs_rows = reinterpret_cast<unsigned long long*>(s_prec);
+  uint32_t* const rs_tags = s_winners;
+  static_assert(!RESID || (sizeof(TriRec) * 64 >= sizeof(unsigned long long) * 8 * kResidSlots && kWinnerWords >= kResidSlots), "the residual rows live in s_prec / s_winners");
+  uint32_t rs_cls[4] = {0u, 0u, 0u, 0u}, rs_lab[4] = {0u, 0u, 0u, 0u};
+  int rs_q[4] = {0, 0, 0, 0};
+  float rs_vbg = 0.0f;
+  if (RESID) {
+    rs_vbg = __fdiv_rn(a.sc_num, __fsub_rn(bgz, a.sc_off));
+    if (tid < kResidSlots * 8) rs_rows[tid] = 0ull;
+    if (tid < kResidSlots) rs_tags[tid] = kResidFree;
+    __syncthreads();
+  }
   // LABELS: lab = the four pixels' link labels, stored to the stream's label plane in either route
   auto finish = [&](int ps, const float (&z)[4], const float (&thr)[4], const bool (&frag)[4], const uint32_t (&lab)[4]) -> uint32_t {
     const int r_ly = r_ly0 + ps * kRowsPerPass, py = y_base + r_ly, px = r_px;
@@ -2474,6 +2562,16 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
       for (int j = 0; j < 4; j++)
         s[j] = j < nvalid ? (U16 ? u16_to_metres(reinterpret_cast<const uint16_t*>(a.depth)[gofs + j]) : a.depth[gofs + j]) : 0.0f;
     }
+    if (RESID) {                             // z = the virtual depths, thr = the thresholds: classes for resid_reduce, no store
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        int q = 0;
+        uint32_t c = frag[j] ? link_residual_class(s[j], z[j], thr[j], q) : link_residual_undrawn(s[j]);
+        if (j >= nvalid) c = 0u;
+        rs_cls[j] = c; rs_lab[j] = lab[j]; rs_q[j] = q;
+      }
+      return 0u;
+    }
     float o[4];
     uint32_t mbits = 0;
 #pragma unroll
@@ -2506,14 +2604,18 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   const bool bg_frag4[4] = {analytic_bg, analytic_bg, analytic_bg, analytic_bg};
   const uint32_t no_lab4[4] = {0u, 0u, 0u, 0u};
   const float empty4[4] = {a.empty_value, a.empty_value, a.empty_value, a.empty_value};      // RENDER
+  const float rs_vbg4[4] = {rs_vbg, rs_vbg, rs_vbg, rs_vbg}, rs_t4[4] = {a.max_diff, a.max_diff, a.max_diff, a.max_diff};      // RESID
 #pragma unroll
   for (int ps = 0; ps < kPasses; ps++) {
     const int r_ly = r_ly0 + ps * kRowsPerPass;
     const bool valid = r_ly < kTileH && y_base + r_ly < a.height && r_px < a.width;
     uint32_t flags4 = 0;
     RTUF_LANES(kLaneResolve, valid);
+    if (RESID) { rs_cls[0] = rs_cls[1] = rs_cls[2] = rs_cls[3] = 0u; }      // (lanes outside the image bring nothing)
     if (valid) {
-      if (RENDER && empty) {                         // tile without geometry: a streaming store of the empty value
+      if (RESID && empty) {                          // tile without geometry: the background plane (or nothing drawn) in every pixel
+        flags4 = finish(ps, rs_vbg4, rs_t4, bg_frag4, no_lab4);
+      } else if (RENDER && empty) {                         // tile without geometry: a streaming store of the empty value
         flags4 = finish(ps, empty4, bg_thr4, bg_frag4, no_lab4);
       } else if (empty) {                            // tile without geometry: a streaming compare against the plane
         if (analytic_bg) {          // (uniform: with the flags known to be set the four selects on them fall away)
@@ -2541,6 +2643,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
           thr[j] = thr_bg;
           lab[j] = drawn ? cov_label : 0u;
           if (RENDER) z[j] = drawn && cov_robot ? shade_virtual(zf, sc) : a.empty_value;
+          else if (RESID) { z[j] = drawn ? shade_virtual(zf, sc) : rs_vbg; thr[j] = drawn && THRESH ? cov_thr : a.max_diff; }
           else if (drawn && !TWO_KERNEL) thr[j] = THRESH ? shade_threshold(zf, sc, cov_thr) : shade_threshold(zf, sc);
 #ifdef RTUF_COUNT
           if (drawn && r_px + j < a.width) atomicAdd(&count_words()[1], 1u);
@@ -2558,6 +2661,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
           thr[j] = thr_bg;
           lab[j] = 0u;
           if (RENDER && k == bgkey) z[j] = a.empty_value;
+          else if (RESID && k == bgkey) { z[j] = rs_vbg; thr[j] = a.max_diff; frag[j] = analytic_bg; }
           else if (k == bgkey) { z[j] = bgz; frag[j] = analytic_bg; }
           else {                                        // the per-pixel division only runs where something was drawn
 #ifdef RTUF_COUNT
@@ -2579,12 +2683,17 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
                 if (khi <= 8388608u) z[j] = near_z_from_key(khi, (uint32_t)k & kf.lowmask, kf.shift);
               }
             }
-            if (!TWO_KERNEL && !THRESH && !RENDER) thr[j] = shade_threshold(z[j], sc);
+            if (!TWO_KERNEL && !THRESH && !RENDER && !RESID) thr[j] = shade_threshold(z[j], sc);
             // the winner's draw order: the key's (or, after the exact-z pass, kept above the float z: resolved_key); 0 is
             // "no fragment" (kNoFragment), whose table entry is label 0 -- and the background quad drawn as geometry, whose
             // threshold entry is max_diff
             if (LABELS && !THRESH) lab[j] = a.order_labels[(k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift];
-            if (THRESH) {
+            if (RESID) {                             // the winner's label, threshold and virtual depth
+              const uint32_t ord = (k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift;
+              lab[j] = a.order_labels[ord];
+              thr[j] = THRESH ? a.order_thr[ord] : a.max_diff;
+              z[j] = shade_virtual(z[j], sc);
+            } else if (THRESH) {
               const uint32_t ord = (k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift;
               thr[j] = shade_threshold(z[j], sc, a.order_thr[ord]);
               if (LABELS) lab[j] = a.order_labels[ord];
@@ -2598,6 +2707,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
         flags4 = finish(ps, z, thr, frag, lab);
       }
     }
+    if (RESID) resid_reduce(rs_cls, rs_lab, rs_q, rs_rows, rs_tags, a.resid_table + (size_t)stream * (size_t)a.n_labels * 8u);
     if (BITS) {
       // 8 neighbouring lanes hold the 32 pixels of one output word (pixel x -> bit x % 32 of word x / 32 of its row):
       // OR their nibbles together (all lanes take part, invalid ones with 0) and let the group's first lane store
@@ -2613,6 +2723,14 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
     }
   }
   if (BITS && __syncthreads_or(uncovered) && tid == 0) a.counters->shard[bin % kCounterShards].uncovered = 1u;
+  if (RESID) {                               // the workgroup's rows go to the table: one 64-byte line per label it saw
+    __syncthreads();
+    if (tid < kResidSlots * 8) {
+      const uint32_t tag = rs_tags[tid >> 3];
+      const unsigned long long v = rs_rows[tid];
+      if (tag != kResidFree && v != 0ull) atomicAdd(&a.resid_table[((size_t)stream * (size_t)a.n_labels + tag) * 8u + (uint32_t)(tid & 7)], v);
+    }
+  }
   RTUF_LANES_FLUSH(a.counters->shard[bin % kCounterShards]);
 #ifdef RTUF_COUNT
   __syncthreads();
@@ -2666,6 +2784,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WA
 #endif
 template <bool U16, bool LABELS, bool COVER, int NT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_RENDER))) void tile_render_kernel(TileArgs a) { tile_body<false, U16, false, COVER, NT, LABELS, false, true>(a); }
+// link residual tables (rtuf_link_residuals_batch*): 4 (2) B/pixel in, no plane out; 64 bytes per (stream, label) by atomics.
+// 72 VGPRs without spills at 7 waves/SIMD for the 256-thread variants.  A 1,024-thread workgroup is four waves per SIMD and a
+// second one would need eight, which 72 registers do not allow: those variants ask for 5 (up to 96 VGPRs) and lose nothing,
+// where at 7 the cover variants among them spilled two registers.
+#ifndef RTUF_TILE_WAVES_RESID
+#define RTUF_TILE_WAVES_RESID 7
+#endif
+template <bool U16, bool THRESH, bool COVER, int NT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT > 256 ? 5 : RTUF_TILE_WAVES_RESID))) void tile_resid_kernel(TileArgs a) { tile_body<false, U16, false, COVER, NT, false, THRESH, false, true>(a); }
 
 // ---------------------------------------------------------------------------------------
 // compare_kernel (two-kernel mode): streaming, 13 B/pixel (4 sensor + 4 z + 4 masked + 1 mask)
@@ -3010,7 +3137,13 @@ template <bool COVER, int NT>
 static void launch_tile_variant(const TileArgs& a, bool two_kernel, hipStream_t st)
 {
   const dim3 grid(a.tiles_x, a.tiles_y, a.group_size);
-  if (a.virtual_out) {                       // (a render batch has neither thresholds nor a z-surface route)
+  if (a.resid_table) {                       // (a residual batch stores no plane and has no z-surface route)
+    if (a.order_thr) {
+      if (a.io_u16) hipLaunchKernelGGL((tile_resid_kernel<true, true, COVER, NT>), grid, dim3(NT), 0, st, a);
+      else hipLaunchKernelGGL((tile_resid_kernel<false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
+    } else if (a.io_u16) hipLaunchKernelGGL((tile_resid_kernel<true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((tile_resid_kernel<false, false, COVER, NT>), grid, dim3(NT), 0, st, a);
+  } else if (a.virtual_out) {                       // (a render batch has neither thresholds nor a z-surface route)
     if (a.labels) {
       if (a.io_u16) hipLaunchKernelGGL((tile_render_kernel<true, true, COVER, NT>), grid, dim3(NT), 0, st, a);
       else hipLaunchKernelGGL((tile_render_kernel<false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
@@ -3046,6 +3179,17 @@ void launch_tile(const TileArgs& a, bool two_kernel, bool cover_pass, hipStream_
     if (cover_pass) launch_tile_variant<true, kTileThreads>(a, two_kernel, st);
     else launch_tile_variant<false, kTileThreads>(a, two_kernel, st);
   }
+}
+// A launch group's rows of a residual table start from zero on every run.  (A kernel, not hipMemsetAsync: the memset node a
+// stream capture makes of it filled the rows with other values when the graph was replayed.)
+__global__ __launch_bounds__(kBlock) void zero_words_kernel(unsigned long long* p, size_t n)
+{
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) p[i] = 0ull;
+}
+void launch_zero_residual_rows(unsigned long long* rows, size_t n_words, hipStream_t st)
+{
+  const size_t blocks = (n_words + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks))), dim3(kBlock), 0, st, rows, n_words);
 }
 void launch_compare(const CompareArgs& a, hipStream_t st)
 {

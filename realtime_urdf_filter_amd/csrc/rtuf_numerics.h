@@ -1,7 +1,7 @@
 // rtuf_numerics.h -- the arithmetic whose exact bits the results depend on and that something besides the kernels checks or
 // shares: the 24-bit depth and its bit-pattern forms, the depth keys' encoding of a near fragment's float z, the set-up's
-// 32-bit edge constants, the key format's host-side rules, and the compare threshold's constants, division core and the rule
-// that admits that core.
+// 32-bit edge constants, the key format's host-side rules, the compare threshold's constants, division core and the rule
+// that admits that core, and the pixel classes of the link residual tables.
 //
 // Included by the kernels (rtuf_kernels.hip, device and host pass), the host API (rtuf_api.cpp), scripts/fdiv_check.hip (which
 // holds div_core against the IEEE division on the GPU) and the CPU checks (tests/fast_class_check.cpp, tests/near_key_check.cpp:
@@ -29,7 +29,15 @@ namespace rtuf {
 // Without HIP: the intrinsics used below, with the same results.  (The bodies call the intrinsics by name, not through wrappers
 // of our own: a wrapper around __mul24 alone changes the instruction schedule of the tile kernel.)
 inline float __fmul_rn(float a, float b) { return a * b; }
-inline int __float2int_rn(float x) { return (int)rintf(x); }      // (round half to even: the default rounding mode)
+inline float __fadd_rn(float a, float b) { return a + b; }
+inline float __fsub_rn(float a, float b) { return a - b; }
+inline int __float2int_rn(float x)      // (round half to even: the default rounding mode; saturating, NaN -> 0: v_cvt_i32_f32)
+{
+  if (!(x == x)) return 0;
+  if (x >= 2147483648.0f) return 2147483647;
+  if (x <= -2147483648.0f) return -2147483647 - 1;
+  return (int)rintf(x);
+}
 inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 inline int __mul24(int a, int b)      // v_mul_i32_i24: the low 32 bits of the product of the sign-extended low 24 bits
@@ -138,6 +146,27 @@ inline bool fast_div_admitted(float num, float off)
   const float a = std::fabs(num);
   return std::isfinite(num) && std::isfinite(off) && a >= 0x1p-40f && a <= 0x1p40f && off >= 1.0f + 0x1p-10f && off <= 0x1p20f;
 }
+
+// ---------------------------------------------------------------------------------------
+// link residual tables (include/rtuf.h, LINK RESIDUAL TABLES): the class of one drawn pixel and its quantised residual
+// ---------------------------------------------------------------------------------------
+
+// One bit per counter of rtuf_link_residuals, in the struct's field order (bit f feeds field f).
+enum : uint32_t { kResPixel = 1u, kResInvalid = 2u, kResFiltered = 4u, kResInFront = 8u, kResBehind = 16u, kResAgree = 32u };
+
+// A drawn pixel: sensor value s, the winner's virtual depth v = to_linear_depth(z) and its threshold t.  lo = v - t is the
+// filter's compare threshold (shade_threshold: the same float subtraction), so kResFiltered is the mask bit -- for an invalid
+// s as well.  q = (s - v) in units of 2^-20 m, round half to even, saturating, NaN -> 0; it counts where kResAgree is set.
+RTUF_NUMERIC uint32_t link_residual_class(float s, float v, float t, int& q)
+{
+  const float lo = __fsub_rn(v, t), hi = __fadd_rn(v, t);
+  const bool valid = s > 0.0f, filtered = s > lo, beyond = s > hi;
+  q = __float2int_rn(__fmul_rn(__fsub_rn(s, v), 1048576.0f));
+  return kResPixel | (valid ? 0u : kResInvalid) | (filtered ? kResFiltered : 0u) | (valid && !filtered ? kResInFront : 0u) |
+         (valid && filtered && beyond ? kResBehind : 0u) | (valid && filtered && !beyond ? kResAgree : 0u);
+}
+// A pixel no fragment reached: it counts as a pixel, and as invalid where the sensor holds no reading.
+RTUF_NUMERIC uint32_t link_residual_undrawn(float s) { return kResPixel | (s > 0.0f ? 0u : kResInvalid); }
 
 #ifdef __HIP__
 // The IEEE division without the instructions that only matter for operands near the ends of the exponent range: the compiler

@@ -384,6 +384,33 @@ class RealtimeURDFFilter:
         if self.want_labels_:
             self.labels_ = labels[0]
 
+    def link_residuals(self, depth, projection_matrix, width, height, timestamp=None):
+        """New, beyond the reference: per link label, how the sensor image compares with the model (include/rtuf.h, LINK
+        RESIDUAL TABLES) for the camera and link poses filter() would use: pixels covered, confirmed (agree), occluded
+        (in_front), seen through (behind), without a reading (invalid), and the summed residual of the confirmed ones.
+        depth: [H,W] float32 metres or uint16 millimetres.  Returns the [numLinkResidualRows()] structured array
+        (_capi.LINK_RESIDUALS_DTYPE) of the frame, row = label (getLinkLabels() with labels=True, else 1 + the renderable's
+        index over all models; row 0: no link), or None where filter() would have returned without a result."""
+        self._ensure_size(width, height)
+        if not self.renderers_:
+            return None
+        try:
+            self._stage_stream(0, projection_matrix, self.tf_, timestamp)
+        except Exception as e:                      # noqa: BLE001 - ROS_ERROR + return (quirk Q6)
+            log.error("%s", e)
+            return None
+        d = np.asarray(depth)
+        d = d.astype(np.uint16 if d.dtype == np.uint16 else np.float32, copy=False).reshape(1, height, width)
+        if d.dtype == np.uint16 and width % 4:      # (the 16UC1 kernels need a width that is a multiple of 4)
+            d = d.astype(np.float32) * np.float32(0.001)
+        return self._ctx.link_residuals_batch(d, self.numLinkResidualRows())[0]
+
+    def numLinkResidualRows(self):
+        """Rows of a link_residuals() table: one more than the largest label in effect."""
+        if self.want_labels_:
+            return max(self.link_labels_.values(), default=0) + 1
+        return sum(len(rd.renderables_) for rd in self.renderers_) + 1
+
     def getVirtualDepth(self):
         """Virtual depth plane [H,W] float32 metres of the last render() (None before the first)."""
         return self.virtual_depth_

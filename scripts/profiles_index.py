@@ -117,6 +117,16 @@ def build(tag):
     text("fuzz campaigns (fuzz_parity 6,000 + fuzz_features 3,000 + FUZZ_BIG 150 scenes)", ["DESIGN.md 2"], T + "_fuzz.txt", "'streams with mismatches' of each of the three runs")
     text("wall time of the default bench command", ["README.md"], T + "_bench_wall_time.txt", "the line")
     text("virtual depth planes on c3: render batches beside the plain fused filter", ["README.md", "DESIGN.md 4"], "virtual_rate_c3.txt", "the last line")
+    text("link residual tables on c3: residual batches beside the plain fused filter", ["README.md", "DESIGN.md 4"], "link_residuals_rate_c3.txt", "the last line")
+    f = "link_residuals_kernel_stats.txt"
+    if os.path.exists(os.path.join(PROFILES, f)):
+        v = {}
+        for line in open(os.path.join(PROFILES, f)):
+            m = re.match(r"void rtuf::(tile_kernel<false, false, false, 256>|tile_resid_kernel<false, false, false, 256>)\(rtuf::TileArgs\)\s+(\d+)\s+[\d.]+\s+([\d.]+)", line)
+            if m:
+                v[m.group(1)] = {"avg_us": float(m.group(3)), "launches": int(m.group(2))}
+        add("link residual tables: tile kernels of filter and residual batches in one rocprofv3 --kernel-trace --stats run", ["DESIGN.md 4"], f,
+            "calls / avg_us of the kernel's row (averages over one-lane launches of 256 streams and three-lane launches of 85 / 86)", v)
     for f, claim, docs in ((T + "_experiment_block_bounds.txt", "block depth bounds (not merged)", ["DESIGN.md 8", "docs/experiments.md R6.1"]),
                            (T + "_experiment_more_lanes.txt", "4-6 raster lanes", ["docs/experiments.md R6.6"]),
                            (T + "_experiment_compiler_flags.txt", "compiler flag sweep", ["docs/experiments.md R6.6"]),
