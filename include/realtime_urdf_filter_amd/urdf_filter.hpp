@@ -15,6 +15,7 @@
 #include <cmath>
 #include <map>
 #include <cstdio>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -245,6 +246,7 @@ class RealtimeURDFFilter {
     p.filter_replace_value = (float)filter_replace_value_;
     p.silhouette_dilation_px = silhouette_dilation_px_;
     if (ctx_) { rtuf_destroy(ctx_); ctx_ = nullptr; }
+    cloud_intr_sent_ = false;                  // (the new context has no cloud intrinsics: cloud_into gives them again)
     if (rtuf_create(&ctx_, device_, width_, height_, 1, &p) != RTUF_OK) throw std::runtime_error(std::string("ERROR: could not initialize the GPU context: ") + rtuf_last_error(nullptr));
     this->loadModels();
     if (renderers_.empty()) throw std::runtime_error("Could not load any models for filtering!");
@@ -286,10 +288,14 @@ class RealtimeURDFFilter {
       const double* k = params_.own_calibration;
       double tx = 0, ty = 0;
       rtuf_projection_from_intrinsics((float)k[0], (float)k[1], (float)k[2], (float)k[3], 0.0, 0.0, info.width, info.height, near_plane_, far_plane_, glTf, &tx, &ty);
+      for (int i = 0; i < 4; i++) cloud_intr_[i] = (double)(float)k[i];      // (own_calibration counts as floats, here as in the projection above and in filter.py)
+      have_cloud_intr_ = true;
       return;
     }
     rtuf_projection_from_intrinsics(info.P[0], info.P[5], info.P[2], info.P[6], info.P[3], info.P[7], info.width, info.height, near_plane_, far_plane_, glTf,
                                     &camera_tx_, &camera_ty_);
+    cloud_intr_[0] = info.P[0]; cloud_intr_[1] = info.P[5]; cloud_intr_[2] = info.P[2]; cloud_intr_[3] = info.P[6];      // (cloud_into: the pinhole the projection was made from)
+    have_cloud_intr_ = true;
   }
 
   // src/urdf_filter.cpp:503-744 without GL
@@ -341,6 +347,37 @@ class RealtimeURDFFilter {
   }
   // the virtual depth plane of the last render_into (width x height metres, row 0 first; empty before the first)
   const std::vector<float>& getVirtualDepth() const { return virtual_depth_; }
+
+  // Filtered point clouds (include/rtuf.h, FILTERED POINT CLOUDS): the pixels filter_into would keep as XYZ points in the
+  // camera's optical frame, with the intrinsics of the last getProjectionMatrix (own_calibration rounded to float with
+  // use_own_calibration, as the projection takes it, else the CameraInfo's fx fy cx cy as doubles).  depth: width x height
+  // float metres, or uint16 millimetres with is_16uc1; the width must be a multiple of 4.  count_out == nullptr: the organized form, points_out width x height x 3 floats, NaN where there is no
+  // point.  count_out != nullptr: the compacted form in row-major order, points_out capacity x 3 floats, index_out nullptr or
+  // capacity words (v * width + u), *count_out the full number of kept pixels; entries from min(*count_out, capacity) on are
+  // not written.
+  bool cloud_into(const void* depth, bool is_16uc1, double* glTf, int width, int height, double timestamp, float* points_out,
+                  uint32_t* index_out = nullptr, uint32_t* count_out = nullptr, int capacity = 0)
+  {
+    prepare(width, height);
+    if (!depth || !points_out) throw std::runtime_error("cloud_into: needs depth and points_out");
+    if (!have_cloud_intr_) throw std::runtime_error("cloud_into: no intrinsics yet (getProjectionMatrix sets them)");
+    if (renderers_.empty() || !stage_frame(glTf, timestamp)) return false;
+    if (!cloud_intr_sent_ || std::memcmp(cloud_intr_given_, cloud_intr_, sizeof cloud_intr_) != 0) {
+      check(rtuf_set_cloud_intrinsics(ctx_, 0, 1, cloud_intr_));
+      cloud_intr_sent_ = true;
+      std::memcpy(cloud_intr_given_, cloud_intr_, sizeof cloud_intr_);
+    }
+    const void* in = depth;
+    if (!count_out) {
+      if (is_16uc1) check(rtuf_cloud_batch_u16(ctx_, 1, reinterpret_cast<const uint16_t* const*>(&in), &points_out));
+      else check(rtuf_cloud_batch(ctx_, 1, reinterpret_cast<const float* const*>(&in), &points_out));
+    } else if (is_16uc1) {
+      check(rtuf_cloud_compact_batch_u16(ctx_, 1, reinterpret_cast<const uint16_t* const*>(&in), &points_out, index_out ? &index_out : nullptr, count_out, capacity));
+    } else {
+      check(rtuf_cloud_compact_batch(ctx_, 1, reinterpret_cast<const float* const*>(&in), &points_out, index_out ? &index_out : nullptr, count_out, capacity));
+    }
+    return true;
+  }
 
   // Link residual tables (include/rtuf.h, LINK RESIDUAL TABLES): per link label, how the sensor image compares with the model
   // for the camera and link poses filter_into would use.  depth: width x height float metres, or uint16 millimetres with
@@ -573,6 +610,10 @@ class RealtimeURDFFilter {
   bool want_labels_;                                 // FilterParameters::link_labels
   std::vector<uint16_t> labels_;                     // label plane of the last frame (getLabels)
   std::vector<float> virtual_depth_;                 // virtual depth plane of the last render_into (getVirtualDepth)
+  double cloud_intr_[4] = {0, 0, 0, 0};              // fx fy cx cy of the last getProjectionMatrix (cloud_into)
+  double cloud_intr_given_[4] = {0, 0, 0, 0};        // ... and what the context was last given
+  bool have_cloud_intr_ = false;
+  bool cloud_intr_sent_ = false;                     // ctx_ holds cloud_intr_given_ (cleared whenever initGL makes a new context)
   std::map<std::pair<int, std::string>, uint16_t> link_labels_;
   std::vector<float> own_masked_;                    // render() with labels: the outputs the library-owned planes hold otherwise
   std::vector<uint8_t> own_mask_;

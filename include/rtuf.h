@@ -476,6 +476,60 @@ int rtuf_link_residuals_batch(rtuf_context *ctx, int n_streams, const float *con
 int rtuf_link_residuals_batch_u16(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in, rtuf_link_residuals *table_out,
                                   int n_labels);
 
+/* FILTERED POINT CLOUDS.  New, beyond the reference: the pixels the filter keeps, as XYZ points in the camera's optical
+ * frame -- what the filter's consumers (octomap, MoveIt, trackers) take -- either organized (one point per pixel, NaN where
+ * there is none) or compacted (the kept points of every stream, densely, in row-major order, with their count).
+ * Intrinsics.  rtuf_set_cloud_intrinsics stores, for streams first_stream .. first_stream + n_streams - 1, four floats from
+ * fx_fy_cx_cy [n][4]: kx = (float)(1.0 / fx), ky = (float)(1.0 / fy), cx = (float)cx, cy = (float)cy.  An fx or fy that is
+ * not finite or not > 0 (and a NULL array or a stream range outside the context) fails with RTUF_ERR_INVALID and changes
+ * nothing.  The call waits for the batches in flight, as the other non-pose setters do, and applies to all pipelines.  A
+ * cloud call on a stream that never got intrinsics fails with RTUF_ERR_STATE and enqueues nothing.
+ * A point.  s = the sensor value (the float as given; 16UC1: uint16 * 0.001f, as every 16UC1 call reads it).  Pixel (u, v),
+ * row 0 first, is KEPT iff its mask bit is 0 -- the filter batch of the same parameters would not mask it -- and
+ * s > 0 && s < +inf.  Its point is
+ *   x = (((float)u - cx) * s) * kx,   y = (((float)v - cy) * s) * ky,   z = s,
+ * every operation a single float operation in that order (as depth_image_proc associates them; cloud_point in
+ * rtuf_numerics.h).  filter_replace_value does not enter.
+ * Organized form (rtuf_cloud_batch_device*): d_points is [n][H][W][3] float; a kept pixel holds its point, every other pixel
+ * three quiet NaNs (0x7fc00000).
+ * Its device forms need d_points 16-byte aligned and d_depth 16-byte aligned (f32) or 8-byte aligned (16UC1) -- the kernel
+ * loads four sensor values and stores four floats at once -- else RTUF_ERR_INVALID; the compacted forms need no more than
+ * the elements' own alignment.
+ * Compacted form (rtuf_cloud_compact_batch_device*): d_points is [n][capacity][3] float, d_index [n][capacity] or NULL,
+ * d_counts [n].  counts[s] is the number of kept pixels of stream s -- the full number even when it exceeds capacity.  Entry
+ * j of stream s is the j-th kept pixel in row-major order (organized[s][kept] in numpy terms) and is written iff
+ * j < min(counts[s], capacity); d_index, when given, holds v * W + u of the same entries.  Entries at or beyond
+ * min(counts[s], capacity) are unspecified (left untouched, or stale).  1 <= capacity <= W * H, else RTUF_ERR_INVALID.
+ * The compaction is a count per row, a scan and a row-major scatter: no atomics, the same output on every run.
+ * Host-plane forms (rtuf_cloud_batch*, rtuf_cloud_compact_batch*): synchronous, planes up, results down.  points_out is one
+ * plane ([H][W][3]) or array ([capacity][3]) per stream, index_out NULL or one array per stream, counts_out [n]; the
+ * compacted forms download only min(counts, capacity) entries per stream.
+ * A cloud batch is a mask-bits batch plus the cloud kernels (rtuf_filter_batch_device_bits* above): the library owns the bits buffer and the
+ * row scratch of the compacted form, per batch slot, allocated on first use and counted in rtuf_stats.device_bytes.  The
+ * bits route's rules hold unchanged: silhouette_dilation_px is honoured (the cloud of the dilated filter), per-link
+ * thresholds are honoured (not together with dilation: RTUF_ERR_INVALID), the width must be a multiple of 4
+ * (RTUF_ERR_INVALID), and a stream whose background quad does not cover its image makes retiring the batch fail with
+ * RTUF_ERR_STATE (RTUF_STATUS_UNCOVERED), as the bits calls do.  RTUF_FLAG_TWO_KERNEL does not enter: the batch is accepted
+ * and takes the fused bits route, as render and residual batches do.  Otherwise it is a batch like any other: raster lanes,
+ * pipelines, launch groups, partial batches, batches in flight (each with outputs of its own), graph replay of small
+ * batches, re-runs after a bin regrowth (counts and points are rewritten: as if the batch had run once),
+ * rtuf_order_stream_after_batches and the status word, which covers the cloud too (the cloud kernels run on each launch
+ * group's lane before its counters are published; timings: ms_compare).  Refusals are those of the filter calls -- a NULL
+ * plane, n out of range, an un-finalized context -- and a refused call enqueues nothing. */
+int rtuf_set_cloud_intrinsics(rtuf_context *ctx, int first_stream, int n_streams, const double *fx_fy_cx_cy /* [n][4] */);
+int rtuf_cloud_batch_device(rtuf_context *ctx, int n_streams, const float *d_depth, float *d_points);
+int rtuf_cloud_batch_device_u16(rtuf_context *ctx, int n_streams, const uint16_t *d_depth_mm, float *d_points);
+int rtuf_cloud_compact_batch_device(rtuf_context *ctx, int n_streams, const float *d_depth, float *d_points, uint32_t *d_index,
+                                    uint32_t *d_counts, int capacity);
+int rtuf_cloud_compact_batch_device_u16(rtuf_context *ctx, int n_streams, const uint16_t *d_depth_mm, float *d_points, uint32_t *d_index,
+                                        uint32_t *d_counts, int capacity);
+int rtuf_cloud_batch(rtuf_context *ctx, int n_streams, const float *const *depth_in, float *const *points_out);
+int rtuf_cloud_batch_u16(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in, float *const *points_out);
+int rtuf_cloud_compact_batch(rtuf_context *ctx, int n_streams, const float *const *depth_in, float *const *points_out,
+                             uint32_t *const *index_out, uint32_t *counts_out, int capacity);
+int rtuf_cloud_compact_batch_u16(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in, float *const *points_out,
+                                 uint32_t *const *index_out, uint32_t *counts_out, int capacity);
+
 /* Counters of the last batch and kernel timings measured with HIP events on the context's
  * stream (replaces the wall-clock statistics of src/urdf_filter.cpp:239-266). */
 typedef struct {

@@ -37,6 +37,8 @@ SYMBOLS = [
     "rtuf_filter_batch_u16_labels", "rtuf_set_link_thresholds", "rtuf_clear_link_thresholds",
     "rtuf_render_batch_device", "rtuf_render_batch_device_u16", "rtuf_render_batch", "rtuf_render_batch_u16",
     "rtuf_link_residuals_batch_device", "rtuf_link_residuals_batch_device_u16", "rtuf_link_residuals_batch", "rtuf_link_residuals_batch_u16",
+    "rtuf_set_cloud_intrinsics", "rtuf_cloud_batch_device", "rtuf_cloud_batch_device_u16", "rtuf_cloud_compact_batch_device",
+    "rtuf_cloud_compact_batch_device_u16", "rtuf_cloud_batch", "rtuf_cloud_batch_u16", "rtuf_cloud_compact_batch", "rtuf_cloud_compact_batch_u16",
 ]
 
 # rtuf_link_residuals (include/rtuf.h, LINK RESIDUAL TABLES): one 64-byte row per (stream, label)
@@ -192,6 +194,15 @@ def load_library(path=None):
     lib.rtuf_link_residuals_batch_device_u16.argtypes = [vp, ci, vp, vp, ci]
     lib.rtuf_link_residuals_batch.argtypes = [vp, ci, vp, vp, ci]
     lib.rtuf_link_residuals_batch_u16.argtypes = [vp, ci, vp, vp, ci]
+    lib.rtuf_set_cloud_intrinsics.argtypes = [vp, ci, ci, vp]
+    lib.rtuf_cloud_batch_device.argtypes = [vp, ci, vp, vp]
+    lib.rtuf_cloud_batch_device_u16.argtypes = [vp, ci, vp, vp]
+    lib.rtuf_cloud_compact_batch_device.argtypes = [vp, ci, vp, vp, vp, vp, ci]
+    lib.rtuf_cloud_compact_batch_device_u16.argtypes = [vp, ci, vp, vp, vp, vp, ci]
+    lib.rtuf_cloud_batch.argtypes = [vp, ci, vp, vp]
+    lib.rtuf_cloud_batch_u16.argtypes = [vp, ci, vp, vp]
+    lib.rtuf_cloud_compact_batch.argtypes = [vp, ci, vp, vp, vp, vp, ci]
+    lib.rtuf_cloud_compact_batch_u16.argtypes = [vp, ci, vp, vp, vp, vp, ci]
     lib.rtuf_set_link_thresholds.argtypes = [vp, ci, vp, ci]
     lib.rtuf_clear_link_thresholds.argtypes = [vp, ci]
     if path is None:
@@ -447,6 +458,69 @@ class Context:
     def link_residuals_batch_device_u16(self, n, d_depth_mm, d_table, n_labels):
         self._check(self._lib.rtuf_link_residuals_batch_device_u16(self._h, n, ctypes.c_void_p(d_depth_mm) if d_depth_mm else None,
                                                                    ctypes.c_void_p(d_table) if d_table else None, int(n_labels)))
+
+    # filtered point clouds (include/rtuf.h, FILTERED POINT CLOUDS)
+    def set_cloud_intrinsics(self, first_stream, fx_fy_cx_cy):
+        """fx, fy, cx, cy of streams first_stream ..: [n,4] (or one row of 4) doubles."""
+        a = np.ascontiguousarray(fx_fy_cx_cy, np.float64).reshape(-1, 4)
+        self._check(self._lib.rtuf_set_cloud_intrinsics(self._h, first_stream, len(a), _ptr(a)))
+
+    def cloud_batch(self, depth):
+        """The kept pixels as XYZ, organized: depth [n,H,W] float32 metres (or uint16 millimetres: the 16UC1 form) ->
+        points [n,H,W,3] float32, NaN where the pixel is masked or holds no reading.  Synchronous."""
+        u16 = np.asarray(depth).dtype == np.uint16
+        d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32).reshape(-1, self.height, self.width)
+        n = d.shape[0]
+        points = np.empty((n, self.height, self.width, 3), np.float32)
+        PP = ctypes.c_void_p * max(n, 1)
+        din = PP(*[d[i].ctypes.data for i in range(n)])
+        pout = PP(*[points[i].ctypes.data for i in range(n)])
+        fn = self._lib.rtuf_cloud_batch_u16 if u16 else self._lib.rtuf_cloud_batch
+        self._check(fn(self._h, n, din, pout))
+        return points
+
+    def cloud_batch_u16(self, depth_mm):
+        return self.cloud_batch(np.ascontiguousarray(depth_mm, np.uint16))
+
+    def cloud_compact_batch(self, depth, capacity, want_index=True):
+        """The kept pixels as XYZ, compacted in row-major order: -> (points [n,capacity,3] float32, index [n,capacity] uint32
+        (v * W + u) or None, counts [n] uint32).  counts is the full number of kept pixels; entries [min(count, capacity):] of a
+        stream are unspecified.  Synchronous."""
+        u16 = np.asarray(depth).dtype == np.uint16
+        d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32).reshape(-1, self.height, self.width)
+        n = d.shape[0]
+        cap = max(int(capacity), 0)
+        points = np.empty((n, cap, 3), np.float32)
+        index = np.empty((n, cap), np.uint32) if want_index else None
+        counts = np.zeros(n, np.uint32)
+        PP = ctypes.c_void_p * max(n, 1)
+        din = PP(*[d[i].ctypes.data for i in range(n)])
+        pout = PP(*[points[i].ctypes.data if cap else points.ctypes.data for i in range(n)])
+        iout = PP(*[index[i].ctypes.data if cap else index.ctypes.data for i in range(n)]) if want_index else None
+        fn = self._lib.rtuf_cloud_compact_batch_u16 if u16 else self._lib.rtuf_cloud_compact_batch
+        self._check(fn(self._h, n, din, pout, iout, _ptr(counts), int(capacity)))
+        return points, index, counts
+
+    def cloud_compact_batch_u16(self, depth_mm, capacity, want_index=True):
+        return self.cloud_compact_batch(np.ascontiguousarray(depth_mm, np.uint16), capacity, want_index)
+
+    def cloud_batch_device(self, n, d_depth, d_points, u16=False):
+        """Device pointers (ints): d_depth [n,H,W] float32 (uint16 with u16), d_points [n,H,W,3] float32; enqueue only; call sync()."""
+        fn = self._lib.rtuf_cloud_batch_device_u16 if u16 else self._lib.rtuf_cloud_batch_device
+        self._check(fn(self._h, n, ctypes.c_void_p(d_depth) if d_depth else None, ctypes.c_void_p(d_points) if d_points else None))
+
+    def cloud_batch_device_u16(self, n, d_depth_mm, d_points):
+        self.cloud_batch_device(n, d_depth_mm, d_points, u16=True)
+
+    def cloud_compact_batch_device(self, n, d_depth, d_points, d_index, d_counts, capacity, u16=False):
+        """Device pointers (ints; d_index may be None): d_points [n,capacity,3] float32, d_index [n,capacity] uint32, d_counts [n]
+        uint32; enqueue only; call sync()."""
+        fn = self._lib.rtuf_cloud_compact_batch_device_u16 if u16 else self._lib.rtuf_cloud_compact_batch_device
+        self._check(fn(self._h, n, ctypes.c_void_p(d_depth) if d_depth else None, ctypes.c_void_p(d_points) if d_points else None,
+                       ctypes.c_void_p(d_index) if d_index else None, ctypes.c_void_p(d_counts) if d_counts else None, int(capacity)))
+
+    def cloud_compact_batch_device_u16(self, n, d_depth_mm, d_points, d_index, d_counts, capacity):
+        self.cloud_compact_batch_device(n, d_depth_mm, d_points, d_index, d_counts, capacity, u16=True)
 
     # asynchronous host planes
     def host_alloc(self, shape, dtype):

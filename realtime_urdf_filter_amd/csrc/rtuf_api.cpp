@@ -107,6 +107,10 @@ struct rtuf_context {
   // keep its address).  The tile kernels read it only while thresh_models > 0 (models with thresholds of their own).
   float* d_order_thr = nullptr;
   int thresh_models = 0;
+  // Filtered point clouds: kx, ky, cx, cy of every stream, [max_streams], allocated by the first rtuf_set_cloud_intrinsics and
+  // rewritten in place after that (captured graphs keep its address), and which streams have been given theirs.
+  CloudIntrinsics* d_cloud_intr = nullptr;
+  std::vector<uint8_t> cloud_intr_set;
 
   // per-frame pose staging
   // Cameras and link matrices are staged in a ring of kMaxInflight + 1 pinned sets, like the joint positions: every
@@ -190,6 +194,14 @@ struct rtuf_context {
     // residual batch (rtuf_link_residuals_batch*): the table [n][n_labels] the tile kernel sums into, zeroed on every run (first
     // runs and re-runs alike); depth is read, masked / mask / bits / labels / virt are unused.  nullptr: not a residual batch.
     rtuf_link_residuals* resid = nullptr; int n_labels = 0;
+    // cloud batch (rtuf_cloud_batch*, rtuf_cloud_compact_batch*): a mask-bits batch (bits = cl_bits, the slot's own buffer) whose
+    // launch groups run the cloud kernels behind their tile / dilate kernel.  cloud_points == nullptr: not a cloud batch;
+    // cloud_capacity == 0: the organized form.  cl_bits / cl_rows ([2][max_streams][H]: row counts, row starts) are allocated
+    // on the slot's first cloud batch for max_streams, so that captured graphs keep their addresses.
+    float* cloud_points = nullptr; uint32_t* cloud_index = nullptr; uint32_t* cloud_counts = nullptr; int cloud_capacity = 0;
+    uint32_t* cl_bits = nullptr; uint32_t* cl_rows = nullptr;
+    float* st_points = nullptr; size_t st_points_floats = 0;      // host-plane cloud batches: device staging of points / index / counts
+    uint32_t* st_index = nullptr; size_t st_index_words = 0; uint32_t* st_counts = nullptr;
     Counters* h_counters = nullptr;          // pinned [max_groups]: one block per launch group, filled by the copies that end the batch
     hipEvent_t done[kMaxLanes] = {};         // recorded on each lane after its copy
     uint32_t lanes_used = 0;                 // bit l: the batch has launch groups on lane l
@@ -657,6 +669,7 @@ static void free_frame_buffers(rtuf_context* c)
   }
   for (auto& b : c->batch) { dev_free(c, b.st_depth); dev_free(c, b.st_masked); dev_free(c, b.st_mask); b.st_streams = 0; b.st_depth_streams = 0; dev_free(c, b.st_bits); b.st_bits_streams = 0; }
   for (auto& b : c->batch) { dev_free(c, b.st_labels); b.st_labels_streams = 0; dev_free(c, b.st_virtual); b.st_virtual_streams = 0; dev_free(c, b.st_table); b.st_table_rows = 0; }
+  for (auto& b : c->batch) { dev_free(c, b.cl_bits); dev_free(c, b.cl_rows); dev_free(c, b.st_points); b.st_points_floats = 0; dev_free(c, b.st_index); b.st_index_words = 0; dev_free(c, b.st_counts); }
   for (auto*& p : c->ring_cams) hfree(p);
   for (auto*& p : c->ring_link_tf) hfree(p);
   c->h_cams = nullptr; c->h_link_tf = nullptr;
@@ -686,6 +699,7 @@ void rtuf_destroy(rtuf_context* c)
   dev_free(c, c->d_cverts); dev_free(c, c->d_ctris); dev_free(c, c->d_corder); dev_free(c, c->d_chunks); dev_free(c, c->d_draws);
   dev_free(c, c->d_order_labels);
   dev_free(c, c->d_order_thr);
+  dev_free(c, c->d_cloud_intr);
   for (auto& b : c->batch) {
     for (hipEvent_t ev : b.events) hipEventDestroy(ev);
     for (hipEvent_t ev : b.done) if (ev) hipEventDestroy(ev);
@@ -1377,7 +1391,7 @@ static hipEvent_t get_event(rtuf_context::Batch& b, size_t i)
 struct BatchPlan {
   std::vector<FkArgs> fks;
   PoseArgs pa{};
-  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; bool compare = false, dilate = false; int lane = 0; };
+  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; CloudArgs cl{}; bool compare = false, dilate = false, cloud = false; int lane = 0; };
   std::vector<Group> groups;
   bool cover_pass = true;
   bool zroute = false;          // the tile kernel writes the z-surface (two-kernel mode, or silhouette dilation)
@@ -1389,6 +1403,7 @@ struct BatchPlan {
     mix(&pa, sizeof pa);
     for (const Group& g : groups) {
       mix(&g.sa, sizeof g.sa); mix(&g.ta, sizeof g.ta); if (g.compare) mix(&g.ca, sizeof g.ca); if (g.dilate) mix(&g.da, sizeof g.da);
+      if (g.cloud) mix(&g.cl, sizeof g.cl);
       mix(&g.lane, sizeof g.lane);
     }
     return h ^ (uint64_t)fks.size() << 56 ^ (uint64_t)groups.size() << 48 ^ (uint64_t)cover_pass << 47 ^ (uint64_t)zroute << 46;
@@ -1464,7 +1479,10 @@ static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& 
     launch_tile(gr.ta, two, plan.cover_pass, st);
     if (b.timing) mark(e0 + 3, st);
     if (gr.compare) { launch_compare(gr.ca, st); if (b.timing) mark(e0 + 4, st); }
-    if (gr.dilate) { launch_dilate_compare(gr.da, st); if (b.timing) mark(e0 + 4, st); }
+    if (gr.dilate) { launch_dilate_compare(gr.da, st); if (b.timing && !gr.cloud) mark(e0 + 4, st); }
+    // a cloud batch: the group's points from the bits the kernel above wrote, before the lane publishes its counters (timed
+    // as ms_compare, with the dilate kernel where there is one)
+    if (gr.cloud) { launch_cloud(gr.cl, st); if (b.timing) mark(e0 + 4, st); }
   }
   // every lane publishes the counter blocks of its own groups
   const int ng = (int)plan.groups.size();
@@ -1484,7 +1502,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   const float* d_depth = b.depth; float* d_masked = b.masked; uint8_t* d_mask = b.mask;
   const bool io_u16 = b.u16;
   const size_t esz = io_u16 ? sizeof(uint16_t) : sizeof(float);
-  const bool two = (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.virt && !b.resid;      // (render and residual batches are always one tile kernel)
+  const bool two = (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.virt && !b.resid && !b.cloud_points;      // (render, residual and cloud batches are always one tile kernel)
   // Launch groups: as many as the lanes' bins ask for, alternating between the lanes; a batch that is not split takes one
   // lane, the next such batch the other.
   const int n_groups = groups_for(c, n);
@@ -1593,6 +1611,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     plan.groups.emplace_back();
     BatchPlan::Group& gr = plan.groups.back();
     memset(&gr.sa, 0, sizeof gr.sa); memset(&gr.ta, 0, sizeof gr.ta); memset(&gr.ca, 0, sizeof gr.ca); memset(&gr.da, 0, sizeof gr.da);
+    memset(&gr.cl, 0, sizeof gr.cl);
     gr.lane = n_groups == 1 ? lane0 : g % c->n_lanes;
     const rtuf_context::Lane& ln = c->lane[gr.lane];
     Counters* const d_counters = b.d_counters + g;
@@ -1631,6 +1650,13 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
       da.group_base = base; da.group_size = gs; da.width = c->width; da.height = c->height; da.radius = dil;
       da.max_diff = ta.max_diff; da.replace_value = ta.replace_value; da.sc_num = sc_num; da.sc_off = sc_off;
       da.io_u16 = io_u16 ? 1 : 0; da.fast_div = fast_div;
+    }
+    gr.cloud = b.cloud_points != nullptr;
+    if (gr.cloud) {
+      CloudArgs& cl = gr.cl;
+      cl.depth = d_depth; cl.bits = b.bits; cl.intr = c->d_cloud_intr; cl.points = b.cloud_points; cl.index = b.cloud_index; cl.counts = b.cloud_counts;
+      cl.row_count = b.cl_rows; cl.row_start = b.cl_rows ? b.cl_rows + (size_t)c->max_streams * c->height : nullptr;
+      cl.group_base = base; cl.group_size = gs; cl.width = c->width; cl.height = c->height; cl.capacity = b.cloud_capacity; cl.io_u16 = io_u16 ? 1 : 0;
     }
     if (gr.compare) {
       CompareArgs& ca = gr.ca;
@@ -1837,7 +1863,7 @@ static int retire_oldest(rtuf_context* c)
       if (b.timing && b.events.size() >= (size_t)(kEvGroup0 + kEvPerGroup * b.n_groups)) {
         // per launch group E0 .. E4 (see issue_plan).  With several lanes the kernels of different groups overlap: the sums
         // below add up per-launch durations, they are not wall time.
-        const bool two = ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.bits && !b.virt && !b.resid) || b.dilation > 0;
+        const bool two = ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.bits && !b.virt && !b.resid) || b.dilation > 0 || b.cloud_points;
         auto el = [&](size_t i, size_t j) { float ms = 0; hipEventElapsedTime(&ms, b.events[i], b.events[j]); return ms; };
         c->stats.ms_pose = c->stats.ms_setup = c->stats.ms_clip = c->stats.ms_raster = c->stats.ms_compare = c->stats.ms_total = 0;
         for (int g = 0; g < b.n_groups; g++) {
@@ -1872,6 +1898,10 @@ static int retire_oldest(rtuf_context* c)
       b.active = false;
       c->oldest = (c->oldest + 1) % kMaxInflight;
       c->pending--;
+      if (b.cloud_points && k.uncovered)
+        return c->fail(RTUF_ERR_STATE, "point cloud: a stream's background quad does not cover its whole image (non-standard projection), so the mask "
+                                       "bits the cloud is built on are undefined there; there is no cloud form for this camera (filter with the "
+                                       "full-plane calls and convert the masked plane)");
       if (b.bits && k.uncovered)
         return c->fail(RTUF_ERR_STATE, "mask bits: a stream's background quad does not cover its whole image (non-standard projection), so "
                                        "masked depth != select(bit, replace, sensor) there; use the full-plane calls for this camera");
@@ -1937,14 +1967,18 @@ static int check_thresh_route(rtuf_context* c)
   return RTUF_OK;
 }
 
+// the outputs of a cloud batch (capacity 0: the organized form; index may be nullptr)
+struct CloudOut { float* points; uint32_t* index; uint32_t* counts; int capacity; };
+
 // d_virtual != nullptr: a render batch (d_depth, d_masked, d_mask, d_bits unused)
+// cloud != nullptr: a cloud batch (d_bits: the slot's own bits buffer; d_masked, d_mask unused)
 // d_resid != nullptr: a residual batch (d_masked, d_mask, d_bits, d_labels, d_virtual unused)
 static int submit_batch(rtuf_context* c, int n, const float* d_depth, float* d_masked, uint8_t* d_mask, bool u16, uint32_t* d_bits = nullptr,
                         bool wait_upload = false, uint16_t* d_labels = nullptr, float* d_virtual = nullptr, float empty_value = 0.0f,
-                        rtuf_link_residuals* d_resid = nullptr, int n_labels = 0)
+                        rtuf_link_residuals* d_resid = nullptr, int n_labels = 0, const CloudOut* cloud = nullptr)
 {
   if (c->broken) return c->fail(RTUF_ERR_STATE, "context unusable: a bin regrowth failed (%s)", c->error.c_str());
-  if (!d_virtual && !d_resid) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
+  if (!d_virtual && !d_resid && !cloud) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
   hipSetDevice(c->device);
   if (uses_zsurface(c) && !d_virtual && !d_resid)
     for (int l = 0; l < c->n_lanes; l++)
@@ -1956,6 +1990,8 @@ static int submit_batch(rtuf_context* c, int n, const float* d_depth, float* d_m
   b.n = n; b.depth = d_depth; b.masked = d_masked; b.mask = d_mask; b.u16 = u16; b.host_io = false; b.bits = d_bits; b.labels = d_labels;
   b.virt = d_virtual; b.empty_value = empty_value;
   b.resid = d_resid; b.n_labels = n_labels;
+  b.cloud_points = cloud ? cloud->points : nullptr; b.cloud_index = cloud ? cloud->index : nullptr; b.cloud_counts = cloud ? cloud->counts : nullptr;
+  b.cloud_capacity = cloud ? cloud->capacity : 0;
   b.wait_upload = wait_upload;
   const int rc = enqueue_batch(c, b, false);
   if (rc == RTUF_OK) { b.active = true; c->pending++; }
@@ -2544,6 +2580,177 @@ int rtuf_link_residuals_batch_u16(rtuf_context* c, int n, const uint16_t* const*
 {
   const int rc = link_residuals_batch_async(c, n, reinterpret_cast<const void* const*>(depth_mm_in), table_out, n_labels, true);
   return rc != RTUF_OK ? rc : rtuf_sync(c);
+}
+
+// ---- filtered point clouds ---------------------------------------------------------------------------
+// A cloud batch is a mask-bits batch (submit_batch with the slot's own bits buffer) whose launch groups run the cloud kernels
+// behind their tile / dilate kernel (issue_plan).  RTUF_FLAG_TWO_KERNEL does not enter: the fused bits route is taken.
+int rtuf_set_cloud_intrinsics(rtuf_context* c, int first, int n, const double* fx_fy_cx_cy)
+{
+  KIDS_ALL(c, rtuf_set_cloud_intrinsics(k, first, n, fx_fy_cx_cy));
+  if (!c) return RTUF_ERR_INVALID;
+  if (!fx_fy_cx_cy || first < 0 || n <= 0 || n > c->max_streams || first > c->max_streams - n) return c->fail(RTUF_ERR_INVALID, "bad stream range (first=%d, n=%d)", first, n);
+  std::vector<CloudIntrinsics> h((size_t)n);
+  for (int s = 0; s < n; s++) {
+    const double fx = fx_fy_cx_cy[4 * s], fy = fx_fy_cx_cy[4 * s + 1];
+    if (!(std::isfinite(fx) && fx > 0.0) || !(std::isfinite(fy) && fy > 0.0))
+      return c->fail(RTUF_ERR_INVALID, "stream %d: fx and fy must be finite and > 0 (got %g, %g)", first + s, fx, fy);
+    h[(size_t)s] = {(float)(1.0 / fx), (float)(1.0 / fy), (float)fx_fy_cx_cy[4 * s + 2], (float)fx_fy_cx_cy[4 * s + 3]};
+  }
+  WAIT_IF_PENDING(c);
+  hipSetDevice(c->device);
+  if (!c->d_cloud_intr) {
+    HIP_TRY(c, dev_alloc(c, &c->d_cloud_intr, (size_t)c->max_streams * sizeof(CloudIntrinsics)));
+    c->cloud_intr_set.assign((size_t)c->max_streams, 0);
+  }
+  HIP_TRY(c, hipMemcpy(c->d_cloud_intr + first, h.data(), (size_t)n * sizeof(CloudIntrinsics), hipMemcpyHostToDevice));
+  std::fill(c->cloud_intr_set.begin() + first, c->cloud_intr_set.begin() + first + n, (uint8_t)1);
+  return RTUF_OK;
+}
+
+static int check_cloud_call(rtuf_context* c, int n, const void* in, const void* points, const void* counts, int capacity, bool compact)
+{
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (n <= 0 || n > c->max_streams || !in || !points || (compact && !counts)) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
+  if (c->width & 3) return c->fail(RTUF_ERR_INVALID, "point clouds are built on the mask bits: they need a width that is a multiple of 4");
+  if (compact && (capacity < 1 || (long long)capacity > (long long)c->width * c->height))
+    return c->fail(RTUF_ERR_INVALID, "capacity = %d: 1 .. width * height (%lld)", capacity, (long long)c->width * c->height);
+  if (c->thresh_models > 0 && c->params.silhouette_dilation_px > 0)
+    return c->fail(RTUF_ERR_INVALID, "per-link depth thresholds are not supported with silhouette dilation yet");
+  for (int s = 0; s < n; s++)
+    if (!c->d_cloud_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
+  return RTUF_OK;
+}
+
+// device planes of the organized form: its kernel loads four sensor values at once (16 bytes of f32, 8 bytes of 16UC1) and stores 16-byte
+// vectors of points
+static int check_cloud_alignment(rtuf_context* c, const void* d_depth, const void* d_points, bool u16)
+{
+  if ((uintptr_t)d_points & 15u) return c->fail(RTUF_ERR_INVALID, "d_points must be 16-byte aligned");
+  if ((uintptr_t)d_depth & (u16 ? 7u : 15u)) return c->fail(RTUF_ERR_INVALID, "d_depth must be %d-byte aligned", u16 ? 8 : 16);
+  return RTUF_OK;
+}
+
+// takes the slot submit_batch takes next, gives it its bits buffer and row scratch, and submits
+static int submit_cloud(rtuf_context* c, int n, const float* d_depth, bool u16, const CloudOut& out, bool wait_upload)
+{
+  if (c->broken) return c->fail(RTUF_ERR_STATE, "context unusable: a bin regrowth failed (%s)", c->error.c_str());
+  hipSetDevice(c->device);
+  const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
+  while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
+  rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];
+  if (!b.cl_bits) HIP_TRY(c, dev_alloc(c, &b.cl_bits, (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
+  if (out.capacity && !b.cl_rows) HIP_TRY(c, dev_alloc(c, &b.cl_rows, 2u * (size_t)c->max_streams * (size_t)c->height * sizeof(uint32_t)));
+  return submit_batch(c, n, d_depth, nullptr, nullptr, u16, b.cl_bits, wait_upload, nullptr, nullptr, 0.0f, nullptr, 0, &out);
+}
+
+int rtuf_cloud_batch_device(rtuf_context* c, int n, const float* d_depth, float* d_points)
+{
+  KIDS_NEXT(c, rtuf_cloud_batch_device(k, n, d_depth, d_points));
+  if (!c) return RTUF_ERR_INVALID;
+  int rc = check_cloud_call(c, n, d_depth, d_points, nullptr, 0, false);
+  if (rc == RTUF_OK) rc = check_cloud_alignment(c, d_depth, d_points, false);
+  return rc != RTUF_OK ? rc : submit_cloud(c, n, d_depth, false, CloudOut{d_points, nullptr, nullptr, 0}, false);
+}
+
+int rtuf_cloud_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth, float* d_points)
+{
+  KIDS_NEXT(c, rtuf_cloud_batch_device_u16(k, n, d_depth, d_points));
+  if (!c) return RTUF_ERR_INVALID;
+  int rc = check_cloud_call(c, n, d_depth, d_points, nullptr, 0, false);
+  if (rc == RTUF_OK) rc = check_cloud_alignment(c, d_depth, d_points, true);
+  return rc != RTUF_OK ? rc : submit_cloud(c, n, reinterpret_cast<const float*>(d_depth), true, CloudOut{d_points, nullptr, nullptr, 0}, false);
+}
+
+int rtuf_cloud_compact_batch_device(rtuf_context* c, int n, const float* d_depth, float* d_points, uint32_t* d_index, uint32_t* d_counts, int capacity)
+{
+  KIDS_NEXT(c, rtuf_cloud_compact_batch_device(k, n, d_depth, d_points, d_index, d_counts, capacity));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_cloud_call(c, n, d_depth, d_points, d_counts, capacity, true);
+  return rc != RTUF_OK ? rc : submit_cloud(c, n, d_depth, false, CloudOut{d_points, d_index, d_counts, capacity}, false);
+}
+
+int rtuf_cloud_compact_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth, float* d_points, uint32_t* d_index, uint32_t* d_counts, int capacity)
+{
+  KIDS_NEXT(c, rtuf_cloud_compact_batch_device_u16(k, n, d_depth, d_points, d_index, d_counts, capacity));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_cloud_call(c, n, d_depth, d_points, d_counts, capacity, true);
+  return rc != RTUF_OK ? rc : submit_cloud(c, n, reinterpret_cast<const float*>(d_depth), true, CloudOut{d_points, d_index, d_counts, capacity}, false);
+}
+
+// host planes, synchronous: planes up into the slot's staging, the batch, and -- once it is retired, re-runs included -- the
+// results down; the compacted forms bring the counts down first and then only min(counts, capacity) entries per stream
+static int cloud_host_batch(rtuf_context* c, int n, const void* const* depth_in, float* const* points_out, uint32_t* const* index_out,
+                            uint32_t* counts_out, int capacity, bool compact, bool u16)
+{
+  KIDS_NEXT(c, cloud_host_batch(k, n, depth_in, points_out, index_out, counts_out, capacity, compact, u16));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = check_cloud_call(c, n, depth_in, points_out, counts_out, capacity, compact); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; s < n; s++)
+    if (!depth_in[s] || !points_out[s] || (index_out && !index_out[s])) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
+  hipSetDevice(c->device);
+  { const int rc = ensure_copy_streams(c); if (rc != RTUF_OK) return rc; }
+  const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
+  while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
+  rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];     // the slot submit_cloud takes next
+  { const int rc = ensure_plane_staging(c, b, n, false); if (rc != RTUF_OK) return rc; }
+  const size_t per = compact ? (size_t)capacity : (size_t)c->width * c->height;   // entries per stream
+  if (b.st_points_floats < (size_t)n * per * 3u) {
+    dev_free(c, b.st_points);
+    b.st_points_floats = 0;
+    HIP_TRY(c, dev_alloc(c, &b.st_points, (size_t)n * per * 3u * sizeof(float)));
+    b.st_points_floats = (size_t)n * per * 3u;
+  }
+  if (compact && index_out && b.st_index_words < (size_t)n * per) {
+    dev_free(c, b.st_index);
+    b.st_index_words = 0;
+    HIP_TRY(c, dev_alloc(c, &b.st_index, (size_t)n * per * sizeof(uint32_t)));
+    b.st_index_words = (size_t)n * per;
+  }
+  if (compact && !b.st_counts) HIP_TRY(c, dev_alloc(c, &b.st_counts, (size_t)c->max_streams * sizeof(uint32_t)));
+  { const int rc = upload_planes(c, b, n, depth_in, u16); if (rc != RTUF_OK) return rc; }
+  const CloudOut out{b.st_points, compact && index_out ? b.st_index : nullptr, compact ? b.st_counts : nullptr, compact ? capacity : 0};
+  { const int rc = submit_cloud(c, n, b.st_depth, u16, out, true); if (rc != RTUF_OK) return rc; }
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  if (!compact) {
+    for (int s = 0; s < n;) {                // consecutive planes as one transfer
+      int e = s + 1;
+      while (e < n && points_out[e] == points_out[e - 1] + per * 3u) e++;
+      HIP_TRY(c, hipMemcpy(points_out[s], b.st_points + (size_t)s * per * 3u, (size_t)(e - s) * per * 3u * sizeof(float), hipMemcpyDeviceToHost));
+      s = e;
+    }
+    return RTUF_OK;
+  }
+  HIP_TRY(c, hipMemcpy(counts_out, b.st_counts, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (int s = 0; s < n; s++) {
+    const size_t m = std::min<size_t>(counts_out[s], per);
+    if (!m) continue;
+    HIP_TRY(c, hipMemcpy(points_out[s], b.st_points + (size_t)s * per * 3u, m * 3u * sizeof(float), hipMemcpyDeviceToHost));
+    if (index_out) HIP_TRY(c, hipMemcpy(index_out[s], b.st_index + (size_t)s * per, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  return RTUF_OK;
+}
+
+int rtuf_cloud_batch(rtuf_context* c, int n, const float* const* depth_in, float* const* points_out)
+{
+  return cloud_host_batch(c, n, reinterpret_cast<const void* const*>(depth_in), points_out, nullptr, nullptr, 0, false, false);
+}
+
+int rtuf_cloud_batch_u16(rtuf_context* c, int n, const uint16_t* const* depth_mm_in, float* const* points_out)
+{
+  return cloud_host_batch(c, n, reinterpret_cast<const void* const*>(depth_mm_in), points_out, nullptr, nullptr, 0, false, true);
+}
+
+int rtuf_cloud_compact_batch(rtuf_context* c, int n, const float* const* depth_in, float* const* points_out, uint32_t* const* index_out,
+                             uint32_t* counts_out, int capacity)
+{
+  return cloud_host_batch(c, n, reinterpret_cast<const void* const*>(depth_in), points_out, index_out, counts_out, capacity, true, false);
+}
+
+int rtuf_cloud_compact_batch_u16(rtuf_context* c, int n, const uint16_t* const* depth_mm_in, float* const* points_out, uint32_t* const* index_out,
+                                 uint32_t* counts_out, int capacity)
+{
+  return cloud_host_batch(c, n, reinterpret_cast<const void* const*>(depth_mm_in), points_out, index_out, counts_out, capacity, true, true);
 }
 
 int rtuf_wait_oldest(rtuf_context* c)

@@ -366,6 +366,24 @@ struct DilateArgs {
   int fast_div;
 };
 
+// Filtered point clouds (include/rtuf.h, FILTERED POINT CLOUDS): the cloud kernels of one launch group.  They run behind the
+// group's tile (or dilate) kernel on its lane and read the mask bits that kernel wrote; streams are batch-absolute.
+struct CloudIntrinsics;
+struct CloudArgs {
+  const float* depth;            // [n][H][W] sensor planes (f32 metres or, with io_u16, uint16 millimetres): the whole batch
+  const uint32_t* bits;          // [n][H][ceil(W/32)] mask bits of the batch (the library's buffer of the batch slot)
+  const CloudIntrinsics* intr;   // [max_streams] kx, ky, cx, cy
+  float* points;                 // organized: [n][H][W][3]; compacted: [n][capacity][3]
+  uint32_t* index;               // compacted: [n][capacity] v * W + u of every entry, or nullptr
+  uint32_t* counts;              // compacted: [n] kept pixels of every stream (the full number)
+  uint32_t* row_count;           // compacted: [n][H] kept pixels of every row (scratch of the batch slot)
+  uint32_t* row_start;           // compacted: [n][H] exclusive scan of row_count per stream (scratch of the batch slot)
+  int group_base, group_size;
+  int width, height;
+  int capacity;                  // compacted: entries per stream; 0: the organized form
+  int io_u16;
+};
+
 struct FkArgs {
   const int32_t* parent;        // [F]
   const int32_t* joint_type;    // [F]
@@ -397,6 +415,7 @@ void launch_zero_residual_rows(unsigned long long* rows, size_t n_words, hipStre
 void launch_tile(const TileArgs& a, bool two_kernel, bool cover_pass, hipStream_t st);   // a.io_u16 selects the 16UC1 variant
 void launch_compare(const CompareArgs& a, hipStream_t st);
 void launch_dilate_compare(const DilateArgs& a, hipStream_t st);     // a.bits selects the mask-only variant, a.io_u16 the 16UC1 one
+void launch_cloud(const CloudArgs& a, hipStream_t st);               // a.capacity selects the compacted form (count, scan, emit), a.io_u16 the 16UC1 variants
 void launch_spin(unsigned long long ticks, hipStream_t st);      // a one-wave kernel that idles for `ticks` of the 100 MHz clock
 
 }  // namespace rtuf

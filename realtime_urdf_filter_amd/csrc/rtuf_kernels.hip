@@ -3210,4 +3210,163 @@ void launch_dilate_compare(const DilateArgs& a, hipStream_t st)
   else hipLaunchKernelGGL((dilate_compare_kernel<false, false>), grid, dim3(kDilThreads), lds, st, a);
 }
 
+// ---- filtered point clouds (include/rtuf.h, FILTERED POINT CLOUDS) ------------------------------------------------------
+// A cloud batch is a mask-bits batch: the kernels below run behind the launch group's tile (or dilate) kernel on its lane,
+// read the bits it wrote and the sensor planes once more, and write the points.  Nothing here is atomic and no result
+// depends on the order of execution: the compacted form is counted, scanned and scattered in row-major order.
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr uint32_t kCloudNaN = 0x7fc00000u;      // what a pixel without a point holds in the organized form
+
+// Organized form: one lane per four pixels of a row -- one 16-byte (f32) or 8-byte (16UC1) sensor load, the group's nibble of
+// its bits word, three 16-byte non-temporal stores (48 contiguous bytes).  grid: (ceil(H * W/4 / kBlock), group_size).
+template <bool U16>
+__global__ __launch_bounds__(kBlock) void cloud_organized_kernel(CloudArgs a)
+{
+  const int w4 = a.width >> 2;
+  const uint32_t t = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  if (t >= (uint32_t)w4 * (uint32_t)a.height) return;
+  const int stream = a.group_base + (int)blockIdx.y;
+  const int v = (int)(t / (uint32_t)w4), u = (int)(t - (uint32_t)v * (uint32_t)w4) * 4;
+  const size_t pix = (size_t)stream * (size_t)a.width * (size_t)a.height + (size_t)t * 4u;      // (rows are contiguous: W = 4 * w4)
+  float s[4];
+  if (U16) {
+    const uint2 q = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(a.depth) + pix);
+    s[0] = u16_to_metres(q.x & 0xffffu); s[1] = u16_to_metres(q.x >> 16); s[2] = u16_to_metres(q.y & 0xffffu); s[3] = u16_to_metres(q.y >> 16);
+  } else {
+    const float4 q = *reinterpret_cast<const float4*>(a.depth + pix);
+    s[0] = q.x; s[1] = q.y; s[2] = q.z; s[3] = q.w;
+  }
+  const int row_words = (a.width + 31) >> 5;
+  const uint32_t nib = a.bits[((size_t)stream * a.height + (size_t)v) * (size_t)row_words + (size_t)(u >> 5)] >> (u & 31);
+  const CloudIntrinsics k = a.intr[stream];
+  float p[12];
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    float x, y, z;
+    cloud_point(u + j, v, s[j], k, x, y, z);
+    const bool kept = !((nib >> j) & 1u) && cloud_sensor_valid(s[j]);
+    p[3 * j] = kept ? x : __uint_as_float(kCloudNaN);
+    p[3 * j + 1] = kept ? y : __uint_as_float(kCloudNaN);
+    p[3 * j + 2] = kept ? z : __uint_as_float(kCloudNaN);
+  }
+  f32x4* dst = reinterpret_cast<f32x4*>(a.points + pix * 3u);
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    f32x4 o;
+    o.x = p[4 * j]; o.y = p[4 * j + 1]; o.z = p[4 * j + 2]; o.w = p[4 * j + 3];
+    __builtin_nontemporal_store(o, dst + j);
+  }
+}
+
+// One 64-pixel chunk of a row, a pixel per lane (the last chunk of a row is partial when W % 64 != 0): the coalesced sensor
+// load, the pixel's bit of the chunk's two bits words, and the wave's ballot of the kept pixels.
+template <bool U16>
+__device__ __forceinline__ unsigned long long cloud_chunk(const CloudArgs& a, size_t row_pix, const uint32_t* row_bits, int u, float& s)
+{
+  bool kept = false;
+  s = 0.0f;
+  if (u < a.width) {
+    s = U16 ? u16_to_metres(reinterpret_cast<const uint16_t*>(a.depth)[row_pix + (size_t)u]) : a.depth[row_pix + (size_t)u];
+    kept = !((row_bits[u >> 5] >> (u & 31)) & 1u) && cloud_sensor_valid(s);
+  }
+  return __ballot(kept);
+}
+
+// Compacted form, step 1: one wave per (stream, row) counts the row's kept pixels; lane 0 stores the count.
+template <bool U16>
+__global__ __launch_bounds__(kBlock) void cloud_row_count_kernel(CloudArgs a)
+{
+  const uint32_t wave = (blockIdx.x * (uint32_t)kBlock + threadIdx.x) >> 6;
+  if (wave >= (uint32_t)a.group_size * (uint32_t)a.height) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int sl = (int)(wave / (uint32_t)a.height), v = (int)(wave - (uint32_t)sl * (uint32_t)a.height), stream = a.group_base + sl;
+  const size_t row = (size_t)stream * a.height + (size_t)v;
+  const uint32_t* row_bits = a.bits + row * (size_t)((a.width + 31) >> 5);
+  uint32_t total = 0;
+  for (int c0 = 0; c0 < a.width; c0 += 64) {
+    float s;
+    total += (uint32_t)__popcll(cloud_chunk<U16>(a, row * (size_t)a.width, row_bits, c0 + lane, s));
+  }
+  if (lane == 0) a.row_count[row] = total;
+}
+
+// Step 2: one workgroup per stream, the exclusive scan of its H row counts (any H: kBlock rows per trip and a carry) and the
+// stream's total.
+__global__ __launch_bounds__(kBlock) void cloud_scan_kernel(CloudArgs a)
+{
+  __shared__ uint32_t s_wave[kBlock / 64];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int stream = a.group_base + (int)blockIdx.x;
+  const uint32_t* rc = a.row_count + (size_t)stream * a.height;
+  uint32_t* rs = a.row_start + (size_t)stream * a.height;
+  uint32_t carry = 0;
+  for (int base = 0; base < a.height; base += kBlock) {
+    const int i = base + tid;
+    const uint32_t x = i < a.height ? rc[i] : 0u;
+    uint32_t inc = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = (uint32_t)__shfl_up((int)inc, o);
+      if (lane >= o) inc += y;
+    }
+    if (lane == 63) s_wave[wid] = inc;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; w++) { const uint32_t t = s_wave[w]; before += w < wid ? t : 0u; all += t; }
+    if (i < a.height) rs[i] = carry + before + inc - x;
+    carry += all;
+    __syncthreads();
+  }
+  if (tid == 0) a.counts[stream] = carry;
+}
+
+// Step 3: the shape of the count kernel again.  Per chunk a kept pixel's place is the row's start + the kept pixels of the
+// row's earlier chunks + those of the lanes below it; places at or beyond the capacity are not written.
+template <bool U16>
+__global__ __launch_bounds__(kBlock) void cloud_emit_kernel(CloudArgs a)
+{
+  const uint32_t wave = (blockIdx.x * (uint32_t)kBlock + threadIdx.x) >> 6;
+  if (wave >= (uint32_t)a.group_size * (uint32_t)a.height) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int sl = (int)(wave / (uint32_t)a.height), v = (int)(wave - (uint32_t)sl * (uint32_t)a.height), stream = a.group_base + sl;
+  const size_t row = (size_t)stream * a.height + (size_t)v;
+  const uint32_t* row_bits = a.bits + row * (size_t)((a.width + 31) >> 5);
+  const CloudIntrinsics k = a.intr[stream];
+  const uint32_t capacity = (uint32_t)a.capacity;
+  uint32_t running = a.row_start[row];
+  for (int c0 = 0; c0 < a.width && running < capacity; c0 += 64) {
+    float s;
+    const int u = c0 + lane;
+    const unsigned long long m = cloud_chunk<U16>(a, row * (size_t)a.width, row_bits, u, s);
+    const uint32_t dst = running + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (((m >> lane) & 1ull) && dst < capacity) {
+      float x, y, z;
+      cloud_point(u, v, s, k, x, y, z);
+      float* p = a.points + ((size_t)stream * capacity + dst) * 3u;
+      p[0] = x; p[1] = y; p[2] = z;
+      if (a.index) a.index[(size_t)stream * capacity + dst] = (uint32_t)(v * a.width + u);
+    }
+    running += (uint32_t)__popcll(m);
+  }
+}
+
+void launch_cloud(const CloudArgs& a, hipStream_t st)
+{
+  if (a.capacity <= 0) {
+    const dim3 grid((unsigned)(((size_t)(a.width >> 2) * a.height + kBlock - 1) / kBlock), (unsigned)a.group_size);
+    if (a.io_u16) hipLaunchKernelGGL(cloud_organized_kernel<true>, grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL(cloud_organized_kernel<false>, grid, dim3(kBlock), 0, st, a);
+    return;
+  }
+  // a wave per (stream, row): batch = 1 still spreads its H rows over the GPU
+  const unsigned row_blocks = (unsigned)(((size_t)a.group_size * a.height * 64u + kBlock - 1) / kBlock);
+  if (a.io_u16) hipLaunchKernelGGL(cloud_row_count_kernel<true>, dim3(row_blocks), dim3(kBlock), 0, st, a);
+  else hipLaunchKernelGGL(cloud_row_count_kernel<false>, dim3(row_blocks), dim3(kBlock), 0, st, a);
+  hipLaunchKernelGGL(cloud_scan_kernel, dim3((unsigned)a.group_size), dim3(kBlock), 0, st, a);
+  if (a.io_u16) hipLaunchKernelGGL(cloud_emit_kernel<true>, dim3(row_blocks), dim3(kBlock), 0, st, a);
+  else hipLaunchKernelGGL(cloud_emit_kernel<false>, dim3(row_blocks), dim3(kBlock), 0, st, a);
+}
+
 }  // namespace rtuf

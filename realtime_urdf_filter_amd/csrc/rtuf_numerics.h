@@ -1,7 +1,7 @@
 // rtuf_numerics.h -- the arithmetic whose exact bits the results depend on and that something besides the kernels checks or
 // shares: the 24-bit depth and its bit-pattern forms, the depth keys' encoding of a near fragment's float z, the set-up's
 // 32-bit edge constants, the key format's host-side rules, the compare threshold's constants, division core and the rule
-// that admits that core, and the pixel classes of the link residual tables.
+// that admits that core, the pixel classes of the link residual tables, and the point of a filtered point cloud.
 //
 // Included by the kernels (rtuf_kernels.hip, device and host pass), the host API (rtuf_api.cpp), scripts/fdiv_check.hip (which
 // holds div_core against the IEEE division on the GPU) and the CPU checks (tests/fast_class_check.cpp, tests/near_key_check.cpp:
@@ -19,8 +19,10 @@
 #ifdef __HIP__
 #include <hip/hip_runtime.h>
 #define RTUF_NUMERIC __device__ __forceinline__
+#define RTUF_NUMERIC_HD __host__ __device__ __forceinline__
 #else
 #define RTUF_NUMERIC inline
+#define RTUF_NUMERIC_HD inline
 #endif
 
 namespace rtuf {
@@ -167,6 +169,28 @@ RTUF_NUMERIC uint32_t link_residual_class(float s, float v, float t, int& q)
 }
 // A pixel no fragment reached: it counts as a pixel, and as invalid where the sensor holds no reading.
 RTUF_NUMERIC uint32_t link_residual_undrawn(float s) { return kResPixel | (s > 0.0f ? 0u : kResInvalid); }
+
+// ---------------------------------------------------------------------------------------
+// filtered point clouds (include/rtuf.h, FILTERED POINT CLOUDS): which sensor values make a point, and the point
+// ---------------------------------------------------------------------------------------
+
+// Per-stream intrinsics as the cloud kernels read them: kx = (float)(1.0 / fx), ky = (float)(1.0 / fy), cx, cy.
+struct CloudIntrinsics { float kx, ky, cx, cy; };
+
+// A sensor value carries a point iff it is a positive finite number (NaN, 0, -0, negatives and +inf do not).
+RTUF_NUMERIC_HD bool cloud_sensor_valid(float s) { return s > 0.0f && s < INFINITY; }
+
+// The point of pixel (u, v) with sensor value s: x = ((u - cx) * s) * kx, y = ((v - cy) * s) * ky, z = s, every operation a
+// single float operation in that order (depth_image_proc's association).  Plain operators on host and device alike: a
+// difference and two products, nothing an -ffp-contract setting could fuse.
+RTUF_NUMERIC_HD void cloud_point(int u, int v, float s, const CloudIntrinsics& k, float& x, float& y, float& z)
+{
+  const float du = (float)u - k.cx, dv = (float)v - k.cy;
+  const float xs = du * s, ys = dv * s;
+  x = xs * k.kx;
+  y = ys * k.ky;
+  z = s;
+}
 
 #ifdef __HIP__
 // The IEEE division without the instructions that only matter for operands near the ends of the exponent range: the compiler

@@ -275,6 +275,7 @@ class RealtimeURDFFilter:
             p.flags |= _capi.FLAG_TWO_KERNEL
         if self._ctx is not None:
             self._ctx.close()
+        self._cloud_intr_given_ = None              # (the new context has no cloud intrinsics: cloud() gives them again)
         self._ctx = _capi.Context(self.width_, self.height_, self.max_streams, self.device, p)
         self.loadModels()
         if not self.renderers_:
@@ -312,10 +313,12 @@ class RealtimeURDFFilter:
         if self.params.use_own_calibration:      # the #ifdef branch: own intrinsics, camera_tx_ / camera_ty_ untouched
             fx, fy, cx, cy = self.params.own_calibration
             P, _, _ = _capi.projection_from_intrinsics(fx, fy, cx, cy, info.width, info.height, self.near_plane_, self.far_plane_, 0.0, 0.0)
+            self.cloud_intrinsics_ = (fx, fy, cx, cy)
             return P
         P, tx, ty = _capi.projection_from_intrinsics(info.P[0], info.P[5], info.P[2], info.P[6], info.width, info.height,
                                                      self.near_plane_, self.far_plane_, info.P[3], info.P[7])
         self.camera_tx_, self.camera_ty_ = tx, ty
+        self.cloud_intrinsics_ = (info.P[0], info.P[5], info.P[2], info.P[6])      # (cloud(): the pinhole the projection was made from)
         return P
 
     def _camera_matrices(self, tf, timestamp):
@@ -404,6 +407,35 @@ class RealtimeURDFFilter:
         if d.dtype == np.uint16 and width % 4:      # (the 16UC1 kernels need a width that is a multiple of 4)
             d = d.astype(np.float32) * np.float32(0.001)
         return self._ctx.link_residuals_batch(d, self.numLinkResidualRows())[0]
+
+    def cloud(self, depth, projection_matrix, width, height, timestamp=None, compact=False):
+        """New, beyond the reference: the pixels filter() would keep as XYZ points in the camera's optical frame (include/rtuf.h,
+        FILTERED POINT CLOUDS), for the camera and link poses filter() would use and the intrinsics of the last
+        getProjectionMatrix() (own_calibration, which FilterParameters keeps rounded to float, with use_own_calibration, as the
+        projection and the C++ façade take it; else the camera info's fx fy cx cy as doubles).
+        depth: [H,W] float32 metres or uint16 millimetres; the width must be a multiple of 4.  Returns [H,W,3] float32 with NaN
+        where there is no point, or with compact=True (points [count,3], index [count] = v * width + u) in row-major order;
+        None where filter() would have returned without a result."""
+        self._ensure_size(width, height)
+        if not self.renderers_:
+            return None
+        intr = getattr(self, "cloud_intrinsics_", None)
+        if intr is None:
+            raise RuntimeError("cloud(): no intrinsics yet (getProjectionMatrix sets them)")
+        try:
+            self._stage_stream(0, projection_matrix, self.tf_, timestamp)
+        except Exception as e:                      # noqa: BLE001 - ROS_ERROR + return (quirk Q6)
+            log.error("%s", e)
+            return None
+        if getattr(self, "_cloud_intr_given_", None) != intr:      # (initGL clears it with every new context)
+            self._ctx.set_cloud_intrinsics(0, intr)
+            self._cloud_intr_given_ = intr
+        d = np.asarray(depth)
+        d = d.astype(np.uint16 if d.dtype == np.uint16 else np.float32, copy=False).reshape(1, height, width)
+        if not compact:
+            return self._ctx.cloud_batch(d)[0]
+        points, index, counts = self._ctx.cloud_compact_batch(d, width * height)
+        return points[0, :counts[0]], index[0, :counts[0]]
 
     def numLinkResidualRows(self):
         """Rows of a link_residuals() table: one more than the largest label in effect."""

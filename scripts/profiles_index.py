@@ -118,6 +118,7 @@ def build(tag):
     text("wall time of the default bench command", ["README.md"], T + "_bench_wall_time.txt", "the line")
     text("virtual depth planes on c3: render batches beside the plain fused filter", ["README.md", "DESIGN.md 4"], "virtual_rate_c3.txt", "the last line")
     text("link residual tables on c3: residual batches beside the plain fused filter", ["README.md", "DESIGN.md 4"], "link_residuals_rate_c3.txt", "the last line")
+    text("filtered point clouds on c3: cloud batches beside the mask-bits batch and beside filter + torch ops", ["README.md", "DESIGN.md 4"], "cloud_rate_c3.txt", "the last line")
     f = "link_residuals_kernel_stats.txt"
     if os.path.exists(os.path.join(PROFILES, f)):
         v = {}
