@@ -62,6 +62,24 @@ struct Kinematics {               // on-device forward kinematics of one model
 // thresholds: rtuf_set_link_thresholds's depth thresholds of the model's links (empty: rtuf_params.depth_distance_threshold)
 struct HostModel { std::vector<HostLink> links; int link_base = 0; Kinematics kin; std::vector<uint16_t> labels; std::vector<float> thresholds; };
 
+// One batch as its caller asked for it: the kind, and the device buffers and scalars that kind has (the rest stays nullptr / 0).
+// A slot keeps the record of its batch (Batch::rq) for re-runs; what a kind does is written down in the predicates before the hot path.
+struct BatchRequest {
+  enum class Kind { Filter, Bits, Render, Residual, Cloud };
+  Kind kind; int n; bool u16;               // (u16: the sensor / masked / virtual planes are 16UC1)
+  bool wait_upload = false;                 // host planes: the lanes wait for the slot's `uploaded` event before the first kernel that reads them
+  const float* depth = nullptr;             // sensor planes (every kind but Render)
+  float* masked = nullptr; uint8_t* mask = nullptr;      // Filter (mask may be nullptr)
+  uint16_t* labels = nullptr;               // Filter, Render: the link label plane, or nullptr
+  uint32_t* bits = nullptr;                 // Bits: the mask-only output, 1 bit per pixel; Cloud: the slot's own cl_bits
+  float* virt = nullptr; float empty_value = 0.0f;       // Render: the virtual depth plane (float, or uint16 with u16) and the value of its empty pixels
+  rtuf_link_residuals* resid = nullptr; int n_labels = 0;      // Residual: the table [n][n_labels] the tile kernel sums into, zeroed on every run, re-runs included
+  // Cloud (a mask-bits batch with the cloud kernels behind it).  capacity == 0: the organized form, index and counts unused; index may be nullptr anyway
+  float* points = nullptr; uint32_t* index = nullptr; uint32_t* counts = nullptr; int capacity = 0;
+  BatchRequest(Kind k = Kind::Filter, int n_ = 0, bool u16_ = false) : kind(k), n(n_), u16(u16_) {}
+};
+using Kind = BatchRequest::Kind;
+
 char g_create_error[512] = "";
 
 constexpr uint32_t kKnownFlags = RTUF_FLAG_TWO_KERNEL | RTUF_FLAG_STRICT_GRID;
@@ -181,27 +199,14 @@ struct rtuf_context {
   // Batches in flight.  Up to kMaxInflight device batches may be enqueued before the oldest is retired
   // (rtuf_sync, or the next rtuf_filter_batch_device* call when the ring is full), so the host round
   // trip of one batch overlaps the GPU work of the next.  A batch keeps what a re-run after a bin
-  // regrowth needs: its buffers and which joint-position staging buffer it read.
+  // regrowth needs: the request it was submitted with and which staging sets of the poses it read.
   struct Batch {
     bool active = false;
-    int n = 0; const float* depth = nullptr; float* masked = nullptr; uint8_t* mask = nullptr; bool u16 = false;
-    uint32_t* bits = nullptr;                // mask-only output (1 bit per pixel) instead of masked / mask
-    uint16_t* labels = nullptr;              // link label plane beside masked / mask (rtuf_filter_batch*_labels) or nullptr
+    BatchRequest rq;                         // what the caller asked for (submit_batch); every run of the batch reads it
     const float* order_thr = nullptr;        // per-link thresholds: the draw order -> threshold table, or nullptr (set when first enqueued)
-    // render batch (rtuf_render_batch*): the virtual depth plane (float, or uint16 with u16) and the value of its empty pixels;
-    // depth / masked / mask / bits are unused, labels may be given.  nullptr: a filter batch.
-    float* virt = nullptr; float empty_value = 0.0f;
-    // residual batch (rtuf_link_residuals_batch*): the table [n][n_labels] the tile kernel sums into, zeroed on every run (first
-    // runs and re-runs alike); depth is read, masked / mask / bits / labels / virt are unused.  nullptr: not a residual batch.
-    rtuf_link_residuals* resid = nullptr; int n_labels = 0;
-    // cloud batch (rtuf_cloud_batch*, rtuf_cloud_compact_batch*): a mask-bits batch (bits = cl_bits, the slot's own buffer) whose
-    // launch groups run the cloud kernels behind their tile / dilate kernel.  cloud_points == nullptr: not a cloud batch;
-    // cloud_capacity == 0: the organized form.  cl_bits / cl_rows ([2][max_streams][H]: row counts, row starts) are allocated
-    // on the slot's first cloud batch for max_streams, so that captured graphs keep their addresses.
-    float* cloud_points = nullptr; uint32_t* cloud_index = nullptr; uint32_t* cloud_counts = nullptr; int cloud_capacity = 0;
+    // cloud batches: the slot's own bits buffer and row scratch ([2][max_streams][H]: row counts, row starts), allocated on the
+    // slot's first (compacted) cloud batch for max_streams, so that captured graphs keep their addresses
     uint32_t* cl_bits = nullptr; uint32_t* cl_rows = nullptr;
-    float* st_points = nullptr; size_t st_points_floats = 0;      // host-plane cloud batches: device staging of points / index / counts
-    uint32_t* st_index = nullptr; size_t st_index_words = 0; uint32_t* st_counts = nullptr;
     Counters* h_counters = nullptr;          // pinned [max_groups]: one block per launch group, filled by the copies that end the batch
     hipEvent_t done[kMaxLanes] = {};         // recorded on each lane after its copy
     uint32_t lanes_used = 0;                 // bit l: the batch has launch groups on lane l
@@ -227,17 +232,16 @@ struct rtuf_context {
     bool cover_pass = true;                  // this batch runs the cover pass (decided when it is first enqueued, kept for re-runs)
     int dilation = 0;                        // silhouette dilation radius of this batch (set when it is first enqueued, kept for re-runs)
     int timing = 0;                          // event timing of this batch: 0 none, 1 every stage, 2 tile/compare kernel only
-    // Host-plane batches (rtuf_filter_batch*): device staging of this slot, the caller's planes, and the
-    // events that order upload -> kernels -> download across the copy streams.
-    bool host_io = false;
-    float* st_depth = nullptr; float* st_masked = nullptr; uint8_t* st_mask = nullptr; size_t st_streams = 0, st_depth_streams = 0;
-    uint32_t* st_bits = nullptr; size_t st_bits_streams = 0;
-    uint16_t* st_labels = nullptr; size_t st_labels_streams = 0;
-    float* st_virtual = nullptr; size_t st_virtual_streams = 0;      // (float-sized: large enough for uint16 planes)
-    std::vector<void*> h_masked, h_mask, h_bits, h_labels, h_virtual;
-    rtuf_link_residuals* st_table = nullptr; size_t st_table_rows = 0; rtuf_link_residuals* h_table = nullptr;      // residual batch with host planes
+    // Host-plane batches (submit_host_planes): grow-only device staging of this slot (ensure_staging; `have` in the units its
+    // user counts in: streams, table rows, floats, words), the caller's planes of an asynchronous download, and the events
+    // that order upload -> kernels -> download across the copy streams.
+    bool host_io = false;                    // the batch ends with a download on d2h (`downloaded`)
+    enum { kStDepth, kStMasked, kStMask, kStBits, kStLabels, kStVirtual, kStTable, kStPoints, kStIndex, kStKinds };
+    struct { char* p = nullptr; size_t have = 0; } st[kStKinds];      // (depth and virtual are float-sized: large enough for uint16 planes)
+    uint32_t* st_counts = nullptr;           // compacted clouds: [max_streams], allocated once
+    std::vector<void*> h_out, h_mask, h_labels;      // masked / bits / virtual planes; byte masks (any may be nullptr); label planes
+    rtuf_link_residuals* h_table = nullptr;
     hipEvent_t uploaded = nullptr, downloaded = nullptr;
-    bool wait_upload = false;                // the lanes wait for `uploaded` before the first kernel that reads the planes
   };
   Batch batch[kMaxInflight];
   hipStream_t side = nullptr;                // pose stages (see Batch)
@@ -667,9 +671,8 @@ static void free_frame_buffers(rtuf_context* c)
     dev_free(c, ln.d_clip_spill); dev_free(c, ln.d_big_list); dev_free(c, ln.d_zsurface);
     for (auto*& it : ln.d_items) dev_free(c, it);
   }
-  for (auto& b : c->batch) { dev_free(c, b.st_depth); dev_free(c, b.st_masked); dev_free(c, b.st_mask); b.st_streams = 0; b.st_depth_streams = 0; dev_free(c, b.st_bits); b.st_bits_streams = 0; }
-  for (auto& b : c->batch) { dev_free(c, b.st_labels); b.st_labels_streams = 0; dev_free(c, b.st_virtual); b.st_virtual_streams = 0; dev_free(c, b.st_table); b.st_table_rows = 0; }
-  for (auto& b : c->batch) { dev_free(c, b.cl_bits); dev_free(c, b.cl_rows); dev_free(c, b.st_points); b.st_points_floats = 0; dev_free(c, b.st_index); b.st_index_words = 0; dev_free(c, b.st_counts); }
+  for (auto& b : c->batch) for (auto& st : b.st) { dev_free(c, st.p); st.have = 0; }
+  for (auto& b : c->batch) { dev_free(c, b.cl_bits); dev_free(c, b.cl_rows); dev_free(c, b.st_counts); }
   for (auto*& p : c->ring_cams) hfree(p);
   for (auto*& p : c->ring_link_tf) hfree(p);
   c->h_cams = nullptr; c->h_link_tf = nullptr;
@@ -1376,6 +1379,25 @@ int rtuf_debug_read_poses(rtuf_context* c, int n, double* link_tf_out, double* c
   return RTUF_OK;
 }
 
+// ---- what a batch of each kind does (everything below decides by kind through these; a new kind answers them here) ----
+// the batches of this context write the z-surface: two-kernel mode, or a silhouette dilation radius
+static bool uses_zsurface(const rtuf_context* c) { return (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 || c->params.silhouette_dilation_px > 0; }
+// RTUF_FLAG_TWO_KERNEL: full planes only (the mask-bits calls refuse the flag; render, residual and cloud batches are always one tile kernel)
+static bool takes_two_kernel(const BatchRequest& r) { return r.kind == Kind::Filter; }
+// silhouette dilation: dilate_compare_kernel makes every output form from the z-surface, mask bits and so clouds included (the render and residual calls refuse it)
+static bool honours_dilation(const BatchRequest& r) { return r.kind != Kind::Render && r.kind != Kind::Residual; }
+// the per-link threshold table (a render batch compares nothing: no thresholds; a residual batch honours them)
+static bool reads_thresholds(const BatchRequest& r) { return r.kind != Kind::Render; }
+// the table draw order -> label: a label plane beside the outputs, or the rows of a residual table
+static bool reads_label_table(const BatchRequest& r) { return r.labels != nullptr || r.kind == Kind::Residual; }
+// may write the z-surface, and so needs d_zsurface and moves last_lane (render and residual batches leave it alone)
+static bool may_write_zsurface(const BatchRequest& r) { return takes_two_kernel(r) || honours_dilation(r); }
+// refused while per-link thresholds meet the z-surface route (check_thresh_route).  Render and residual batches never take that
+// route; a cloud batch takes it for dilation only, which check_cloud_call refuses with thresholds
+static bool subject_to_thresh_route(const BatchRequest& r) { return r.kind == Kind::Filter || r.kind == Kind::Bits; }
+// retire_oldest fills ms_compare: a kernel runs behind the tile kernel (compare, dilate + compare, or the cloud kernels)
+static bool fills_ms_compare(const rtuf_context* c, const rtuf_context::Batch& b) { return ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && takes_two_kernel(b.rq)) || b.dilation > 0 || b.rq.kind == Kind::Cloud; }
+
 // ---- the hot path ---------------------------------------------------------------------
 static hipEvent_t get_event(rtuf_context::Batch& b, size_t i)
 {
@@ -1498,11 +1520,12 @@ static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& 
 
 static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
 {
-  const int n = b.n;
-  const float* d_depth = b.depth; float* d_masked = b.masked; uint8_t* d_mask = b.mask;
-  const bool io_u16 = b.u16;
+  const BatchRequest& r = b.rq;
+  const int n = r.n;
+  const float* d_depth = r.depth; float* d_masked = r.masked; uint8_t* d_mask = r.mask;
+  const bool io_u16 = r.u16;
   const size_t esz = io_u16 ? sizeof(uint16_t) : sizeof(float);
-  const bool two = (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.virt && !b.resid && !b.cloud_points;      // (render, residual and cloud batches are always one tile kernel)
+  const bool two = (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && takes_two_kernel(r);
   // Launch groups: as many as the lanes' bins ask for, alternating between the lanes; a batch that is not split takes one
   // lane, the next such batch the other.
   const int n_groups = groups_for(c, n);
@@ -1556,13 +1579,10 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   BatchPlan plan;
   if (!rerun) b.cover_pass = c->cover_on;
   plan.cover_pass = b.cover_pass;
-  // silhouette dilation: the tile kernel writes the z-surface and dilate_compare_kernel makes every output form from it (the
-  // mask bits included); without it nothing here differs from before
-  // (a render batch compares nothing: no thresholds, and the render calls refuse silhouette dilation)
-  if (!rerun) b.dilation = b.virt || b.resid ? 0 : (int)c->params.silhouette_dilation_px;      // (a residual batch honours the thresholds and refuses dilation too)
-  if (!rerun) b.order_thr = c->thresh_models > 0 && !b.virt ? c->d_order_thr : nullptr;
+  if (!rerun) b.dilation = honours_dilation(r) ? (int)c->params.silhouette_dilation_px : 0;
+  if (!rerun) b.order_thr = c->thresh_models > 0 && reads_thresholds(r) ? c->d_order_thr : nullptr;
   const int dil = b.dilation;
-  plan.zroute = dil > 0 || (two && !b.bits);
+  plan.zroute = dil > 0 || two;
   // on-device forward kinematics overwrites the link matrices (and camera) of the streams that use it
   for (HostModel& m : c->models) {
     Kinematics& k = m.kin;
@@ -1636,27 +1656,27 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     ta.io_u16 = io_u16 ? 1 : 0;
     ta.key_shift = c->key_shift;
     ta.fast_div = fast_div;
-    ta.bits = dil ? nullptr : b.bits;
-    ta.labels = b.labels;                    // (the label calls refuse silhouette dilation and mask bits)
-    ta.order_labels = b.labels || b.resid ? c->d_order_labels : nullptr;
+    ta.bits = dil ? nullptr : r.bits;
+    ta.labels = r.labels;                    // (the label calls refuse silhouette dilation and mask bits)
+    ta.order_labels = reads_label_table(r) ? c->d_order_labels : nullptr;
     ta.order_thr = b.order_thr;              // (batches with per-link thresholds never take the z-surface route: check_thresh_route)
-    ta.virtual_out = b.virt; ta.empty_value = b.empty_value;
-    ta.resid_table = reinterpret_cast<unsigned long long*>(b.resid); ta.n_labels = b.n_labels;
-    gr.compare = two && !b.bits && !dil;
+    ta.virtual_out = r.virt; ta.empty_value = r.empty_value;
+    ta.resid_table = reinterpret_cast<unsigned long long*>(r.resid); ta.n_labels = r.n_labels;
+    gr.compare = two && !dil;
     gr.dilate = dil > 0;
     if (gr.dilate) {
       DilateArgs& da = gr.da;
-      da.depth = d_depth; da.zsurface = ln.d_zsurface; da.masked = d_masked; da.mask = d_mask; da.bits = b.bits; da.counters = d_counters;
+      da.depth = d_depth; da.zsurface = ln.d_zsurface; da.masked = d_masked; da.mask = d_mask; da.bits = r.bits; da.counters = d_counters;
       da.group_base = base; da.group_size = gs; da.width = c->width; da.height = c->height; da.radius = dil;
       da.max_diff = ta.max_diff; da.replace_value = ta.replace_value; da.sc_num = sc_num; da.sc_off = sc_off;
       da.io_u16 = io_u16 ? 1 : 0; da.fast_div = fast_div;
     }
-    gr.cloud = b.cloud_points != nullptr;
+    gr.cloud = r.kind == Kind::Cloud;
     if (gr.cloud) {
       CloudArgs& cl = gr.cl;
-      cl.depth = d_depth; cl.bits = b.bits; cl.intr = c->d_cloud_intr; cl.points = b.cloud_points; cl.index = b.cloud_index; cl.counts = b.cloud_counts;
+      cl.depth = d_depth; cl.bits = r.bits; cl.intr = c->d_cloud_intr; cl.points = r.points; cl.index = r.index; cl.counts = r.counts;
       cl.row_count = b.cl_rows; cl.row_start = b.cl_rows ? b.cl_rows + (size_t)c->max_streams * c->height : nullptr;
-      cl.group_base = base; cl.group_size = gs; cl.width = c->width; cl.height = c->height; cl.capacity = b.cloud_capacity; cl.io_u16 = io_u16 ? 1 : 0;
+      cl.group_base = base; cl.group_size = gs; cl.width = c->width; cl.height = c->height; cl.capacity = r.capacity; cl.io_u16 = io_u16 ? 1 : 0;
     }
     if (gr.compare) {
       CompareArgs& ca = gr.ca;
@@ -1670,9 +1690,9 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   }
   b.n_groups = (int)plan.groups.size();          // (= n_groups: the loop makes ceil(n / per_group) groups, checked above)
   b.setup_grid.assign(plan.groups.size(), 0xffffffffu);
-  if (!b.virt && !b.resid) c->last_lane = plan.groups.back().lane;      // (render and residual batches leave the z-surface alone)
+  if (may_write_zsurface(r)) c->last_lane = plan.groups.back().lane;
   // host-plane batches: the lanes' first kernels wait for the upload of the planes
-  if (b.wait_upload)
+  if (r.wait_upload)
     for (int l = 0; l < c->n_lanes; l++)
       if (b.lanes_used >> l & 1u) HIP_TRY(c, hipStreamWaitEvent(c->lane[l].stream, b.uploaded, 0));
   bool launched = false;
@@ -1740,54 +1760,50 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   return RTUF_OK;
 }
 
-// Copies the results of a host-plane batch to the caller's planes on the download stream, after the
-// batch's kernels; consecutive planes go out as one transfer.
+// Copies n planes of `stride` bytes between a packed device buffer and the caller's planes (kind: which way), on *stream --
+// or, stream == nullptr, with the synchronous hipMemcpy.  Consecutive host planes go as one transfer; a plane whose host
+// pointer is nullptr is skipped (byte masks only some streams asked for).
+static int copy_planes(rtuf_context* c, const void* dev, void* const* host, int n, size_t stride, hipMemcpyKind kind, const hipStream_t* stream)
+{
+  for (int s = 0; s < n;) {
+    if (!host[s]) { s++; continue; }
+    int e = s + 1;
+    while (e < n && host[e] && (char*)host[e] == (char*)host[e - 1] + stride) e++;
+    void* const d = (char*)dev + (size_t)s * stride;
+    void* const dst = kind == hipMemcpyHostToDevice ? d : host[s];
+    const void* const src = kind == hipMemcpyHostToDevice ? host[s] : d;
+    if (stream) HIP_TRY(c, hipMemcpyAsync(dst, src, (size_t)(e - s) * stride, kind, *stream));
+    else HIP_TRY(c, hipMemcpy(dst, src, (size_t)(e - s) * stride, kind));
+    s = e;
+  }
+  return RTUF_OK;
+}
+
+// Copies the results of a host-plane batch from the slot's staging (where the request points) to the caller's planes on the
+// download stream, after the batch's kernels.  (Not the clouds: their download is synchronous, download_cloud.)
 static int enqueue_download(rtuf_context* c, rtuf_context::Batch& b)
 {
+  const BatchRequest& r = b.rq;
   const size_t plane = (size_t)c->width * c->height;
-  const size_t esz = b.u16 ? sizeof(uint16_t) : sizeof(float);
+  const size_t esz = r.u16 ? sizeof(uint16_t) : sizeof(float);
   for (int l = 0; l < c->n_lanes; l++)
     if (b.lanes_used >> l & 1u) HIP_TRY(c, hipStreamWaitEvent(c->d2h, b.done[l], 0));
-  if (b.resid) {                             // a residual batch: the table is all that comes back
-    HIP_TRY(c, hipMemcpyAsync(b.h_table, b.st_table, (size_t)b.n * (size_t)b.n_labels * sizeof(rtuf_link_residuals), hipMemcpyDeviceToHost, c->d2h));
-    HIP_TRY(c, hipEventRecord(b.downloaded, c->d2h));
-    return RTUF_OK;
+  auto down = [&](const void* dev, const std::vector<void*>& host, size_t stride) { return copy_planes(c, dev, host.data(), r.n, stride, hipMemcpyDeviceToHost, &c->d2h); };
+  int rc = RTUF_OK;
+  switch (r.kind) {
+    case Kind::Residual:                     // the table is all that comes back
+      HIP_TRY(c, hipMemcpyAsync(b.h_table, r.resid, (size_t)r.n * (size_t)r.n_labels * sizeof(rtuf_link_residuals), hipMemcpyDeviceToHost, c->d2h));
+      break;
+    case Kind::Bits: rc = down(r.bits, b.h_out, rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)); break;
+    case Kind::Render: rc = down(r.virt, b.h_out, plane * esz); break;
+    case Kind::Filter:
+      rc = down(r.masked, b.h_out, plane * esz);
+      if (rc == RTUF_OK) rc = down(r.mask, b.h_mask, plane);
+      break;
+    case Kind::Cloud: break;
   }
-  if (b.bits) {
-    const size_t words = (size_t)c->height * (size_t)((c->width + 31) / 32);
-    for (int s = 0; s < b.n;) {
-      int e = s + 1;
-      while (e < b.n && (char*)b.h_bits[e] == (char*)b.h_bits[e - 1] + words * 4) e++;
-      HIP_TRY(c, hipMemcpyAsync(b.h_bits[s], b.st_bits + (size_t)s * words, (size_t)(e - s) * words * 4, hipMemcpyDeviceToHost, c->d2h));
-      s = e;
-    }
-    HIP_TRY(c, hipEventRecord(b.downloaded, c->d2h));
-    return RTUF_OK;
-  }
-  // (a render batch: the virtual depth planes in place of masked / mask)
-  const std::vector<void*>& h_planes = b.virt ? b.h_virtual : b.h_masked;
-  const char* st_planes = b.virt ? (const char*)b.st_virtual : (const char*)b.st_masked;
-  for (int s = 0; s < b.n;) {
-    int e = s + 1;
-    while (e < b.n && (char*)h_planes[e] == (char*)h_planes[e - 1] + plane * esz) e++;
-    HIP_TRY(c, hipMemcpyAsync(h_planes[s], st_planes + (size_t)s * plane * esz, (size_t)(e - s) * plane * esz, hipMemcpyDeviceToHost, c->d2h));
-    s = e;
-  }
-  for (int s = 0; s < b.n && !b.virt;) {
-    if (!b.h_mask[s]) { s++; continue; }
-    int e = s + 1;
-    while (e < b.n && b.h_mask[e] && (char*)b.h_mask[e] == (char*)b.h_mask[e - 1] + plane) e++;
-    HIP_TRY(c, hipMemcpyAsync(b.h_mask[s], b.st_mask + (size_t)s * plane, (size_t)(e - s) * plane, hipMemcpyDeviceToHost, c->d2h));
-    s = e;
-  }
-  if (b.labels) {
-    for (int s = 0; s < b.n;) {
-      int e = s + 1;
-      while (e < b.n && (char*)b.h_labels[e] == (char*)b.h_labels[e - 1] + plane * sizeof(uint16_t)) e++;
-      HIP_TRY(c, hipMemcpyAsync(b.h_labels[s], b.st_labels + (size_t)s * plane, (size_t)(e - s) * plane * sizeof(uint16_t), hipMemcpyDeviceToHost, c->d2h));
-      s = e;
-    }
-  }
+  if (rc == RTUF_OK && r.labels) rc = down(r.labels, b.h_labels, plane * sizeof(uint16_t));
+  if (rc != RTUF_OK) return rc;
   HIP_TRY(c, hipEventRecord(b.downloaded, c->d2h));
   return RTUF_OK;
 }
@@ -1827,15 +1843,15 @@ static int retire_oldest(rtuf_context* c)
         k.raster_atomics += sh.raster_atomics; k.drawn_pixels += sh.drawn_pixels;
       }
     }
-    group_streams = (b.n + b.n_groups - 1) / std::max(b.n_groups, 1);
+    group_streams = (b.rq.n + b.n_groups - 1) / std::max(b.n_groups, 1);
     c->items_hint = k.max_items;               // sizes the next batches' set-up grids (the longest list of this batch's groups ...
     c->items_hint_streams = group_streams;     // ... of so many streams each)
     c->group_items.resize((size_t)b.n_groups); c->group_streams.resize((size_t)b.n_groups);
     for (int g = 0; g < b.n_groups; g++) {
       c->group_items[(size_t)g] = b.h_counters[g].work.n_items;
-      c->group_streams[(size_t)g] = std::min(group_streams, b.n - g * group_streams);
+      c->group_streams[(size_t)g] = std::min(group_streams, b.rq.n - g * group_streams);
     }
-    c->stats.triangles_submitted = (uint64_t)c->n_tris * (uint64_t)b.n;
+    c->stats.triangles_submitted = (uint64_t)c->n_tris * (uint64_t)b.rq.n;
     c->stats.triangles_binned = k.tris_binned;
     c->stats.bin_entries = k.bin_entries;
     c->stats.triangles_clipped = k.clip_count;
@@ -1863,7 +1879,7 @@ static int retire_oldest(rtuf_context* c)
       if (b.timing && b.events.size() >= (size_t)(kEvGroup0 + kEvPerGroup * b.n_groups)) {
         // per launch group E0 .. E4 (see issue_plan).  With several lanes the kernels of different groups overlap: the sums
         // below add up per-launch durations, they are not wall time.
-        const bool two = ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && !b.bits && !b.virt && !b.resid) || b.dilation > 0 || b.cloud_points;
+        const bool two = fills_ms_compare(c, b);
         auto el = [&](size_t i, size_t j) { float ms = 0; hipEventElapsedTime(&ms, b.events[i], b.events[j]); return ms; };
         c->stats.ms_pose = c->stats.ms_setup = c->stats.ms_clip = c->stats.ms_raster = c->stats.ms_compare = c->stats.ms_total = 0;
         for (int g = 0; g < b.n_groups; g++) {
@@ -1898,11 +1914,11 @@ static int retire_oldest(rtuf_context* c)
       b.active = false;
       c->oldest = (c->oldest + 1) % kMaxInflight;
       c->pending--;
-      if (b.cloud_points && k.uncovered)
+      if (b.rq.kind == Kind::Cloud && k.uncovered)
         return c->fail(RTUF_ERR_STATE, "point cloud: a stream's background quad does not cover its whole image (non-standard projection), so the mask "
                                        "bits the cloud is built on are undefined there; there is no cloud form for this camera (filter with the "
                                        "full-plane calls and convert the masked plane)");
-      if (b.bits && k.uncovered)
+      if (b.rq.kind == Kind::Bits && k.uncovered)
         return c->fail(RTUF_ERR_STATE, "mask bits: a stream's background quad does not cover its whole image (non-standard projection), so "
                                        "masked depth != select(bit, replace, sensor) there; use the full-plane calls for this camera");
       return RTUF_OK;
@@ -1956,9 +1972,7 @@ static int retire_oldest(rtuf_context* c)
   return c->fail(RTUF_ERR_CAPACITY, "tile bins still overflow after regrowth");
 }
 
-// the batches of this context write the z-surface: two-kernel mode, or a silhouette dilation radius
-static bool uses_zsurface(const rtuf_context* c) { return (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 || c->params.silhouette_dilation_px > 0; }
-
+// ---- submission -----------------------------------------------------------------------
 // per-link depth thresholds exist in the fused route only: the z-surface does not carry the winning link
 static int check_thresh_route(rtuf_context* c)
 {
@@ -1967,60 +1981,89 @@ static int check_thresh_route(rtuf_context* c)
   return RTUF_OK;
 }
 
-// the outputs of a cloud batch (capacity 0: the organized form; index may be nullptr)
-struct CloudOut { float* points; uint32_t* index; uint32_t* counts; int capacity; };
+static int check_u16_width(rtuf_context* c, bool u16) { return u16 && (c->width & 3) ? c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4") : RTUF_OK; }
+// What every batch call checks first: the models are final, n is in range and the arrays the call cannot do without are there
+// (have_args) and -- u16: the filter calls; the kinds that test something of their own first call check_u16_width after it -- the 16UC1 width.
+static int check_batch_call(rtuf_context* c, int n, bool have_args, bool u16)
+{
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (n <= 0 || n > c->max_streams || !have_args) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
+  return check_u16_width(c, u16);
+}
 
-// d_virtual != nullptr: a render batch (d_depth, d_masked, d_mask, d_bits unused)
-// cloud != nullptr: a cloud batch (d_bits: the slot's own bits buffer; d_masked, d_mask unused)
-// d_resid != nullptr: a residual batch (d_masked, d_mask, d_bits, d_labels, d_virtual unused)
-static int submit_batch(rtuf_context* c, int n, const float* d_depth, float* d_masked, uint8_t* d_mask, bool u16, uint32_t* d_bits = nullptr,
-                        bool wait_upload = false, uint16_t* d_labels = nullptr, float* d_virtual = nullptr, float empty_value = 0.0f,
-                        rtuf_link_residuals* d_resid = nullptr, int n_labels = 0, const CloudOut* cloud = nullptr)
+// The slot of the next batch: once the ring has room for it (the oldest batches are retired as needed), the one behind the
+// newest batch in flight.  Called once per batch, before anything of the slot is touched.
+static int take_slot(rtuf_context* c, rtuf_context::Batch*& slot)
 {
   if (c->broken) return c->fail(RTUF_ERR_STATE, "context unusable: a bin regrowth failed (%s)", c->error.c_str());
-  if (!d_virtual && !d_resid && !cloud) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
   hipSetDevice(c->device);
-  if (uses_zsurface(c) && !d_virtual && !d_resid)
-    for (int l = 0; l < c->n_lanes; l++)
-      if (!c->lane[l].d_zsurface) HIP_TRY(c, dev_alloc(c, &c->lane[l].d_zsurface, (size_t)c->group * c->width * c->height * sizeof(float)));
   // two-kernel mode and silhouette dilation keep one z-surface per lane: their batches do not overlap
   const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
   while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
-  rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];
-  b.n = n; b.depth = d_depth; b.masked = d_masked; b.mask = d_mask; b.u16 = u16; b.host_io = false; b.bits = d_bits; b.labels = d_labels;
-  b.virt = d_virtual; b.empty_value = empty_value;
-  b.resid = d_resid; b.n_labels = n_labels;
-  b.cloud_points = cloud ? cloud->points : nullptr; b.cloud_index = cloud ? cloud->index : nullptr; b.cloud_counts = cloud ? cloud->counts : nullptr;
-  b.cloud_capacity = cloud ? cloud->capacity : 0;
-  b.wait_upload = wait_upload;
+  slot = &c->batch[(c->oldest + c->pending) % kMaxInflight];
+  return RTUF_OK;
+}
+
+// Enqueues the request in the slot take_slot gave: the slot keeps the record, and is in flight when this returns RTUF_OK.  A
+// cloud batch gets the slot's own bits buffer and row scratch here.
+static int submit_batch(rtuf_context* c, rtuf_context::Batch& b, const BatchRequest& rq)
+{
+  if (rq.kind == Kind::Cloud) {
+    if (!b.cl_bits) HIP_TRY(c, dev_alloc(c, &b.cl_bits, (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
+    if (rq.capacity && !b.cl_rows) HIP_TRY(c, dev_alloc(c, &b.cl_rows, 2u * (size_t)c->max_streams * (size_t)c->height * sizeof(uint32_t)));
+  }
+  if (uses_zsurface(c) && may_write_zsurface(rq))
+    for (int l = 0; l < c->n_lanes; l++)
+      if (!c->lane[l].d_zsurface) HIP_TRY(c, dev_alloc(c, &c->lane[l].d_zsurface, (size_t)c->group * c->width * c->height * sizeof(float)));
+  b.rq = rq;
+  if (rq.kind == Kind::Cloud) b.rq.bits = b.cl_bits;
+  b.host_io = false;
   const int rc = enqueue_batch(c, b, false);
   if (rc == RTUF_OK) { b.active = true; c->pending++; }
   return rc;
+}
+
+// a batch on the caller's device buffers
+static int submit_device(rtuf_context* c, const BatchRequest& rq)
+{
+  if (subject_to_thresh_route(rq)) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
+  rtuf_context::Batch* b = nullptr;
+  const int rc = take_slot(c, b);
+  return rc != RTUF_OK ? rc : submit_batch(c, *b, rq);
+}
+
+static BatchRequest filter_request(int n, const void* d_depth, void* d_masked, uint8_t* d_mask, uint16_t* d_labels, bool u16)
+{
+  BatchRequest rq(Kind::Filter, n, u16);
+  rq.depth = static_cast<const float*>(d_depth); rq.masked = static_cast<float*>(d_masked); rq.mask = d_mask; rq.labels = d_labels;
+  return rq;
+}
+static BatchRequest bits_request(int n, const void* d_depth, uint32_t* d_bits, bool u16)
+{
+  BatchRequest rq(Kind::Bits, n, u16);
+  rq.depth = static_cast<const float*>(d_depth); rq.bits = d_bits;
+  return rq;
 }
 
 int rtuf_filter_batch_device(rtuf_context* c, int n, const float* d_depth, float* d_masked, uint8_t* d_mask)
 {
   KIDS_NEXT(c, rtuf_filter_batch_device(k, n, d_depth, d_masked, d_mask));
   if (!c) return RTUF_ERR_INVALID;
-  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
-  if (n <= 0 || n > c->max_streams || !d_depth || !d_masked) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
-  return submit_batch(c, n, d_depth, d_masked, d_mask, false);
+  const int rc = check_batch_call(c, n, d_depth && d_masked, false);
+  return rc != RTUF_OK ? rc : submit_device(c, filter_request(n, d_depth, d_masked, d_mask, nullptr, false));
 }
 
 int rtuf_filter_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth, uint16_t* d_masked, uint8_t* d_mask)
 {
   KIDS_NEXT(c, rtuf_filter_batch_device_u16(k, n, d_depth, d_masked, d_mask));
   if (!c) return RTUF_ERR_INVALID;
-  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
-  if (n <= 0 || n > c->max_streams || !d_depth || !d_masked) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
-  if (c->width & 3) return c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4");
-  return submit_batch(c, n, reinterpret_cast<const float*>(d_depth), reinterpret_cast<float*>(d_masked), d_mask, true);
+  const int rc = check_batch_call(c, n, d_depth && d_masked, true);
+  return rc != RTUF_OK ? rc : submit_device(c, filter_request(n, d_depth, d_masked, d_mask, nullptr, true));
 }
 
 static int check_bits_call(rtuf_context* c, int n, const void* in, const void* out)
 {
-  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
-  if (n <= 0 || n > c->max_streams || !in || !out) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
+  { const int rc = check_batch_call(c, n, in && out, false); if (rc != RTUF_OK) return rc; }
   if (c->width & 3) return c->fail(RTUF_ERR_INVALID, "mask-bits output needs a width that is a multiple of 4");
   if (c->params.flags & RTUF_FLAG_TWO_KERNEL) return c->fail(RTUF_ERR_INVALID, "mask-bits output exists in fused mode only (RTUF_FLAG_TWO_KERNEL is set)");
   return RTUF_OK;
@@ -2036,7 +2079,7 @@ int rtuf_filter_batch_device_bits(rtuf_context* c, int n, const float* d_depth, 
   KIDS_NEXT(c, rtuf_filter_batch_device_bits(k, n, d_depth, d_bits));
   if (!c) return RTUF_ERR_INVALID;
   const int rc = check_bits_call(c, n, d_depth, d_bits);
-  return rc != RTUF_OK ? rc : submit_batch(c, n, d_depth, nullptr, nullptr, false, d_bits);
+  return rc != RTUF_OK ? rc : submit_device(c, bits_request(n, d_depth, d_bits, false));
 }
 
 int rtuf_filter_batch_device_bits_u16(rtuf_context* c, int n, const uint16_t* d_depth, uint32_t* d_bits)
@@ -2044,7 +2087,7 @@ int rtuf_filter_batch_device_bits_u16(rtuf_context* c, int n, const uint16_t* d_
   KIDS_NEXT(c, rtuf_filter_batch_device_bits_u16(k, n, d_depth, d_bits));
   if (!c) return RTUF_ERR_INVALID;
   const int rc = check_bits_call(c, n, d_depth, d_bits);
-  return rc != RTUF_OK ? rc : submit_batch(c, n, reinterpret_cast<const float*>(d_depth), nullptr, nullptr, true, d_bits);
+  return rc != RTUF_OK ? rc : submit_device(c, bits_request(n, d_depth, d_bits, true));
 }
 
 // Host side of the mask-bits calls: masked depth / byte mask of one frame from its sensor plane and its mask bits,
@@ -2145,90 +2188,117 @@ static int ensure_copy_streams(rtuf_context* c)
   return RTUF_OK;
 }
 
-// the slot's device staging of the sensor planes and -- with_outputs: not for a residual batch, which writes no plane -- of
-// the filter's outputs, for n streams
-static int ensure_plane_staging(rtuf_context* c, rtuf_context::Batch& b, int n, bool with_outputs)
+// grow-only device staging of a slot: *ptr holds `have` units of bytes_per bytes and is replaced when `need` are asked for
+static int ensure_staging(rtuf_context* c, char*& ptr, size_t& have, size_t need, size_t bytes_per)
 {
-  const size_t plane = (size_t)c->width * c->height;
-  if (b.st_depth_streams < (size_t)n) {
-    dev_free(c, b.st_depth);
-    b.st_depth_streams = 0;
-    HIP_TRY(c, dev_alloc(c, &b.st_depth, (size_t)n * plane * sizeof(float)));     // float-sized: large enough for uint16 planes
-    b.st_depth_streams = (size_t)n;
-  }
-  if (with_outputs && b.st_streams < (size_t)n) {
-    dev_free(c, b.st_masked); dev_free(c, b.st_mask);
-    b.st_streams = 0;
-    HIP_TRY(c, dev_alloc(c, &b.st_masked, (size_t)n * plane * sizeof(float)));
-    HIP_TRY(c, dev_alloc(c, &b.st_mask, (size_t)n * plane));
-    b.st_streams = (size_t)n;
+  if (have >= need) return RTUF_OK;
+  dev_free(c, ptr);
+  have = 0;
+  HIP_TRY(c, dev_alloc(c, &ptr, need * bytes_per));
+  have = need;
+  return RTUF_OK;
+}
+
+// The caller's side of a host-plane batch: n host pointers per array, nullptr for what the kind or the call does not have.
+struct HostPlanes {
+  const void* const* depth;          // sensor planes: go up (not Render)
+  void* const* out;                  // masked / bits / virtual / points planes
+  void* const* mask;                 // Filter: byte masks (nullptr, or any entry nullptr: not wanted)
+  void* const* labels;               // Filter, Render
+  void* const* index; uint32_t* counts;      // compacted Cloud
+  rtuf_link_residuals* table;        // Residual
+};
+
+// the results of a host-plane cloud batch, synchronous: once the batch is retired -- re-runs included -- the organized planes
+// come down whole; the compacted forms bring the counts down first and then only min(counts, capacity) entries per stream
+static int download_cloud(rtuf_context* c, const BatchRequest& r, const HostPlanes& hp)
+{
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  const size_t per = r.capacity ? (size_t)r.capacity : (size_t)c->width * c->height;      // entries per stream
+  if (!r.capacity) return copy_planes(c, r.points, hp.out, r.n, per * 3u * sizeof(float), hipMemcpyDeviceToHost, nullptr);
+  HIP_TRY(c, hipMemcpy(hp.counts, r.counts, (size_t)r.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (int s = 0; s < r.n; s++) {
+    const size_t m = std::min<size_t>(hp.counts[s], per);
+    if (!m) continue;
+    HIP_TRY(c, hipMemcpy(hp.out[s], r.points + (size_t)s * per * 3u, m * 3u * sizeof(float), hipMemcpyDeviceToHost));
+    if (hp.index) HIP_TRY(c, hipMemcpy(hp.index[s], r.index + (size_t)s * per, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
   }
   return RTUF_OK;
 }
 
-// the sensor planes go up on the upload stream (consecutive planes as one transfer); `uploaded` marks their arrival
-static int upload_planes(rtuf_context* c, rtuf_context::Batch& b, int n, const void* const* depth_in, bool u16)
+// A batch of any kind on the caller's host planes: the slot's staging grows to the batch, the sensor planes go up on the upload
+// stream (`uploaded`: the lanes' first kernels wait for it, enqueue_batch), the request -- it arrives with kind and scalars -- is
+// pointed at the staging and submitted, and the results come back on the download stream (`downloaded`), the clouds synchronously.
+static int submit_host_planes(rtuf_context* c, BatchRequest rq, const HostPlanes& hp)
 {
-  const size_t plane = (size_t)c->width * c->height;
-  if (!b.uploaded) HIP_TRY(c, hipEventCreateWithFlags(&b.uploaded, hipEventDisableTiming));
-  if (!b.downloaded) HIP_TRY(c, hipEventCreateWithFlags(&b.downloaded, hipEventDisableTiming));
-  const size_t esz = u16 ? sizeof(uint16_t) : sizeof(float);
-  for (int s = 0; s < n;) {
-    int e = s + 1;
-    while (e < n && (const char*)depth_in[e] == (const char*)depth_in[e - 1] + plane * esz) e++;
-    HIP_TRY(c, hipMemcpyAsync((char*)b.st_depth + (size_t)s * plane * esz, depth_in[s], (size_t)(e - s) * plane * esz, hipMemcpyHostToDevice, c->h2d));
-    s = e;
-  }
-  HIP_TRY(c, hipEventRecord(b.uploaded, c->h2d));          // (the lanes' first kernels wait for it: enqueue_batch)
-  return RTUF_OK;
-}
-
-static int submit_host_batch(rtuf_context* c, int n, const void* const* depth_in, void* const* masked_out,
-                             void* const* mask_out, bool u16, uint32_t* const* bits_out = nullptr, uint16_t* const* labels_out = nullptr)
-{
-  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
-  if (n <= 0 || n > c->max_streams || !depth_in || (!masked_out && !bits_out)) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
-  if (u16 && (c->width & 3)) return c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4");
-  if (bits_out) { const int rc = check_bits_call(c, n, depth_in, bits_out); if (rc != RTUF_OK) return rc; }
+  using B = rtuf_context::Batch;
+  const int n = rq.n;
   for (int s = 0; s < n; s++)
-    if (!depth_in[s] || (bits_out ? !bits_out[s] : !masked_out[s]) || (labels_out && !labels_out[s])) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
-  { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }      // (before the planes are staged)
-  hipSetDevice(c->device);
+    if ((hp.depth && !hp.depth[s]) || (hp.out && !hp.out[s]) || (hp.labels && !hp.labels[s]) || (hp.index && !hp.index[s]))
+      return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
+  if (subject_to_thresh_route(rq)) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }      // (before the planes are staged)
+  B* slot = nullptr;
+  { const int rc = take_slot(c, slot); if (rc != RTUF_OK) return rc; }
+  B& b = *slot;
   { const int rc = ensure_copy_streams(c); if (rc != RTUF_OK) return rc; }
-  const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
-  while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
-  rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];     // the slot submit_batch takes next
   const size_t plane = (size_t)c->width * c->height;
-  { const int rc = ensure_plane_staging(c, b, n, true); if (rc != RTUF_OK) return rc; }
-  if (bits_out && b.st_bits_streams < (size_t)n) {
-    dev_free(c, b.st_bits);
-    b.st_bits_streams = 0;
-    HIP_TRY(c, dev_alloc(c, &b.st_bits, (size_t)n * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
-    b.st_bits_streams = (size_t)n;
+  const size_t per = rq.capacity ? (size_t)rq.capacity : plane;      // cloud entries per stream
+  // what the kind stages, in units of `bytes`; 0 units: not staged.  (A mask-bits batch stages masked / mask planes it never
+  // writes, as it always has: rtuf_stats.device_bytes counts them, and the masked pointer is in its argument blocks.)
+  const bool planes_out = rq.kind == Kind::Filter || rq.kind == Kind::Bits, cloud = rq.kind == Kind::Cloud;
+  const struct { int st; size_t need, bytes; } staged[] = {
+    {B::kStDepth, hp.depth ? (size_t)n : 0, plane * sizeof(float)},
+    {B::kStMasked, planes_out ? (size_t)n : 0, plane * sizeof(float)}, {B::kStMask, planes_out ? (size_t)n : 0, plane},
+    {B::kStBits, rq.kind == Kind::Bits ? (size_t)n : 0, rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)},
+    {B::kStVirtual, rq.kind == Kind::Render ? (size_t)n : 0, plane * sizeof(float)},
+    {B::kStLabels, hp.labels ? (size_t)n : 0, plane * sizeof(uint16_t)},
+    {B::kStTable, rq.kind == Kind::Residual ? (size_t)n * (size_t)rq.n_labels : 0, sizeof(rtuf_link_residuals)},
+    {B::kStPoints, cloud ? (size_t)n * per * 3u : 0, sizeof(float)}, {B::kStIndex, hp.index ? (size_t)n * per : 0, sizeof(uint32_t)}};
+  for (const auto& s : staged) { const int rc = ensure_staging(c, b.st[s.st].p, b.st[s.st].have, s.need, s.bytes); if (rc != RTUF_OK) return rc; }
+  if (cloud && rq.capacity && !b.st_counts) HIP_TRY(c, dev_alloc(c, &b.st_counts, (size_t)c->max_streams * sizeof(uint32_t)));
+  if (hp.depth && !b.uploaded) HIP_TRY(c, hipEventCreateWithFlags(&b.uploaded, hipEventDisableTiming));
+  if (!b.downloaded) HIP_TRY(c, hipEventCreateWithFlags(&b.downloaded, hipEventDisableTiming));
+  if (hp.depth) {
+    const int rc = copy_planes(c, b.st[B::kStDepth].p, const_cast<void* const*>(hp.depth), n, plane * (rq.u16 ? sizeof(uint16_t) : sizeof(float)), hipMemcpyHostToDevice, &c->h2d);
+    if (rc != RTUF_OK) return rc;
+    HIP_TRY(c, hipEventRecord(b.uploaded, c->h2d));
+    rq.depth = reinterpret_cast<const float*>(b.st[B::kStDepth].p); rq.wait_upload = true;
   }
-  if (labels_out && b.st_labels_streams < (size_t)n) {
-    dev_free(c, b.st_labels);
-    b.st_labels_streams = 0;
-    HIP_TRY(c, dev_alloc(c, &b.st_labels, (size_t)n * plane * sizeof(uint16_t)));
-    b.st_labels_streams = (size_t)n;
-  }
-  { const int rc = upload_planes(c, b, n, depth_in, u16); if (rc != RTUF_OK) return rc; }
+  // the caller's arrays may be gone when a re-run downloads again: the slot keeps the pointers
   bool any_mask = false;
-  b.h_bits.clear();
-  b.h_labels.clear();
-  if (labels_out) b.h_labels.assign(reinterpret_cast<void* const*>(labels_out), reinterpret_cast<void* const*>(labels_out) + n);
-  if (bits_out) {
-    b.h_bits.assign(reinterpret_cast<void* const*>(bits_out), reinterpret_cast<void* const*>(bits_out) + n);
-  } else {
-    b.h_masked.assign(masked_out, masked_out + n);
-    b.h_mask.assign((size_t)n, nullptr);
-    if (mask_out) for (int s = 0; s < n; s++) { b.h_mask[s] = mask_out[s]; any_mask |= mask_out[s] != nullptr; }
+  b.h_out.clear(); b.h_labels.clear();
+  if (hp.out) b.h_out.assign(hp.out, hp.out + n);
+  if (hp.labels) b.h_labels.assign(hp.labels, hp.labels + n);
+  b.h_mask.assign((size_t)n, nullptr);
+  if (hp.mask) for (int s = 0; s < n; s++) { b.h_mask[s] = hp.mask[s]; any_mask |= hp.mask[s] != nullptr; }
+  b.h_table = hp.table;
+  auto at = [&](int st) { return b.st[st].p; };
+  if (hp.labels) rq.labels = reinterpret_cast<uint16_t*>(at(B::kStLabels));
+  switch (rq.kind) {
+    case Kind::Filter: rq.masked = reinterpret_cast<float*>(at(B::kStMasked)); rq.mask = any_mask ? reinterpret_cast<uint8_t*>(at(B::kStMask)) : nullptr; break;
+    case Kind::Bits: rq.bits = reinterpret_cast<uint32_t*>(at(B::kStBits)); rq.masked = reinterpret_cast<float*>(at(B::kStMasked)); break;      // (masked: unused, but part of the argument blocks since the first mask-bits call)
+    case Kind::Render: rq.virt = reinterpret_cast<float*>(at(B::kStVirtual)); break;
+    case Kind::Residual: rq.resid = reinterpret_cast<rtuf_link_residuals*>(at(B::kStTable)); break;
+    case Kind::Cloud:
+      rq.points = reinterpret_cast<float*>(at(B::kStPoints));
+      rq.index = hp.index ? reinterpret_cast<uint32_t*>(at(B::kStIndex)) : nullptr; rq.counts = rq.capacity ? b.st_counts : nullptr;
+      break;
   }
-  int rc = submit_batch(c, n, b.st_depth, b.st_masked, any_mask ? b.st_mask : nullptr, u16, bits_out ? b.st_bits : nullptr, true,
-                        labels_out ? b.st_labels : nullptr);
-  if (rc != RTUF_OK) return rc;
+  { const int rc = submit_batch(c, b, rq); if (rc != RTUF_OK) return rc; }
+  if (cloud) return download_cloud(c, rq, hp);
   b.host_io = true;
   return enqueue_download(c, b);
+}
+
+// the filter and mask-bits calls on host planes (out: masked planes or bits; labels_out may be nullptr)
+static int filter_host_planes(rtuf_context* c, Kind kind, int n, const void* const* depth_in, void* const* out, void* const* mask_out,
+                              uint16_t* const* labels_out, bool u16)
+{
+  { const int rc = check_batch_call(c, n, depth_in && out, u16); if (rc != RTUF_OK) return rc; }
+  if (kind == Kind::Bits) { const int rc = check_bits_call(c, n, depth_in, out); if (rc != RTUF_OK) return rc; }
+  HostPlanes hp{};
+  hp.depth = depth_in; hp.out = out; hp.mask = mask_out; hp.labels = reinterpret_cast<void* const*>(labels_out);
+  return submit_host_planes(c, BatchRequest(kind, n, u16), hp);
 }
 
 int rtuf_filter_batch_async(rtuf_context* c, int n, const float* const* depth_in, float* const* masked_out,
@@ -2236,8 +2306,8 @@ int rtuf_filter_batch_async(rtuf_context* c, int n, const float* const* depth_in
 {
   KIDS_NEXT(c, rtuf_filter_batch_async(k, n, depth_in, masked_out, mask_out));
   if (!c) return RTUF_ERR_INVALID;
-  return submit_host_batch(c, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(masked_out),
-                           reinterpret_cast<void* const*>(mask_out), false);
+  return filter_host_planes(c, Kind::Filter, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(masked_out),
+                            reinterpret_cast<void* const*>(mask_out), nullptr, false);
 }
 
 int rtuf_filter_batch_u16_async(rtuf_context* c, int n, const uint16_t* const* depth_in, uint16_t* const* masked_out,
@@ -2245,22 +2315,22 @@ int rtuf_filter_batch_u16_async(rtuf_context* c, int n, const uint16_t* const* d
 {
   KIDS_NEXT(c, rtuf_filter_batch_u16_async(k, n, depth_in, masked_out, mask_out));
   if (!c) return RTUF_ERR_INVALID;
-  return submit_host_batch(c, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(masked_out),
-                           reinterpret_cast<void* const*>(mask_out), true);
+  return filter_host_planes(c, Kind::Filter, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(masked_out),
+                            reinterpret_cast<void* const*>(mask_out), nullptr, true);
 }
 
 int rtuf_filter_batch_bits_async(rtuf_context* c, int n, const float* const* depth_in, uint32_t* const* bits_out)
 {
   KIDS_NEXT(c, rtuf_filter_batch_bits_async(k, n, depth_in, bits_out));
   if (!c) return RTUF_ERR_INVALID;
-  return submit_host_batch(c, n, reinterpret_cast<const void* const*>(depth_in), nullptr, nullptr, false, bits_out);
+  return filter_host_planes(c, Kind::Bits, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(bits_out), nullptr, nullptr, false);
 }
 
 int rtuf_filter_batch_bits_u16_async(rtuf_context* c, int n, const uint16_t* const* depth_in, uint32_t* const* bits_out)
 {
   KIDS_NEXT(c, rtuf_filter_batch_bits_u16_async(k, n, depth_in, bits_out));
   if (!c) return RTUF_ERR_INVALID;
-  return submit_host_batch(c, n, reinterpret_cast<const void* const*>(depth_in), nullptr, nullptr, true, bits_out);
+  return filter_host_planes(c, Kind::Bits, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(bits_out), nullptr, nullptr, true);
 }
 
 int rtuf_filter_batch(rtuf_context* c, int n, const float* const* depth_in, float* const* masked_out,
@@ -2324,8 +2394,7 @@ int rtuf_set_link_labels(rtuf_context* c, int model, const uint16_t* labels, int
 
 static int check_labels_call(rtuf_context* c, int n, const void* in, const void* out, const void* labels)
 {
-  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
-  if (n <= 0 || n > c->max_streams || !in || !out || !labels) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
+  { const int rc = check_batch_call(c, n, in && out && labels, false); if (rc != RTUF_OK) return rc; }
   if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "link labels are not supported with silhouette dilation yet");
   return ensure_label_table(c);
 }
@@ -2335,17 +2404,16 @@ int rtuf_filter_batch_device_labels(rtuf_context* c, int n, const float* d_depth
   KIDS_NEXT(c, rtuf_filter_batch_device_labels(k, n, d_depth, d_masked, d_mask, d_labels));
   if (!c) return RTUF_ERR_INVALID;
   const int rc = check_labels_call(c, n, d_depth, d_masked, d_labels);
-  return rc != RTUF_OK ? rc : submit_batch(c, n, d_depth, d_masked, d_mask, false, nullptr, false, d_labels);
+  return rc != RTUF_OK ? rc : submit_device(c, filter_request(n, d_depth, d_masked, d_mask, d_labels, false));
 }
 
 int rtuf_filter_batch_device_u16_labels(rtuf_context* c, int n, const uint16_t* d_depth, uint16_t* d_masked, uint8_t* d_mask, uint16_t* d_labels)
 {
   KIDS_NEXT(c, rtuf_filter_batch_device_u16_labels(k, n, d_depth, d_masked, d_mask, d_labels));
   if (!c) return RTUF_ERR_INVALID;
-  const int rc = check_labels_call(c, n, d_depth, d_masked, d_labels);
-  if (rc != RTUF_OK) return rc;
-  if (c->width & 3) return c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4");
-  return submit_batch(c, n, reinterpret_cast<const float*>(d_depth), reinterpret_cast<float*>(d_masked), d_mask, true, nullptr, false, d_labels);
+  int rc = check_labels_call(c, n, d_depth, d_masked, d_labels);
+  if (rc == RTUF_OK) rc = check_u16_width(c, true);
+  return rc != RTUF_OK ? rc : submit_device(c, filter_request(n, d_depth, d_masked, d_mask, d_labels, true));
 }
 
 static int filter_batch_labels_async(rtuf_context* c, int n, const void* const* depth_in, void* const* masked_out, uint8_t* const* mask_out,
@@ -2354,7 +2422,7 @@ static int filter_batch_labels_async(rtuf_context* c, int n, const void* const* 
   KIDS_NEXT(c, filter_batch_labels_async(k, n, depth_in, masked_out, mask_out, labels_out, u16));
   if (!c) return RTUF_ERR_INVALID;
   const int rc = check_labels_call(c, n, depth_in, masked_out, labels_out);
-  return rc != RTUF_OK ? rc : submit_host_batch(c, n, depth_in, masked_out, reinterpret_cast<void* const*>(mask_out), u16, nullptr, labels_out);
+  return rc != RTUF_OK ? rc : filter_host_planes(c, Kind::Filter, n, depth_in, masked_out, reinterpret_cast<void* const*>(mask_out), labels_out, u16);
 }
 
 int rtuf_filter_batch_labels(rtuf_context* c, int n, const float* const* depth_in, float* const* masked_out, uint8_t* const* mask_out,
@@ -2434,15 +2502,21 @@ int rtuf_clear_link_thresholds(rtuf_context* c, int model)
 }
 
 // ---- virtual depth ---------------------------------------------------------------------------------
-// A render batch is a batch like any other (submit_batch) whose tile kernel stores the winners' virtual depth instead of
+// A render batch is a batch like any other (Kind::Render) whose tile kernel stores the winners' virtual depth instead of
 // comparing a sensor plane with it.  Parameters of the compare do not enter, and the z-surface is never used.
 static int check_render_call(rtuf_context* c, int n, const void* out, bool want_labels, bool u16)
 {
-  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
-  if (n <= 0 || n > c->max_streams || !out) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
+  { const int rc = check_batch_call(c, n, out != nullptr, false); if (rc != RTUF_OK) return rc; }
   if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "virtual depth is not supported with silhouette dilation yet");
-  if (u16 && (c->width & 3)) return c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4");
+  { const int rc = check_u16_width(c, u16); if (rc != RTUF_OK) return rc; }
   return want_labels ? ensure_label_table(c) : RTUF_OK;
+}
+
+static BatchRequest render_request(int n, void* d_virtual, uint16_t* d_labels, float empty_value, bool u16)
+{
+  BatchRequest rq(Kind::Render, n, u16);
+  rq.virt = static_cast<float*>(d_virtual); rq.labels = d_labels; rq.empty_value = empty_value;
+  return rq;
 }
 
 int rtuf_render_batch_device(rtuf_context* c, int n, float* d_virtual, uint16_t* d_labels, float empty_value)
@@ -2450,7 +2524,7 @@ int rtuf_render_batch_device(rtuf_context* c, int n, float* d_virtual, uint16_t*
   KIDS_NEXT(c, rtuf_render_batch_device(k, n, d_virtual, d_labels, empty_value));
   if (!c) return RTUF_ERR_INVALID;
   const int rc = check_render_call(c, n, d_virtual, d_labels != nullptr, false);
-  return rc != RTUF_OK ? rc : submit_batch(c, n, nullptr, nullptr, nullptr, false, nullptr, false, d_labels, d_virtual, empty_value);
+  return rc != RTUF_OK ? rc : submit_device(c, render_request(n, d_virtual, d_labels, empty_value, false));
 }
 
 int rtuf_render_batch_device_u16(rtuf_context* c, int n, uint16_t* d_virtual, uint16_t* d_labels, float empty_value)
@@ -2458,7 +2532,7 @@ int rtuf_render_batch_device_u16(rtuf_context* c, int n, uint16_t* d_virtual, ui
   KIDS_NEXT(c, rtuf_render_batch_device_u16(k, n, d_virtual, d_labels, empty_value));
   if (!c) return RTUF_ERR_INVALID;
   const int rc = check_render_call(c, n, d_virtual, d_labels != nullptr, true);
-  return rc != RTUF_OK ? rc : submit_batch(c, n, nullptr, nullptr, nullptr, true, nullptr, false, d_labels, reinterpret_cast<float*>(d_virtual), empty_value);
+  return rc != RTUF_OK ? rc : submit_device(c, render_request(n, d_virtual, d_labels, empty_value, true));
 }
 
 // host planes: the batch renders into the slot's device staging, the planes come back on the download stream
@@ -2467,34 +2541,11 @@ static int render_batch_async(rtuf_context* c, int n, void* const* virtual_out, 
   KIDS_NEXT(c, render_batch_async(k, n, virtual_out, labels_out, empty_value, u16));
   if (!c) return RTUF_ERR_INVALID;
   { const int rc = check_render_call(c, n, virtual_out, labels_out != nullptr, u16); if (rc != RTUF_OK) return rc; }
-  for (int s = 0; s < n; s++)
-    if (!virtual_out[s] || (labels_out && !labels_out[s])) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
-  hipSetDevice(c->device);
-  { const int rc = ensure_copy_streams(c); if (rc != RTUF_OK) return rc; }
-  const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
-  while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
-  rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];     // the slot submit_batch takes next
-  const size_t plane = (size_t)c->width * c->height;
-  if (b.st_virtual_streams < (size_t)n) {
-    dev_free(c, b.st_virtual);
-    b.st_virtual_streams = 0;
-    HIP_TRY(c, dev_alloc(c, &b.st_virtual, (size_t)n * plane * sizeof(float)));
-    b.st_virtual_streams = (size_t)n;
-  }
-  if (labels_out && b.st_labels_streams < (size_t)n) {
-    dev_free(c, b.st_labels);
-    b.st_labels_streams = 0;
-    HIP_TRY(c, dev_alloc(c, &b.st_labels, (size_t)n * plane * sizeof(uint16_t)));
-    b.st_labels_streams = (size_t)n;
-  }
-  if (!b.downloaded) HIP_TRY(c, hipEventCreateWithFlags(&b.downloaded, hipEventDisableTiming));
-  b.h_virtual.assign(virtual_out, virtual_out + n);
-  b.h_labels.clear();
-  if (labels_out) b.h_labels.assign(reinterpret_cast<void* const*>(labels_out), reinterpret_cast<void* const*>(labels_out) + n);
-  const int rc = submit_batch(c, n, nullptr, nullptr, nullptr, u16, nullptr, false, labels_out ? b.st_labels : nullptr, b.st_virtual, empty_value);
-  if (rc != RTUF_OK) return rc;
-  b.host_io = true;
-  return enqueue_download(c, b);
+  BatchRequest rq(Kind::Render, n, u16);
+  rq.empty_value = empty_value;
+  HostPlanes hp{};
+  hp.out = virtual_out; hp.labels = reinterpret_cast<void* const*>(labels_out);
+  return submit_host_planes(c, rq, hp);
 }
 
 int rtuf_render_batch(rtuf_context* c, int n, float* const* virtual_out, uint16_t* const* labels_out, float empty_value)
@@ -2510,19 +2561,25 @@ int rtuf_render_batch_u16(rtuf_context* c, int n, uint16_t* const* virtual_out, 
 }
 
 // ---- link residual tables ----------------------------------------------------------------------------
-// A residual batch is a batch like any other (submit_batch) whose tile kernel stores no plane: it classifies every pixel
+// A residual batch is a batch like any other (Kind::Residual) whose tile kernel stores no plane: it classifies every pixel
 // against the sensor plane and sums the classes per label into the caller's table.  Per-link thresholds are honoured, the
 // two-kernel flag and the replace value do not enter, and the z-surface is never used.
 static int check_residuals_call(rtuf_context* c, int n, const void* in, const void* table, int n_labels, bool u16)
 {
-  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
-  if (n <= 0 || n > c->max_streams || !in || !table) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
+  { const int rc = check_batch_call(c, n, in && table, false); if (rc != RTUF_OK) return rc; }
   if (n_labels < 1) return c->fail(RTUF_ERR_INVALID, "a residual table needs at least one row per stream (n_labels=%d)", n_labels);
   if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "link residual tables are not supported with silhouette dilation yet");
-  if (u16 && (c->width & 3)) return c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4");
+  { const int rc = check_u16_width(c, u16); if (rc != RTUF_OK) return rc; }
   { const int rc = ensure_label_table(c); if (rc != RTUF_OK) return rc; }
   if (c->max_label >= (uint32_t)n_labels) return c->fail(RTUF_ERR_INVALID, "a link has label %u: the table needs n_labels > %u (got %d)", c->max_label, c->max_label, n_labels);
   return RTUF_OK;
+}
+
+static BatchRequest residual_request(int n, const void* d_depth, rtuf_link_residuals* d_table, int n_labels, bool u16)
+{
+  BatchRequest rq(Kind::Residual, n, u16);
+  rq.depth = static_cast<const float*>(d_depth); rq.resid = d_table; rq.n_labels = n_labels;
+  return rq;
 }
 
 int rtuf_link_residuals_batch_device(rtuf_context* c, int n, const float* d_depth, rtuf_link_residuals* d_table, int n_labels)
@@ -2530,7 +2587,7 @@ int rtuf_link_residuals_batch_device(rtuf_context* c, int n, const float* d_dept
   KIDS_NEXT(c, rtuf_link_residuals_batch_device(k, n, d_depth, d_table, n_labels));
   if (!c) return RTUF_ERR_INVALID;
   const int rc = check_residuals_call(c, n, d_depth, d_table, n_labels, false);
-  return rc != RTUF_OK ? rc : submit_batch(c, n, d_depth, nullptr, nullptr, false, nullptr, false, nullptr, nullptr, 0.0f, d_table, n_labels);
+  return rc != RTUF_OK ? rc : submit_device(c, residual_request(n, d_depth, d_table, n_labels, false));
 }
 
 int rtuf_link_residuals_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth, rtuf_link_residuals* d_table, int n_labels)
@@ -2538,7 +2595,7 @@ int rtuf_link_residuals_batch_device_u16(rtuf_context* c, int n, const uint16_t*
   KIDS_NEXT(c, rtuf_link_residuals_batch_device_u16(k, n, d_depth, d_table, n_labels));
   if (!c) return RTUF_ERR_INVALID;
   const int rc = check_residuals_call(c, n, d_depth, d_table, n_labels, true);
-  return rc != RTUF_OK ? rc : submit_batch(c, n, reinterpret_cast<const float*>(d_depth), nullptr, nullptr, true, nullptr, false, nullptr, nullptr, 0.0f, d_table, n_labels);
+  return rc != RTUF_OK ? rc : submit_device(c, residual_request(n, d_depth, d_table, n_labels, true));
 }
 
 // host planes: planes up into the slot's staging, the table back from its device copy on the download stream
@@ -2547,27 +2604,11 @@ static int link_residuals_batch_async(rtuf_context* c, int n, const void* const*
   KIDS_NEXT(c, link_residuals_batch_async(k, n, depth_in, table_out, n_labels, u16));
   if (!c) return RTUF_ERR_INVALID;
   { const int rc = check_residuals_call(c, n, depth_in, table_out, n_labels, u16); if (rc != RTUF_OK) return rc; }
-  for (int s = 0; s < n; s++)
-    if (!depth_in[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
-  hipSetDevice(c->device);
-  { const int rc = ensure_copy_streams(c); if (rc != RTUF_OK) return rc; }
-  const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
-  while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
-  rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];     // the slot submit_batch takes next
-  { const int rc = ensure_plane_staging(c, b, n, false); if (rc != RTUF_OK) return rc; }
-  const size_t rows = (size_t)n * (size_t)n_labels;
-  if (b.st_table_rows < rows) {
-    dev_free(c, b.st_table);
-    b.st_table_rows = 0;
-    HIP_TRY(c, dev_alloc(c, &b.st_table, rows * sizeof(rtuf_link_residuals)));
-    b.st_table_rows = rows;
-  }
-  { const int rc = upload_planes(c, b, n, depth_in, u16); if (rc != RTUF_OK) return rc; }
-  b.h_table = table_out;
-  const int rc = submit_batch(c, n, b.st_depth, nullptr, nullptr, u16, nullptr, true, nullptr, nullptr, 0.0f, b.st_table, n_labels);
-  if (rc != RTUF_OK) return rc;
-  b.host_io = true;
-  return enqueue_download(c, b);
+  BatchRequest rq(Kind::Residual, n, u16);
+  rq.n_labels = n_labels;
+  HostPlanes hp{};
+  hp.depth = depth_in; hp.table = table_out;
+  return submit_host_planes(c, rq, hp);
 }
 
 int rtuf_link_residuals_batch(rtuf_context* c, int n, const float* const* depth_in, rtuf_link_residuals* table_out, int n_labels)
@@ -2583,7 +2624,7 @@ int rtuf_link_residuals_batch_u16(rtuf_context* c, int n, const uint16_t* const*
 }
 
 // ---- filtered point clouds ---------------------------------------------------------------------------
-// A cloud batch is a mask-bits batch (submit_batch with the slot's own bits buffer) whose launch groups run the cloud kernels
+// A cloud batch (Kind::Cloud) is a mask-bits batch on the slot's own bits buffer whose launch groups run the cloud kernels
 // behind their tile / dilate kernel (issue_plan).  RTUF_FLAG_TWO_KERNEL does not enter: the fused bits route is taken.
 int rtuf_set_cloud_intrinsics(rtuf_context* c, int first, int n, const double* fx_fy_cx_cy)
 {
@@ -2610,8 +2651,7 @@ int rtuf_set_cloud_intrinsics(rtuf_context* c, int first, int n, const double* f
 
 static int check_cloud_call(rtuf_context* c, int n, const void* in, const void* points, const void* counts, int capacity, bool compact)
 {
-  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
-  if (n <= 0 || n > c->max_streams || !in || !points || (compact && !counts)) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
+  { const int rc = check_batch_call(c, n, in && points && (!compact || counts), false); if (rc != RTUF_OK) return rc; }
   if (c->width & 3) return c->fail(RTUF_ERR_INVALID, "point clouds are built on the mask bits: they need a width that is a multiple of 4");
   if (compact && (capacity < 1 || (long long)capacity > (long long)c->width * c->height))
     return c->fail(RTUF_ERR_INVALID, "capacity = %d: 1 .. width * height (%lld)", capacity, (long long)c->width * c->height);
@@ -2631,17 +2671,12 @@ static int check_cloud_alignment(rtuf_context* c, const void* d_depth, const voi
   return RTUF_OK;
 }
 
-// takes the slot submit_batch takes next, gives it its bits buffer and row scratch, and submits
-static int submit_cloud(rtuf_context* c, int n, const float* d_depth, bool u16, const CloudOut& out, bool wait_upload)
+// (capacity 0: the organized form)
+static BatchRequest cloud_request(int n, const void* d_depth, float* d_points, uint32_t* d_index, uint32_t* d_counts, int capacity, bool u16)
 {
-  if (c->broken) return c->fail(RTUF_ERR_STATE, "context unusable: a bin regrowth failed (%s)", c->error.c_str());
-  hipSetDevice(c->device);
-  const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
-  while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
-  rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];
-  if (!b.cl_bits) HIP_TRY(c, dev_alloc(c, &b.cl_bits, (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
-  if (out.capacity && !b.cl_rows) HIP_TRY(c, dev_alloc(c, &b.cl_rows, 2u * (size_t)c->max_streams * (size_t)c->height * sizeof(uint32_t)));
-  return submit_batch(c, n, d_depth, nullptr, nullptr, u16, b.cl_bits, wait_upload, nullptr, nullptr, 0.0f, nullptr, 0, &out);
+  BatchRequest rq(Kind::Cloud, n, u16);
+  rq.depth = static_cast<const float*>(d_depth); rq.points = d_points; rq.index = d_index; rq.counts = d_counts; rq.capacity = capacity;
+  return rq;
 }
 
 int rtuf_cloud_batch_device(rtuf_context* c, int n, const float* d_depth, float* d_points)
@@ -2650,7 +2685,7 @@ int rtuf_cloud_batch_device(rtuf_context* c, int n, const float* d_depth, float*
   if (!c) return RTUF_ERR_INVALID;
   int rc = check_cloud_call(c, n, d_depth, d_points, nullptr, 0, false);
   if (rc == RTUF_OK) rc = check_cloud_alignment(c, d_depth, d_points, false);
-  return rc != RTUF_OK ? rc : submit_cloud(c, n, d_depth, false, CloudOut{d_points, nullptr, nullptr, 0}, false);
+  return rc != RTUF_OK ? rc : submit_device(c, cloud_request(n, d_depth, d_points, nullptr, nullptr, 0, false));
 }
 
 int rtuf_cloud_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth, float* d_points)
@@ -2659,7 +2694,7 @@ int rtuf_cloud_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth,
   if (!c) return RTUF_ERR_INVALID;
   int rc = check_cloud_call(c, n, d_depth, d_points, nullptr, 0, false);
   if (rc == RTUF_OK) rc = check_cloud_alignment(c, d_depth, d_points, true);
-  return rc != RTUF_OK ? rc : submit_cloud(c, n, reinterpret_cast<const float*>(d_depth), true, CloudOut{d_points, nullptr, nullptr, 0}, false);
+  return rc != RTUF_OK ? rc : submit_device(c, cloud_request(n, d_depth, d_points, nullptr, nullptr, 0, true));
 }
 
 int rtuf_cloud_compact_batch_device(rtuf_context* c, int n, const float* d_depth, float* d_points, uint32_t* d_index, uint32_t* d_counts, int capacity)
@@ -2667,7 +2702,7 @@ int rtuf_cloud_compact_batch_device(rtuf_context* c, int n, const float* d_depth
   KIDS_NEXT(c, rtuf_cloud_compact_batch_device(k, n, d_depth, d_points, d_index, d_counts, capacity));
   if (!c) return RTUF_ERR_INVALID;
   const int rc = check_cloud_call(c, n, d_depth, d_points, d_counts, capacity, true);
-  return rc != RTUF_OK ? rc : submit_cloud(c, n, d_depth, false, CloudOut{d_points, d_index, d_counts, capacity}, false);
+  return rc != RTUF_OK ? rc : submit_device(c, cloud_request(n, d_depth, d_points, d_index, d_counts, capacity, false));
 }
 
 int rtuf_cloud_compact_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth, float* d_points, uint32_t* d_index, uint32_t* d_counts, int capacity)
@@ -2675,60 +2710,22 @@ int rtuf_cloud_compact_batch_device_u16(rtuf_context* c, int n, const uint16_t* 
   KIDS_NEXT(c, rtuf_cloud_compact_batch_device_u16(k, n, d_depth, d_points, d_index, d_counts, capacity));
   if (!c) return RTUF_ERR_INVALID;
   const int rc = check_cloud_call(c, n, d_depth, d_points, d_counts, capacity, true);
-  return rc != RTUF_OK ? rc : submit_cloud(c, n, reinterpret_cast<const float*>(d_depth), true, CloudOut{d_points, d_index, d_counts, capacity}, false);
+  return rc != RTUF_OK ? rc : submit_device(c, cloud_request(n, d_depth, d_points, d_index, d_counts, capacity, true));
 }
 
-// host planes, synchronous: planes up into the slot's staging, the batch, and -- once it is retired, re-runs included -- the
-// results down; the compacted forms bring the counts down first and then only min(counts, capacity) entries per stream
+// host planes, synchronous (download_cloud)
 static int cloud_host_batch(rtuf_context* c, int n, const void* const* depth_in, float* const* points_out, uint32_t* const* index_out,
                             uint32_t* counts_out, int capacity, bool compact, bool u16)
 {
   KIDS_NEXT(c, cloud_host_batch(k, n, depth_in, points_out, index_out, counts_out, capacity, compact, u16));
   if (!c) return RTUF_ERR_INVALID;
   { const int rc = check_cloud_call(c, n, depth_in, points_out, counts_out, capacity, compact); if (rc != RTUF_OK) return rc; }
-  for (int s = 0; s < n; s++)
-    if (!depth_in[s] || !points_out[s] || (index_out && !index_out[s])) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
-  hipSetDevice(c->device);
-  { const int rc = ensure_copy_streams(c); if (rc != RTUF_OK) return rc; }
-  const int limit = uses_zsurface(c) ? 1 : kMaxInflight;
-  while (c->pending >= limit) { const int rc = retire_oldest(c); if (rc != RTUF_OK) return rc; }
-  rtuf_context::Batch& b = c->batch[(c->oldest + c->pending) % kMaxInflight];     // the slot submit_cloud takes next
-  { const int rc = ensure_plane_staging(c, b, n, false); if (rc != RTUF_OK) return rc; }
-  const size_t per = compact ? (size_t)capacity : (size_t)c->width * c->height;   // entries per stream
-  if (b.st_points_floats < (size_t)n * per * 3u) {
-    dev_free(c, b.st_points);
-    b.st_points_floats = 0;
-    HIP_TRY(c, dev_alloc(c, &b.st_points, (size_t)n * per * 3u * sizeof(float)));
-    b.st_points_floats = (size_t)n * per * 3u;
-  }
-  if (compact && index_out && b.st_index_words < (size_t)n * per) {
-    dev_free(c, b.st_index);
-    b.st_index_words = 0;
-    HIP_TRY(c, dev_alloc(c, &b.st_index, (size_t)n * per * sizeof(uint32_t)));
-    b.st_index_words = (size_t)n * per;
-  }
-  if (compact && !b.st_counts) HIP_TRY(c, dev_alloc(c, &b.st_counts, (size_t)c->max_streams * sizeof(uint32_t)));
-  { const int rc = upload_planes(c, b, n, depth_in, u16); if (rc != RTUF_OK) return rc; }
-  const CloudOut out{b.st_points, compact && index_out ? b.st_index : nullptr, compact ? b.st_counts : nullptr, compact ? capacity : 0};
-  { const int rc = submit_cloud(c, n, b.st_depth, u16, out, true); if (rc != RTUF_OK) return rc; }
-  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
-  if (!compact) {
-    for (int s = 0; s < n;) {                // consecutive planes as one transfer
-      int e = s + 1;
-      while (e < n && points_out[e] == points_out[e - 1] + per * 3u) e++;
-      HIP_TRY(c, hipMemcpy(points_out[s], b.st_points + (size_t)s * per * 3u, (size_t)(e - s) * per * 3u * sizeof(float), hipMemcpyDeviceToHost));
-      s = e;
-    }
-    return RTUF_OK;
-  }
-  HIP_TRY(c, hipMemcpy(counts_out, b.st_counts, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  for (int s = 0; s < n; s++) {
-    const size_t m = std::min<size_t>(counts_out[s], per);
-    if (!m) continue;
-    HIP_TRY(c, hipMemcpy(points_out[s], b.st_points + (size_t)s * per * 3u, m * 3u * sizeof(float), hipMemcpyDeviceToHost));
-    if (index_out) HIP_TRY(c, hipMemcpy(index_out[s], b.st_index + (size_t)s * per, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  }
-  return RTUF_OK;
+  HostPlanes hp{};
+  hp.depth = depth_in; hp.out = reinterpret_cast<void* const*>(points_out);
+  hp.index = compact ? reinterpret_cast<void* const*>(index_out) : nullptr; hp.counts = counts_out;
+  BatchRequest rq(Kind::Cloud, n, u16);
+  rq.capacity = compact ? capacity : 0;
+  return submit_host_planes(c, rq, hp);
 }
 
 int rtuf_cloud_batch(rtuf_context* c, int n, const float* const* depth_in, float* const* points_out)
