@@ -546,6 +546,54 @@ inline std::vector<DrawCall> mesh_draws(const std::vector<float>& verts, const s
   return {d};
 }
 
+// Spheres around a draw's vertices for rtuf_set_link_spheres (include/rtuf.h, LINK CLEARANCE TABLES), the twin of
+// geometry.py's bounding_spheres: the bounding box's longest axis (the first of equals) is split into `segments` slabs of
+// equal width, and every slab that holds vertices gives one sphere -- centre = the middle of the box of its vertices (float),
+// radius = the largest distance from that centre to one of them, rounded up to float.  verts: xyz per vertex; returns x, y, z,
+// r per sphere, in slab order.  All arithmetic in double, in geometry.py's order.
+inline std::vector<float> bounding_spheres(const std::vector<float>& verts, int segments = 1)
+{
+  std::vector<float> out;
+  const size_t n = verts.size() / 3;
+  if (segments < 1) segments = 1;
+  if (!n) return out;
+  double lo[3], hi[3];
+  for (int a = 0; a < 3; a++) lo[a] = hi[a] = verts[a];
+  for (size_t i = 0; i < n; i++)
+    for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], (double)verts[3 * i + a]); hi[a] = std::max(hi[a], (double)verts[3 * i + a]); }
+  int ax = 0;
+  for (int a = 1; a < 3; a++) if (hi[a] - lo[a] > hi[ax] - lo[ax]) ax = a;
+  const double ext = hi[ax] - lo[ax];
+  std::vector<int> slab(n, 0);
+  if (ext > 0)
+    for (size_t i = 0; i < n; i++) slab[i] = std::min((int)std::floor((((double)verts[3 * i + ax] - lo[ax]) / ext) * segments), segments - 1);
+  for (int k = 0; k < segments; k++) {
+    bool any = false;
+    double mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+    for (size_t i = 0; i < n; i++) {
+      if (slab[i] != k) continue;
+      for (int a = 0; a < 3; a++) {
+        const double x = verts[3 * i + a];
+        mn[a] = any ? std::min(mn[a], x) : x; mx[a] = any ? std::max(mx[a], x) : x;
+      }
+      any = true;
+    }
+    if (!any) continue;
+    float c[3];
+    for (int a = 0; a < 3; a++) c[a] = (float)((mn[a] + mx[a]) * 0.5);
+    double dist = 0;
+    for (size_t i = 0; i < n; i++) {
+      if (slab[i] != k) continue;
+      const double dx = (double)verts[3 * i] - (double)c[0], dy = (double)verts[3 * i + 1] - (double)c[1], dz = (double)verts[3 * i + 2] - (double)c[2];
+      dist = std::max(dist, std::sqrt(((dx * dx) + (dy * dy)) + (dz * dz)));
+    }
+    float r = (float)dist;
+    if ((double)r < dist) r = std::nextafter(r, INFINITY);
+    out.insert(out.end(), {c[0], c[1], c[2], r});
+  }
+  return out;
+}
+
 // Binary (incl. headers starting with "solid", README.md:121-143) and ASCII STL; no vertex welding.
 inline bool load_stl(const std::string& data, std::vector<float>& verts, std::vector<uint32_t>& tris)
 {

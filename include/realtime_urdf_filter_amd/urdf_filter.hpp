@@ -247,6 +247,7 @@ class RealtimeURDFFilter {
     p.silhouette_dilation_px = silhouette_dilation_px_;
     if (ctx_) { rtuf_destroy(ctx_); ctx_ = nullptr; }
     cloud_intr_sent_ = false;                  // (the new context has no cloud intrinsics: cloud_into gives them again)
+    spheres_sent_ = false;                     // (... and no link spheres: clearance_into gives them again)
     if (rtuf_create(&ctx_, device_, width_, height_, 1, &p) != RTUF_OK) throw std::runtime_error(std::string("ERROR: could not initialize the GPU context: ") + rtuf_last_error(nullptr));
     this->loadModels();
     if (renderers_.empty()) throw std::runtime_error("Could not load any models for filtering!");
@@ -402,6 +403,38 @@ class RealtimeURDFFilter {
     } else {
       check(rtuf_link_residuals_batch(ctx_, 1, reinterpret_cast<const float* const*>(&in), table_out, n_labels));
     }
+    return true;
+  }
+  // Link clearance tables (include/rtuf.h, LINK CLEARANCE TABLES): per link label, the nearest kept point to the spheres of
+  // setLinkSpheres (link = renderable index within the model, centres in the renderable's frame: a draw's pre_op applied to its vertices first), for the camera, link poses and intrinsics cloud_into would use.  depth: width x height float metres, or
+  // uint16 millimetres with is_16uc1 (any width); table_out: n_labels rows, row = label as in link_residuals_into, row 0 = the
+  // whole robot.  No plane is written.
+  void setLinkSpheres(int model, const std::vector<int32_t>& link, const std::vector<float>& xyzr)
+  {
+    if (xyzr.size() != 4 * link.size()) throw std::runtime_error("setLinkSpheres: xyzr must hold four floats per sphere");
+    link_spheres_[model] = std::make_pair(link, xyzr);
+    spheres_sent_ = false;
+  }
+  bool clearance_into(const void* depth, bool is_16uc1, double* glTf, int width, int height, double timestamp, rtuf_link_clearance* table_out,
+                      int n_labels, float max_distance)
+  {
+    prepare(width, height);
+    if (!depth || !table_out) throw std::runtime_error("clearance_into: needs depth and table_out");
+    if (!have_cloud_intr_) throw std::runtime_error("clearance_into: no intrinsics yet (getProjectionMatrix sets them)");
+    if (renderers_.empty() || !stage_frame(glTf, timestamp)) return false;
+    if (!cloud_intr_sent_ || std::memcmp(cloud_intr_given_, cloud_intr_, sizeof cloud_intr_) != 0) {
+      check(rtuf_set_cloud_intrinsics(ctx_, 0, 1, cloud_intr_));
+      cloud_intr_sent_ = true;
+      std::memcpy(cloud_intr_given_, cloud_intr_, sizeof cloud_intr_);
+    }
+    if (!spheres_sent_) {
+      for (const auto& kv : link_spheres_)
+        check(rtuf_set_link_spheres(ctx_, kv.first, kv.second.first.data(), kv.second.second.data(), (int)kv.second.first.size()));
+      spheres_sent_ = true;
+    }
+    const void* in = depth;
+    if (is_16uc1) check(rtuf_link_clearance_batch_u16(ctx_, 1, reinterpret_cast<const uint16_t* const*>(&in), table_out, n_labels, max_distance));
+    else check(rtuf_link_clearance_batch(ctx_, 1, reinterpret_cast<const float* const*>(&in), table_out, n_labels, max_distance));
     return true;
   }
   // rows a link_residuals_into table needs: one more than the largest label in effect (0 before the models are loaded)
@@ -613,6 +646,8 @@ class RealtimeURDFFilter {
   double cloud_intr_[4] = {0, 0, 0, 0};              // fx fy cx cy of the last getProjectionMatrix (cloud_into)
   double cloud_intr_given_[4] = {0, 0, 0, 0};        // ... and what the context was last given
   bool have_cloud_intr_ = false;
+  std::map<int, std::pair<std::vector<int32_t>, std::vector<float>>> link_spheres_;      // setLinkSpheres: per model, link and xyzr of every sphere
+  bool spheres_sent_ = false;                        // ctx_ holds link_spheres_ (cleared whenever initGL makes a new context)
   bool cloud_intr_sent_ = false;                     // ctx_ holds cloud_intr_given_ (cleared whenever initGL makes a new context)
   std::map<std::pair<int, std::string>, uint16_t> link_labels_;
   std::vector<float> own_masked_;                    // render() with labels: the outputs the library-owned planes hold otherwise

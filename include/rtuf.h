@@ -530,6 +530,60 @@ int rtuf_cloud_compact_batch(rtuf_context *ctx, int n_streams, const float *cons
 int rtuf_cloud_compact_batch_u16(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in, float *const *points_out,
                                  uint32_t *const *index_out, uint32_t *counts_out, int capacity);
 
+/* LINK CLEARANCE TABLES.  New, beyond the reference: per stream and link label, how close the nearest kept point -- the
+ * nearest thing that is not the robot -- is to the link, as a table [n_streams][n_labels] of 16-byte rows with no plane
+ * written at all: what speed-and-separation monitors and reactive controllers ask of the filtered cloud.
+ * Spheres.  rtuf_set_link_spheres gives `model` its list: sphere i is attached to link link[i] of the model, its centre
+ * xyzr[i][0..2] is in the link's frame -- the frame rtuf_set_link_poses places, in which a draw's vertices stand once its
+ * pre_op (glScalef / glTranslatef) has been applied to them: no pre_op is ever applied to a sphere, so a caller that derives
+ * spheres from a draw's vertices scales or translates those vertices first -- and its radius xyzr[i][3] is >= 0.
+ * Callable after rtuf_finalize_models, between batches (it waits for the batches in flight); it replaces the model's list,
+ * n_spheres = 0 clears it.  More than 4096 spheres in the context, more than 256 distinct non-zero labels among them, a bad
+ * link index, a non-finite centre or a negative or non-finite radius fail with RTUF_ERR_INVALID and change nothing.  A sphere
+ * takes the label of its link (LINK LABELS: default labels or rtuf_set_link_labels) when a batch is enqueued -- a batch after
+ * a relabelling that leaves more than 256 labels fails with RTUF_ERR_INVALID -- and spheres of label 0 are ignored.  Spheres
+ * have a context-global id: model order, then list order (ignored spheres keep theirs).
+ * A kept point is the cloud batch's (FILTERED POINT CLOUDS): mask bit 0 -- silhouette dilation and per-link thresholds
+ * honoured -- and sensor > 0 && sensor < +inf; the point is cloud_point with the stream's rtuf_set_cloud_intrinsics.
+ * A sphere's centre in the camera frame is offset_inv * (cam_tf * (link_tf[stream][link] * (c, 1))): three matrix-vector
+ * products in double, every row ((m0 x + m4 y) + m8 z) + m12 with each product and sum rounded on its own, the result rounded
+ * to float (clearance_centre in rtuf_numerics.h).  That is the cloud's optical frame: the reference applies its look-at after
+ * camera_offset_inv.  The clearance of a (point, sphere) pair is sqrt((dx dx + dy dy) + dz dz) - r, d = point - centre, in
+ * single float operations with a correctly rounded square root (clearance_point_sphere); it is negative inside the sphere.
+ * A pair COUNTS iff clearance < max_distance, strictly; max_distance > 0, +inf allowed (NaN or <= 0: RTUF_ERR_INVALID).
+ * Row l >= 1 of stream s, over the spheres of label l of the models the stream renders (rtuf_set_stream_models):
+ * points_within = the kept points with a counting pair; clearance / pixel / sphere = the counting pair with the smallest
+ * clearance, then the smallest pixel index v * width + u, then the smallest sphere id; {+inf, 0xFFFFFFFF, 0xFFFFFFFF, 0} when
+ * no pair counts (also: no spheres of that label).  Row 0 is the whole robot: the same over the spheres of all labels
+ * 1 .. n_labels - 1 together, so its points_within is not the sum of the other rows.  Spheres of labels >= n_labels are
+ * dropped, from row 0 too.  Every call overwrites its table.  Minima and integer counts only: the table does not depend on
+ * the order of execution, and the kernels' culling is conservative -- the result is that of all pairs.
+ * A clearance batch is a mask-bits batch plus the clearance kernels, as a cloud batch is, with the cloud batch's rules --
+ * the library's own bits buffer per batch slot (and the posed spheres), RTUF_FLAG_TWO_KERNEL does not enter, thresholds not
+ * together with dilation (RTUF_ERR_INVALID), a stream without intrinsics fails with RTUF_ERR_STATE, an uncovered image makes
+ * retiring the batch fail with RTUF_ERR_STATE -- except that any width is accepted, 16UC1 included.  Otherwise it is a batch
+ * like any other: raster lanes, pipelines, launch groups, partial batches, batches in flight (each with a table of its own),
+ * graph replay of small batches, re-runs after a bin regrowth (the rows start over: as if the batch had run once), the status
+ * word, which covers the table (timings: ms_compare), rtuf_order_stream_after_batches.  The device forms only enqueue
+ * (d_table: [n][n_labels], 8-byte aligned); the host-plane forms are synchronous: planes up, table down.  n_labels < 1, a
+ * NULL plane or table, n out of range or an un-finalized context fail as the filter calls do; a refused call enqueues nothing. */
+int rtuf_set_link_spheres(rtuf_context *ctx, int model, const int32_t *link /* [n] */, const float *xyzr /* [n][4] */, int n_spheres);
+typedef struct {
+  float clearance;        /* metres, may be negative (point inside a sphere); +inf: nothing within max_distance          */
+  uint32_t pixel;         /* v * width + u of the nearest kept pixel; 0xFFFFFFFF when clearance is +inf                  */
+  uint32_t sphere;        /* context-global id of the sphere it is nearest to; 0xFFFFFFFF likewise                       */
+  uint32_t points_within; /* kept points whose clearance to this label's spheres is < max_distance                       */
+} rtuf_link_clearance;    /* 16 bytes */
+
+int rtuf_link_clearance_batch_device(rtuf_context *ctx, int n_streams, const float *d_depth, rtuf_link_clearance *d_table, int n_labels,
+                                     float max_distance);
+int rtuf_link_clearance_batch_device_u16(rtuf_context *ctx, int n_streams, const uint16_t *d_depth_mm, rtuf_link_clearance *d_table, int n_labels,
+                                         float max_distance);
+int rtuf_link_clearance_batch(rtuf_context *ctx, int n_streams, const float *const *depth_in, rtuf_link_clearance *table_out, int n_labels,
+                              float max_distance);
+int rtuf_link_clearance_batch_u16(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in, rtuf_link_clearance *table_out,
+                                  int n_labels, float max_distance);
+
 /* Counters of the last batch and kernel timings measured with HIP events on the context's
  * stream (replaces the wall-clock statistics of src/urdf_filter.cpp:239-266). */
 typedef struct {

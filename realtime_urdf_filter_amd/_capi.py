@@ -39,11 +39,15 @@ SYMBOLS = [
     "rtuf_link_residuals_batch_device", "rtuf_link_residuals_batch_device_u16", "rtuf_link_residuals_batch", "rtuf_link_residuals_batch_u16",
     "rtuf_set_cloud_intrinsics", "rtuf_cloud_batch_device", "rtuf_cloud_batch_device_u16", "rtuf_cloud_compact_batch_device",
     "rtuf_cloud_compact_batch_device_u16", "rtuf_cloud_batch", "rtuf_cloud_batch_u16", "rtuf_cloud_compact_batch", "rtuf_cloud_compact_batch_u16",
+    "rtuf_set_link_spheres", "rtuf_link_clearance_batch_device", "rtuf_link_clearance_batch_device_u16", "rtuf_link_clearance_batch",
+    "rtuf_link_clearance_batch_u16",
 ]
 
 # rtuf_link_residuals (include/rtuf.h, LINK RESIDUAL TABLES): one 64-byte row per (stream, label)
 LINK_RESIDUALS_DTYPE = np.dtype([("pixels", "<u8"), ("invalid", "<u8"), ("filtered", "<u8"), ("in_front", "<u8"), ("behind", "<u8"),
                                  ("agree", "<u8"), ("sum_residual", "<i8"), ("sum_abs_residual", "<u8")])
+# rtuf_link_clearance (include/rtuf.h, LINK CLEARANCE TABLES): one 16-byte row per (stream, label)
+LINK_CLEARANCE_DTYPE = np.dtype([("clearance", "<f4"), ("pixel", "<u4"), ("sphere", "<u4"), ("points_within", "<u4")])
 
 
 class Params(ctypes.Structure):
@@ -203,6 +207,11 @@ def load_library(path=None):
     lib.rtuf_cloud_batch_u16.argtypes = [vp, ci, vp, vp]
     lib.rtuf_cloud_compact_batch.argtypes = [vp, ci, vp, vp, vp, vp, ci]
     lib.rtuf_cloud_compact_batch_u16.argtypes = [vp, ci, vp, vp, vp, vp, ci]
+    lib.rtuf_set_link_spheres.argtypes = [vp, ci, vp, vp, ci]
+    lib.rtuf_link_clearance_batch_device.argtypes = [vp, ci, vp, vp, ci, ctypes.c_float]
+    lib.rtuf_link_clearance_batch_device_u16.argtypes = [vp, ci, vp, vp, ci, ctypes.c_float]
+    lib.rtuf_link_clearance_batch.argtypes = [vp, ci, vp, vp, ci, ctypes.c_float]
+    lib.rtuf_link_clearance_batch_u16.argtypes = [vp, ci, vp, vp, ci, ctypes.c_float]
     lib.rtuf_set_link_thresholds.argtypes = [vp, ci, vp, ci]
     lib.rtuf_clear_link_thresholds.argtypes = [vp, ci]
     if path is None:
@@ -521,6 +530,42 @@ class Context:
 
     def cloud_compact_batch_device_u16(self, n, d_depth_mm, d_points, d_index, d_counts, capacity):
         self.cloud_compact_batch_device(n, d_depth_mm, d_points, d_index, d_counts, capacity, u16=True)
+
+    # link clearance tables (include/rtuf.h, LINK CLEARANCE TABLES)
+    def set_link_spheres(self, model, link, xyzr):
+        """The sphere list of model `model`: link [n] (index within the model) and xyzr [n,4] (centre in the link's frame -- a draw's
+        pre_op applied to its vertices first -- and radius).  Replaces the model's list; empty arrays clear it."""
+        li = np.ascontiguousarray(link, np.int32).reshape(-1)
+        q = np.ascontiguousarray(xyzr, np.float32).reshape(-1, 4)
+        if len(li) != len(q):
+            raise ValueError("link and xyzr differ in length")
+        self._check(self._lib.rtuf_set_link_spheres(self._h, model, _ptr(li) if len(li) else None, _ptr(q) if len(q) else None, len(li)))
+
+    def link_clearance_batch(self, depth, n_labels, max_distance):
+        """Per stream and label, the nearest kept point to the label's spheres: depth [n,H,W] float32 metres (or uint16
+        millimetres: the 16UC1 form) -> table [n, n_labels] of LINK_CLEARANCE_DTYPE.  Synchronous."""
+        u16 = np.asarray(depth).dtype == np.uint16
+        d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32).reshape(-1, self.height, self.width)
+        n = d.shape[0]
+        table = np.empty((n, max(int(n_labels), 0)), LINK_CLEARANCE_DTYPE)
+        PP = ctypes.c_void_p * max(n, 1)
+        din = PP(*[d[i].ctypes.data for i in range(n)])
+        fn = self._lib.rtuf_link_clearance_batch_u16 if u16 else self._lib.rtuf_link_clearance_batch
+        self._check(fn(self._h, n, din, ctypes.c_void_p(table.ctypes.data), int(n_labels), float(max_distance)))
+        return table
+
+    def link_clearance_batch_u16(self, depth_mm, n_labels, max_distance):
+        return self.link_clearance_batch(np.ascontiguousarray(depth_mm, np.uint16), n_labels, max_distance)
+
+    def link_clearance_batch_device(self, n, d_depth, d_table, n_labels, max_distance, u16=False):
+        """Device pointers (ints): d_depth [n,H,W] float32 (uint16 with u16), d_table [n, n_labels] rows of 16 bytes; enqueue only;
+        call sync()."""
+        fn = self._lib.rtuf_link_clearance_batch_device_u16 if u16 else self._lib.rtuf_link_clearance_batch_device
+        self._check(fn(self._h, n, ctypes.c_void_p(d_depth) if d_depth else None, ctypes.c_void_p(d_table) if d_table else None, int(n_labels),
+                       float(max_distance)))
+
+    def link_clearance_batch_device_u16(self, n, d_depth_mm, d_table, n_labels, max_distance):
+        self.link_clearance_batch_device(n, d_depth_mm, d_table, n_labels, max_distance, u16=True)
 
     # asynchronous host planes
     def host_alloc(self, shape, dtype):

@@ -60,12 +60,14 @@ struct Kinematics {               // on-device forward kinematics of one model
 };
 // labels: rtuf_set_link_labels's labels of the model's links (empty: the default, 1 + link_base + link)
 // thresholds: rtuf_set_link_thresholds's depth thresholds of the model's links (empty: rtuf_params.depth_distance_threshold)
-struct HostModel { std::vector<HostLink> links; int link_base = 0; Kinematics kin; std::vector<uint16_t> labels; std::vector<float> thresholds; };
+// sph_link / sph_xyzr: rtuf_set_link_spheres's list of the model (the link and x, y, z, r of every sphere)
+struct HostModel { std::vector<HostLink> links; int link_base = 0; Kinematics kin; std::vector<uint16_t> labels; std::vector<float> thresholds;
+                   std::vector<int32_t> sph_link; std::vector<float> sph_xyzr; };
 
 // One batch as its caller asked for it: the kind, and the device buffers and scalars that kind has (the rest stays nullptr / 0).
 // A slot keeps the record of its batch (Batch::rq) for re-runs; what a kind does is written down in the predicates before the hot path.
 struct BatchRequest {
-  enum class Kind { Filter, Bits, Render, Residual, Cloud };
+  enum class Kind { Filter, Bits, Render, Residual, Cloud, Clearance };
   Kind kind; int n; bool u16;               // (u16: the sensor / masked / virtual planes are 16UC1)
   bool wait_upload = false;                 // host planes: the lanes wait for the slot's `uploaded` event before the first kernel that reads them
   const float* depth = nullptr;             // sensor planes (every kind but Render)
@@ -76,6 +78,8 @@ struct BatchRequest {
   rtuf_link_residuals* resid = nullptr; int n_labels = 0;      // Residual: the table [n][n_labels] the tile kernel sums into, zeroed on every run, re-runs included
   // Cloud (a mask-bits batch with the cloud kernels behind it).  capacity == 0: the organized form, index and counts unused; index may be nullptr anyway
   float* points = nullptr; uint32_t* index = nullptr; uint32_t* counts = nullptr; int capacity = 0;
+  // Clearance (a mask-bits batch with the clearance kernels behind it): the table [n][n_labels] and the cutoff
+  rtuf_link_clearance* clr = nullptr; float max_distance = 0.0f;
   BatchRequest(Kind k = Kind::Filter, int n_ = 0, bool u16_ = false) : kind(k), n(n_), u16(u16_) {}
 };
 using Kind = BatchRequest::Kind;
@@ -129,6 +133,13 @@ struct rtuf_context {
   // rewritten in place after that (captured graphs keep its address), and which streams have been given theirs.
   CloudIntrinsics* d_cloud_intr = nullptr;
   std::vector<uint8_t> cloud_intr_set;
+  // Link clearance tables: the spheres of every model sorted by label (label 0 left out) with their label slots, rebuilt on
+  // the host when the lists or the labels changed (clr_dirty) and uploaded before the next clearance batch; the device
+  // arrays are allocated once for the most a context can hold (captured graphs keep their addresses).
+  std::vector<ClearanceSphere> clr_spheres;
+  std::vector<uint32_t> clr_slot_label;
+  ClearanceSphere* d_clr_spheres = nullptr; uint32_t* d_clr_slot_label = nullptr;
+  bool clr_dirty = true;
 
   // per-frame pose staging
   // Cameras and link matrices are staged in a ring of kMaxInflight + 1 pinned sets, like the joint positions: every
@@ -207,6 +218,8 @@ struct rtuf_context {
     // cloud batches: the slot's own bits buffer and row scratch ([2][max_streams][H]: row counts, row starts), allocated on the
     // slot's first (compacted) cloud batch for max_streams, so that captured graphs keep their addresses
     uint32_t* cl_bits = nullptr; uint32_t* cl_rows = nullptr;
+    // clearance batches: the posed spheres of the slot's batch, [max_streams][clr_posed_have], regrown when the context holds more spheres
+    float4* clr_posed = nullptr; size_t clr_posed_have = 0;
     Counters* h_counters = nullptr;          // pinned [max_groups]: one block per launch group, filled by the copies that end the batch
     hipEvent_t done[kMaxLanes] = {};         // recorded on each lane after its copy
     uint32_t lanes_used = 0;                 // bit l: the batch has launch groups on lane l
@@ -236,7 +249,7 @@ struct rtuf_context {
     // user counts in: streams, table rows, floats, words), the caller's planes of an asynchronous download, and the events
     // that order upload -> kernels -> download across the copy streams.
     bool host_io = false;                    // the batch ends with a download on d2h (`downloaded`)
-    enum { kStDepth, kStMasked, kStMask, kStBits, kStLabels, kStVirtual, kStTable, kStPoints, kStIndex, kStKinds };
+    enum { kStDepth, kStMasked, kStMask, kStBits, kStLabels, kStVirtual, kStTable, kStPoints, kStIndex, kStClearance, kStKinds };
     struct { char* p = nullptr; size_t have = 0; } st[kStKinds];      // (depth and virtual are float-sized: large enough for uint16 planes)
     uint32_t* st_counts = nullptr;           // compacted clouds: [max_streams], allocated once
     std::vector<void*> h_out, h_mask, h_labels;      // masked / bits / virtual planes; byte masks (any may be nullptr); label planes
@@ -672,7 +685,7 @@ static void free_frame_buffers(rtuf_context* c)
     for (auto*& it : ln.d_items) dev_free(c, it);
   }
   for (auto& b : c->batch) for (auto& st : b.st) { dev_free(c, st.p); st.have = 0; }
-  for (auto& b : c->batch) { dev_free(c, b.cl_bits); dev_free(c, b.cl_rows); dev_free(c, b.st_counts); }
+  for (auto& b : c->batch) { dev_free(c, b.cl_bits); dev_free(c, b.cl_rows); dev_free(c, b.st_counts); dev_free(c, b.clr_posed); }
   for (auto*& p : c->ring_cams) hfree(p);
   for (auto*& p : c->ring_link_tf) hfree(p);
   c->h_cams = nullptr; c->h_link_tf = nullptr;
@@ -703,6 +716,7 @@ void rtuf_destroy(rtuf_context* c)
   dev_free(c, c->d_order_labels);
   dev_free(c, c->d_order_thr);
   dev_free(c, c->d_cloud_intr);
+  dev_free(c, c->d_clr_spheres); dev_free(c, c->d_clr_slot_label);
   for (auto& b : c->batch) {
     for (hipEvent_t ev : b.events) hipEventDestroy(ev);
     for (hipEvent_t ev : b.done) if (ev) hipEventDestroy(ev);
@@ -1384,7 +1398,7 @@ int rtuf_debug_read_poses(rtuf_context* c, int n, double* link_tf_out, double* c
 static bool uses_zsurface(const rtuf_context* c) { return (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 || c->params.silhouette_dilation_px > 0; }
 // RTUF_FLAG_TWO_KERNEL: full planes only (the mask-bits calls refuse the flag; render, residual and cloud batches are always one tile kernel)
 static bool takes_two_kernel(const BatchRequest& r) { return r.kind == Kind::Filter; }
-// silhouette dilation: dilate_compare_kernel makes every output form from the z-surface, mask bits and so clouds included (the render and residual calls refuse it)
+// silhouette dilation: dilate_compare_kernel makes every output form from the z-surface, mask bits and so clouds included (the render and residual calls refuse it; clearance batches follow the clouds)
 static bool honours_dilation(const BatchRequest& r) { return r.kind != Kind::Render && r.kind != Kind::Residual; }
 // the per-link threshold table (a render batch compares nothing: no thresholds; a residual batch honours them)
 static bool reads_thresholds(const BatchRequest& r) { return r.kind != Kind::Render; }
@@ -1396,7 +1410,7 @@ static bool may_write_zsurface(const BatchRequest& r) { return takes_two_kernel(
 // route; a cloud batch takes it for dilation only, which check_cloud_call refuses with thresholds
 static bool subject_to_thresh_route(const BatchRequest& r) { return r.kind == Kind::Filter || r.kind == Kind::Bits; }
 // retire_oldest fills ms_compare: a kernel runs behind the tile kernel (compare, dilate + compare, or the cloud kernels)
-static bool fills_ms_compare(const rtuf_context* c, const rtuf_context::Batch& b) { return ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && takes_two_kernel(b.rq)) || b.dilation > 0 || b.rq.kind == Kind::Cloud; }
+static bool fills_ms_compare(const rtuf_context* c, const rtuf_context::Batch& b) { return ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && takes_two_kernel(b.rq)) || b.dilation > 0 || b.rq.kind == Kind::Cloud || b.rq.kind == Kind::Clearance; }
 
 // ---- the hot path ---------------------------------------------------------------------
 static hipEvent_t get_event(rtuf_context::Batch& b, size_t i)
@@ -1413,7 +1427,7 @@ static hipEvent_t get_event(rtuf_context::Batch& b, size_t i)
 struct BatchPlan {
   std::vector<FkArgs> fks;
   PoseArgs pa{};
-  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; CloudArgs cl{}; bool compare = false, dilate = false, cloud = false; int lane = 0; };
+  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; CloudArgs cl{}; ClearanceArgs cr{}; bool compare = false, dilate = false, cloud = false, clearance = false; int lane = 0; };
   std::vector<Group> groups;
   bool cover_pass = true;
   bool zroute = false;          // the tile kernel writes the z-surface (two-kernel mode, or silhouette dilation)
@@ -1426,6 +1440,7 @@ struct BatchPlan {
     for (const Group& g : groups) {
       mix(&g.sa, sizeof g.sa); mix(&g.ta, sizeof g.ta); if (g.compare) mix(&g.ca, sizeof g.ca); if (g.dilate) mix(&g.da, sizeof g.da);
       if (g.cloud) mix(&g.cl, sizeof g.cl);
+      if (g.clearance) mix(&g.cr, sizeof g.cr);
       mix(&g.lane, sizeof g.lane);
     }
     return h ^ (uint64_t)fks.size() << 56 ^ (uint64_t)groups.size() << 48 ^ (uint64_t)cover_pass << 47 ^ (uint64_t)zroute << 46;
@@ -1501,10 +1516,12 @@ static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& 
     launch_tile(gr.ta, two, plan.cover_pass, st);
     if (b.timing) mark(e0 + 3, st);
     if (gr.compare) { launch_compare(gr.ca, st); if (b.timing) mark(e0 + 4, st); }
-    if (gr.dilate) { launch_dilate_compare(gr.da, st); if (b.timing && !gr.cloud) mark(e0 + 4, st); }
+    if (gr.dilate) { launch_dilate_compare(gr.da, st); if (b.timing && !gr.cloud && !gr.clearance) mark(e0 + 4, st); }
     // a cloud batch: the group's points from the bits the kernel above wrote, before the lane publishes its counters (timed
     // as ms_compare, with the dilate kernel where there is one)
     if (gr.cloud) { launch_cloud(gr.cl, st); if (b.timing) mark(e0 + 4, st); }
+    // a clearance batch: the group's rows of the table, in the same place and timed the same way
+    if (gr.clearance) { launch_clearance(gr.cr, st); if (b.timing) mark(e0 + 4, st); }
   }
   // every lane publishes the counter blocks of its own groups
   const int ng = (int)plan.groups.size();
@@ -1631,7 +1648,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     plan.groups.emplace_back();
     BatchPlan::Group& gr = plan.groups.back();
     memset(&gr.sa, 0, sizeof gr.sa); memset(&gr.ta, 0, sizeof gr.ta); memset(&gr.ca, 0, sizeof gr.ca); memset(&gr.da, 0, sizeof gr.da);
-    memset(&gr.cl, 0, sizeof gr.cl);
+    memset(&gr.cl, 0, sizeof gr.cl); memset(&gr.cr, 0, sizeof gr.cr);
     gr.lane = n_groups == 1 ? lane0 : g % c->n_lanes;
     const rtuf_context::Lane& ln = c->lane[gr.lane];
     Counters* const d_counters = b.d_counters + g;
@@ -1677,6 +1694,19 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
       cl.depth = d_depth; cl.bits = r.bits; cl.intr = c->d_cloud_intr; cl.points = r.points; cl.index = r.index; cl.counts = r.counts;
       cl.row_count = b.cl_rows; cl.row_start = b.cl_rows ? b.cl_rows + (size_t)c->max_streams * c->height : nullptr;
       cl.group_base = base; cl.group_size = gs; cl.width = c->width; cl.height = c->height; cl.capacity = r.capacity; cl.io_u16 = io_u16 ? 1 : 0;
+    }
+    gr.clearance = r.kind == Kind::Clearance;
+    if (gr.clearance) {
+      ClearanceArgs& cr = gr.cr;
+      // (the spheres of labels below n_labels: the list is sorted by label)
+      int used = 0, slots = 0;
+      while (used < (int)c->clr_spheres.size() && (int)(c->clr_spheres[(size_t)used].label_slot & 0xffffu) < r.n_labels) used++;
+      while (slots < (int)c->clr_slot_label.size() && (int)c->clr_slot_label[(size_t)slots] < r.n_labels) slots++;
+      cr.depth = d_depth; cr.bits = r.bits; cr.intr = c->d_cloud_intr; cr.spheres = c->d_clr_spheres; cr.slot_label = c->d_clr_slot_label;
+      cr.cams = b.d_cams; cr.link_tf = b.d_link_tf; cr.model_mask = c->d_model_mask; cr.posed = b.clr_posed;
+      cr.table = reinterpret_cast<unsigned long long*>(r.clr);
+      cr.n_spheres = used; cr.n_slots = slots; cr.n_links = (int)L; cr.n_labels = r.n_labels;
+      cr.group_base = base; cr.group_size = gs; cr.width = c->width; cr.height = c->height; cr.max_distance = r.max_distance; cr.io_u16 = io_u16 ? 1 : 0;
     }
     if (gr.compare) {
       CompareArgs& ca = gr.ca;
@@ -1800,7 +1830,7 @@ static int enqueue_download(rtuf_context* c, rtuf_context::Batch& b)
       rc = down(r.masked, b.h_out, plane * esz);
       if (rc == RTUF_OK) rc = down(r.mask, b.h_mask, plane);
       break;
-    case Kind::Cloud: break;
+    case Kind::Cloud: case Kind::Clearance: break;
   }
   if (rc == RTUF_OK && r.labels) rc = down(r.labels, b.h_labels, plane * sizeof(uint16_t));
   if (rc != RTUF_OK) return rc;
@@ -1918,6 +1948,9 @@ static int retire_oldest(rtuf_context* c)
         return c->fail(RTUF_ERR_STATE, "point cloud: a stream's background quad does not cover its whole image (non-standard projection), so the mask "
                                        "bits the cloud is built on are undefined there; there is no cloud form for this camera (filter with the "
                                        "full-plane calls and convert the masked plane)");
+      if (b.rq.kind == Kind::Clearance && k.uncovered)
+        return c->fail(RTUF_ERR_STATE, "link clearance: a stream's background quad does not cover its whole image (non-standard projection), so the "
+                                       "mask bits the kept points are taken from are undefined there");
       if (b.rq.kind == Kind::Bits && k.uncovered)
         return c->fail(RTUF_ERR_STATE, "mask bits: a stream's background quad does not cover its whole image (non-standard projection), so "
                                        "masked depth != select(bit, replace, sensor) there; use the full-plane calls for this camera");
@@ -2005,18 +2038,27 @@ static int take_slot(rtuf_context* c, rtuf_context::Batch*& slot)
 }
 
 // Enqueues the request in the slot take_slot gave: the slot keeps the record, and is in flight when this returns RTUF_OK.  A
-// cloud batch gets the slot's own bits buffer and row scratch here.
+// cloud batch gets the slot's own bits buffer and row scratch here, a clearance batch the bits buffer and its posed spheres.
 static int submit_batch(rtuf_context* c, rtuf_context::Batch& b, const BatchRequest& rq)
 {
   if (rq.kind == Kind::Cloud) {
     if (!b.cl_bits) HIP_TRY(c, dev_alloc(c, &b.cl_bits, (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
     if (rq.capacity && !b.cl_rows) HIP_TRY(c, dev_alloc(c, &b.cl_rows, 2u * (size_t)c->max_streams * (size_t)c->height * sizeof(uint32_t)));
   }
+  if (rq.kind == Kind::Clearance) {
+    if (!b.cl_bits) HIP_TRY(c, dev_alloc(c, &b.cl_bits, (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
+    if (b.clr_posed_have < c->clr_spheres.size()) {
+      dev_free(c, b.clr_posed);
+      b.clr_posed_have = 0;
+      HIP_TRY(c, dev_alloc(c, &b.clr_posed, (size_t)c->max_streams * c->clr_spheres.size() * sizeof(float4)));
+      b.clr_posed_have = c->clr_spheres.size();
+    }
+  }
   if (uses_zsurface(c) && may_write_zsurface(rq))
     for (int l = 0; l < c->n_lanes; l++)
       if (!c->lane[l].d_zsurface) HIP_TRY(c, dev_alloc(c, &c->lane[l].d_zsurface, (size_t)c->group * c->width * c->height * sizeof(float)));
   b.rq = rq;
-  if (rq.kind == Kind::Cloud) b.rq.bits = b.cl_bits;
+  if (rq.kind == Kind::Cloud || rq.kind == Kind::Clearance) b.rq.bits = b.cl_bits;
   b.host_io = false;
   const int rc = enqueue_batch(c, b, false);
   if (rc == RTUF_OK) { b.active = true; c->pending++; }
@@ -2207,6 +2249,7 @@ struct HostPlanes {
   void* const* labels;               // Filter, Render
   void* const* index; uint32_t* counts;      // compacted Cloud
   rtuf_link_residuals* table;        // Residual
+  rtuf_link_clearance* clr_table;    // Clearance
 };
 
 // the results of a host-plane cloud batch, synchronous: once the batch is retired -- re-runs included -- the organized planes
@@ -2253,6 +2296,7 @@ static int submit_host_planes(rtuf_context* c, BatchRequest rq, const HostPlanes
     {B::kStVirtual, rq.kind == Kind::Render ? (size_t)n : 0, plane * sizeof(float)},
     {B::kStLabels, hp.labels ? (size_t)n : 0, plane * sizeof(uint16_t)},
     {B::kStTable, rq.kind == Kind::Residual ? (size_t)n * (size_t)rq.n_labels : 0, sizeof(rtuf_link_residuals)},
+    {B::kStClearance, rq.kind == Kind::Clearance ? (size_t)n * (size_t)rq.n_labels : 0, sizeof(rtuf_link_clearance)},
     {B::kStPoints, cloud ? (size_t)n * per * 3u : 0, sizeof(float)}, {B::kStIndex, hp.index ? (size_t)n * per : 0, sizeof(uint32_t)}};
   for (const auto& s : staged) { const int rc = ensure_staging(c, b.st[s.st].p, b.st[s.st].have, s.need, s.bytes); if (rc != RTUF_OK) return rc; }
   if (cloud && rq.capacity && !b.st_counts) HIP_TRY(c, dev_alloc(c, &b.st_counts, (size_t)c->max_streams * sizeof(uint32_t)));
@@ -2283,9 +2327,16 @@ static int submit_host_planes(rtuf_context* c, BatchRequest rq, const HostPlanes
       rq.points = reinterpret_cast<float*>(at(B::kStPoints));
       rq.index = hp.index ? reinterpret_cast<uint32_t*>(at(B::kStIndex)) : nullptr; rq.counts = rq.capacity ? b.st_counts : nullptr;
       break;
+    case Kind::Clearance: rq.clr = reinterpret_cast<rtuf_link_clearance*>(at(B::kStClearance)); break;
   }
   { const int rc = submit_batch(c, b, rq); if (rc != RTUF_OK) return rc; }
   if (cloud) return download_cloud(c, rq, hp);
+  if (rq.kind == Kind::Clearance) {          // synchronous, as the clouds: the table comes down once the batch is retired, re-runs included
+    const int rc = rtuf_sync(c);
+    if (rc != RTUF_OK) return rc;
+    HIP_TRY(c, hipMemcpy(hp.clr_table, rq.clr, (size_t)n * (size_t)rq.n_labels * sizeof(rtuf_link_clearance), hipMemcpyDeviceToHost));
+    return RTUF_OK;
+  }
   b.host_io = true;
   return enqueue_download(c, b);
 }
@@ -2389,6 +2440,7 @@ int rtuf_set_link_labels(rtuf_context* c, int model, const uint16_t* labels, int
   WAIT_IF_PENDING(c);
   m.labels.assign(labels, labels + n_links);
   c->labels_dirty = true;
+  c->clr_dirty = true;                       // (a sphere takes its link's label when the next clearance batch is enqueued)
   return ensure_label_table(c);
 }
 
@@ -2748,6 +2800,143 @@ int rtuf_cloud_compact_batch_u16(rtuf_context* c, int n, const uint16_t* const* 
                                  uint32_t* counts_out, int capacity)
 {
   return cloud_host_batch(c, n, reinterpret_cast<const void* const*>(depth_mm_in), points_out, index_out, counts_out, capacity, true, true);
+}
+
+// ---- link clearance tables ---------------------------------------------------------------------------
+// A clearance batch (Kind::Clearance) is a mask-bits batch on the slot's own bits buffer, as a cloud batch is, whose launch
+// groups run the clearance kernels behind their tile / dilate kernel (issue_plan).  The spheres live on the host per model
+// (rtuf_set_link_spheres) and go to the device sorted by the label their link has when the batch is enqueued.
+static int build_clearance_spheres(rtuf_context* c, std::vector<ClearanceSphere>& out, std::vector<uint32_t>& slot_label)
+{
+  out.clear(); slot_label.clear();
+  uint32_t id = 0;
+  for (size_t mi = 0; mi < c->models.size(); mi++) {
+    const HostModel& m = c->models[mi];
+    for (size_t i = 0; i < m.sph_link.size(); i++, id++) {
+      const int l = m.sph_link[i];
+      const int label = m.labels.empty() ? 1 + m.link_base + l : (int)m.labels[(size_t)l];
+      if (label > 65535) return c->fail(RTUF_ERR_CAPACITY, "link %d: default labels are limited to 65535 links (set them with rtuf_set_link_labels)", label - 1);
+      if (!label) continue;                  // spheres of label 0 are ignored
+      const float* q = &m.sph_xyzr[4 * i];
+      out.push_back({q[0], q[1], q[2], q[3], (uint32_t)(m.link_base + l), (uint32_t)mi, (uint32_t)label, id});
+    }
+  }
+  std::stable_sort(out.begin(), out.end(), [](const ClearanceSphere& a, const ClearanceSphere& b) { return a.label_slot < b.label_slot; });
+  for (ClearanceSphere& sp : out) {
+    if (slot_label.empty() || slot_label.back() != sp.label_slot) slot_label.push_back(sp.label_slot);
+    sp.label_slot |= (uint32_t)(slot_label.size() - 1) << 16;
+  }
+  if (slot_label.size() > (size_t)kMaxClearanceLabels)
+    return c->fail(RTUF_ERR_INVALID, "the link spheres carry %d distinct non-zero labels (at most %d)", (int)slot_label.size(), kMaxClearanceLabels);
+  return RTUF_OK;
+}
+
+int rtuf_set_link_spheres(rtuf_context* c, int model, const int32_t* link, const float* xyzr, int n_spheres)
+{
+  KIDS_ALL(c, rtuf_set_link_spheres(k, model, link, xyzr, n_spheres));
+  if (!c) return RTUF_ERR_INVALID;
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (model < 0 || model >= (int)c->models.size()) return c->fail(RTUF_ERR_INVALID, "bad model id %d", model);
+  if (n_spheres < 0 || (n_spheres > 0 && (!link || !xyzr))) return c->fail(RTUF_ERR_INVALID, "bad sphere list (n_spheres=%d)", n_spheres);
+  HostModel& m = c->models[model];
+  size_t total = (size_t)n_spheres;
+  for (const HostModel& o : c->models) if (&o != &m) total += o.sph_link.size();
+  if (total > (size_t)kMaxClearanceSpheres) return c->fail(RTUF_ERR_INVALID, "%zu spheres in the context (at most %d)", total, kMaxClearanceSpheres);
+  for (int i = 0; i < n_spheres; i++) {
+    const float* q = xyzr + 4 * (size_t)i;
+    if (link[i] < 0 || link[i] >= (int)m.links.size()) return c->fail(RTUF_ERR_INVALID, "sphere %d: model %d has no link %d", i, model, (int)link[i]);
+    if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2])) return c->fail(RTUF_ERR_INVALID, "sphere %d: the centre is not finite", i);
+    if (!(std::isfinite(q[3]) && q[3] >= 0.0f)) return c->fail(RTUF_ERR_INVALID, "sphere %d: the radius must be finite and >= 0 (got %g)", i, (double)q[3]);
+  }
+  WAIT_IF_PENDING(c);
+  std::vector<int32_t> old_link(link, link + n_spheres);
+  std::vector<float> old_xyzr(xyzr, xyzr + 4 * (size_t)n_spheres);
+  old_link.swap(m.sph_link); old_xyzr.swap(m.sph_xyzr);
+  std::vector<ClearanceSphere> sorted; std::vector<uint32_t> slots;
+  const int rc = build_clearance_spheres(c, sorted, slots);
+  if (rc != RTUF_OK) { old_link.swap(m.sph_link); old_xyzr.swap(m.sph_xyzr); return rc; }      // (a refused list changes nothing)
+  c->clr_dirty = true;
+  return RTUF_OK;
+}
+
+// the device copy of the sorted spheres, as the labels stand now (no batch in flight reads it while it is dirty: the setters
+// that make it so wait for the batches in flight, and a clearance batch is enqueued only behind this)
+static int ensure_clearance_spheres(rtuf_context* c)
+{
+  if (!c->clr_dirty && c->d_clr_spheres) return RTUF_OK;
+  std::vector<ClearanceSphere> sorted; std::vector<uint32_t> slots;
+  { const int rc = build_clearance_spheres(c, sorted, slots); if (rc != RTUF_OK) return rc; }
+  hipSetDevice(c->device);
+  if (!c->d_clr_spheres) HIP_TRY(c, dev_alloc(c, &c->d_clr_spheres, (size_t)kMaxClearanceSpheres * sizeof(ClearanceSphere)));
+  if (!c->d_clr_slot_label) HIP_TRY(c, dev_alloc(c, &c->d_clr_slot_label, (size_t)kMaxClearanceLabels * sizeof(uint32_t)));
+  if (!sorted.empty()) HIP_TRY(c, hipMemcpy(c->d_clr_spheres, sorted.data(), sorted.size() * sizeof(ClearanceSphere), hipMemcpyHostToDevice));
+  if (!slots.empty()) HIP_TRY(c, hipMemcpy(c->d_clr_slot_label, slots.data(), slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  c->clr_spheres.swap(sorted); c->clr_slot_label.swap(slots);
+  c->clr_dirty = false;
+  return RTUF_OK;
+}
+
+// (no width rule: the tile and dilate kernels pack the bits of any width, and the clearance kernels read single pixels)
+static int check_clearance_call(rtuf_context* c, int n, const void* in, const void* table, int n_labels, float max_distance)
+{
+  { const int rc = check_batch_call(c, n, in && table, false); if (rc != RTUF_OK) return rc; }
+  if (n_labels < 1) return c->fail(RTUF_ERR_INVALID, "a clearance table needs at least one row per stream (n_labels=%d)", n_labels);
+  if (!(max_distance > 0.0f)) return c->fail(RTUF_ERR_INVALID, "max_distance must be > 0 (+inf is allowed; got %g)", (double)max_distance);
+  if (c->thresh_models > 0 && c->params.silhouette_dilation_px > 0)
+    return c->fail(RTUF_ERR_INVALID, "per-link depth thresholds are not supported with silhouette dilation yet");
+  for (int s = 0; s < n; s++)
+    if (!c->d_cloud_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
+  return ensure_clearance_spheres(c);
+}
+
+static BatchRequest clearance_request(int n, const void* d_depth, rtuf_link_clearance* d_table, int n_labels, float max_distance, bool u16)
+{
+  BatchRequest rq(Kind::Clearance, n, u16);
+  rq.depth = static_cast<const float*>(d_depth); rq.clr = d_table; rq.n_labels = n_labels; rq.max_distance = max_distance;
+  return rq;
+}
+
+static int link_clearance_device(rtuf_context* c, int n, const void* d_depth, rtuf_link_clearance* d_table, int n_labels, float max_distance, bool u16)
+{
+  KIDS_NEXT(c, link_clearance_device(k, n, d_depth, d_table, n_labels, max_distance, u16));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_clearance_call(c, n, d_depth, d_table, n_labels, max_distance);
+  if (rc != RTUF_OK) return rc;
+  if ((uintptr_t)d_table & 7u) return c->fail(RTUF_ERR_INVALID, "d_table must be 8-byte aligned");
+  return submit_device(c, clearance_request(n, d_depth, d_table, n_labels, max_distance, u16));
+}
+
+int rtuf_link_clearance_batch_device(rtuf_context* c, int n, const float* d_depth, rtuf_link_clearance* d_table, int n_labels, float max_distance)
+{
+  return link_clearance_device(c, n, d_depth, d_table, n_labels, max_distance, false);
+}
+
+int rtuf_link_clearance_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth, rtuf_link_clearance* d_table, int n_labels, float max_distance)
+{
+  return link_clearance_device(c, n, d_depth, d_table, n_labels, max_distance, true);
+}
+
+// host planes, synchronous: planes up, table down
+static int link_clearance_host(rtuf_context* c, int n, const void* const* depth_in, rtuf_link_clearance* table_out, int n_labels, float max_distance, bool u16)
+{
+  KIDS_NEXT(c, link_clearance_host(k, n, depth_in, table_out, n_labels, max_distance, u16));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = check_clearance_call(c, n, depth_in, table_out, n_labels, max_distance); if (rc != RTUF_OK) return rc; }
+  BatchRequest rq(Kind::Clearance, n, u16);
+  rq.n_labels = n_labels; rq.max_distance = max_distance;
+  HostPlanes hp{};
+  hp.depth = depth_in; hp.clr_table = table_out;
+  return submit_host_planes(c, rq, hp);
+}
+
+int rtuf_link_clearance_batch(rtuf_context* c, int n, const float* const* depth_in, rtuf_link_clearance* table_out, int n_labels, float max_distance)
+{
+  return link_clearance_host(c, n, reinterpret_cast<const void* const*>(depth_in), table_out, n_labels, max_distance, false);
+}
+
+int rtuf_link_clearance_batch_u16(rtuf_context* c, int n, const uint16_t* const* depth_mm_in, rtuf_link_clearance* table_out, int n_labels, float max_distance)
+{
+  return link_clearance_host(c, n, reinterpret_cast<const void* const*>(depth_mm_in), table_out, n_labels, max_distance, true);
 }
 
 int rtuf_wait_oldest(rtuf_context* c)

@@ -384,6 +384,39 @@ struct CloudArgs {
   int io_u16;
 };
 
+// Link clearance tables (include/rtuf.h, LINK CLEARANCE TABLES): the clearance kernels of one launch group.  Like the cloud
+// kernels they run behind the group's tile (or dilate) kernel on its lane and read the mask bits it wrote; streams are
+// batch-absolute.  The context's spheres are sorted by label (label 0 left out); a batch uses the first n_spheres of them,
+// those whose label is below n_labels.
+constexpr int kMaxClearanceSpheres = 4096;   // spheres of a context
+constexpr int kMaxClearanceLabels = 256;     // distinct non-zero labels among them (the label slots of a workgroup's LDS rows)
+constexpr int kClearanceTrip = 1024;         // spheres staged in LDS at a time
+struct alignas(16) ClearanceSphere {         // one sphere as rtuf_set_link_spheres gave it
+  float x, y, z, r;                          // centre in the link's vertex frame, radius
+  uint32_t link;                             // global link index (row of link_tf)
+  uint32_t model;
+  uint32_t label_slot;                       // label | slot << 16: slot = rank of the label among the distinct labels in use
+  uint32_t id;                               // context-global id: model order, then list order
+};
+static_assert(sizeof(ClearanceSphere) == 32, "two 16-byte loads");
+struct ClearanceArgs {
+  const float* depth;            // [n][H][W] sensor planes (f32 metres or, with io_u16, uint16 millimetres): the whole batch
+  const uint32_t* bits;          // [n][H][ceil(W/32)] mask bits of the batch (the library's buffer of the batch slot)
+  const CloudIntrinsics* intr;   // [max_streams] kx, ky, cx, cy
+  const ClearanceSphere* spheres;// [n_spheres] sorted by label
+  const uint32_t* slot_label;    // [n_slots] the label of every slot
+  const Camera* cams;            // [n]
+  const double* link_tf;         // [n][n_links][16]
+  const uint64_t* model_mask;    // [n]
+  float4* posed;                 // [max_streams][kMaxClearanceSpheres slots used: n_spheres]: camera-frame centre and radius; radius -1: not of this stream
+  unsigned long long* table;     // [n][n_labels] rows of 16 bytes: while the batch runs {key, count, 0}, then rtuf_link_clearance
+  int n_spheres, n_slots, n_links, n_labels;
+  int group_base, group_size;
+  int width, height;
+  float max_distance;
+  int io_u16;
+};
+
 struct FkArgs {
   const int32_t* parent;        // [F]
   const int32_t* joint_type;    // [F]
@@ -416,6 +449,7 @@ void launch_tile(const TileArgs& a, bool two_kernel, bool cover_pass, hipStream_
 void launch_compare(const CompareArgs& a, hipStream_t st);
 void launch_dilate_compare(const DilateArgs& a, hipStream_t st);     // a.bits selects the mask-only variant, a.io_u16 the 16UC1 one
 void launch_cloud(const CloudArgs& a, hipStream_t st);               // a.capacity selects the compacted form (count, scan, emit), a.io_u16 the 16UC1 variants
+void launch_clearance(const ClearanceArgs& a, hipStream_t st);       // spheres, zero, clearance, finish: the group's rows of the table, a.io_u16 selects the 16UC1 variant
 void launch_spin(unsigned long long ticks, hipStream_t st);      // a one-wave kernel that idles for `ticks` of the 100 MHz clock
 
 }  // namespace rtuf

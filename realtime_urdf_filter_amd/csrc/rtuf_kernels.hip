@@ -3369,4 +3369,217 @@ void launch_cloud(const CloudArgs& a, hipStream_t st)
   else hipLaunchKernelGGL(cloud_emit_kernel<false>, dim3(row_blocks), dim3(kBlock), 0, st, a);
 }
 
+
+// ---- link clearance tables (include/rtuf.h, LINK CLEARANCE TABLES) -------------------------------------------------------
+// A clearance batch is a mask-bits batch too: behind the launch group's tile (or dilate) kernel its lane poses the spheres of
+// the group's streams, sets the group's rows to "nothing", takes per (stream, label) the minimum of {clearance, pixel} and the
+// number of kept points within max_distance over all (kept point, sphere) pairs, and turns the rows into rtuf_link_clearance.
+// Minima and integer counts only: no result depends on the order of execution, and the box culling below is conservative.
+
+constexpr unsigned long long kClearanceNone = ~0ull;      // a row's key while no pair is within max_distance
+
+// One lane per (stream, sphere): centre in the camera frame and radius; radius -1 where the stream does not render the model.
+__global__ __launch_bounds__(kBlock) void clearance_spheres_kernel(ClearanceArgs a)
+{
+  const uint32_t t = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  if (t >= (uint32_t)a.n_spheres) return;
+  const int stream = a.group_base + (int)blockIdx.y;
+  const ClearanceSphere sp = a.spheres[t];
+  float4 o = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+  if ((a.model_mask[stream] >> sp.model) & 1ull) {
+    const float c[3] = {sp.x, sp.y, sp.z};
+    float out[3];
+    const Camera* cam = a.cams + stream;
+    clearance_centre(a.link_tf + ((size_t)stream * (size_t)a.n_links + sp.link) * 16u, cam->cam_tf, cam->offset_inv, c, out);
+    o = make_float4(out[0], out[1], out[2], sp.r);
+  }
+  a.posed[(size_t)stream * (size_t)a.n_spheres + t] = o;
+}
+
+// The group's rows start from {no key, count 0} on every run, re-run and replay.  (A kernel, not a captured memset: see
+// zero_words_kernel.)
+__global__ __launch_bounds__(kBlock) void clearance_zero_kernel(unsigned long long* rows, size_t n_rows)
+{
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_rows; i += (size_t)gridDim.x * kBlock) {
+    rows[2 * i] = kClearanceNone;
+    rows[2 * i + 1] = 0ull;
+  }
+}
+
+__device__ __forceinline__ float clr_wave_min(float v)
+{
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ float clr_wave_max(float v)
+{
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ unsigned long long clr_wave_min_u64(unsigned long long v)
+{
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
+    const unsigned long long w = ((unsigned long long)hi << 32) | lo;
+    v = w < v ? w : v;
+  }
+  return v;
+}
+__device__ __forceinline__ float clr_uniform(float v) { return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v))); }
+
+// One wave per 64-pixel chunk of a row (cloud_chunk's pixels), four chunks per workgroup, all of one stream.  The stream's posed
+// spheres pass through LDS in trips of kClearanceTrip; every wave with a kept point walks them in label order, skips a sphere
+// whose distance to the wave's box of points is beyond max_distance + r by more than the arithmetic could be wrong, and keeps
+// per lane the smallest key {order bits of the clearance, pixel} of the label's pairs within max_distance.  Where the label
+// changes the wave's minimum and its number of lanes with such a pair go to the workgroup's LDS rows; the rows the workgroup
+// touched go to the table at the end: one 64-bit atomicMin and one atomicAdd each.  Row 0 takes every label's pairs.
+template <bool U16>
+__global__ __launch_bounds__(kBlock) void clearance_kernel(ClearanceArgs a)
+{
+  __shared__ float4 s_sph[kClearanceTrip];
+  __shared__ uint32_t s_slot[kClearanceTrip];
+  __shared__ unsigned long long s_key[kMaxClearanceLabels + 1];
+  __shared__ uint32_t s_cnt[kMaxClearanceLabels + 1];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int stream = a.group_base + (int)blockIdx.y;
+  const int cpr = (a.width + 63) >> 6;                      // chunks per row
+  const uint32_t w = blockIdx.x * (uint32_t)(kBlock / 64) + (uint32_t)wid;
+  for (int i = tid; i <= a.n_slots; i += kBlock) { s_key[i] = kClearanceNone; s_cnt[i] = 0u; }
+  float px = 0.0f, py = 0.0f, pz = 0.0f;
+  bool kept = false;
+  uint32_t pixel = 0;
+  if (w < (uint32_t)a.height * (uint32_t)cpr) {
+    const int v = (int)(w / (uint32_t)cpr), u = (int)(w - (uint32_t)v * (uint32_t)cpr) * 64 + lane;
+    if (u < a.width) {
+      const size_t row = (size_t)stream * a.height + (size_t)v;
+      const size_t pix = row * (size_t)a.width + (size_t)u;
+      const float s = U16 ? u16_to_metres(reinterpret_cast<const uint16_t*>(a.depth)[pix]) : a.depth[pix];
+      const uint32_t word = a.bits[row * (size_t)((a.width + 31) >> 5) + (size_t)(u >> 5)];
+      kept = !((word >> (u & 31)) & 1u) && cloud_sensor_valid(s);
+      cloud_point(u, v, s, a.intr[stream], px, py, pz);
+      pixel = (uint32_t)(v * a.width + u);
+    }
+  }
+  const bool any = __ballot(kept) != 0ull;                  // (wave-uniform)
+  // a workgroup without a kept point stages no sphere and touches no row (the barrier also publishes the rows' initial values)
+  if (!__syncthreads_or(any ? 1 : 0)) return;
+  const float inf = __uint_as_float(0x7f800000u);
+  const float lox = clr_wave_min(kept ? px : inf), loy = clr_wave_min(kept ? py : inf), loz = clr_wave_min(kept ? pz : inf);
+  const float hix = clr_wave_max(kept ? px : -inf), hiy = clr_wave_max(kept ? py : -inf), hiz = clr_wave_max(kept ? pz : -inf);
+  unsigned long long best = kClearanceNone, best0 = kClearanceNone;
+  bool hit = false, hit0 = false;
+  int cur_slot = -1;
+  auto flush = [&](int row, unsigned long long& b, bool& h) {
+    const unsigned long long m = __ballot(h);
+    if (m) {
+      const unsigned long long k = clr_wave_min_u64(b);
+      if (lane == 0) { atomicMin(&s_key[row], k); atomicAdd(&s_cnt[row], (uint32_t)__popcll(m)); }
+    }
+    b = kClearanceNone; h = false;
+  };
+  for (int t0 = 0; t0 < a.n_spheres; t0 += kClearanceTrip) {
+    const int nt = min(kClearanceTrip, a.n_spheres - t0);
+    __syncthreads();                         // (the rows are initialised; every wave is done with the trip before)
+    for (int i = tid; i < nt; i += kBlock) {
+      s_sph[i] = a.posed[(size_t)stream * (size_t)a.n_spheres + (size_t)(t0 + i)];
+      s_slot[i] = a.spheres[t0 + i].label_slot >> 16;
+    }
+    __syncthreads();
+    if (!any) continue;
+    for (int j = 0; j < nt; j++) {
+      const float4 q = s_sph[j];
+      const float cx = clr_uniform(q.x), cy = clr_uniform(q.y), cz = clr_uniform(q.z), r = clr_uniform(q.w);
+      if (r < 0.0f) continue;                // the stream does not render this sphere's model
+      const int slot = __builtin_amdgcn_readfirstlane((int)s_slot[j]);
+      if (slot != cur_slot) {
+        if (cur_slot >= 0) flush(cur_slot + 1, best, hit);
+        cur_slot = slot;
+      }
+      // distance from the centre to the box of the wave's kept points: no point of the wave is nearer.  A computed clearance
+      // is below max_distance only if the computed distance is below (max_distance + r)(1 + 2^-23); distance and bound carry
+      // a few rounding errors of 2^-24 each: a margin of a thousandth is far beyond them (and +inf never rejects)
+      const float ex = fmaxf(fmaxf(lox - cx, cx - hix), 0.0f), ey = fmaxf(fmaxf(loy - cy, cy - hiy), 0.0f), ez = fmaxf(fmaxf(loz - cz, cz - hiz), 0.0f);
+      const float bound = sqrtf((ex * ex + ey * ey) + ez * ez);
+      if (bound > (a.max_distance + r) * 1.001f + 1e-30f) continue;
+      const float c = clearance_point_sphere(px, py, pz, cx, cy, cz, r);
+      if (kept && c < a.max_distance) {
+        const unsigned long long key = ((unsigned long long)clearance_order_bits(c) << 32) | pixel;
+        best = key < best ? key : best; hit = true;
+        best0 = key < best0 ? key : best0; hit0 = true;
+      }
+    }
+  }
+  if (any) {
+    if (cur_slot >= 0) flush(cur_slot + 1, best, hit);
+    flush(0, best0, hit0);
+  }
+  __syncthreads();
+  for (int i = tid; i <= a.n_slots; i += kBlock) {
+    const uint32_t cnt = s_cnt[i];
+    if (!cnt) continue;
+    const uint32_t label = i ? a.slot_label[i - 1] : 0u;
+    unsigned long long* row = a.table + ((size_t)stream * (size_t)a.n_labels + label) * 2u;
+    atomicMin(row, s_key[i]);
+    atomicAdd(reinterpret_cast<uint32_t*>(row + 1), cnt);
+  }
+}
+
+// One wave per (stream, label): the row's key becomes clearance and pixel, and the sphere is the smallest id among the row's
+// spheres (row 0: all of them) that give exactly that clearance at that pixel.
+template <bool U16>
+__global__ __launch_bounds__(kBlock) void clearance_finish_kernel(ClearanceArgs a)
+{
+  const uint32_t w = (blockIdx.x * (uint32_t)kBlock + threadIdx.x) >> 6;
+  if (w >= (uint32_t)a.group_size * (uint32_t)a.n_labels) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int sl = (int)(w / (uint32_t)a.n_labels), label = (int)(w - (uint32_t)sl * (uint32_t)a.n_labels), stream = a.group_base + sl;
+  unsigned long long* row = a.table + ((size_t)stream * (size_t)a.n_labels + (size_t)label) * 2u;
+  const unsigned long long key = row[0];
+  const uint32_t cnt = (uint32_t)row[1];
+  uint32_t cbits = 0x7f800000u, pixel = 0xffffffffu, id = 0xffffffffu;
+  if (key != kClearanceNone) {
+    cbits = clearance_bits_of_order((uint32_t)(key >> 32));
+    pixel = (uint32_t)key;
+    const int v = (int)(pixel / (uint32_t)a.width), u = (int)(pixel - (uint32_t)v * (uint32_t)a.width);
+    const size_t pix = (size_t)stream * (size_t)a.width * (size_t)a.height + (size_t)pixel;
+    const float s = U16 ? u16_to_metres(reinterpret_cast<const uint16_t*>(a.depth)[pix]) : a.depth[pix];
+    float px, py, pz;
+    cloud_point(u, v, s, a.intr[stream], px, py, pz);
+    for (int j = lane; j < a.n_spheres; j += 64) {
+      const ClearanceSphere sp = a.spheres[j];
+      if (label != 0 && (int)(sp.label_slot & 0xffffu) != label) continue;
+      const float4 q = a.posed[(size_t)stream * (size_t)a.n_spheres + (size_t)j];
+      if (q.w < 0.0f) continue;
+      if (__float_as_uint(clearance_point_sphere(px, py, pz, q.x, q.y, q.z, q.w)) == cbits) id = min(id, sp.id);
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) id = min(id, (uint32_t)__shfl_xor((int)id, o));
+  }
+  if (lane == 0) {
+    row[0] = (unsigned long long)cbits | (unsigned long long)pixel << 32;
+    row[1] = (unsigned long long)id | (unsigned long long)cnt << 32;
+  }
+}
+
+void launch_clearance(const ClearanceArgs& a, hipStream_t st)
+{
+  const size_t rows = (size_t)a.group_size * (size_t)a.n_labels;
+  const size_t zblocks = (rows + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(clearance_zero_kernel, dim3((unsigned)(zblocks > 4096 ? 4096 : zblocks)), dim3(kBlock), 0, st,
+                     a.table + (size_t)a.group_base * (size_t)a.n_labels * 2u, rows);
+  if (a.n_spheres > 0) {
+    hipLaunchKernelGGL(clearance_spheres_kernel, dim3((unsigned)((a.n_spheres + kBlock - 1) / kBlock), (unsigned)a.group_size), dim3(kBlock), 0, st, a);
+    const size_t waves = (size_t)a.height * (size_t)((a.width + 63) >> 6);
+    const dim3 grid((unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64)), (unsigned)a.group_size);
+    if (a.io_u16) hipLaunchKernelGGL(clearance_kernel<true>, grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL(clearance_kernel<false>, grid, dim3(kBlock), 0, st, a);
+  }
+  const unsigned fblocks = (unsigned)((rows * 64u + kBlock - 1) / kBlock);
+  if (a.io_u16) hipLaunchKernelGGL(clearance_finish_kernel<true>, dim3(fblocks), dim3(kBlock), 0, st, a);
+  else hipLaunchKernelGGL(clearance_finish_kernel<false>, dim3(fblocks), dim3(kBlock), 0, st, a);
+}
+
 }  // namespace rtuf

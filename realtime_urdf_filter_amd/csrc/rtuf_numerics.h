@@ -1,14 +1,15 @@
 // rtuf_numerics.h -- the arithmetic whose exact bits the results depend on and that something besides the kernels checks or
 // shares: the 24-bit depth and its bit-pattern forms, the depth keys' encoding of a near fragment's float z, the set-up's
 // 32-bit edge constants, the key format's host-side rules, the compare threshold's constants, division core and the rule
-// that admits that core, the pixel classes of the link residual tables, and the point of a filtered point cloud.
+// that admits that core, the pixel classes of the link residual tables, the point of a filtered point cloud, and the sphere centres and
+// point-to-sphere clearances of the link clearance tables.
 //
 // Included by the kernels (rtuf_kernels.hip, device and host pass), the host API (rtuf_api.cpp), scripts/fdiv_check.hip (which
 // holds div_core against the IEEE division on the GPU) and the CPU checks (tests/fast_class_check.cpp, tests/near_key_check.cpp:
 // plain g++, no ROCm headers), which hold every function here against a reference form of their own.  Every function has ONE
 // body, written with the HIP intrinsics the kernels use; only where HIP is absent (the CPU checks) does this file define the
-// handful of them it needs, as portable forms with the same results.  No product here feeds an addition, so the includer's
-// -ffp-contract has nothing to fuse.
+// handful of them it needs, as portable forms with the same results.  No product here feeds an addition -- except in the link clearance
+// functions at the end, which say so: their includers compile with -ffp-contract=off (the library, tests/clearance_check.cpp).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -191,6 +192,55 @@ RTUF_NUMERIC_HD void cloud_point(int u, int v, float s, const CloudIntrinsics& k
   y = ys * k.ky;
   z = s;
 }
+
+// ---------------------------------------------------------------------------------------
+// link clearance tables (include/rtuf.h, LINK CLEARANCE TABLES): a sphere's centre in the camera frame, and the clearance of
+// a cloud point to a sphere.  Products feed sums here: both functions need -ffp-contract=off, which the library and the CPU
+// check compile with, so that every product and every sum is rounded on its own.
+// ---------------------------------------------------------------------------------------
+
+// One row-times-point product chain of a column-major OpenGL matrix: ((m0 x + m4 y) + m8 z) + m12, rows 0 .. 2.
+RTUF_NUMERIC_HD void clearance_transform(const double* m, const double p[3], double out[3])
+{
+  for (int r = 0; r < 3; r++) {
+    const double a = m[r] * p[0], b = m[4 + r] * p[1], c = m[8 + r] * p[2];
+    out[r] = ((a + b) + c) + m[12 + r];
+  }
+}
+
+// Centre of a link sphere in the camera's optical frame: offset_inv * (cam_tf * (link_tf * (c, 1))), three matrix-vector
+// products in double (the matrices' last rows are not read: they are 0 0 0 1), the result rounded to float.
+RTUF_NUMERIC_HD void clearance_centre(const double* link_tf, const double* cam_tf, const double* offset_inv, const float c[3], float out[3])
+{
+  const double p0[3] = {(double)c[0], (double)c[1], (double)c[2]};
+  double p1[3], p2[3], p3[3];
+  clearance_transform(link_tf, p0, p1);
+  clearance_transform(cam_tf, p1, p2);
+  clearance_transform(offset_inv, p2, p3);
+  out[0] = (float)p3[0]; out[1] = (float)p3[1]; out[2] = (float)p3[2];
+}
+
+// Clearance of point (px, py, pz) to the sphere (cx, cy, cz, r): sqrt((dx dx + dy dy) + dz dz) - r with d = point - centre,
+// every operation a single float operation, the square root correctly rounded (sqrtf: IEEE on host and device).
+RTUF_NUMERIC_HD float clearance_point_sphere(float px, float py, float pz, float cx, float cy, float cz, float r)
+{
+  const float dx = px - cx, dy = py - cy, dz = pz - cz;
+  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+  const float d2 = (xx + yy) + zz;
+  return sqrtf(d2) - r;
+}
+
+// The bits of a clearance (never NaN where it is used, never -0) as an unsigned number of the same order.
+RTUF_NUMERIC_HD uint32_t clearance_order_bits(float c)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+  const uint32_t b = __float_as_uint(c);
+#else
+  uint32_t b; memcpy(&b, &c, 4);
+#endif
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+RTUF_NUMERIC_HD uint32_t clearance_bits_of_order(uint32_t o) { return (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o; }
 
 #ifdef __HIP__
 // The IEEE division without the instructions that only matter for operands near the ends of the exponent range: the compiler

@@ -224,6 +224,8 @@ class RealtimeURDFFilter:
         self.masked_depth_ = None
         self.mask_ = None
         self._ctx = None
+        self.link_spheres_ = {}                     # setLinkSpheres: {model: (link, xyzr)}, kept across contexts
+        self._spheres_given_ = False                # the context holds link_spheres_ (cleared by initGL and setLinkSpheres)
         self._model_ids = []
         self._batch_masked = None
         self._batch_mask = None
@@ -276,6 +278,7 @@ class RealtimeURDFFilter:
         if self._ctx is not None:
             self._ctx.close()
         self._cloud_intr_given_ = None              # (the new context has no cloud intrinsics: cloud() gives them again)
+        self._spheres_given_ = False                # (... and no link spheres: clearance() gives them again)
         self._ctx = _capi.Context(self.width_, self.height_, self.max_streams, self.device, p)
         self.loadModels()
         if not self.renderers_:
@@ -436,6 +439,44 @@ class RealtimeURDFFilter:
             return self._ctx.cloud_batch(d)[0]
         points, index, counts = self._ctx.cloud_compact_batch(d, width * height)
         return points[0, :counts[0]], index[0, :counts[0]]
+
+    def setLinkSpheres(self, model, link, xyzr):
+        """New, beyond the reference: the sphere list of model `model` (index into the loaded models) for clearance(): link [n] =
+        renderable index within the model, xyzr [n,4] = centre in the renderable's (link's) frame -- a draw's pre_op applied to its
+        vertices first -- and radius
+        (geometry.bounding_spheres makes them from a draw's vertices).  Kept across image-size changes."""
+        li = np.ascontiguousarray(link, np.int32).reshape(-1).copy()
+        q = np.ascontiguousarray(xyzr, np.float32).reshape(-1, 4).copy()
+        self.link_spheres_[int(model)] = (li, q)
+        self._spheres_given_ = False
+
+    def clearance(self, depth, projection_matrix, width, height, max_distance, timestamp=None):
+        """New, beyond the reference: per link label, the nearest kept point to the link's spheres (include/rtuf.h, LINK
+        CLEARANCE TABLES) for the camera, link poses and intrinsics cloud() would use and the spheres of setLinkSpheres().
+        depth: [H,W] float32 metres or uint16 millimetres.  Returns the [numLinkResidualRows()] structured array
+        (_capi.LINK_CLEARANCE_DTYPE), row = label, row 0 = the whole robot; None where filter() would have returned without a
+        result."""
+        self._ensure_size(width, height)
+        if not self.renderers_:
+            return None
+        intr = getattr(self, "cloud_intrinsics_", None)
+        if intr is None:
+            raise RuntimeError("clearance(): no intrinsics yet (getProjectionMatrix sets them)")
+        try:
+            self._stage_stream(0, projection_matrix, self.tf_, timestamp)
+        except Exception as e:                      # noqa: BLE001 - ROS_ERROR + return (quirk Q6)
+            log.error("%s", e)
+            return None
+        if getattr(self, "_cloud_intr_given_", None) != intr:      # (initGL clears it with every new context)
+            self._ctx.set_cloud_intrinsics(0, intr)
+            self._cloud_intr_given_ = intr
+        if not self._spheres_given_:
+            for model, (li, q) in sorted(self.link_spheres_.items()):
+                self._ctx.set_link_spheres(model, li, q)
+            self._spheres_given_ = True
+        d = np.asarray(depth)
+        d = d.astype(np.uint16 if d.dtype == np.uint16 else np.float32, copy=False).reshape(1, height, width)
+        return self._ctx.link_clearance_batch(d, self.numLinkResidualRows(), max_distance)[0]
 
     def numLinkResidualRows(self):
         """Rows of a link_residuals() table: one more than the largest label in effect."""

@@ -272,3 +272,35 @@ class PackageResolver:
         path = self.path_of(uri)
         with open(path, "rb") as f:
             return meshes.load_mesh(path, f.read(), up_axis_to_y=self.up_axis_to_y, apply_unit=self.apply_unit)
+
+
+def bounding_spheres(vertices, segments=1):
+    """Spheres around a draw's vertices for rtuf_set_link_spheres (include/rtuf.h, LINK CLEARANCE TABLES): the bounding box's
+    longest axis (the first of equals) is split into `segments` slabs of equal width, and every slab that holds vertices
+    gives one sphere (give it vertices in the link's frame, i.e. with the draw's pre_op applied) -- centre = the middle of the box of ITS vertices (float32), radius = the largest distance from that
+    centre to one of them, rounded up to float32, so every vertex lies inside.  vertices [n,3] -> [m,4] float32 (x, y, z, r),
+    m <= segments, in slab order.  All arithmetic in double; host.hpp's bounding_spheres is the same, bit for bit."""
+    v = np.asarray(vertices, np.float32).reshape(-1, 3).astype(np.float64)
+    segments = max(int(segments), 1)
+    if not len(v):
+        return np.zeros((0, 4), np.float32)
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    ext = hi - lo
+    a = int(np.argmax(ext))
+    if ext[a] > 0:
+        slab = np.minimum(np.floor(((v[:, a] - lo[a]) / ext[a]) * segments).astype(np.int64), segments - 1)
+    else:
+        slab = np.zeros(len(v), np.int64)
+    out = []
+    for k in range(segments):
+        p = v[slab == k]
+        if not len(p):
+            continue
+        c = ((p.min(axis=0) + p.max(axis=0)) * 0.5).astype(np.float32)
+        d = p - c.astype(np.float64)
+        dist = float(np.sqrt(((d[:, 0] * d[:, 0]) + (d[:, 1] * d[:, 1])) + (d[:, 2] * d[:, 2])).max())
+        r = np.float32(dist)
+        if float(r) < dist:
+            r = np.nextafter(r, np.float32(np.inf))
+        out.append((c[0], c[1], c[2], r))
+    return np.array(out, np.float32).reshape(-1, 4)
