@@ -1,0 +1,205 @@
+"""GPU (-m gpu): the fill rule on exact ties in every coverage path, on the lattice scenes of tests/lattice_scenes.py.
+
+Every scene's triangles lie on the 1/256 px lattice, edge to edge, one robot link per colour with neighbours in different
+colours, so the label plane and the virtual depth plane show which triangle got every pixel.  The expectation is the CPU
+oracle's (tests/test_fill_rule_cpu.py shows it equal to the integer rasteriser of tests/fill_rule.py; the prim plane is
+checked against that here as well), compared bit for bit on every route that rasterises.  The sensor plane lies half a metre
+behind the front layer of the geometry, so the mask is the coverage.
+
+Each scene runs in two draw orders.  Where two triangles claim one pixel at one depth the earlier draw keeps it, so a
+triangle that wrongly covers a neighbour's pixel shows only if it is drawn first: in one of the two orders it is.
+
+ctx.stats() pins the path a scene is built for (fragments, records, the cover pass, the exact-z pass), so that a scene cannot
+take another route unnoticed.
+
+Run as a script (RTUF_SMALL_LAUNCH=0 python tests/test_fill_rule_gpu.py) every scene goes through the 256-thread tile kernels:
+the threshold is read once per process, so test_every_scene_256_thread_kernels starts one."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if __name__ == "__main__":
+    sys.path.insert(0, ROOT)
+
+import lattice_scenes as L
+import realtime_urdf_filter_amd as R
+from bench_support.labels_check import expected_labels, workload_draws
+from bench_support.virtual_check import bits_equal_f32, expected_virtual, metres_to_u16
+from oracle import bindings as O
+from realtime_urdf_filter_amd.filter import depth_f32_to_u16, depth_u16_to_f32
+from test_batch_status_gpu import bits_equal, params
+from test_silhouette_dilation_gpu import pack_bits
+
+pytestmark = pytest.mark.gpu
+REPLACE, MAX_DIFF = 5.0, 0.05
+
+
+class GScene:
+    """A lattice scene as a batch of identical streams under different sensor planes, with the oracle's planes of each."""
+
+    def __init__(self, name, reverse):
+        self.name, self.sc = name + ("_reversed" if reverse else ""), L.scene(name)
+        self.W, self.H = self.sc.W, self.sc.H
+        self.n = 1 if name.startswith("limit") else 3
+        self.wl, _ = L.workload(name, self.n, reverse)
+        front = min(self.sc.zs)
+        yy, xx = np.mgrid[0:self.H, 0:self.W]
+        self.mm = np.stack([(int(round((front + 0.5) * 1000)) + 7 * s + (xx + yy) % 3).astype(np.uint16) for s in range(self.n)])
+        self.depth = np.ascontiguousarray(depth_u16_to_f32(self.mm), np.float32)          # whole millimetres: one oracle run serves f32 and 16UC1
+        assert np.array_equal(depth_f32_to_u16(self.depth), self.mm)
+        wl = self.wl
+        prep = [O.PreparedFrame(self.depth[s], wl.projection[s], wl.oracle_draws(s), wl.offset_inv[s], wl.cam_tf[s], z_near=L.NEAR, z_far=L.FAR,
+                                max_diff=MAX_DIFF, replace_value=REPLACE, want_debug=True) for s in range(self.n)]
+        O.run_prepared(prep, O.usable_threads())
+        self.masked, self.mask = np.stack([f.masked for f in prep]), np.stack([f.mask for f in prep])
+        self.zwin, self.prim = np.stack([f.zwin for f in prep]), np.stack([f.prim for f in prep])
+        want = L.expected_prim(name, self.n, reverse)
+        for s in range(self.n):
+            assert np.array_equal(self.prim[s], want), "%s: the oracle and the integer rule differ" % self.name
+        winner = L.reference(name)[0]
+        assert np.array_equal(self.mask[0] > 0, (winner >= 0) & (np.asarray(self.sc.zs)[np.maximum(winner, 0)] == front))       # the mask is the front layer's coverage
+        lab, nt = workload_draws(wl)
+        self.labels = np.stack([expected_labels(self.prim[s], lab, nt) for s in range(self.n)])
+        self.n_labels = len(wl.models[0]) + 1
+        self.zsurface = np.where(self.prim == -1, np.float32(np.nan), self.zwin).astype(np.float32)
+
+    def virtual(self, empty, u16=False):
+        v = expected_virtual(self.zwin, self.prim, L.NEAR, L.FAR, empty)
+        return metres_to_u16(v) if u16 else v
+
+    def context(self, max_streams, n, **kw):
+        p = params(replace=REPLACE, max_diff=MAX_DIFF, **kw)
+        p.near_plane, p.far_plane = L.NEAR, L.FAR
+        ctx = R.Context(self.W, self.H, max_streams, 0, p)
+        ids = self.wl.load_into(ctx)
+        self.wl.stage(ctx, ids, n=n)
+        return ctx
+
+
+_scenes = {}
+
+
+def gscene(name, reverse=False):
+    if (name, reverse) not in _scenes:
+        _scenes[(name, reverse)] = GScene(name, reverse)
+    return _scenes[(name, reverse)]
+
+
+def same(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, what
+    bad = ~((got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))) if got.dtype == np.float32 else got != want
+    if bad.any():
+        s, y, x = np.argwhere(bad)[0]
+        raise AssertionError("%s: %d pixels differ (first: stream %d y %d x %d: %r instead of %r)" % (what, int(bad.sum()), s, y, x, got[s, y, x], want[s, y, x]))
+
+
+def filter_routes(g, ctx, n, what, two_kernel=False):
+    """Every route of one context, each batch twice (the cover pass has made up its mind by the second); returns the
+    statistics of the second plain batch."""
+    for rep in range(2):
+        w = "%s %s batch %d" % (g.name, what, rep)
+        masked, mask = ctx.filter_batch(g.depth[:n])
+        same(mask, g.mask[:n], w + ": mask")
+        assert bits_equal(masked, g.masked[:n]), w + ": masked depth"
+        if two_kernel:
+            assert bits_equal_f32(ctx.read_zsurface(n), g.zsurface[:n]), w + ": z surface"
+    stats = ctx.stats()
+    for rep in range(2):
+        w = "%s %s batch %d" % (g.name, what, rep)
+        masked, mask = ctx.filter_batch_u16(g.mm[:n])
+        same(mask, g.mask[:n], w + ": 16UC1 mask")
+        same(masked, depth_f32_to_u16(g.masked[:n]), w + ": 16UC1 masked depth")
+        if two_kernel:          # (the other kinds of batch take the fused kernels in such a context too: met below)
+            continue
+        bits = np.zeros((n, ctx.mask_bits_words()), np.uint32)
+        ctx.filter_batch_bits_async(g.depth[:n], bits)
+        ctx.sync()
+        for s in range(n):
+            assert np.array_equal(bits[s], pack_bits(g.mask[s])), "%s: mask bits, stream %d" % (w, s)
+        masked, mask, lab = ctx.filter_batch_labels(g.depth[:n])
+        same(lab, g.labels[:n], w + ": labels")
+        same(mask, g.mask[:n], w + ": mask beside the labels")
+        assert bits_equal(masked, g.masked[:n]), w + ": masked depth beside the labels"
+        for u16 in (False, True):
+            v, lab = ctx.render_batch(n, -1.5, labels=True, u16=u16)
+            same(v, g.virtual(-1.5, u16)[:n], w + ": virtual depth%s" % (" 16UC1" if u16 else ""))
+            same(lab, g.labels[:n], w + ": rendered labels")
+        table = ctx.link_residuals_batch(g.depth[:n], g.n_labels)
+        for s in range(n):
+            want = np.bincount(g.labels[s].reshape(-1), minlength=g.n_labels)
+            assert np.array_equal(table[s]["pixels"], want), "%s: residual table pixels, stream %d: %s instead of %s" % (w, s, table[s]["pixels"], want)
+    return stats
+
+
+def path_checks(name, g, st, n):
+    """What ctx.stats() must show after the scene's second plain filter batch of n streams."""
+    kind, sc = L.kind_of(name), g.sc
+    winner = L.reference(name)[0]
+    assert st["batch_status"] == 0, (name, st)
+    if kind in ("tiny", "small"):
+        frag_pixels = int(np.isin(winner, np.flatnonzero(sc.fragment_sized())).sum())
+        assert frag_pixels > 0 and st["fragments_binned"] == n * frag_pixels, (name, frag_pixels, n, st)
+        if kind == "small":          # the squares across tile borders are records
+            assert st["triangles_binned"] > 0 and st["bin_entries"] > 0, (name, st)
+    elif kind == "near":
+        assert st["fragments_binned"] == 0 and st["exact_tiles"] > 0, (name, st)
+    elif kind == "records":
+        assert st["triangles_binned"] > 0 and st["bin_entries"] > 0, (name, st)
+    elif kind == "tiles":
+        assert st["cover_pass"] == 1, (name, st)
+        if L.covered_tiles(name):
+            assert st["cover_tiles"] > 0, (name, st)
+        if "_cover_" in name:
+            assert st["occluded_entries"] > 0, (name, st)
+
+
+def run_scene(name):
+    limit = name.startswith("limit")
+    g = gscene(name)
+    # a batch of one stream
+    ctx = g.context(1, 1)
+    st = filter_routes(g, ctx, 1, "one stream")
+    path_checks(name, g, st, 1)
+    ctx.close()
+    # two-kernel mode
+    ctx = g.context(g.n, g.n, flags=R.FLAG_TWO_KERNEL)
+    st = filter_routes(g, ctx, g.n, "two-kernel", two_kernel=True)
+    path_checks(name, g, st, g.n)
+    ctx.close()
+    if limit:
+        return
+    # a batch of 3 in a context of 4 with three raster lanes
+    ctx = g.context(4, 3, raster_lanes=3)
+    st = filter_routes(g, ctx, 3, "3 of 4 streams, 3 lanes")
+    path_checks(name, g, st, 3)
+    ctx.close()
+    # the other draw order
+    g = gscene(name, reverse=True)
+    ctx = g.context(4, 3, raster_lanes=3)
+    filter_routes(g, ctx, 3, "3 of 4 streams, 3 lanes")
+    ctx.close()
+
+
+@pytest.mark.parametrize("name", L.NAMES)
+def test_every_route_gives_every_pixel_to_the_triangle_the_rule_names(name):
+    run_scene(name)
+
+
+def test_every_scene_256_thread_kernels():
+    """The same checks with RTUF_SMALL_LAUNCH=0: every launch takes the 256-thread tile kernels (the 2048 x 2048 scene does
+    anyway)."""
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, cwd=ROOT, timeout=600,
+                       env=dict(os.environ, RTUF_SMALL_LAUNCH="0"))
+    assert r.returncode == 0 and "scenes ok" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+
+
+if __name__ == "__main__":
+    for scene_name in L.NAMES:
+        if not scene_name.startswith("limit"):
+            run_scene(scene_name)
+    print("scenes ok")
