@@ -9,6 +9,7 @@ import pytest
 import realtime_urdf_filter_amd as R
 from bench_support import configs as CF
 from bench_support import workloads as WL
+from gpu_support import bits_equal
 from oracle import bindings as O
 
 pytestmark = pytest.mark.gpu
@@ -21,10 +22,6 @@ def params(wl, two_kernel=False):
     if two_kernel:
         p.flags |= R.FLAG_TWO_KERNEL
     return p
-
-
-def bits_equal(a, b):
-    return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32))
 
 
 def check_properties(depth, masked, mask, replace_value):

@@ -5,19 +5,16 @@ A context keeps two batch slots, and the batch enqueued two calls later takes th
 kind alone; here every kind follows every other one in a slot, with device buffers and with host planes, across a re-run after
 a bin regrowth, and through captured graphs.
 
-One scene, soup_scene(1, 160, 120), three streams.  Every expectation comes from the CPU oracle through the kinds' own test
-helpers and bench_support/{cloud,residuals,virtual,labels}_check.py, never from the library; every comparison is bit for bit."""
+One scene, soup_scene(1, 160, 120), three streams.  Every expectation comes from the CPU oracle through the kinds' shared
+helpers (tests/gpu_support.py) and bench_support/{cloud,residuals,virtual,labels}_check.py, never from the library; every comparison is bit for bit."""
 import numpy as np
 import pytest
 
-import test_link_residuals_gpu as TR
-import test_point_clouds_gpu as PC
-import test_virtual_depth_gpu as TV
+import gpu_support as K
+from gpu_support import pack_bits, soup_scene, torch_device
 from realtime_urdf_filter_amd.filter import depth_f32_to_u16
-from test_silhouette_dilation_gpu import pack_bits
 
 gpu = pytest.mark.gpu
-NAME = "soup_160x120"
 KINDS = ("filter", "bits", "render", "residual", "cloud")
 LINK_LABEL = (3, 7, 7, 1, 12, 5)             # of the scene's six links: two share a label, the order is not the links'
 N_LABELS = 13
@@ -26,36 +23,29 @@ EMPTY = 0.25
 CAP = 9000                                    # compacted clouds: below stream 0's 9976 kept pixels, above the others'
 
 
-def _torch():
-    import torch
-    return torch, torch.device("cuda:0")
-
-
 class World:
     """The scene with the expectations of every kind, built once."""
 
     def __init__(self):
-        self.sc = PC.scene(NAME)
+        self.sc = soup_scene(1, 160, 120)
         sc = self.sc
         assert sc.n == 3 and len(LINK_LABEL) == sum(len(links) for links in sc.wl.models)
         self.depth16 = depth_f32_to_u16(sc.depth)
-        vs = TV.VScene(sc.wl, sc.depth)
-        self.virtual, self.labels = vs.virtual(EMPTY), vs.labels(LINK_LABEL)
-        rs = TR.RScene(sc.wl)
-        self.table = {False: rs.want(sc.depth, N_LABELS, link_label=LINK_LABEL), True: rs.want(self.depth16, N_LABELS, link_label=LINK_LABEL)}
-        self.bits = {u16: np.stack([pack_bits(m) for m in sc.expected(0, u16)[1]]) for u16 in (False, True)}
+        self.virtual, self.labels = K.virtual_planes(sc, EMPTY), K.label_planes(sc, LINK_LABEL)
+        self.table = {u16: K.residual_tables(sc, self.sensor(u16), N_LABELS, link_label=LINK_LABEL) for u16 in (False, True)}
+        self.bits = {u16: np.stack([pack_bits(m) for m in K.filter_expected(sc, 0, u16)[1]]) for u16 in (False, True)}
 
     def sensor(self, u16):
         return self.depth16 if u16 else self.sc.depth
 
     def context(self, **kw):
-        ctx = PC.context(self.sc, **kw)
+        ctx = K.cloud_context(self.sc, **kw)
         ctx.set_link_labels(0, np.array(LINK_LABEL, np.uint16))
         return ctx
 
     # -- expectations of streams `streams` against host arrays ---------------------------------------------------------------
     def check_filter(self, masked, mask, labels, u16, what, streams=(0, 1, 2)):
-        em, ek = self.sc.expected(0, u16)
+        em, ek = K.filter_expected(self.sc, 0, u16)
         for i, s in enumerate(streams):
             view = np.uint16 if u16 else np.uint32
             assert np.array_equal(np.ascontiguousarray(masked[i]).view(view), em[s].view(view)), "%s stream %d: masked depth" % (what, s)
@@ -67,19 +57,19 @@ class World:
             assert np.array_equal(np.asarray(bits[i]).reshape(-1), self.bits[u16][s]), "%s stream %d: mask bits" % (what, s)
 
     def check_render(self, virt, labels, what, streams=(0, 1, 2)):
-        TV.check_virtual(np.asarray(virt), self.virtual[list(streams)], what)
+        K.same_planes(np.asarray(virt), self.virtual[list(streams)], what)
         if labels is not None:
-            TV.check_labels(labels, self.labels[list(streams)], what)
+            K.compare_labels(labels, self.labels[list(streams)], what)
 
     def check_table(self, table, u16, what, streams=(0, 1, 2)):
-        TR.check(table, self.table[u16][list(streams)], what)
+        K.check_tables(table, self.table[u16][list(streams)], what)
 
     def check_cloud(self, points, index, counts, u16, cap, what, streams=(0, 1, 2)):
-        ex = PC.expect(NAME, 0, u16, streams)
+        ex = K.cloud_expect(self.sc, 0, u16, streams)
         if cap is None:
-            PC.check_org(points, ex, what)
+            K.check_org(points, ex, what)
         else:
-            PC.check_comp(points, index, counts, ex, cap, what)
+            K.check_comp(points, index, counts, ex, cap, what)
 
 
 _world = []
@@ -113,7 +103,7 @@ class DeviceJob:
     them are computed."""
 
     def __init__(self, w, kind, v, n):
-        torch, dev = _torch()
+        torch, dev = torch_device()
         self.w, self.kind, self.n = w, kind, n
         sc = w.sc
         self.u16 = bool(v & 1)
@@ -122,7 +112,7 @@ class DeviceJob:
         self.what = "%s variant %d n=%d" % (kind, v, n)
         shape = (3, sc.H, sc.W)
         full = lambda sh, val, dt: torch.full(sh, val, dtype=dt, device=dev)
-        self.d = PC.upload(w.sensor(self.u16))
+        self.d = K.upload(w.sensor(self.u16))
         self.out = {}
         if kind == "filter":
             self.out["masked"] = full(shape, SENT16, torch.int16) if self.u16 else full(shape, SENT32, torch.int32)
@@ -137,7 +127,7 @@ class DeviceJob:
         if kind == "residual":
             self.out["table"] = full((3, N_LABELS, 8), SENT64, torch.int64)
         if kind == "cloud":
-            self.buf = PC.Buffers(sc, 3, self.cap)
+            self.buf = K.CloudBuffers(sc, 3, self.cap)
             self.out = {k: t for k, t in (("points", self.buf.points), ("index", self.buf.index), ("counts", self.buf.counts)) if t is not None}
 
     def enqueue(self, ctx):
@@ -154,7 +144,7 @@ class DeviceJob:
         elif self.kind == "residual":
             (ctx.link_residuals_batch_device_u16 if self.u16 else ctx.link_residuals_batch_device)(n, d, o["table"].data_ptr(), N_LABELS)
         else:
-            PC.enqueue(ctx, self.d, n, self.buf, self.u16)
+            K.cloud_enqueue(ctx, self.d, n, self.buf, self.u16)
 
     def check(self):
         w, n, what = self.w, self.n, self.what
@@ -171,7 +161,7 @@ class DeviceJob:
         elif self.kind == "render":
             w.check_render(host["virtual"][:n].view(np.float32), labels, what, streams)
         elif self.kind == "residual":
-            w.check_table(TR.host(self.out["table"])[:n], self.u16, what, streams)
+            w.check_table(K.table_host(self.out["table"])[:n], self.u16, what, streams)
         else:
             p, i, c = self.buf.host()
             w.check_cloud(p[:n], None if i is None else i[:n], None if c is None else c[:n], self.u16, self.cap, what, streams)
@@ -192,7 +182,7 @@ def test_every_kind_behind_every_other_device_buffers():
     for job in jobs:                              # nothing waits in between: the ring retires its oldest batch as needed
         job.enqueue(ctx)
     ctx.sync()
-    _torch()[0].cuda.synchronize()
+    torch_device()[0].cuda.synchronize()
     assert ctx.stats()["batch_status"] == 0
     for job in jobs:
         job.check()
@@ -287,7 +277,7 @@ def test_rerun_of_two_kinds_in_flight(pair):
     ctx.wait_oldest()
     reruns = ctx.stats()["batch_reruns"]
     ctx.sync()
-    _torch()[0].cuda.synchronize()
+    torch_device()[0].cuda.synchronize()
     st = ctx.stats()
     assert max(reruns, st["batch_reruns"]) >= 1 and st["regrowths"] >= 1, (reruns, st)
     for f in checks:
@@ -302,7 +292,7 @@ def test_graph_replay_across_kinds():
     """One raster lane, pipelines = 2, one stream: small batches replay captured graphs.  Filter, render, residual and organized
     cloud batches alternate on the same buffers, the order turned by one every round, so that every slot of both pipelines
     meets every kind again and again; the stream's sensor plane and poses change from call to call."""
-    torch, dev = _torch()
+    torch, dev = torch_device()
     w = world()
     sc = w.sc
     ctx = w.context(n=1, max_streams=1, raster_lanes=1, pipelines=2)
@@ -310,7 +300,7 @@ def test_graph_replay_across_kinds():
     masked, mask = torch.empty_like(d), torch.empty((1, sc.H, sc.W), dtype=torch.uint8, device=dev)
     virt, labels = torch.empty_like(d), torch.empty((1, sc.H, sc.W), dtype=torch.int16, device=dev)
     table = torch.empty((1, N_LABELS, 8), dtype=torch.int64, device=dev)
-    cloud = PC.Buffers(sc, 1)
+    cloud = K.CloudBuffers(sc, 1)
     kinds = ["filter", "render", "residual", "cloud"]
     for i in range(48):
         kind = kinds[(i + i // 4) % 4]
@@ -331,9 +321,9 @@ def test_graph_replay_across_kinds():
         elif kind == "residual":
             ctx.link_residuals_batch_device(1, d.data_ptr(), table.data_ptr(), N_LABELS)
             ctx.sync()
-            w.check_table(TR.host(table), False, what, (s,))
+            w.check_table(K.table_host(table), False, what, (s,))
         else:
-            PC.enqueue(ctx, d, 1, cloud)
+            K.cloud_enqueue(ctx, d, 1, cloud)
             ctx.sync()
             w.check_cloud(cloud.host()[0], None, None, False, None, what, (s,))
     st = ctx.stats()

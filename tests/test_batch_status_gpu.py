@@ -13,45 +13,10 @@ import launch_groups as LG
 import scenes as S
 import realtime_urdf_filter_amd as R
 from bench_support import workloads as WL
+from gpu_support import Consumer, bits_equal, params
 from oracle import bindings as O
 
 pytestmark = pytest.mark.gpu
-
-
-def params(replace=5.0, max_diff=0.05, **kw):
-    p = R.default_params()
-    p.filter_replace_value = replace
-    p.depth_distance_threshold = max_diff
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def bits_equal(a, b):
-    return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32))
-
-
-class _DeviceWord:
-    """One uint32 of device memory as a __cuda_array_interface__ object (torch.as_tensor wraps it without a copy)."""
-    def __init__(self, ptr):
-        self.__cuda_array_interface__ = {"data": (int(ptr), False), "shape": (1,), "typestr": "<i4", "version": 2}
-
-
-class Consumer:
-    """A caller's own HIP stream behind the filter: ordered after the batches on the device, never waits for the host."""
-    def __init__(self, ctx):
-        import torch
-        self.torch, self.ctx, self.stream = torch, ctx, torch.cuda.Stream()
-
-    def read(self, masked, mask):
-        """Copies (status word, planes) of the batch enqueued last on the consumer's stream; returns host values."""
-        torch = self.torch
-        word = torch.as_tensor(_DeviceWord(self.ctx.batch_status_device()), device=masked.device)
-        self.ctx.order_stream_after_batches(self.stream.cuda_stream)
-        with torch.cuda.stream(self.stream):
-            w, m, k = word.clone(), masked.clone(), mask.clone()
-        self.stream.synchronize()                       # the consumer's stream only: nothing is retired
-        return int(w.cpu().numpy()[0]) & 0xffffffff, m.cpu().numpy(), k.cpu().numpy(), word
 
 
 def test_status_word_marks_overflowed_batches_until_the_host_has_rerun_them():

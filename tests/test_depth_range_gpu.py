@@ -11,10 +11,10 @@ import golden_io
 import realtime_urdf_filter_amd as R
 import scenes as S
 from bench_support import workloads as WL
+from gpu_support import bits_equal, params
+from gpu_support import run_modes, threshold_sensor
 from oracle import bindings as O
 from realtime_urdf_filter_amd.filter import depth_f32_to_u16, depth_u16_to_f32
-from test_batch_status_gpu import bits_equal, params
-from test_key_shifts_gpu import run_modes, threshold_sensor
 
 pytestmark = pytest.mark.gpu
 

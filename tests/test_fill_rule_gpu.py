@@ -27,57 +27,35 @@ if __name__ == "__main__":
 
 import lattice_scenes as L
 import realtime_urdf_filter_amd as R
-from bench_support.labels_check import expected_labels, workload_draws
-from bench_support.virtual_check import bits_equal_f32, expected_virtual, metres_to_u16
-from oracle import bindings as O
+from bench_support.virtual_check import bits_equal_f32
+from gpu_support import OracleScene, bits_equal, label_planes, pack_bits, same_planes, virtual_planes
 from realtime_urdf_filter_amd.filter import depth_f32_to_u16, depth_u16_to_f32
-from test_batch_status_gpu import bits_equal, params
-from test_silhouette_dilation_gpu import pack_bits
 
 pytestmark = pytest.mark.gpu
 REPLACE, MAX_DIFF = 5.0, 0.05
 
 
-class GScene:
+def build(name, reverse):
     """A lattice scene as a batch of identical streams under different sensor planes, with the oracle's planes of each."""
-
-    def __init__(self, name, reverse):
-        self.name, self.sc = name + ("_reversed" if reverse else ""), L.scene(name)
-        self.W, self.H = self.sc.W, self.sc.H
-        self.n = 1 if name.startswith("limit") else 3
-        self.wl, _ = L.workload(name, self.n, reverse)
-        front = min(self.sc.zs)
-        yy, xx = np.mgrid[0:self.H, 0:self.W]
-        self.mm = np.stack([(int(round((front + 0.5) * 1000)) + 7 * s + (xx + yy) % 3).astype(np.uint16) for s in range(self.n)])
-        self.depth = np.ascontiguousarray(depth_u16_to_f32(self.mm), np.float32)          # whole millimetres: one oracle run serves f32 and 16UC1
-        assert np.array_equal(depth_f32_to_u16(self.depth), self.mm)
-        wl = self.wl
-        prep = [O.PreparedFrame(self.depth[s], wl.projection[s], wl.oracle_draws(s), wl.offset_inv[s], wl.cam_tf[s], z_near=L.NEAR, z_far=L.FAR,
-                                max_diff=MAX_DIFF, replace_value=REPLACE, want_debug=True) for s in range(self.n)]
-        O.run_prepared(prep, O.usable_threads())
-        self.masked, self.mask = np.stack([f.masked for f in prep]), np.stack([f.mask for f in prep])
-        self.zwin, self.prim = np.stack([f.zwin for f in prep]), np.stack([f.prim for f in prep])
-        want = L.expected_prim(name, self.n, reverse)
-        for s in range(self.n):
-            assert np.array_equal(self.prim[s], want), "%s: the oracle and the integer rule differ" % self.name
-        winner = L.reference(name)[0]
-        assert np.array_equal(self.mask[0] > 0, (winner >= 0) & (np.asarray(self.sc.zs)[np.maximum(winner, 0)] == front))       # the mask is the front layer's coverage
-        lab, nt = workload_draws(wl)
-        self.labels = np.stack([expected_labels(self.prim[s], lab, nt) for s in range(self.n)])
-        self.n_labels = len(wl.models[0]) + 1
-        self.zsurface = np.where(self.prim == -1, np.float32(np.nan), self.zwin).astype(np.float32)
-
-    def virtual(self, empty, u16=False):
-        v = expected_virtual(self.zwin, self.prim, L.NEAR, L.FAR, empty)
-        return metres_to_u16(v) if u16 else v
-
-    def context(self, max_streams, n, **kw):
-        p = params(replace=REPLACE, max_diff=MAX_DIFF, **kw)
-        p.near_plane, p.far_plane = L.NEAR, L.FAR
-        ctx = R.Context(self.W, self.H, max_streams, 0, p)
-        ids = self.wl.load_into(ctx)
-        self.wl.stage(ctx, ids, n=n)
-        return ctx
+    sc = L.scene(name)
+    n = 1 if name.startswith("limit") else 3
+    wl, _ = L.workload(name, n, reverse)
+    assert (wl.near, wl.far, wl.max_diff, wl.replace_value) == (L.NEAR, L.FAR, MAX_DIFF, REPLACE)
+    front = min(sc.zs)
+    yy, xx = np.mgrid[0:sc.H, 0:sc.W]
+    mm = np.stack([(int(round((front + 0.5) * 1000)) + 7 * s + (xx + yy) % 3).astype(np.uint16) for s in range(n)])
+    g = OracleScene(wl, depth_u16_to_f32(mm), name + ("_reversed" if reverse else ""))          # whole millimetres: one oracle run serves f32 and 16UC1
+    g.sc, g.mm = sc, mm
+    assert np.array_equal(depth_f32_to_u16(g.depth), mm)
+    want = L.expected_prim(name, n, reverse)
+    for s in range(n):
+        assert np.array_equal(g.prim[s], want), "%s: the oracle and the integer rule differ" % g.name
+    winner = L.reference(name)[0]
+    assert np.array_equal(g.mask[0] > 0, (winner >= 0) & (np.asarray(sc.zs)[np.maximum(winner, 0)] == front))       # the mask is the front layer's coverage
+    g.labels = label_planes(g)
+    g.n_labels = len(wl.models[0]) + 1
+    g.zsurface = np.where(g.prim == -1, np.float32(np.nan), g.zwin).astype(np.float32)
+    return g
 
 
 _scenes = {}
@@ -85,17 +63,8 @@ _scenes = {}
 
 def gscene(name, reverse=False):
     if (name, reverse) not in _scenes:
-        _scenes[(name, reverse)] = GScene(name, reverse)
+        _scenes[(name, reverse)] = build(name, reverse)
     return _scenes[(name, reverse)]
-
-
-def same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    bad = ~((got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))) if got.dtype == np.float32 else got != want
-    if bad.any():
-        s, y, x = np.argwhere(bad)[0]
-        raise AssertionError("%s: %d pixels differ (first: stream %d y %d x %d: %r instead of %r)" % (what, int(bad.sum()), s, y, x, got[s, y, x], want[s, y, x]))
 
 
 def filter_routes(g, ctx, n, what, two_kernel=False):
@@ -104,7 +73,7 @@ def filter_routes(g, ctx, n, what, two_kernel=False):
     for rep in range(2):
         w = "%s %s batch %d" % (g.name, what, rep)
         masked, mask = ctx.filter_batch(g.depth[:n])
-        same(mask, g.mask[:n], w + ": mask")
+        same_planes(mask, g.mask[:n], w + ": mask")
         assert bits_equal(masked, g.masked[:n]), w + ": masked depth"
         if two_kernel:
             assert bits_equal_f32(ctx.read_zsurface(n), g.zsurface[:n]), w + ": z surface"
@@ -112,8 +81,8 @@ def filter_routes(g, ctx, n, what, two_kernel=False):
     for rep in range(2):
         w = "%s %s batch %d" % (g.name, what, rep)
         masked, mask = ctx.filter_batch_u16(g.mm[:n])
-        same(mask, g.mask[:n], w + ": 16UC1 mask")
-        same(masked, depth_f32_to_u16(g.masked[:n]), w + ": 16UC1 masked depth")
+        same_planes(mask, g.mask[:n], w + ": 16UC1 mask")
+        same_planes(masked, depth_f32_to_u16(g.masked[:n]), w + ": 16UC1 masked depth")
         if two_kernel:          # (the other kinds of batch take the fused kernels in such a context too: met below)
             continue
         bits = np.zeros((n, ctx.mask_bits_words()), np.uint32)
@@ -122,13 +91,13 @@ def filter_routes(g, ctx, n, what, two_kernel=False):
         for s in range(n):
             assert np.array_equal(bits[s], pack_bits(g.mask[s])), "%s: mask bits, stream %d" % (w, s)
         masked, mask, lab = ctx.filter_batch_labels(g.depth[:n])
-        same(lab, g.labels[:n], w + ": labels")
-        same(mask, g.mask[:n], w + ": mask beside the labels")
+        same_planes(lab, g.labels[:n], w + ": labels")
+        same_planes(mask, g.mask[:n], w + ": mask beside the labels")
         assert bits_equal(masked, g.masked[:n]), w + ": masked depth beside the labels"
         for u16 in (False, True):
             v, lab = ctx.render_batch(n, -1.5, labels=True, u16=u16)
-            same(v, g.virtual(-1.5, u16)[:n], w + ": virtual depth%s" % (" 16UC1" if u16 else ""))
-            same(lab, g.labels[:n], w + ": rendered labels")
+            same_planes(v, virtual_planes(g, -1.5, u16)[:n], w + ": virtual depth%s" % (" 16UC1" if u16 else ""))
+            same_planes(lab, g.labels[:n], w + ": rendered labels")
         table = ctx.link_residuals_batch(g.depth[:n], g.n_labels)
         for s in range(n):
             want = np.bincount(g.labels[s].reshape(-1), minlength=g.n_labels)

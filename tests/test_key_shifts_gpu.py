@@ -34,8 +34,9 @@ import pytest
 
 import realtime_urdf_filter_amd as R
 import scenes as S
+from gpu_support import params
+from gpu_support import run_modes, threshold_sensor
 from oracle import bindings as O
-from test_batch_status_gpu import bits_equal, params
 
 pytestmark = pytest.mark.gpu
 
@@ -86,22 +87,6 @@ def front_rect(x0, y0, x1, y1, d):
     d = float(np.float32(d))
     c = [[(x - CX) / FX * d, (y - (H - CY)) / FX * d, d] for x, y in ((x0, y0), (x1, y0), (x1, y1), (x0, y1))]
     return [[c[0], c[1], c[3]], [c[1], c[2], c[3]]]
-
-
-def threshold_sensor(zwin, near=NEAR, far=FAR, max_diff=MAX_DIFF, seed=0):
-    """Sensor depth ON the shader's threshold of the oracle's winners (urdf_filter.frag:14-23, in float32), one ulp above or
-    below in a third of the pixels each; NaN where nothing but the background won."""
-    n, f = np.float32(near), np.float32(far)
-    num = np.float32(np.float32(n * f) / np.float32(n - f))
-    off = np.float32(f / np.float32(f - n))
-    with np.errstate(all="ignore"):
-        virt = (num / (zwin - off).astype(np.float32)).astype(np.float32)
-        thr = (virt - np.float32(max_diff)).astype(np.float32)
-    sel = np.random.default_rng(seed).integers(0, 3, thr.shape)
-    d = thr.copy()
-    d[sel == 1] = np.nextafter(thr[sel == 1], np.float32(np.inf))
-    d[sel == 2] = np.nextafter(thr[sel == 2], np.float32(-np.inf))
-    return d.astype(np.float32)
 
 
 def oracle_z(draws):
@@ -218,52 +203,6 @@ def load_context(A, B, n_total):
     ctx.set_link_poses(0, ma, IDENT[None])
     ctx.set_link_poses(0, mb, IDENT[None])
     return ctx, t_fin, [(IDENT, 0, [0.0, 0.0, 0.0], vA, tA), (IDENT, 0, [0.0, 0.0, 0.0], vB, tB)]
-
-
-def mode_params(base, two_kernel):
-    p = R.Params.from_buffer_copy(base)
-    p.flags = (base.flags | R.FLAG_TWO_KERNEL) if two_kernel else (base.flags & ~R.FLAG_TWO_KERNEL)
-    return p
-
-
-def run_modes(ctx, base, depth, om, ok, zwin, prim, what, batches=2, bits=True):
-    """Fused, two-kernel (with its z-surface) and bit-packed batches, `batches` of each (the cover pass runs from the
-    second on; bits=False: no bit-packed batches), with parameters `base`: every output against the oracle's, bit for bit.  The z-surface holds the winner's
-    float z, NaN where nothing was drawn (prim -1: no fragment, not even the background quad's)."""
-    n = depth.shape[0]
-    for two_kernel in (False, True):
-        ctx.set_params(mode_params(base, two_kernel))
-        for b in range(batches):
-            masked, mask = ctx.filter_batch(depth)
-            for s in range(n):
-                bad = int((ok[s] != mask[s]).sum())
-                assert bad == 0, "%s two_kernel=%d batch %d stream %d: %d mask pixels differ" % (what, two_kernel, b, s, bad)
-                assert bits_equal(om[s], masked[s]), "%s two_kernel=%d batch %d stream %d: masked depth differs" % (what, two_kernel, b, s)
-            if two_kernel:
-                z = ctx.read_zsurface(n)
-                for s in range(n):
-                    want = np.where(prim[s] == -1, np.float32(np.nan), zwin[s]).astype(np.float32)
-                    diff = z[s].view(np.uint32) != want.view(np.uint32)
-                    diff &= ~(np.isnan(z[s]) & np.isnan(want))
-                    assert not diff.any(), "%s batch %d stream %d: z-surface differs from the oracle's z in %d pixels, first %s" % (
-                        what, b, s, int(diff.sum()), np.argwhere(diff)[:4].tolist())
-    ctx.set_params(mode_params(base, False))
-    if not bits:
-        return ctx.stats()
-    pin_in = ctx.host_alloc(depth.shape, np.float32)
-    pin_bits = ctx.host_alloc((n, ctx.mask_bits_words()), np.uint32)
-    pin_in[...] = depth
-    for b in range(batches):
-        pin_bits[...] = 0xdeadbeef
-        ctx.filter_batch_bits_async(pin_in, pin_bits)
-        ctx.sync()
-        for s in range(n):
-            m2, k2 = R.expand_mask_bits(depth[s], pin_bits[s], base.filter_replace_value)
-            assert np.array_equal(k2, ok[s]), "%s bits batch %d stream %d: %d mask pixels differ" % (what, b, s, int((k2 != ok[s]).sum()))
-            assert bits_equal(m2, om[s]), "%s bits batch %d stream %d: masked depth differs" % (what, b, s)
-    ctx.host_free(pin_in)
-    ctx.host_free(pin_bits)
-    return ctx.stats()
 
 
 _scene = {}

@@ -10,10 +10,10 @@ import pytest
 from bench_support import clearance_check as KC
 from bench_support import cloud_check as CC
 from bench_support import workloads as WL
+from gpu_support import INTR, info, example_facade, sensor_plane
 from oracle import bindings as O
 from realtime_urdf_filter_amd import OP_SCALE, OP_TRANSLATE
 from realtime_urdf_filter_amd.geometry import bounding_spheres
-from test_point_clouds_facade_gpu import INTR, info, python_facade, sensor_plane
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -110,7 +110,7 @@ def expectation(f, tf, depth, P, link, xyzr, n_labels):
 
 def loaded():
     depth = sensor_plane()
-    f, tf = python_facade()
+    f, tf = example_facade()
     P = f.getProjectionMatrix(info())
     f.cloud(depth, P, 640, 480)                  # (loads the models and poses the links: the spheres come from the façade's draw list)
     link, xyzr = spheres_of(f)

@@ -16,11 +16,11 @@ from bench_support import cloud_check as CC
 from bench_support import workloads as WL
 from bench_support.link_thresholds_check import expected_planes
 from bench_support.link_thresholds_check import workload_draws as thr_draws
+from gpu_support import OracleScene, centred_projection, filter_expected, params, quad, torch_device, workload_of
+from gpu_support import intrinsics, upload
 from oracle import bindings as O
 from realtime_urdf_filter_amd.filter import depth_f32_to_u16
 from realtime_urdf_filter_amd.geometry import bounding_spheres
-from test_batch_status_gpu import params
-from test_silhouette_dilation_gpu import Scene, _centred, _quad, _workload
 
 gpu = pytest.mark.gpu
 INVALID = -1
@@ -32,14 +32,9 @@ SPHERES = [(0, 0.0, 0.0, 1.2, 0.15), (0, 0.1, 0.0, 1.2, 0.1), (1, -0.45, 0.0, 1.
            (4, 0.05, 0.05, 1.2, 0.12), (5, 0.0, 0.0, 1.0, 9.0), (2, 0.45, 0.2, 1.0, 0.0)]
 
 
-def _torch():
-    import torch
-    return torch, torch.device("cuda:0")
-
-
 def arm_geometry():
-    return [_quad(-0.25, 0.25, -0.25, 0.25, 1.2), _quad(-0.55, -0.35, -0.3, 0.3, 1.0), _quad(0.35, 0.55, -0.3, 0.3, 1.0),
-            _quad(-0.1, 0.1, 0.3, 0.4, 1.5), _quad(-0.2, 0.2, -0.4, -0.3, 1.4), _quad(-0.6, -0.5, 0.35, 0.45, 1.6)]
+    return [quad(-0.25, 0.25, -0.25, 0.25, 1.2), quad(-0.55, -0.35, -0.3, 0.3, 1.0), quad(0.35, 0.55, -0.3, 0.3, 1.0),
+            quad(-0.1, 0.1, 0.3, 0.4, 1.5), quad(-0.2, 0.2, -0.4, -0.3, 1.4), quad(-0.6, -0.5, 0.35, 0.45, 1.6)]
 
 
 def arm_sensor(W, H, s):
@@ -74,7 +69,7 @@ class Arm:
         off, cam = np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams])
         cam[:, 12:15] *= 0.1                       # (keep the arm in view: the camera moves by centimetres)
         cam[:, [0, 2, 8, 10]] = np.array([1.0, 0.0, 0.0, 1.0])
-        wl = _workload("arm_%dx%d" % (W, H), W, H, geo, tfs, np.tile(_centred(W, H), (n, 1)), off, cam)
+        wl = workload_of("arm_%dx%d" % (W, H), W, H, geo, tfs, np.tile(centred_projection(W, H), (n, 1)), off, cam)
         if len(models) > 1:                        # the same links split over several models
             links, wl.models, wl.link_tf, b = wl.models[0], [], [], 0
             for m in models:
@@ -84,33 +79,19 @@ class Arm:
         self.wl, self.W, self.H, self.n, self.models = wl, W, H, n, models
         self.depth = np.stack([arm_sensor(W, H, s) for s in range(n)])
         self.link_tf = tfs
-        self._scene, self._masks = None, {}
-
-    def scene(self):
-        if self._scene is None:
-            self._scene = Scene(self.wl.name, self.wl, self.depth)
-        return self._scene
+        self.scene = OracleScene(wl, self.depth)
 
     def sensor(self, u16):
         return CC.u16_to_metres(depth_f32_to_u16(self.depth)) if u16 else self.depth
 
     def mask(self, u16=False, r=0):
-        return self.scene().expected(r, u16)[1]
+        return filter_expected(self.scene, r, u16)[1]
 
     def context(self, max_streams=None, spheres=SPHERES, labels=LABELS, **kw):
-        p = params(replace=self.wl.replace_value, max_diff=self.wl.max_diff, **kw)
-        p.near_plane, p.far_plane = self.wl.near, self.wl.far
-        ctx = R.Context(self.W, self.H, max_streams or self.n, 0, p)
-        ids = self.wl.load_into(ctx)
-        self.wl.stage(ctx, ids, n=min(self.n, max_streams or self.n))
+        ctx = self.scene.context(max_streams, **kw)
         ctx.set_cloud_intrinsics(0, [intrinsics(self, i) for i in range(max_streams or self.n)])
         give_spheres(ctx, self, spheres, labels)
         return ctx
-
-
-def intrinsics(sc, slot):
-    f = 262.5 * sc.W / 320.0
-    return (f + slot, f - 0.5 * slot, (sc.W - 1) / 2.0 + 0.25 * slot, (sc.H - 1) / 2.0 - 0.5 * slot)
 
 
 def give_spheres(ctx, sc, spheres, labels):
@@ -173,13 +154,8 @@ def conditions(t):
     assert (t["points_within"][:, 0] < t["points_within"][:, 1:].sum(axis=1)).any(), t["points_within"]
 
 
-def upload(a):
-    torch, dev = _torch()
-    return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(dev)
-
-
 def run_device(ctx, sc, n, max_distance, u16=False, n_labels=N_LABELS, total=None, depth=None, table=None):
-    torch, dev = _torch()
+    torch, dev = torch_device()
     d = upload(depth_f32_to_u16(sc.depth[:n]) if u16 else sc.depth[:n]) if depth is None else depth
     t = torch.full((total or n, n_labels, 4), 0x5A5A5A5A, dtype=torch.int32, device=dev) if table is None else table
     ctx.link_clearance_batch_device(n, d.data_ptr(), t.data_ptr(), n_labels, max_distance, u16=u16)
@@ -387,7 +363,7 @@ def test_max_distance_small_infinite_and_exactly_at_a_pair():
 
 @gpu
 def test_graph_replay_rezeroes_the_rows():
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = arm(n=2)
     ctx = sc.context(max_streams=1, raster_lanes=1, pipelines=2)
     d = torch.empty((1, sc.H, sc.W), dtype=torch.float32, device=dev)
@@ -448,8 +424,8 @@ def test_invalid_input_is_refused_and_the_context_stays_usable():
     ctx.set_link_spheres(0, [0] * 4096, one * 4096)                             # 4,096 are fine
     ctx.close()
     # 257 distinct labels: a robot of 257 links with default labels and a sphere on each
-    wl = _workload("many_links", 160, 120, [_quad(-0.1, 0.1, -0.1, 0.1, 1.0 + 0.001 * i) for i in range(257)], np.tile(S.gl(np.eye(4)), (1, 257, 1)),
-                   _centred(160, 120)[None])
+    wl = workload_of("many_links", 160, 120, [quad(-0.1, 0.1, -0.1, 0.1, 1.0 + 0.001 * i) for i in range(257)], np.tile(S.gl(np.eye(4)), (1, 257, 1)),
+                   centred_projection(160, 120)[None])
     ctx = R.Context(160, 120, 1, 0, params())
     wl.load_into(ctx)
     refused(lambda: ctx.set_link_spheres(0, list(range(257)), one * 257))

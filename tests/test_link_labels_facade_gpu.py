@@ -9,9 +9,9 @@ import pytest
 import golden_io
 from bench_support import workloads as WL
 from bench_support.labels_check import expected_labels
+from gpu_support import example_facade, info
 from oracle import bindings as O
-from realtime_urdf_filter_amd import urdf
-from realtime_urdf_filter_amd.filter import CameraInfo, FilterParameters, RealtimeURDFFilter
+from realtime_urdf_filter_amd.filter import CameraInfo, RealtimeURDFFilter
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -65,15 +65,10 @@ int main(int argc, char** argv)
 
 
 def python_facade(depth):
-    tf = urdf.StaticTransformProvider()
-    tf.set_frames(urdf.forward_kinematics(urdf.Model.from_string(WL.EXAMPLE_URDF)), "/EXAMPLE/")
-    tf.frames["/world"] = urdf.Transform()
-    tf.frames["/cam"] = urdf.Transform(np.array([[1.0, 0, 0], [0, 0, 1.0], [0, -1.0, 0]]), (0, 0, 0))
-    prm = FilterParameters("/world", "/cam", [{"model": "d", "tf_prefix": "/EXAMPLE", "geometry_type": "visual"}], 0.05, filter_replace_value=5.0)
-    f = RealtimeURDFFilter(prm, tf, {"d": WL.EXAMPLE_URDF}, labels=True)
-    info = CameraInfo(640, 480, [FX, 0, CX, 0, 0, FY, CY, 0, 0, 0, 1, 0])
-    out, mask = f.filter_callback(depth, "32FC1", info)
-    return f, out, mask, f.getProjectionMatrix(info), tf
+    f, tf = example_facade(labels=True)
+    ci = info(intr=(FX, FY, CX, CY))
+    out, mask = f.filter_callback(depth, "32FC1", ci)
+    return f, out, mask, f.getProjectionMatrix(ci), tf
 
 
 def test_python_facade_labels_follow_the_link_map():

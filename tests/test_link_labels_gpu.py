@@ -7,66 +7,15 @@ import numpy as np
 import pytest
 
 import golden_io
-import scenes as S
 import realtime_urdf_filter_amd as R
 from bench_support import configs as CF
 from bench_support import workloads as WL
-from bench_support.labels_check import expected_labels, share_draws, workload_draws
-from oracle import bindings as O
+from bench_support.labels_check import expected_labels, share_draws
+from gpu_support import OracleScene, compare_labels, label_planes, oracle_frames, params, quad, share_frames, soup_scene, tie_scene, torch_device
 from realtime_urdf_filter_amd.filter import depth_f32_to_u16
-from test_batch_status_gpu import bits_equal, params
-from test_silhouette_dilation_gpu import _centred, _quad, _workload, soup_scene
 
 pytestmark = pytest.mark.gpu
 INVALID = -1
-
-
-def _torch():
-    import torch
-    return torch, torch.device("cuda:0")
-
-
-# ---- expectations -------------------------------------------------------------------------------------------------------
-
-def oracle_prims(frames, depth):
-    """[n,H,W] prim planes of (projection, draws, offset_inv, cam_tf, near, far) frames on all usable host cores."""
-    prep = [O.PreparedFrame(depth[s], P, draws, off, cam, z_near=zn, z_far=zf, want_debug=True)
-            for s, (P, draws, off, cam, zn, zf) in enumerate(frames)]
-    O.run_prepared(prep, O.usable_threads())
-    return np.stack([f.prim for f in prep])
-
-
-class WlScene:
-    """A Workload (one model or several, one draw list for every stream) with its oracle prim planes."""
-
-    def __init__(self, wl, depth=None):
-        self.wl = wl
-        self.W, self.H, self.n = wl.width, wl.height, wl.n_streams
-        self.depth = np.ascontiguousarray(wl.depth_batch() if depth is None else depth, np.float32)
-        self.prim = oracle_prims([(wl.projection[s], wl.oracle_draws(s), wl.offset_inv[s], wl.cam_tf[s], wl.near, wl.far)
-                                  for s in range(self.n)], self.depth)
-
-    def expected(self, link_label=None):
-        lab, nt = workload_draws(self.wl, link_label)
-        return np.stack([expected_labels(self.prim[s], lab, nt) for s in range(self.n)])
-
-    def context(self, max_streams=None, n=None, **kw):
-        p = params(replace=self.wl.replace_value, max_diff=self.wl.max_diff, **kw)
-        p.near_plane, p.far_plane = self.wl.near, self.wl.far
-        ctx = R.Context(self.W, self.H, max_streams or self.n, 0, p)
-        self.ids = self.wl.load_into(ctx)
-        self.wl.stage(ctx, self.ids, n=n or min(self.n, max_streams or self.n))
-        return ctx
-
-
-def check_labels(got, want, what):
-    got = np.asarray(got)
-    assert got.shape == want.shape, what
-    bad = got != want
-    if bad.any():
-        s, y, x = np.argwhere(bad)[0]
-        raise AssertionError("%s: %d label pixels differ (first: stream %d y %d x %d: %d instead of %d)"
-                             % (what, int(bad.sum()), s, y, x, int(got[s, y, x]), int(want[s, y, x])))
 
 
 def run_host(ctx, depth, u16=False, want_mask=True):
@@ -80,7 +29,7 @@ def run_host(ctx, depth, u16=False, want_mask=True):
 
 
 def run_device(ctx, depth, u16=False, with_mask=True):
-    torch, dev = _torch()
+    torch, dev = torch_device()
     n = depth.shape[0]
     if u16:
         d = torch.from_numpy(depth_f32_to_u16(depth).view(np.int16)).to(dev)
@@ -123,9 +72,9 @@ def test_golden_fixture_labels(name, two_kernel):
         ctx.set_link_poses(0, m, tfs)
     masked, mask, lab = ctx.filter_batch_labels(fx.depth[None])
     fx.check(masked[0], mask[0])
-    prim = oracle_prims([(fx.projection, fx.draws, fx.offset_inv, fx.cam_tf, fx.z_near, fx.z_far)], fx.depth[None])
+    prim = oracle_frames([(fx.projection, fx.draws, fx.offset_inv, fx.cam_tf, fx.z_near, fx.z_far)], fx.depth[None])[1]
     want = expected_labels(prim[0], np.arange(1, len(fx.draws) + 1), [len(d[4]) for d in fx.draws])[None]
-    check_labels(lab, want, name)
+    compare_labels(lab, want, name)
     ctx.close()
 
 
@@ -137,13 +86,13 @@ _scenes = {}
 def scene(name):
     if name not in _scenes:
         if name == "c1_640x480":
-            _scenes[name] = WlScene(WL.example_workload(640, 480))
+            wl = WL.example_workload(640, 480)
+            _scenes[name] = OracleScene(wl, wl.depth_batch())
         elif name == "soup_517x389":
-            sc = soup_scene(2, 517, 389, n=2)
-            _scenes[name] = WlScene(sc.wl, sc.depth)
+            _scenes[name] = soup_scene(2, 517, 389, n=2)
         elif name == "pr2_near_walls":
             wl = WL.pr2_workload(3, 640, 480, total_triangles=40000, near_arm=True, walls=True)
-            _scenes[name] = WlScene(wl)
+            _scenes[name] = OracleScene(wl, wl.depth_batch())
     return _scenes[name]
 
 
@@ -153,14 +102,14 @@ def scene(name):
 def test_labels_every_route(name, two_kernel, lanes):
     sc = scene(name)
     ctx = sc.context(flags=R.FLAG_TWO_KERNEL if two_kernel else 0, raster_lanes=lanes)
-    want = sc.expected()
-    check_labels(run_host(ctx, sc.depth), want, "%s host f32" % name)
-    check_labels(run_host(ctx, sc.depth, want_mask=False), want, "%s host f32 without mask" % name)
-    check_labels(run_device(ctx, sc.depth), want, "%s device f32" % name)
-    check_labels(run_device(ctx, sc.depth, with_mask=False), want, "%s device f32 without mask" % name)
+    want = label_planes(sc)
+    compare_labels(run_host(ctx, sc.depth), want, "%s host f32" % name)
+    compare_labels(run_host(ctx, sc.depth, want_mask=False), want, "%s host f32 without mask" % name)
+    compare_labels(run_device(ctx, sc.depth), want, "%s device f32" % name)
+    compare_labels(run_device(ctx, sc.depth, with_mask=False), want, "%s device f32 without mask" % name)
     if sc.W % 4 == 0:
-        check_labels(run_host(ctx, sc.depth, u16=True), want, "%s host 16UC1" % name)
-        check_labels(run_device(ctx, sc.depth, u16=True), want, "%s device 16UC1" % name)
+        compare_labels(run_host(ctx, sc.depth, u16=True), want, "%s host 16UC1" % name)
+        compare_labels(run_device(ctx, sc.depth, u16=True), want, "%s device 16UC1" % name)
     assert ctx.stats()["batch_status"] == 0
     if name == "pr2_near_walls":
         st = ctx.stats()
@@ -172,17 +121,17 @@ def test_labels_every_route(name, two_kernel, lanes):
 def test_pipelines_and_partial_batches(two_kernel):
     """pipelines = 2 (the child contexts take turns), and a partial batch: max_streams 64, max_inflight_streams 8, n = 49."""
     wl = WL.pr2_workload(49, 320, 240, total_triangles=20000, near_arm=True)
-    sc = WlScene(wl)
-    want = sc.expected()
+    sc = OracleScene(wl, wl.depth_batch())
+    want = label_planes(sc)
     flags = R.FLAG_TWO_KERNEL if two_kernel else 0
     ctx = sc.context(flags=flags, pipelines=2)
     for _ in range(3):
-        check_labels(run_device(ctx, sc.depth), want, "pipelines=2 device")
-        check_labels(run_host(ctx, sc.depth), want, "pipelines=2 host")
+        compare_labels(run_device(ctx, sc.depth), want, "pipelines=2 device")
+        compare_labels(run_host(ctx, sc.depth), want, "pipelines=2 host")
     ctx.close()
     ctx = sc.context(max_streams=64, n=49, flags=flags, max_inflight_streams=8)
-    check_labels(run_device(ctx, sc.depth), want, "partial batch device")
-    check_labels(run_host(ctx, sc.depth, u16=True), want, "partial batch host 16UC1")
+    compare_labels(run_device(ctx, sc.depth), want, "partial batch device")
+    compare_labels(run_host(ctx, sc.depth, u16=True), want, "partial batch host 16UC1")
     ctx.close()
 
 
@@ -200,12 +149,7 @@ def run_share(share, n, two_kernel=False, link_label=None, custom=None):
     share.stage(ctx, 0)
     depth = np.ascontiguousarray(share.depth_host(0), np.float32)
     lab = run_device(ctx, depth)
-    link_dev, cam_dev = ctx.read_poses(n, share.n_links_total)
-    frames = []
-    for s in range(n):
-        P, draws, off, cam = share.oracle_frame(0, s, link_dev, cam_dev)
-        frames.append((P, draws, off, cam, share.wl0.near, share.wl0.far))
-    prim = oracle_prims(frames, depth)
+    prim = oracle_frames(share_frames(share, ctx, n), depth)[1]
     want = np.stack([expected_labels(prim[s], *share_draws(share, s, link_label)) for s in range(n)])
     st = ctx.stats()
     ctx.close()
@@ -215,7 +159,7 @@ def run_share(share, n, two_kernel=False, link_label=None, custom=None):
 def test_config3_256_streams():
     share = CF.build("c3", 1, 0)
     lab, want, _ = run_share(share, share.n)
-    check_labels(lab, want, "C3")
+    compare_labels(lab, want, "C3")
     assert len(np.unique(want)) > 20
 
 
@@ -223,14 +167,14 @@ def test_config3_256_streams():
 def test_config3_near_arm(two_kernel):
     share = CF.build("c3", 1, 0, streams=16, near_arm=True)
     lab, want, st = run_share(share, share.n, two_kernel)
-    check_labels(lab, want, "C3 near-arm")
+    compare_labels(lab, want, "C3 near-arm")
     assert st["exact_tiles"] > 0
 
 
 def test_config4_share_720p_walls():
     share = CF.build("c4", 8, 0, streams=64)
     lab, want, st = run_share(share, share.n)
-    check_labels(lab, want, "C4 share")
+    compare_labels(lab, want, "C4 share")
     assert st["cover_tiles"] > 0
     # the walls are links of their own models: their labels show
     wall_models = share.groups[0].model_ids[1:]
@@ -241,7 +185,7 @@ def test_config4_share_720p_walls():
 def test_config5_share_several_models():
     share = CF.build("c5", 8, 0, per_urdf=8)
     lab, want, _ = run_share(share, share.n)
-    check_labels(lab, want, "C5 share")
+    compare_labels(lab, want, "C5 share")
     # every stream shows only its own robot's links
     for g in share.groups:
         lo = 1 + share.link_base[g.model_ids[0]]
@@ -271,33 +215,18 @@ def test_config5_custom_labels_group_links_per_robot():
 
 # ---- ties: identical triangles, the earlier draw's label wins -------------------------------------------------------------
 
-def _tie_workload(geo_models, W=160, H=128):
-    """geo_models: per model a list of links, per link one (pre_op, op, verts, tris) draw; identity poses, one stream."""
-    wl = WL.Workload("ties", W, H, 1)
-
-    class D:
-        def __init__(self, g):
-            self.pre_op, self.op, self.verts, self.tris = g
-    wl.models = [[[D(g)] for g in links] for links in geo_models]
-    wl.link_tf = [np.tile(S.gl(np.eye(4)), (1, len(links), 1)) for links in geo_models]
-    wl.projection = _centred(W, H)[None]
-    wl.offset_inv = S.gl(np.eye(4))[None]
-    wl.cam_tf = S.gl(np.eye(4))[None]
-    return WlScene(wl, np.full((1, H, W), 3.0, np.float32))
-
-
 @pytest.mark.parametrize("two_kernel", [False, True])
 @pytest.mark.parametrize("case", ["links", "models", "cover_links", "cover_models", "near_links", "near_models"])
 def test_ties_go_to_the_earlier_draw(case, two_kernel):
     if case.startswith("cover"):
-        q = _quad(-3.0, 3.0, -3.0, 3.0, 1.5)              # covers every tile of the image
+        q = quad(-3.0, 3.0, -3.0, 3.0, 1.5)              # covers every tile of the image
     elif case.startswith("near"):
-        q = _quad(-0.02, 0.02, -0.015, 0.015, 0.100003)   # just beyond the near plane: winners need the exact-z pass
+        q = quad(-0.02, 0.02, -0.015, 0.015, 0.100003)   # just beyond the near plane: winners need the exact-z pass
     else:
-        q = _quad(-0.2, 0.2, -0.15, 0.15, 1.0)
-    other = _quad(-0.5, -0.3, -0.3, 0.3, 1.2)
+        q = quad(-0.2, 0.2, -0.15, 0.15, 1.0)
+    other = quad(-0.5, -0.3, -0.3, 0.3, 1.2)
     geo = [[other, q], [q]] if case.endswith("models") else [[other, q, q]]
-    sc = _tie_workload(geo)
+    sc = tie_scene(geo)
     flags = R.FLAG_TWO_KERNEL if two_kernel else 0
     ctx = sc.context(flags=flags)
     n_links = 3
@@ -307,10 +236,10 @@ def test_ties_go_to_the_earlier_draw(case, two_kernel):
             ctx.set_link_labels(sc.ids[1], np.array(labels[2:], np.uint16))
         else:
             ctx.set_link_labels(sc.ids[0], np.array(labels, np.uint16))
-        want = sc.expected(np.array(labels))
+        want = label_planes(sc, np.array(labels))
         assert (want == labels[1]).sum() > 50 and not (want == labels[2]).any()
-        check_labels(run_device(ctx, sc.depth), want, "%s labels %s" % (case, labels))
-        check_labels(run_host(ctx, sc.depth), want, "%s labels %s host" % (case, labels))
+        compare_labels(run_device(ctx, sc.depth), want, "%s labels %s" % (case, labels))
+        compare_labels(run_host(ctx, sc.depth), want, "%s labels %s host" % (case, labels))
     st = ctx.stats()
     if case.startswith("near"):
         assert st["exact_tiles"] > 0, st
@@ -329,8 +258,8 @@ def test_regrown_bins_rerun_the_labels(two_kernel):
     masked, mask, lab = ctx.filter_batch_labels(sc.depth)
     st = ctx.stats()
     assert st["regrowths"] >= 1 and st["batch_reruns"] >= 1 and st["batch_status"] != 0
-    check_labels(lab, sc.expected(), "re-run")
-    check_labels(run_device(ctx, sc.depth), sc.expected(), "after the re-run")
+    compare_labels(lab, label_planes(sc), "re-run")
+    compare_labels(run_device(ctx, sc.depth), label_planes(sc), "after the re-run")
     ctx.close()
 
 
@@ -353,16 +282,16 @@ def test_set_link_labels_custom_zero_grouping_and_changes():
         for m, nl in zip(sc.ids, n_links):
             ctx.set_link_labels(m, np.asarray(t[base:base + nl], np.uint16))
             base += nl
-        want = sc.expected(t)
-        check_labels(run_device(ctx, sc.depth), want, "device, table %s" % t[:4])
-        check_labels(run_host(ctx, sc.depth), want, "host, table %s" % t[:4])
+        want = label_planes(sc, t)
+        compare_labels(run_device(ctx, sc.depth), want, "device, table %s" % t[:4])
+        compare_labels(run_host(ctx, sc.depth), want, "host, table %s" % t[:4])
     ctx.close()
 
 
 def test_graph_replay_picks_up_new_labels_and_buffers():
     """One raster lane, pipelines = 2, batches of one stream: graph replay is on.  Two label buffers alternate and the
     labels change between batches; every batch must carry its own labels into its own buffer."""
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = scene("c1_640x480")
     ctx = sc.context(max_streams=1, n=1, raster_lanes=1, pipelines=2)
     n_links = ctx.num_links(sc.ids[0])
@@ -378,7 +307,7 @@ def test_graph_replay_picks_up_new_labels_and_buffers():
         ctx.filter_batch_device_labels(1, d.data_ptr(), m.data_ptr(), None, buf.data_ptr())
         ctx.sync()
         got = buf.cpu().numpy().view(np.uint16)
-        check_labels(got, sc.expected(labels)[:1], "batch %d" % i)
+        compare_labels(got, label_planes(sc, labels)[:1], "batch %d" % i)
     st = ctx.stats()
     assert st["graphs_enabled"] == 1 and st["graph_hits"] > 0
     ctx.close()
@@ -387,7 +316,7 @@ def test_graph_replay_picks_up_new_labels_and_buffers():
 # ---- refusals --------------------------------------------------------------------------------------------------------------
 
 def test_refusals():
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = scene("c1_640x480")
     ctx = sc.context()
     n = sc.n
@@ -413,5 +342,5 @@ def test_refusals():
     assert e.value.code == INVALID
     # the context still works, labels included, once the radius is 0 again
     ctx.set_params(params(replace=sc.wl.replace_value, max_diff=sc.wl.max_diff))
-    check_labels(run_host(ctx, sc.depth), sc.expected(), "after the refusals")
+    compare_labels(run_host(ctx, sc.depth), label_planes(sc), "after the refusals")
     ctx.close()

@@ -9,10 +9,9 @@ import pytest
 
 import golden_io
 from bench_support import workloads as WL
-from bench_support.residuals_check import ROW, expected_table, tables_equal
+from bench_support.residuals_check import ROW, expected_table
+from gpu_support import check_tables, example_facade, info
 from oracle import bindings as O
-from realtime_urdf_filter_amd import urdf
-from realtime_urdf_filter_amd.filter import CameraInfo, FilterParameters, RealtimeURDFFilter
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -71,14 +70,8 @@ int main(int argc, char** argv)
 
 
 def python_facade(labels=True):
-    tf = urdf.StaticTransformProvider()
-    tf.set_frames(urdf.forward_kinematics(urdf.Model.from_string(WL.EXAMPLE_URDF)), "/EXAMPLE/")
-    tf.frames["/world"] = urdf.Transform()
-    tf.frames["/cam"] = urdf.Transform(np.array([[1.0, 0, 0], [0, 0, 1.0], [0, -1.0, 0]]), (0, 0, 0))
-    prm = FilterParameters("/world", "/cam", [{"model": "d", "tf_prefix": "/EXAMPLE", "geometry_type": "visual"}], 0.05, filter_replace_value=5.0)
-    f = RealtimeURDFFilter(prm, tf, {"d": WL.EXAMPLE_URDF}, labels=labels)
-    info = CameraInfo(640, 480, [FX, 0, CX, 0, 0, FY, CY, 0, 0, 0, 1, 0])
-    return f, f.getProjectionMatrix(info), tf
+    f, tf = example_facade(labels=labels)
+    return f, f.getProjectionMatrix(info(intr=(FX, FY, CX, CY))), tf
 
 
 def sensor_plane():
@@ -87,11 +80,6 @@ def sensor_plane():
     d[::9, ::4] = np.nan
     d[5::13, 2::7] = 0.0
     return d
-
-
-def check(got, want, what):
-    ok, text = tables_equal(got, want)
-    assert ok, "%s: %s" % (what, text)
 
 
 def test_python_facade_against_the_oracle_and_the_device_call():
@@ -108,7 +96,7 @@ def test_python_facade_against_the_oracle_and_the_device_call():
     offset_inv, cam_tf = f._camera_matrices(tf, None)
     _, _, zwin, prim, _ = O.filter_frame(depth, P, draws, offset_inv, cam_tf, max_diff=0.05, replace_value=5.0, want_debug=True)
     want = expected_table(zwin, prim, depth, dlab, [len(d[4]) for d in draws], None, 0.05, f.near_plane_, f.far_plane_, rows)
-    check(tab, want, "python facade")
+    check_tables(tab, want, "python facade")
     assert tab["pixels"].sum() == 640 * 480 and (tab["pixels"][1:] > 0).any() and tab["agree"].sum() > 0 and tab["invalid"].sum() > 0
     # the device call on the facade's own context, staged by the facade
     dev = torch.device("cuda:0")
@@ -116,12 +104,12 @@ def test_python_facade_against_the_oracle_and_the_device_call():
     table = torch.full((1, rows, 8), -1, dtype=torch.int64, device=dev)
     f._ctx.link_residuals_batch_device(1, d.data_ptr(), table.data_ptr(), rows)
     f._ctx.sync()
-    check(np.ascontiguousarray(table.cpu().numpy()).view(ROW).reshape(rows), want, "device call")
+    check_tables(np.ascontiguousarray(table.cpu().numpy()).view(ROW).reshape(rows), want, "device call")
     # 16UC1 input
     mm = np.where((depth > 0) & (depth < 65.0), depth * np.float32(1000.0), 0).astype(np.uint16)
     want_mm = expected_table(zwin, prim, mm.astype(np.float32) * np.float32(0.001), dlab, [len(d[4]) for d in draws], None, 0.05, f.near_plane_,
                              f.far_plane_, rows)
-    check(f.link_residuals(mm, P, 640, 480), want_mm, "python facade 16UC1")
+    check_tables(f.link_residuals(mm, P, 640, 480), want_mm, "python facade 16UC1")
     # a facade without labels: default labels, one row per renderable
     g, _, _ = python_facade(labels=False)
     tab_g = g.link_residuals(depth, P, 640, 480)
@@ -149,6 +137,6 @@ def test_cpp_facade_link_residuals_into_matches_the_python_facade(tmp_path):
     rows = int(np.frombuffer(raw[:4], np.int32)[0])
     assert rows == len(tab)
     big = np.frombuffer(raw[4:4 + 64 * 64], ROW)
-    check(big[:rows], tab, "C++ facade f32")
+    check_tables(big[:rows], tab, "C++ facade f32")
     assert not np.ascontiguousarray(big[rows:]).view(np.uint64).any()          # spare rows are zeroed
-    check(np.frombuffer(raw[4 + 64 * 64:], ROW), tab_mm, "C++ facade 16UC1")
+    check_tables(np.frombuffer(raw[4 + 64 * 64:], ROW), tab_mm, "C++ facade 16UC1")

@@ -7,6 +7,7 @@ negative value, +inf, or a value at or one ulp either side of lo = v - t and hi 
 
 Run as a script (RTUF_SMALL_LAUNCH=0 python tests/test_link_residuals_gpu.py) the scene checks go through the 256-thread tile
 kernels: the threshold is read once per process, so test_scenes_256_thread_kernels starts one."""
+import functools
 import os
 import subprocess
 import sys
@@ -18,16 +19,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if __name__ == "__main__":
     sys.path.insert(0, ROOT)
 
-import golden_io
 import realtime_urdf_filter_amd as R
-import scenes as S
-from bench_support.labels_check import workload_draws as label_draws
 from bench_support.link_thresholds_check import pixel_thresholds
 from bench_support.link_thresholds_check import workload_draws as thr_draws
-from bench_support.residuals_check import ROW, expected_table, tables_equal, u16_to_metres, virtual_depth
-from oracle import bindings as O
-from test_batch_status_gpu import Consumer, params
-from test_silhouette_dilation_gpu import _centred, _quad, _workload, soup_scene, undrawn_scene
+from bench_support.residuals_check import ROW, tables_equal, virtual_depth
+from gpu_support import (Consumer, OracleScene, cached, check_tables, fixture_scene, label_planes, near_quad_scene, params, residual_tables, small_links_scene,
+                         soup_scene, table_host, torch_device, undrawn_scene, wall_scene)
 
 pytestmark = pytest.mark.gpu
 INVALID, STATE = -1, -6
@@ -35,26 +32,14 @@ SENTINEL = 0x5a5a5a5a5a5a5a5a
 F = np.float32
 
 
-def _torch():
-    import torch
-    return torch, torch.device("cuda:0")
-
-
 # ---- scenes and expectations -----------------------------------------------------------------------------------------------
 
-class RScene:
-    """A Workload with the oracle's zwin / prim of every stream (they do not depend on the sensor plane)."""
+class RScene(OracleScene):
+    """A workload without sensor planes (zwin and prim do not depend on them) and the sensors the tests make from the oracle's."""
 
-    def __init__(self, wl):
-        self.wl, self.name = wl, wl.name
-        self.W, self.H, self.n = wl.width, wl.height, wl.n_streams
-        zero = np.zeros((self.H, self.W), np.float32)
-        prep = [O.PreparedFrame(zero, wl.projection[s], wl.oracle_draws(s), wl.offset_inv[s], wl.cam_tf[s], z_near=wl.near, z_far=wl.far,
-                                max_diff=wl.max_diff, replace_value=wl.replace_value, want_debug=True) for s in range(self.n)]
-        O.run_prepared(prep, O.usable_threads())
-        self.zwin, self.prim = np.stack([f.zwin for f in prep]), np.stack([f.prim for f in prep])
-        self.n_links = sum(len(links) for links in wl.models)
-        self.virt = virtual_depth(self.zwin, wl.near, wl.far)
+    @functools.cached_property
+    def virt(self):
+        return virtual_depth(self.zwin, self.wl.near, self.wl.far)
 
     def thresholds(self, link_thr=None, global_thr=None):
         """[n,H,W] threshold of every pixel."""
@@ -88,95 +73,20 @@ class RScene:
         mm = np.where(pick == 0, 0, np.where(pick == 1, 65535, np.where(pick == 2, rng.integers(1, 9000, mm.shape), mm)))
         return np.ascontiguousarray(mm.astype(np.uint16))
 
-    def want(self, sensor, n_labels, link_label=None, link_thr=None, global_thr=None, n=None):
-        """[n, n_labels] expected table; sensor float32 metres or uint16 millimetres."""
-        s = u16_to_metres(sensor) if sensor.dtype == np.uint16 else sensor
-        lab, nt = label_draws(self.wl, link_label)
-        thr = thr_draws(self.wl, link_thr)[0] if link_thr is not None else None
-        g = self.wl.max_diff if global_thr is None else global_thr
-        return np.stack([expected_table(self.zwin[i], self.prim[i], s[i], lab, nt, thr, g, self.wl.near, self.wl.far, n_labels)
-                         for i in range(n or self.n)])
 
-    def context(self, max_streams=None, n=None, **kw):
-        p = params(replace=self.wl.replace_value, max_diff=self.wl.max_diff, **kw)
-        p.near_plane, p.far_plane = self.wl.near, self.wl.far
-        ctx = R.Context(self.W, self.H, max_streams or self.n, 0, p)
-        self.ids = self.wl.load_into(ctx)
-        self.wl.stage(ctx, self.ids, n=n or min(self.n, max_streams or self.n))
-        return ctx
+BUILDERS = {"undrawn": undrawn_scene, "small_links": small_links_scene, "wall": wall_scene, "near_quad": near_quad_scene,
+            "soup": lambda: soup_scene(31, 160, 120), "soup_164x100": lambda: soup_scene(32, 164, 100),
+            "soup_49_streams": lambda: soup_scene(33, 128, 96, n=49)}
 
 
-def fixture_scene(name, n=2):
-    """A golden fixture as n streams: one link per draw, stream s looks from 2 cm * s to the side of the fixture's camera."""
-    fx = golden_io.Fixture(name)
-    geo = [(pre, op, v, t) for _, pre, op, v, t in fx.draws]
-    tfs = np.tile(np.stack([np.asarray(d[0], np.float64).reshape(16) for d in fx.draws])[None], (n, 1, 1))
-    cams = np.tile(np.asarray(fx.cam_tf, np.float64).reshape(16), (n, 1))
-    cams[:, 12] += 0.02 * np.arange(n)
-    wl = _workload(name, fx.width, fx.height, geo, tfs, np.tile(np.asarray(fx.projection, np.float64).reshape(16), (n, 1)),
-                   np.tile(np.asarray(fx.offset_inv, np.float64).reshape(16), (n, 1)), cams)
-    wl.near, wl.far, wl.max_diff, wl.replace_value = fx.z_near, fx.z_far, fx.max_diff, fx.replace_value
-    return RScene(wl)
-
-
-def small_links_scene(W=160, H=96):
-    """A grid of 20 x 12 links of about 6 x 6 pixels each in front of the background: every wave's block of 64 x 4 pixels
-    holds ten labels or so, and a 64 x 32 tile more labels than the workgroup keeps rows for."""
-    geo = []
-    for iy in range(12):
-        for ix in range(20):
-            x0, y0 = -0.58 + 0.058 * ix, -0.35 + 0.058 * iy          # (a pixel is 0.0076 at z = 1)
-            geo.append(_quad(x0, x0 + 0.046, y0, y0 + 0.046, 1.0 + 0.01 * ((ix + iy) % 5)))
-    wl = _workload("small_links_%dx%d" % (W, H), W, H, geo, np.tile(S.gl(np.eye(4)), (1, len(geo), 1)), _centred(W, H)[None])
-    return RScene(wl)
-
-
-def wall_scene(W=192, H=128):
-    """A wall over the whole image (cover-only tiles) behind two small links."""
-    geo = [_quad(-3.0, 3.0, -3.0, 3.0, 1.5), _quad(-0.1, 0.0, -0.1, 0.0, 1.0), _quad(0.2, 0.3, 0.1, 0.2, 1.2)]
-    wl = _workload("wall_%dx%d" % (W, H), W, H, geo, np.tile(S.gl(np.eye(4)), (2, len(geo), 1)), np.tile(_centred(W, H), (2, 1)))
-    return RScene(wl)
-
-
-def near_quad_scene(W=160, H=128):
-    """A link three micrometres behind the near plane (its winners need the exact-z pass) beside one at 1.2 m."""
-    geo = [_quad(-0.5, -0.3, -0.3, 0.3, 1.2), _quad(-0.02, 0.02, -0.015, 0.015, 0.100003)]
-    wl = _workload("near_quad_%dx%d" % (W, H), W, H, geo, np.tile(S.gl(np.eye(4)), (1, len(geo), 1)), _centred(W, H)[None])
-    return RScene(wl)
-
-
-_scenes = {}
-
-
+@cached
 def scene(name):
-    if name not in _scenes:
-        if name == "undrawn":
-            _scenes[name] = RScene(undrawn_scene().wl)
-        elif name == "small_links":
-            _scenes[name] = small_links_scene()
-        elif name == "wall":
-            _scenes[name] = wall_scene()
-        elif name == "near_quad":
-            _scenes[name] = near_quad_scene()
-        elif name == "soup":
-            _scenes[name] = RScene(soup_scene(31, 160, 120).wl)
-        elif name == "soup_164x100":
-            _scenes[name] = RScene(soup_scene(32, 164, 100).wl)
-        elif name == "soup_49_streams":
-            _scenes[name] = RScene(soup_scene(33, 128, 96, n=49).wl)
-        else:
-            _scenes[name] = fixture_scene(name)
-    return _scenes[name]
-
-
-def check(got, want, what):
-    ok, text = tables_equal(got, want)
-    assert ok, "%s: %s" % (what, text)
+    return RScene((BUILDERS[name]() if name in BUILDERS else fixture_scene(name, 2)).wl)
 
 
 def run_device(ctx, sensor, n_labels, n=None, total=None, table=None):
     """One residual batch with device planes; returns (host table [total, n_labels], the device table)."""
-    torch, dev = _torch()
+    torch, dev = torch_device()
     u16 = sensor.dtype == np.uint16
     d = torch.from_numpy(sensor.view(np.int16) if u16 else sensor).to(dev)
     if table is None:
@@ -184,12 +94,7 @@ def run_device(ctx, sensor, n_labels, n=None, total=None, table=None):
     fn = ctx.link_residuals_batch_device_u16 if u16 else ctx.link_residuals_batch_device
     fn(n or sensor.shape[0], d.data_ptr(), table.data_ptr(), n_labels)
     ctx.sync()
-    return host(table), table
-
-
-def host(table):
-    a = table.cpu().numpy()
-    return np.ascontiguousarray(a).view(ROW).reshape(a.shape[0], a.shape[1])
+    return table_host(table), table
 
 
 # ---- scenes: many labels per wave, tile edges, cover-only and exact-z tiles, undrawn pixels -------------------------------------
@@ -203,18 +108,18 @@ def scene_checks(name, lanes):
     n_labels = sc.n_links + 1
     for rep in range(2):                       # (the second round runs after the cover pass has gone to sleep where no tile has a cover)
         s = sc.sensor(100 + rep)
-        want = sc.want(s, n_labels)
+        want = residual_tables(sc, s, n_labels)
         got, _ = run_device(ctx, s, n_labels)
-        check(got, want, "%s lanes %d f32 device round %d" % (name, lanes, rep))
+        check_tables(got, want, "%s lanes %d f32 device round %d" % (name, lanes, rep))
         assert (got["pixels"].sum(axis=1) == sc.W * sc.H).all()
-        check(ctx.link_residuals_batch(s, n_labels), want, "%s f32 host" % name)
+        check_tables(ctx.link_residuals_batch(s, n_labels), want, "%s f32 host" % name)
         if sc.W % 4 == 0:
             mm = sc.sensor_u16(200 + rep)
-            want = sc.want(mm, n_labels)
+            want = residual_tables(sc, mm, n_labels)
             got, _ = run_device(ctx, mm, n_labels)
-            check(got, want, "%s lanes %d 16UC1 device round %d" % (name, lanes, rep))
+            check_tables(got, want, "%s lanes %d 16UC1 device round %d" % (name, lanes, rep))
             assert (got["pixels"].sum(axis=1) == sc.W * sc.H).all()
-            check(ctx.link_residuals_batch(mm, n_labels), want, "%s 16UC1 host" % name)
+            check_tables(ctx.link_residuals_batch(mm, n_labels), want, "%s 16UC1 host" % name)
         assert ctx.stats()["batch_status"] == 0
     st = ctx.stats()
     if name == "near_quad":
@@ -224,14 +129,8 @@ def scene_checks(name, lanes):
     if name == "undrawn":
         assert (sc.prim == -1).any() and (sc.prim == -2).any()
     if name == "small_links":                  # (more labels in one 64 x 32 tile than the workgroup keeps rows for)
-        assert len(np.unique(label_plane(sc)[0, :32, :64])) > 16
+        assert len(np.unique(label_planes(sc)[0, :32, :64])) > 16
     ctx.close()
-
-
-def label_plane(sc, link_label=None):
-    from bench_support.labels_check import expected_labels
-    lab, nt = label_draws(sc.wl, link_label)
-    return np.stack([expected_labels(sc.prim[s], lab, nt) for s in range(sc.n)])
 
 
 @pytest.mark.parametrize("lanes", [1, 3])
@@ -256,9 +155,9 @@ def test_per_link_thresholds_special_values_and_clear():
     link_thr = np.array([np.nan, -np.inf, np.inf, 0.0, 0.2, 0.01][:sc.n_links], np.float32)
     ctx.set_link_thresholds(sc.ids[0], link_thr)
     s = sc.sensor(7, link_thr)
-    want = sc.want(s, n_labels, link_thr=link_thr)
+    want = residual_tables(sc, s, n_labels, link_thr=link_thr)
     got, _ = run_device(ctx, s, n_labels)
-    check(got, want, "thresholds f32")
+    check_tables(got, want, "thresholds f32")
     for link, row in enumerate(got[0][1:]):
         valid = row["pixels"] - row["invalid"]
         if link < 2:                           # NaN, -inf: every valid pixel in front
@@ -267,10 +166,10 @@ def test_per_link_thresholds_special_values_and_clear():
             assert row["agree"] == valid and row["in_front"] == 0 and row["behind"] == 0
     assert got["pixels"][:, 1:].sum() > 500
     mm = sc.sensor_u16(8)
-    check(run_device(ctx, mm, n_labels)[0], sc.want(mm, n_labels, link_thr=link_thr), "thresholds 16UC1")
-    check(ctx.link_residuals_batch(s, n_labels), want, "thresholds host")
+    check_tables(run_device(ctx, mm, n_labels)[0], residual_tables(sc, mm, n_labels, link_thr=link_thr), "thresholds 16UC1")
+    check_tables(ctx.link_residuals_batch(s, n_labels), want, "thresholds host")
     ctx.clear_link_thresholds(sc.ids[0])
-    check(run_device(ctx, s, n_labels)[0], sc.want(s, n_labels), "after clear")
+    check_tables(run_device(ctx, s, n_labels)[0], residual_tables(sc, s, n_labels), "after clear")
     ctx.close()
 
 
@@ -281,16 +180,16 @@ def test_custom_labels_grouping_zero_and_spare_rows():
     ctx.set_link_labels(sc.ids[0], labels)
     s = sc.sensor(9)
     got, _ = run_device(ctx, s, 8)
-    check(got, sc.want(s, 8, link_label=labels), "custom labels")
+    check_tables(got, residual_tables(sc, s, 8, link_label=labels), "custom labels")
     assert (got["pixels"][:, [2, 4, 5, 6]] == 0).all() and (got["pixels"][:, [3, 7]] > 0).all()
     got, _ = run_device(ctx, s, 40)            # more rows than labels: the spare rows are all zero
-    check(got, sc.want(s, 40, link_label=labels), "spare rows")
+    check_tables(got, residual_tables(sc, s, 40, link_label=labels), "spare rows")
     assert not np.ascontiguousarray(got[:, 8:]).view(np.uint64).any()
     ctx.close()
 
 
 def test_refusals_write_nothing_and_leave_the_context_usable():
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = scene("soup")
     p = params(replace=sc.wl.replace_value, max_diff=sc.wl.max_diff)
     p.near_plane, p.far_plane = sc.wl.near, sc.wl.far
@@ -328,7 +227,7 @@ def test_refusals_write_nothing_and_leave_the_context_usable():
     ctx.set_params(p)
     ctx.set_link_labels(ids[0], np.array([1, 2, 0, 0, 2, 1][:sc.n_links], np.uint16))                              # now three rows are enough
     got, _ = run_device(ctx, s, 3)
-    check(got, sc.want(s, 3, link_label=np.array([1, 2, 0, 0, 2, 1][:sc.n_links])), "after the refusals")
+    check_tables(got, residual_tables(sc, s, 3, link_label=np.array([1, 2, 0, 0, 2, 1][:sc.n_links])), "after the refusals")
     ctx.close()
 
 
@@ -340,16 +239,16 @@ def test_three_lanes_several_groups_partial_batch():
     n_labels = sc.n_links + 3
     s = sc.sensor(11)
     got, _ = run_device(ctx, s, n_labels, n=49, total=64)
-    check(got[:49], sc.want(s, n_labels), "49 of 64 streams")
+    check_tables(got[:49], residual_tables(sc, s, n_labels), "49 of 64 streams")
     assert (np.ascontiguousarray(got[49:]).view(np.uint64) == SENTINEL).all()                    # rows of streams beyond n are not touched
     assert ctx.stats()["groups_last_batch"] > 3
     mm = sc.sensor_u16(12)
-    check(run_device(ctx, mm, n_labels, n=49, total=64)[0][:49], sc.want(mm, n_labels), "49 of 64 streams 16UC1")
+    check_tables(run_device(ctx, mm, n_labels, n=49, total=64)[0][:49], residual_tables(sc, mm, n_labels), "49 of 64 streams 16UC1")
     ctx.close()
 
 
 def test_two_pipelines_batches_in_flight_with_tables_of_their_own():
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = scene("soup")
     ctx = sc.context(pipelines=2)
     n_labels = sc.n_links + 1
@@ -362,7 +261,7 @@ def test_two_pipelines_batches_in_flight_with_tables_of_their_own():
         rounds.append((s, d, table))
     ctx.sync()
     for i, (s, _, table) in enumerate(rounds):
-        check(host(table), sc.want(s, n_labels), "round %d" % i)
+        check_tables(table_host(table), residual_tables(sc, s, n_labels), "round %d" % i)
     ctx.close()
 
 
@@ -374,8 +273,8 @@ def test_regrown_bins_rerun_leaves_the_single_run_table():
     got, _ = run_device(ctx, s, n_labels)
     st = ctx.stats()
     assert st["regrowths"] > 0 and st["batch_reruns"] > 0 and st["batch_status"] != 0, st
-    check(got, sc.want(s, n_labels), "re-run")
-    check(ctx.link_residuals_batch(s, n_labels), sc.want(s, n_labels), "after the re-run, host planes")
+    check_tables(got, residual_tables(sc, s, n_labels), "re-run")
+    check_tables(ctx.link_residuals_batch(s, n_labels), residual_tables(sc, s, n_labels), "after the re-run, host planes")
     ctx.close()
 
 
@@ -386,7 +285,7 @@ def test_regrown_bins_rerun_host_planes():
     mm = sc.sensor_u16(31)
     got = ctx.link_residuals_batch(mm, n_labels)
     assert ctx.stats()["batch_reruns"] > 0
-    check(got, sc.want(mm, n_labels), "re-run, host planes")
+    check_tables(got, residual_tables(sc, mm, n_labels), "re-run, host planes")
     ctx.close()
 
 
@@ -396,16 +295,16 @@ def test_a_table_is_overwritten_never_accumulated():
     n_labels = sc.n_links + 1
     a, b = sc.sensor(40), sc.sensor(41)
     got_a, table = run_device(ctx, a, n_labels)
-    check(got_a, sc.want(a, n_labels), "first")
+    check_tables(got_a, residual_tables(sc, a, n_labels), "first")
     got_b, _ = run_device(ctx, b, n_labels, table=table)
-    check(got_b, sc.want(b, n_labels), "second, same table")
+    check_tables(got_b, residual_tables(sc, b, n_labels), "second, same table")
     assert not tables_equal(got_a, got_b)[0]
     ctx.close()
 
 
 def test_graph_replay_of_small_batches():
     """One raster lane, pipelines = 2, one stream: small batches replay a captured graph, the zeroing of the table included."""
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = scene("soup")
     ctx = sc.context(max_streams=1, n=1, raster_lanes=1, pipelines=2)
     n_labels = sc.n_links + 1
@@ -419,14 +318,14 @@ def test_graph_replay_of_small_batches():
         table = tb if i >= 6 else ta
         ctx.link_residuals_batch_device(1, d.data_ptr(), table.data_ptr(), n_labels)
         ctx.sync()
-        check(host(table), sc.want(s, n_labels, n=1), "replay %d" % i)
+        check_tables(table_host(table), residual_tables(sc, s, n_labels, n=1), "replay %d" % i)
     st = ctx.stats()
     assert st["graphs_enabled"] == 1 and st["graph_hits"] > 0, st
     ctx.close()
 
 
 def test_status_word_is_zero_behind_a_final_residual_batch():
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = scene("soup")
     ctx = sc.context()
     n_labels = sc.n_links + 1
@@ -438,7 +337,7 @@ def test_status_word_is_zero_behind_a_final_residual_batch():
     ctx.link_residuals_batch_device(sc.n, d.data_ptr(), table.data_ptr(), n_labels)
     word, early, _, _ = user.read(table, table)
     assert word == 0, hex(word)
-    check(np.ascontiguousarray(early).view(ROW).reshape(sc.n, n_labels), sc.want(s, n_labels), "behind the batch")
+    check_tables(np.ascontiguousarray(early).view(ROW).reshape(sc.n, n_labels), residual_tables(sc, s, n_labels), "behind the batch")
     ctx.sync()
     st = ctx.stats()
     assert st["batch_status"] == 0 and st["batch_reruns"] == 0, st
@@ -459,7 +358,7 @@ def test_timings_land_in_ms_raster():
 
 @pytest.mark.parametrize("with_thresholds", [False, True])
 def test_pixels_and_filtered_equal_the_bincounts_of_the_label_filter(with_thresholds):
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = scene("soup")
     ctx = sc.context()
     n_labels = sc.n_links + 1
@@ -477,7 +376,7 @@ def test_pixels_and_filtered_equal_the_bincounts_of_the_label_filter(with_thresh
         li = lab[i].to(torch.int64).flatten() & 0xffff
         assert torch.equal(torch.bincount(li, minlength=n_labels), table[i, :, 0])
         assert torch.equal(torch.bincount(li[k[i].flatten() == 255], minlength=n_labels), table[i, :, 2])
-    check(got, sc.want(s, n_labels, link_thr=link_thr), "table")
+    check_tables(got, residual_tables(sc, s, n_labels, link_thr=link_thr), "table")
     ctx.close()
 
 
@@ -496,10 +395,10 @@ def test_two_kernel_context_is_accepted_and_gives_the_same_table(with_thresholds
         if flags and not with_thresholds:      # the context filters as before, and the residual batch again behind it
             masked, mask = ctx.filter_batch(s)
             assert mask.any()
-            check(run_device(ctx, s, n_labels)[0], tables[0], "behind a two-kernel filter batch")
+            check_tables(run_device(ctx, s, n_labels)[0], tables[0], "behind a two-kernel filter batch")
         ctx.close()
-    check(tables[1], tables[0], "two-kernel context")
-    check(tables[0], sc.want(s, n_labels, link_thr=link_thr), "fused context")
+    check_tables(tables[1], tables[0], "two-kernel context")
+    check_tables(tables[0], residual_tables(sc, s, n_labels, link_thr=link_thr), "fused context")
 
 
 if __name__ == "__main__":

@@ -10,8 +10,8 @@ import pytest
 import golden_io
 from bench_support import workloads as WL
 from bench_support.link_thresholds_check import expected_planes
+from gpu_support import example_facade, example_transforms, info
 from oracle import bindings as O
-from realtime_urdf_filter_amd import urdf
 from realtime_urdf_filter_amd.filter import CameraInfo, FilterParameters, RealtimeURDFFilter
 
 pytestmark = pytest.mark.gpu
@@ -66,22 +66,11 @@ int main(int argc, char** argv)
 '''.replace("FX_", repr(FX)).replace("FY_", repr(FY)).replace("CX_", repr(CX)).replace("CY_", repr(CY)).replace("WALL1_", repr(WALL1))
 
 
-def _tf():
-    tf = urdf.StaticTransformProvider()
-    tf.set_frames(urdf.forward_kinematics(urdf.Model.from_string(WL.EXAMPLE_URDF)), "/EXAMPLE/")
-    tf.frames["/world"] = urdf.Transform()
-    tf.frames["/cam"] = urdf.Transform(np.array([[1.0, 0, 0], [0, 0, 1.0], [0, -1.0, 0]]), (0, 0, 0))
-    return tf
-
-
 def python_facade(depth, entries):
-    tf = _tf()
-    model = {"model": "d", "tf_prefix": "/EXAMPLE", "geometry_type": "visual", "link_depth_distance_thresholds": entries}
-    prm = FilterParameters("/world", "/cam", [model], 0.05, filter_replace_value=5.0)
-    f = RealtimeURDFFilter(prm, tf, {"d": WL.EXAMPLE_URDF})
-    info = CameraInfo(640, 480, [FX, 0, CX, 0, 0, FY, CY, 0, 0, 0, 1, 0])
-    out, mask = f.filter_callback(depth, "32FC1", info)
-    return f, out, mask, f.getProjectionMatrix(info), tf
+    f, tf = example_facade(model_entries={"link_depth_distance_thresholds": entries})
+    ci = info(intr=(FX, FY, CX, CY))
+    out, mask = f.filter_callback(depth, "32FC1", ci)
+    return f, out, mask, f.getProjectionMatrix(ci), tf
 
 
 def _depth():
@@ -110,7 +99,7 @@ def test_python_facade_per_link_thresholds():
     _, k0 = expected(f, depth, P, tf, {})
     assert (wk != k0).sum() > 1000                            # (the wide margin shows)
     # an entry for a link on the ignore list is accepted and has no effect
-    tf2 = _tf()
+    tf2 = example_transforms()
     model = {"model": "d", "tf_prefix": "/EXAMPLE", "geometry_type": "visual", "ignore": ["wall2"],
              "link_depth_distance_thresholds": [{"link": "wall2", "threshold": 9.0}]}
     g = RealtimeURDFFilter(FilterParameters("/world", "/cam", [model], 0.05, filter_replace_value=5.0), tf2, {"d": WL.EXAMPLE_URDF})

@@ -15,10 +15,9 @@ from bench_support import configs as CF
 from bench_support import workloads as WL
 from bench_support.link_thresholds_check import (expected_planes, link_values, share_draws, workload_draws,
                                                  workload_link_base)
-from oracle import bindings as O
+from gpu_support import (OracleScene, centred_projection, compare_labels, compare_planes, oracle_frames, params, quad, share_frames, soup_scene,
+                         torch_device, unpack_bits, workload_of)
 from realtime_urdf_filter_amd.filter import depth_f32_to_u16, depth_u16_to_f32
-from test_batch_status_gpu import params
-from test_silhouette_dilation_gpu import _centred, _quad, soup_scene
 
 pytestmark = pytest.mark.gpu
 INVALID = -1
@@ -26,20 +25,7 @@ F = np.float32
 SPECIAL = [0.0, -0.03, np.nan, np.inf, -np.inf, 0.05, 0.5, 1e-4]
 
 
-def _torch():
-    import torch
-    return torch, torch.device("cuda:0")
-
-
 # ---- expectations -------------------------------------------------------------------------------------------------------
-
-def oracle_planes(frames, depth):
-    """([n,H,W] window z, [n,H,W] prim) of (projection, draws, offset_inv, cam_tf, near, far) frames on all usable host cores."""
-    prep = [O.PreparedFrame(depth[s], P, draws, off, cam, z_near=zn, z_far=zf, want_debug=True)
-            for s, (P, draws, off, cam, zn, zf) in enumerate(frames)]
-    O.run_prepared(prep, O.usable_threads())
-    return np.stack([f.zwin for f in prep]), np.stack([f.prim for f in prep])
-
 
 class Planes:
     """Oracle planes of a batch and the expected outputs for any link thresholds.  draws(s, link_thr) -> (threshold,
@@ -63,39 +49,22 @@ class Planes:
 
 
 def wl_planes(wl, depth=None):
-    depth = np.ascontiguousarray(wl.depth_batch() if depth is None else depth, np.float32)
-    zwin, prim = oracle_planes([(wl.projection[s], wl.oracle_draws(s), wl.offset_inv[s], wl.cam_tf[s], wl.near, wl.far)
-                                for s in range(wl.n_streams)], depth)
-    return Planes(depth, zwin, prim, lambda s, t: workload_draws(wl, t), wl.near, wl.far, wl.replace_value, wl.max_diff)
+    sc = OracleScene(wl, wl.depth_batch() if depth is None else depth)
+    return Planes(sc.depth, sc.zwin, sc.prim, lambda s, t: workload_draws(wl, t), wl.near, wl.far, wl.replace_value, wl.max_diff)
 
 
-def wl_context(wl, max_streams=None, n=None, global_thr=None, **kw):
-    p = params(replace=wl.replace_value, max_diff=wl.max_diff if global_thr is None else global_thr, **kw)
-    p.near_plane, p.far_plane = wl.near, wl.far
-    ctx = R.Context(wl.width, wl.height, max_streams or wl.n_streams, 0, p)
-    ids = wl.load_into(ctx)
-    wl.stage(ctx, ids, n=n or min(wl.n_streams, max_streams or wl.n_streams))
-    return ctx, ids
+def wl_context(wl, **kw):
+    sc = OracleScene(wl)
+    return sc.context(**kw), sc.ids
 
 
 # ---- every output form of the fused route --------------------------------------------------------------------------------
 
 def _cmp(got_m, got_k, want_m, want_k, what, u16):
     if got_k is not None:
-        bad = np.asarray(got_k) != want_k
-        if bad.any():
-            s, y, x = np.argwhere(bad)[0]
-            raise AssertionError("%s: %d mask pixels differ (first: stream %d y %d x %d: %d instead of %d)"
-                                 % (what, int(bad.sum()), s, y, x, int(np.asarray(got_k)[s, y, x]), int(want_k[s, y, x])))
+        compare_labels(got_k, want_k, what, "mask")
     if got_m is not None:
-        g = np.asarray(got_m)
-        bad = (g != want_m) if u16 else (np.ascontiguousarray(g, np.float32).view(np.uint32) != want_m.view(np.uint32))
-        assert not bad.any(), "%s: %d masked pixels differ" % (what, int(bad.sum()))
-
-
-def _unpack_bits(bits, n, H, W):
-    b = np.ascontiguousarray(bits).view(np.uint8).reshape(n, H, -1)
-    return (np.unpackbits(b, axis=2, bitorder="little")[:, :, :W] * 255).astype(np.uint8)
+        compare_planes(got_m, want_m, what, "masked")
 
 
 def run_form(ctx, form, depth, n):
@@ -122,17 +91,17 @@ def run_form(ctx, form, depth, n):
         pin_in[:] = d
         ctx.filter_batch_bits_async(pin_in, pin_bits)
         ctx.sync()
-        k = _unpack_bits(pin_bits.copy(), n, H, W)
+        k = unpack_bits(pin_bits.copy(), W, H).astype(np.uint8) * 255
         ctx.host_free(pin_in)
         ctx.host_free(pin_bits)
         return None, k
-    torch, dev = _torch()
+    torch, dev = torch_device()
     td = torch.from_numpy(d.view(np.int16) if u16 else d).to(dev)
     if form.startswith("bits_device"):
         bits = torch.zeros((n, ctx.mask_bits_words()), dtype=torch.int32, device=dev)
         ctx.filter_batch_device_bits(n, td.data_ptr(), bits.data_ptr(), u16=u16)
         ctx.sync()
-        return None, _unpack_bits(bits.cpu().numpy(), n, H, W)
+        return None, unpack_bits(bits.cpu().numpy(), W, H).astype(np.uint8) * 255
     m = torch.empty_like(td)
     k = torch.empty(td.shape, dtype=torch.uint8, device=dev)
     if form.startswith("labels_device"):
@@ -172,25 +141,15 @@ def check_forms(ctx, pl, link_thr, what, forms=None, n=None, global_thr=None):
 # ---- 1. two links at one depth ---------------------------------------------------------------------------------------------
 
 def _two_link_workload(W=160, H=128, n=1):
-    wl = WL.Workload("two_links", W, H, n)
-
-    class D:
-        def __init__(self, g):
-            self.pre_op, self.op, self.verts, self.tris = g
-    geo = [_quad(-0.5, -0.05, -0.3, 0.3, 1.0), _quad(0.05, 0.5, -0.3, 0.3, 1.0)]
-    wl.models = [[[D(g)] for g in geo]]
-    wl.link_tf = [np.tile(S.gl(np.eye(4)), (n, len(geo), 1))]
-    wl.projection = np.tile(_centred(W, H), (n, 1))
-    wl.offset_inv = np.tile(S.gl(np.eye(4)), (n, 1))
-    wl.cam_tf = np.tile(S.gl(np.eye(4)), (n, 1))
-    return wl
+    geo = [quad(-0.5, -0.05, -0.3, 0.3, 1.0), quad(0.05, 0.5, -0.3, 0.3, 1.0)]
+    return workload_of("two_links", W, H, geo, np.tile(S.gl(np.eye(4)), (n, len(geo), 1)), np.tile(centred_projection(W, H), (n, 1)))
 
 
 def test_two_links_one_depth_only_the_wide_link_filters():
     """Two boxes side by side at one depth, the sensor 0.10 m in front of both: the global threshold 0.05 keeps them, link
     A's 0.20 filters exactly A's pixels -- in every output form, rtuf_filter included."""
     wl = _two_link_workload()
-    zwin, prim = oracle_planes([(wl.projection[0], wl.oracle_draws(0), wl.offset_inv[0], wl.cam_tf[0], wl.near, wl.far)],
+    zwin, prim = oracle_frames([(wl.projection[0], wl.oracle_draws(0), wl.offset_inv[0], wl.cam_tf[0], wl.near, wl.far)],
                                np.zeros((1, wl.height, wl.width), np.float32))
     drawn = prim[0] >= 0
     virt = (F(wl.near) * F(wl.far) / (F(wl.near) - F(wl.far))) / (zwin[0] - F(wl.far) / (F(wl.far) - F(wl.near)))
@@ -224,7 +183,7 @@ def test_golden_fixtures_random_thresholds(name):
     ctx.set_camera(0, fx.projection, fx.offset_inv, fx.cam_tf)
     if len(tfs):
         ctx.set_link_poses(0, m, tfs)
-    zwin, prim = oracle_planes([(fx.projection, fx.draws, fx.offset_inv, fx.cam_tf, fx.z_near, fx.z_far)], fx.depth[None])
+    zwin, prim = oracle_frames([(fx.projection, fx.draws, fx.offset_inv, fx.cam_tf, fx.z_near, fx.z_far)], fx.depth[None])
     ntris = [len(d[4]) for d in fx.draws]
     pl = Planes(fx.depth[None], zwin, prim, lambda s, t: (list(t), ntris), fx.z_near, fx.z_far, fx.replace_value, fx.max_diff)
     masked, mask = ctx.filter_batch(fx.depth[None])
@@ -263,12 +222,7 @@ def run_share(share, n, set_thr, link_thr, forms=("device",)):
     share.stage(ctx, 0)
     depth = np.ascontiguousarray(share.depth_host(0), np.float32)
     run_form(ctx, "device", depth, n)                # (the share poses its links on the device: one batch before they are read)
-    link_dev, cam_dev = ctx.read_poses(n, share.n_links_total)
-    frames = []
-    for s in range(n):
-        P, draws, off, cam = share.oracle_frame(0, s, link_dev, cam_dev)
-        frames.append((P, draws, off, cam, share.wl0.near, share.wl0.far))
-    zwin, prim = oracle_planes(frames, depth)
+    zwin, prim = oracle_frames(share_frames(share, ctx, n), depth)
     pl = Planes(depth, zwin, prim, lambda s, t: share_draws(share, s, t), share.wl0.near, share.wl0.far,
                 share.wl0.replace_value, share.wl0.max_diff)
     _, k = check_forms(ctx, pl, link_thr, "share", forms=list(forms))
@@ -434,7 +388,7 @@ def test_regrown_bins_rerun_with_the_thresholds():
 
 def test_graph_replay_picks_up_changed_thresholds():
     """One raster lane, pipelines = 2, batches of one stream: graph replay is on; the thresholds change between batches."""
-    torch, dev = _torch()
+    torch, dev = torch_device()
     wl = WL.example_workload(640, 480)
     pl = wl_planes(wl)
     ctx, ids = wl_context(wl, max_streams=1, n=1, raster_lanes=1, pipelines=2)
@@ -459,7 +413,7 @@ def test_graph_replay_picks_up_changed_thresholds():
 # ---- 7. refusals -----------------------------------------------------------------------------------------------------------
 
 def test_refusals_leave_the_state_unchanged():
-    torch, dev = _torch()
+    torch, dev = torch_device()
     wl = WL.example_workload(640, 480)
     pl = wl_planes(wl)
     ctx, ids = wl_context(wl)

@@ -14,6 +14,7 @@ import realtime_urdf_filter_amd as R
 from bench_support import workloads as WL
 from realtime_urdf_filter_amd import _capi, urdf
 from realtime_urdf_filter_amd.filter import CameraInfo, FilterParameters, RealtimeURDFFilter, depth_f32_to_u16, depth_u16_to_f32
+from gpu_support import bits_equal, unpack_bits
 from oracle import bindings as O
 
 pytestmark = pytest.mark.gpu
@@ -28,10 +29,6 @@ def params(replace=5.0, max_diff=0.05, two_kernel=False, **kw):
     for k, v in kw.items():
         setattr(p, k, v)
     return p
-
-
-def bits_equal(a, b):
-    return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1203,13 +1200,6 @@ def test_fused_16uc1_io(two_kernel):
         assert np.array_equal(out16[s][ok == 0], mm[s][ok == 0])          # unfiltered pixels round-trip exactly
         assert (out16[s][ok > 0] == 5000).all()
     ctx.close()
-
-
-def unpack_bits(bits, W, H):
-    """[words] uint32 -> [H, W] bool (pixel x = bit x % 32 of word y * ceil(W/32) + x / 32)."""
-    rw = (W + 31) // 32
-    b = np.unpackbits(np.ascontiguousarray(bits, np.uint32).reshape(H, rw).view(np.uint8), axis=1, bitorder="little")
-    return b[:, :W].astype(bool)
 
 
 @pytest.mark.parametrize("size", [(640, 480), (324, 100), (1280, 720)])

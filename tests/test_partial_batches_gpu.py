@@ -8,6 +8,7 @@ batch reports no more launch groups than its slot has counter blocks, and the st
 when the planes it saw were final.  Streams beyond n are staged with cameras and depth of their own, so a launch group that
 renders the wrong stream -- an uneven last group's offset into the planes, a stale upload -- shows up."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -15,9 +16,8 @@ import pytest
 import launch_groups as LG
 import scenes as S
 import realtime_urdf_filter_amd as R
+from gpu_support import Consumer, OracleScene, bits_equal, unpack_bits, workload_of
 from realtime_urdf_filter_amd.filter import depth_f32_to_u16, depth_u16_to_f32
-from oracle import bindings as O
-from test_batch_status_gpu import Consumer, bits_equal, params
 
 pytestmark = pytest.mark.gpu
 
@@ -26,44 +26,19 @@ SENTINEL_U8 = 0xA5
 RTUF_ERR_INVALID = -1
 
 
-class Scene:
+class Scene(OracleScene):
     """A soup model and M streams, each with its own camera, link poses and sensor plane; the oracle's frames for all M."""
 
-    def __init__(self, W, H, M, seed, **pkw):
-        rng = np.random.default_rng(seed)
-        self.W, self.H, self.M = W, H, M
-        self.P = S.projection(525.0 * W / 640, 525.0 * W / 640, (W - 1) / 2, (H - 1) / 2, W, H)
-        self.geo = S.soup_geometry(rng, n_links=7, tris_per_link=50)
-        self.ctx = R.Context(W, H, M, 0, params(5.0, 0.05, **pkw))
-        m = self.ctx.add_model()
-        for pre, op, v, t in self.geo:
-            self.ctx.add_draw(m, self.ctx.add_link(m), v, t, pre, op)
-        self.ctx.finalize_models()
-        self.depth = np.stack([S.sensor_depth(W, H, 0.3 * s + seed) for s in range(M)])
-        self.mm = depth_f32_to_u16(np.nan_to_num(self.depth, nan=0.0, posinf=0.0))
-        self.per = []
-        for s in range(M):
-            tfs = S.random_link_poses(rng, len(self.geo), near=(s % 3 == 1), far=(s % 3 == 2))
-            offinv, camtf = S.random_camera(rng, small=bool(s & 1))
-            self.ctx.set_camera(s, self.P, offinv, camtf)
-            self.ctx.set_link_poses(s, m, np.stack(tfs))
-            self.per.append((tfs, offinv, camtf))
-        self._want, self._want16 = {}, {}
-
     def want(self, s):
-        if s not in self._want:
-            tfs, offinv, camtf = self.per[s]
-            draws = [(tfs[i],) + self.geo[i] for i in range(len(self.geo))]
-            self._want[s] = O.filter_frame(self.depth[s], self.P, draws, offinv, camtf, replace_value=5.0)
-        return self._want[s]
+        return self.masked[s], self.mask[s]
+
+    @functools.cached_property
+    def _u16(self):
+        sc = OracleScene(self.wl, depth_u16_to_f32(self.mm))
+        return depth_f32_to_u16(sc.masked), sc.mask
 
     def want16(self, s):
-        if s not in self._want16:
-            tfs, offinv, camtf = self.per[s]
-            draws = [(tfs[i],) + self.geo[i] for i in range(len(self.geo))]
-            om, ok = O.filter_frame(depth_u16_to_f32(self.mm[s]), self.P, draws, offinv, camtf, replace_value=5.0)
-            self._want16[s] = (depth_f32_to_u16(om), ok)
-        return self._want16[s]
+        return self._u16[0][s], self._u16[1][s]
 
     def exact(self, n, masked, mask, u16=False):
         """Streams 0 .. n-1 of (masked, mask) are the oracle's frames (mask None: not checked)."""
@@ -84,6 +59,23 @@ class Scene:
             assert same, "%s stream %d of %d: masked depth differs" % (what, s, n)
 
 
+def scene(W, H, M, seed, **pkw):
+    """The scene with its context (sc.ctx, parameters pkw) of M streams, every one of them staged."""
+    rng = np.random.default_rng(seed)
+    P = S.projection(525.0 * W / 640, 525.0 * W / 640, (W - 1) / 2, (H - 1) / 2, W, H)
+    geo = S.soup_geometry(rng, n_links=7, tris_per_link=50)
+    tfs, cams = [], []
+    for s in range(M):
+        tfs.append(np.stack(S.random_link_poses(rng, len(geo), near=(s % 3 == 1), far=(s % 3 == 2))))
+        cams.append(S.random_camera(rng, small=bool(s & 1)))
+    wl = workload_of("partial_%dx%d_%d" % (W, H, M), W, H, geo, np.stack(tfs), np.tile(P, (M, 1)), np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
+    sc = Scene(wl, np.stack([S.sensor_depth(W, H, 0.3 * s + seed) for s in range(M)]))
+    sc.M = M
+    sc.mm = depth_f32_to_u16(np.nan_to_num(sc.depth, nan=0.0, posinf=0.0))
+    sc.ctx = sc.context(**pkw)
+    return sc
+
+
 def untouched(a, n, what):
     """Streams n.. of a buffer pre-filled with the sentinel still hold it, byte for byte."""
     rest = np.ascontiguousarray(a[n:]).view(np.uint8).reshape(-1)
@@ -92,13 +84,6 @@ def untouched(a, n, what):
     else:
         want = np.full(rest.shape, SENTINEL_U8, np.uint8)
     assert np.array_equal(rest, want), "%s: streams %d.. were written" % (what, n)
-
-
-def unpack_bits(bits, W, H):
-    """[words] uint32 -> [H, W] bool (pixel x = bit x % 32 of word y * ceil(W/32) + x / 32)."""
-    rw = (W + 31) // 32
-    b = np.unpackbits(np.ascontiguousarray(bits, np.uint32).reshape(H, rw).view(np.uint8), axis=1, bitorder="little")
-    return b[:, :W].astype(bool)
 
 
 def fill(a):
@@ -170,7 +155,7 @@ SPLITS = [(3, 8, 64, 49), (3, 6, 64, 56), (3, 6, 64, 60), (3, 8, 128, 121), (2, 
                          [sp + ((131, 77),) for sp in ((3, 8, 64, 49), (2, 5, 33, 32), (1, 5, 40, 37))])
 def test_partial_batch_split_matrix(lanes, group, M, n, size):
     """131 x 77: the last tile row and column are partial."""
-    sc = Scene(size[0], size[1], M, seed=1000 + 7 * n + M + lanes, max_inflight_streams=group, raster_lanes=lanes)
+    sc = scene(size[0], size[1], M, seed=1000 + 7 * n + M + lanes, max_inflight_streams=group, raster_lanes=lanes)
     ctx = sc.ctx
     st = ctx.stats()
     assert st["launch_group"] == group and st["counter_blocks"] == LG.counter_blocks_for(M, group, lanes), st
@@ -191,7 +176,7 @@ def test_memory_limit_shrink_then_partial_batches():
     full batch, up to five of the partial batches that need more groups than a full one at the new launch group (there may
     be none: groups of 2 streams have none), and a full batch after them."""
     M, lanes = 64, 3
-    sc = Scene(128, 96, M, seed=79, bin_capacity=1, memory_limit_mb=1, raster_lanes=lanes)
+    sc = scene(128, 96, M, seed=79, bin_capacity=1, memory_limit_mb=1, raster_lanes=lanes)
     ctx = sc.ctx
     before = ctx.stats()
     g0 = before["launch_group"]
@@ -217,7 +202,7 @@ def test_every_entry_point_at_a_partial_batch():
     0 .. 48 of buffers sized for 64 streams and pre-filled with a sentinel; streams 49 .. 63 stay untouched."""
     import torch
     M, n = 64, 49
-    sc = Scene(128, 96, M, seed=80, max_inflight_streams=8, raster_lanes=3)
+    sc = scene(128, 96, M, seed=80, max_inflight_streams=8, raster_lanes=3)
     ctx, H, W = sc.ctx, sc.H, sc.W
     assert LG.groups_for(n, 8, 3) == 9 > LG.groups_for(M, 8, 3) and ctx.stats()["counter_blocks"] == 9
     words = ctx.mask_bits_words()
@@ -287,7 +272,7 @@ def test_batch_size_changes_between_batches_in_flight():
     0 exactly when the planes it saw were the oracle's.  After retirement every frame is exact."""
     import torch
     M = 64
-    sc = Scene(128, 96, M, seed=81, max_inflight_streams=8, raster_lanes=3)
+    sc = scene(128, 96, M, seed=81, max_inflight_streams=8, raster_lanes=3)
     ctx, H, W = sc.ctx, sc.H, sc.W
     d = torch.from_numpy(sc.depth).to("cuda:0")
     user = Consumer(ctx)
@@ -328,7 +313,7 @@ def test_graph_cache_never_replays_another_batch_size():
     own size -- the outputs are exact and streams beyond n untouched, so a graph of 5 streams never stands in for 7."""
     import torch
     M = 8
-    sc = Scene(128, 96, M, seed=82, pipelines=2)
+    sc = scene(128, 96, M, seed=82, pipelines=2)
     ctx, H, W = sc.ctx, sc.H, sc.W
     d = torch.from_numpy(sc.depth).to("cuda:0")
     masked = torch.empty((M, H, W), dtype=torch.float32, device="cuda:0")
@@ -362,7 +347,7 @@ def test_batch_sizes_outside_1_to_max_streams_are_refused(bad):
     out of bounds even if one were not), and the context filters exactly afterwards."""
     import torch
     M = 40
-    sc = Scene(128, 96, M, seed=83, max_inflight_streams=8, raster_lanes=3)
+    sc = scene(128, 96, M, seed=83, max_inflight_streams=8, raster_lanes=3)
     ctx, H, W = sc.ctx, sc.H, sc.W
     n = 0 if bad == "zero" else M + 1
     N = M + 1

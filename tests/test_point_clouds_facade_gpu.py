@@ -9,8 +9,7 @@ import pytest
 
 from bench_support import cloud_check as CC
 from bench_support import workloads as WL
-from realtime_urdf_filter_amd import urdf
-from realtime_urdf_filter_amd.filter import CameraInfo, FilterParameters, RealtimeURDFFilter
+from gpu_support import INTR, info, example_facade, sensor_plane
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -101,15 +100,6 @@ int main(int argc, char** argv)
 '''
 
 
-def python_facade(**kw):
-    tf = urdf.StaticTransformProvider()
-    tf.set_frames(urdf.forward_kinematics(urdf.Model.from_string(WL.EXAMPLE_URDF)), "/EXAMPLE/")
-    tf.frames["/world"] = urdf.Transform()
-    tf.frames["/cam"] = urdf.Transform(np.array([[1.0, 0, 0], [0, 0, 1.0], [0, -1.0, 0]]), (0, 0, 0))
-    prm = FilterParameters("/world", "/cam", [{"model": "d", "tf_prefix": "/EXAMPLE", "geometry_type": "visual"}], 0.05, filter_replace_value=5.0, **kw)
-    return RealtimeURDFFilter(prm, tf, {"d": WL.EXAMPLE_URDF}), tf
-
-
 def facade_expectation(f, tf, depth, P, intr):
     """The oracle's mask over the façade's own draw list and camera, and cloud_check on it."""
     from oracle import bindings as O
@@ -122,20 +112,9 @@ def facade_expectation(f, tf, depth, P, intr):
     return CC.organized(depth, mask, intr), CC.compacted(depth, mask, intr)
 
 
-def sensor_plane():
-    d = np.ascontiguousarray(WL.example_workload(640, 480).depth_batch()[0], np.float32).copy()      # (example_scene's sensor plane)
-    d[::9, ::4] = np.nan
-    d[5::13, 2::7] = 0.0
-    d[7::31, 3::11] = np.inf
-    return d
-
-
-INTR = (525.0, 520.0, 319.5, 239.5)
-
-
 def test_python_facade_cloud_matches_the_expectation():
     depth = sensor_plane()
-    f, tf = python_facade()
+    f, tf = example_facade()
     P = f.getProjectionMatrix(info())
     first = f.cloud(depth, P, 640, 480)          # (loads the models and poses the links: the expectation reads the façade's draw list)
     org, (pts, idx, count) = facade_expectation(f, tf, depth, P, INTR)
@@ -153,15 +132,11 @@ OWN = (585.260, 585.028, 317.387, 239.264)      # (none of them a float)
 OWN_F = tuple(float(np.float32(v)) for v in OWN)
 
 
-def info(width=640, height=480, intr=INTR):
-    return CameraInfo(width, height, [intr[0], 0, intr[2], 0, 0, intr[1], intr[3], 0, 0, 0, 1, 0])
-
-
 def test_python_facade_cloud_at_a_second_image_size():
     """The same intrinsics at 320 x 240: the façade makes a new context, which must be given the intrinsics again."""
     depth = sensor_plane()
     half = np.ascontiguousarray(depth[::2, ::2])
-    f, tf = python_facade()
+    f, tf = example_facade()
     P = f.getProjectionMatrix(info())
     first = f.cloud(depth, P, 640, 480)
     P2 = f.getProjectionMatrix(info(320, 240))
@@ -174,7 +149,7 @@ def test_python_facade_cloud_at_a_second_image_size():
 
 def test_python_facade_own_calibration_counts_as_floats():
     depth = sensor_plane()
-    f, tf = python_facade(use_own_calibration=True, own_calibration=OWN)
+    f, tf = example_facade(use_own_calibration=True, own_calibration=OWN)
     P = f.getProjectionMatrix(info(intr=(100.0, 100.0, 1.0, 1.0)))          # (the camera info's intrinsics are ignored)
     got = f.cloud(depth, P, 640, 480)
     assert OWN_F != OWN and f.cloud_intrinsics_ == OWN_F
@@ -184,7 +159,7 @@ def test_python_facade_own_calibration_counts_as_floats():
 
 def test_cpp_facade_cloud_into_matches_the_expectation(tmp_path):
     depth = sensor_plane()
-    f, tf = python_facade()
+    f, tf = example_facade()
     P = f.getProjectionMatrix(info())
     first = f.cloud(depth, P, 640, 480)          # (loads the models and poses the links: the expectation reads the façade's draw list)
     org, (pts, idx, count) = facade_expectation(f, tf, depth, P, INTR)
@@ -194,7 +169,7 @@ def test_cpp_facade_cloud_into_matches_the_expectation(tmp_path):
     P2 = f.getProjectionMatrix(info(320, 240))
     f.cloud(half, P2, 320, 240)
     org_half, _ = facade_expectation(f, tf, half, P2, INTR)
-    g, tfg = python_facade(use_own_calibration=True, own_calibration=OWN)
+    g, tfg = example_facade(use_own_calibration=True, own_calibration=OWN)
     Pg = g.getProjectionMatrix(info())
     g.cloud(depth, Pg, 640, 480)
     org_own, _ = facade_expectation(g, tfg, depth, Pg, OWN_F)

@@ -1,6 +1,6 @@
 """GPU (-m gpu, except the expectation's self-check): filtered point clouds (include/rtuf.h, FILTERED POINT CLOUDS).
 
-The expectation is bench_support/cloud_check.py applied to the mask the dilation tests expect (Scene.expected(r)[1], built
+The expectation is bench_support/cloud_check.py applied to the mask the dilation tests expect (gpu_support.filter_expected(sc, r)[1], built
 from the CPU oracle's planes; with per-link thresholds link_thresholds_check.expected_planes) and the scene's sensor plane --
 never the library's own mask.  Organized planes are compared as uint32 bit patterns; compacted output for equality on
 [:count], together with counts and index.  Every stream has intrinsics of its own, so a point computed with another stream's
@@ -12,20 +12,16 @@ import realtime_urdf_filter_amd as R
 from bench_support import cloud_check as CC
 from bench_support.link_thresholds_check import expected_planes
 from bench_support.link_thresholds_check import workload_draws as thr_draws
+from gpu_support import CLOUD_SENTINEL as SENTINEL
+from gpu_support import (CloudBuffers, CloudExpect, Consumer, OracleScene, border_scene, cached, check_comp, check_org, cloud_context, cloud_enqueue,
+                         cloud_expect, filter_expected, intrinsics, neighbour_scene, params, sensor_of, set_radius, soup_scene, torch_device,
+                         undrawn_scene, upload)
 from oracle import bindings as O
 from realtime_urdf_filter_amd.filter import depth_f32_to_u16
-from test_batch_status_gpu import Consumer, params
-from test_silhouette_dilation_gpu import Scene, border_scene, neighbour_scene, set_radius, soup_scene, undrawn_scene
 
 gpu = pytest.mark.gpu
 INVALID, STATE = -1, -6
 STATUS_UNCOVERED = 1 << 20
-SENTINEL = 0x5A5A5A5A
-
-
-def _torch():
-    import torch
-    return torch, torch.device("cuda:0")
 
 
 # ---- scenes and expectations -------------------------------------------------------------------------------------------------
@@ -37,113 +33,30 @@ def _neighbours_with_invalid_pixels():
     depth[0, 50:54, 7:90] = np.nan
     depth[2, 60, :] = 0.0
     depth[2, 61, 3:40] = np.inf
-    return Scene(nb.name, nb.wl, depth)
+    return OracleScene(nb.wl, depth, nb.name)
 
 
 BUILDERS = {"soup_160x120": lambda: soup_scene(1, 160, 120), "soup_100x75": lambda: soup_scene(3, 100, 75), "neighbours": _neighbours_with_invalid_pixels,
             "borders": border_scene, "undrawn": undrawn_scene}
-_scenes, _expect = {}, {}
 
 
+@cached
 def scene(name):
-    if name not in _scenes:
-        _scenes[name] = BUILDERS[name]()
-    return _scenes[name]
-
-
-def intrinsics(sc, slot):
-    """fx, fy, cx, cy of stream slot `slot`: different for every slot."""
-    f = 262.5 * sc.W / 320.0
-    return (f + slot, f - 0.5 * slot, (sc.W - 1) / 2.0 + 0.25 * slot, (sc.H - 1) / 2.0 - 0.5 * slot)
-
-
-def sensor_of(sc, u16):
-    return CC.u16_to_metres(depth_f32_to_u16(sc.depth)) if u16 else sc.depth
-
-
-class Expect:
-    """Organized planes and compacted lists of streams `streams` of a scene (in slots 0 ..) for a given mask."""
-
-    def __init__(self, sc, mask, u16, streams):
-        sensor = sensor_of(sc, u16)
-        self.org = np.stack([CC.organized(sensor[s], mask[s], intrinsics(sc, i)) for i, s in enumerate(streams)])
-        self.comp = [CC.compacted(sensor[s], mask[s], intrinsics(sc, i)) for i, s in enumerate(streams)]
-        self.counts = np.array([c[2] for c in self.comp], np.uint32)
-        cls = np.array([CC.classes(sensor[s], mask[s]) for s in streams])
-        # (a vacuous pass must not hide: the batch has kept, filtered and invalid pixels)
-        assert (cls.sum(axis=0) > 0).all(), cls
+    return BUILDERS[name]()
 
 
 def expect(name, r=0, u16=False, streams=None):
-    sc = scene(name)
-    streams = tuple(range(sc.n)) if streams is None else tuple(streams)
-    key = (name, r, u16, streams)
-    if key not in _expect:
-        _expect[key] = Expect(sc, sc.expected(r, u16)[1], u16, streams)
-    return _expect[key]
-
-
-def context(sc, n=None, intr=True, **kw):
-    ctx = sc.context(**kw)
-    if intr:
-        ctx.set_cloud_intrinsics(0, [intrinsics(sc, i) for i in range(n or sc.n)])
-    return ctx
-
-
-def check_org(got, ex, what, n=None):
-    got = np.ascontiguousarray(got, np.float32)
-    want = ex.org[:n or len(ex.org)]
-    bad = int((got.view(np.uint32) != want.view(np.uint32)).sum())
-    assert got.shape == want.shape and bad == 0, "%s: %d words differ" % (what, bad)
-
-
-def check_comp(points, index, counts, ex, cap, what, n=None):
-    n = n or len(ex.comp)
-    assert np.array_equal(np.asarray(counts)[:n], ex.counts[:n]), "%s: counts %s, expected %s" % (what, counts, ex.counts)
-    for s in range(n):
-        p, i, c = ex.comp[s]
-        m = min(c, cap)
-        assert np.array_equal(np.ascontiguousarray(points[s][:m]).view(np.uint32), p[:m].view(np.uint32)), "%s stream %d: points" % (what, s)
-        if index is not None:
-            assert np.array_equal(np.asarray(index[s][:m]).view(np.uint32), i[:m]), "%s stream %d: index" % (what, s)
-
-
-class Buffers:
-    """Device outputs of one cloud batch, filled with a sentinel."""
-
-    def __init__(self, sc, total, capacity=None):
-        torch, dev = _torch()
-        self.cap = capacity
-        per = (sc.H, sc.W) if capacity is None else (capacity,)
-        self.points = torch.full((total,) + per + (3,), SENTINEL, dtype=torch.int32, device=dev)
-        self.index = torch.full((total, capacity), SENTINEL, dtype=torch.int32, device=dev) if capacity else None
-        self.counts = torch.full((total,), SENTINEL, dtype=torch.int32, device=dev) if capacity else None
-
-    def host(self):
-        f = lambda t, d: None if t is None else np.ascontiguousarray(t.cpu().numpy()).view(d)
-        return f(self.points, np.float32), f(self.index, np.uint32), f(self.counts, np.uint32)
-
-
-def upload(sensor):
-    torch, dev = _torch()
-    return torch.from_numpy(sensor.view(np.int16) if sensor.dtype == np.uint16 else sensor).to(dev)
-
-
-def enqueue(ctx, d, n, buf, u16=False, index=True):
-    if buf.cap is None:
-        ctx.cloud_batch_device(n, d.data_ptr(), buf.points.data_ptr(), u16=u16)
-    else:
-        ctx.cloud_compact_batch_device(n, d.data_ptr(), buf.points.data_ptr(), buf.index.data_ptr() if index else None, buf.counts.data_ptr(), buf.cap, u16=u16)
+    return cloud_expect(scene(name), r, u16, streams)
 
 
 def device_forms(ctx, sc, ex, u16, what, n=None, total=None):
     """The organized and the compacted device form of one sensor batch against ex."""
     n, total = n or sc.n, total or sc.n
     d = upload(depth_f32_to_u16(sc.depth) if u16 else sc.depth)
-    org = Buffers(sc, total)
-    enqueue(ctx, d, n, org, u16)
-    comp = Buffers(sc, total, sc.W * sc.H)
-    enqueue(ctx, d, n, comp, u16)
+    org = CloudBuffers(sc, total)
+    cloud_enqueue(ctx, d, n, org, u16)
+    comp = CloudBuffers(sc, total, sc.W * sc.H)
+    cloud_enqueue(ctx, d, n, comp, u16)
     ctx.sync()
     assert ctx.stats()["batch_status"] == 0
     check_org(org.host()[0][:n], ex, what + " organized", n)
@@ -158,9 +71,9 @@ def test_expected_counts_of_the_soup_scenes():
     ex = expect("soup_160x120")
     assert ex.counts.tolist() == [9976, 117, 7727]
     sc = scene("soup_160x120")
-    inv = [CC.classes(sc.depth[s], sc.expected(0)[1][s])[2] for s in range(sc.n)]
+    inv = [CC.classes(sc.depth[s], filter_expected(sc, 0)[1][s])[2] for s in range(sc.n)]
     assert all(591 <= v <= 636 for v in inv), inv
-    rows = CC.kept(sc.depth[1], sc.expected(0)[1][1]).any(axis=1)
+    rows = CC.kept(sc.depth[1], filter_expected(sc, 0)[1][1]).any(axis=1)
     assert int((~rows).sum()) == 112                         # stream 1: 112 rows without a kept pixel
     assert expect("soup_100x75").counts.tolist() == [5045, 4757, 4715]
     assert expect("soup_100x75", 2).counts.tolist() == [4561, 3744, 3453]
@@ -173,7 +86,7 @@ def test_expected_counts_of_the_soup_scenes():
 @pytest.mark.parametrize("name", ["soup_160x120", "soup_100x75"])
 def test_all_forms_match_the_expectation(name):
     sc = scene(name)
-    ctx = context(sc)
+    ctx = cloud_context(sc)
     depth16 = depth_f32_to_u16(sc.depth)
     ctx.filter_batch(sc.depth)                    # (sizes the bins: the batches below are final at once)
     for r in (0, 2):
@@ -198,12 +111,12 @@ def test_capacity_filled_exactly_and_exceeded():
     sc = scene("neighbours")
     ex = expect("neighbours")
     assert ex.counts[1] == sc.W * sc.H
-    ctx = context(sc)
+    ctx = cloud_context(sc)
     d = upload(sc.depth)
-    full = Buffers(sc, sc.n, sc.W * sc.H)
-    enqueue(ctx, d, sc.n, full)
-    small = Buffers(sc, sc.n, 1000)
-    enqueue(ctx, d, sc.n, small, index=False)
+    full = CloudBuffers(sc, sc.n, sc.W * sc.H)
+    cloud_enqueue(ctx, d, sc.n, full)
+    small = CloudBuffers(sc, sc.n, 1000)
+    cloud_enqueue(ctx, d, sc.n, small, index=False)
     ctx.sync()
     p, i, c = full.host()
     check_comp(p, i, c, ex, sc.W * sc.H, "capacity = W*H")
@@ -233,14 +146,14 @@ def test_per_link_thresholds_are_honoured():
                                                  z_far=wl.far, max_diff=wl.max_diff, replace_value=wl.replace_value, want_debug=True)
             planes.append(expected_planes(zwin, prim, sensor[s], thr, nt, wl.max_diff, wl.near, wl.far, wl.replace_value)[1])
         masks[u16] = np.stack(planes)
-    assert (masks[False] != sc.expected(0)[1]).any()                    # the thresholds change the mask
-    ctx = context(sc)
+    assert (masks[False] != filter_expected(sc, 0)[1]).any()                    # the thresholds change the mask
+    ctx = cloud_context(sc)
     ids = list(range(len(wl.models)))
     ctx.set_link_thresholds(ids[0], link_thr)
     for u16 in (False, True):
-        ex = Expect(sc, masks[u16], u16, range(sc.n))
+        ex = CloudExpect(sc, masks[u16], u16, range(sc.n))
         device_forms(ctx, sc, ex, u16, "thresholds u16=%s" % u16)
-    check_org(ctx.cloud_batch(sc.depth), Expect(sc, masks[False], False, range(sc.n)), "thresholds, host planes")
+    check_org(ctx.cloud_batch(sc.depth), CloudExpect(sc, masks[False], False, range(sc.n)), "thresholds, host planes")
     ctx.clear_link_thresholds(ids[0])
     device_forms(ctx, sc, expect("borders"), False, "after clear")
     ctx.close()
@@ -249,10 +162,10 @@ def test_per_link_thresholds_are_honoured():
 @gpu
 def test_uncovered_image_fails_when_the_batch_is_retired():
     sc = scene("undrawn")
-    ctx = context(sc)
+    ctx = cloud_context(sc)
     d = upload(sc.depth)
-    for buf in (Buffers(sc, sc.n), Buffers(sc, sc.n, 500)):
-        enqueue(ctx, d, sc.n, buf)
+    for buf in (CloudBuffers(sc, sc.n), CloudBuffers(sc, sc.n, 500)):
+        cloud_enqueue(ctx, d, sc.n, buf)
         with pytest.raises(R.RtufError) as e:
             ctx.sync()
         assert e.value.code == STATE and "background quad" in str(e.value)
@@ -268,7 +181,7 @@ def test_refusals_enqueue_nothing_and_a_good_call_still_matches():
     sc = scene("soup_160x120")
     ex = expect("soup_160x120")
     d = upload(sc.depth)
-    org, comp = Buffers(sc, sc.n), Buffers(sc, sc.n, 3000)
+    org, comp = CloudBuffers(sc, sc.n), CloudBuffers(sc, sc.n, 3000)
 
     def refused(code, call):
         with pytest.raises(R.RtufError) as e:
@@ -277,7 +190,7 @@ def test_refusals_enqueue_nothing_and_a_good_call_still_matches():
 
     def untouched():
         ctx.sync()
-        _torch()[0].cuda.synchronize()
+        torch_device()[0].cuda.synchronize()
         for buf in (org, comp):
             for t in (buf.points, buf.index, buf.counts):
                 assert t is None or bool((t == SENTINEL).all())
@@ -285,21 +198,21 @@ def test_refusals_enqueue_nothing_and_a_good_call_still_matches():
     p = params(replace=sc.wl.replace_value, max_diff=sc.wl.max_diff)
     p.near_plane, p.far_plane = sc.wl.near, sc.wl.far
     ctx = R.Context(sc.W, sc.H, sc.n, 0, p)
-    refused(STATE, lambda: enqueue(ctx, d, sc.n, org))                  # before finalize
+    refused(STATE, lambda: cloud_enqueue(ctx, d, sc.n, org))                  # before finalize
     ids = sc.wl.load_into(ctx)
     sc.wl.stage(ctx, ids)
-    refused(STATE, lambda: enqueue(ctx, d, sc.n, org))                  # no intrinsics at all
+    refused(STATE, lambda: cloud_enqueue(ctx, d, sc.n, org))                  # no intrinsics at all
     refused(STATE, lambda: ctx.cloud_batch(sc.depth))
     ctx.set_cloud_intrinsics(0, [intrinsics(sc, i) for i in range(2)])
-    refused(STATE, lambda: enqueue(ctx, d, sc.n, comp))                 # stream 2 has none yet
+    refused(STATE, lambda: cloud_enqueue(ctx, d, sc.n, comp))                 # stream 2 has none yet
     for bad in ((0.0, 100.0, 1.0, 1.0), (100.0, -2.0, 1.0, 1.0), (np.nan, 100.0, 1.0, 1.0), (100.0, np.inf, 1.0, 1.0)):
         refused(INVALID, lambda: ctx.set_cloud_intrinsics(1, [intrinsics(sc, 1), bad]))      # ... and a refused set changes nothing
     refused(INVALID, lambda: ctx.set_cloud_intrinsics(2, [intrinsics(sc, 2)] * 2))           # beyond max_streams
-    refused(STATE, lambda: enqueue(ctx, d, sc.n, comp))
+    refused(STATE, lambda: cloud_enqueue(ctx, d, sc.n, comp))
     ctx.set_cloud_intrinsics(2, intrinsics(sc, 2))
     for cap in (0, sc.W * sc.H + 1, -5):
         comp.cap = cap
-        refused(INVALID, lambda: enqueue(ctx, d, sc.n, comp))
+        refused(INVALID, lambda: cloud_enqueue(ctx, d, sc.n, comp))
         refused(INVALID, lambda: ctx.cloud_compact_batch(sc.depth, cap))
     comp.cap = 3000
     refused(INVALID, lambda: ctx.cloud_batch_device(sc.n, None, org.points.data_ptr()))      # NULL planes
@@ -308,11 +221,11 @@ def test_refusals_enqueue_nothing_and_a_good_call_still_matches():
     refused(INVALID, lambda: ctx.cloud_batch_device(sc.n, d.data_ptr() + 4, org.points.data_ptr()))            # organized: 16-byte alignment
     refused(INVALID, lambda: ctx.cloud_batch_device(sc.n, d.data_ptr(), org.points.data_ptr() + 8))
     refused(INVALID, lambda: ctx.cloud_batch_device(sc.n, d.data_ptr() + 4, org.points.data_ptr(), u16=True))  # (16UC1: 8 bytes)
-    refused(INVALID, lambda: enqueue(ctx, d, 0, org))                   # n out of range
-    refused(INVALID, lambda: enqueue(ctx, d, sc.n + 1, comp))
+    refused(INVALID, lambda: cloud_enqueue(ctx, d, 0, org))                   # n out of range
+    refused(INVALID, lambda: cloud_enqueue(ctx, d, sc.n + 1, comp))
     untouched()
-    enqueue(ctx, d, sc.n, org)
-    enqueue(ctx, d, sc.n, comp)
+    cloud_enqueue(ctx, d, sc.n, org)
+    cloud_enqueue(ctx, d, sc.n, comp)
     ctx.sync()
     check_org(org.host()[0], ex, "after the refusals")
     pp, ii, cc = comp.host()
@@ -323,11 +236,11 @@ def test_refusals_enqueue_nothing_and_a_good_call_still_matches():
 @gpu
 def test_width_that_is_no_multiple_of_4_is_refused():
     sc = soup_scene(2, 517, 389, n=1)
-    ctx = context(sc)
+    ctx = cloud_context(sc)
     d = upload(sc.depth)
-    buf = Buffers(sc, 1)
+    buf = CloudBuffers(sc, 1)
     with pytest.raises(R.RtufError) as e:
-        enqueue(ctx, d, 1, buf)
+        cloud_enqueue(ctx, d, 1, buf)
     assert e.value.code == INVALID and "multiple of 4" in str(e.value)
     with pytest.raises(R.RtufError) as e:
         ctx.cloud_compact_batch(sc.depth, 100)
@@ -335,7 +248,7 @@ def test_width_that_is_no_multiple_of_4_is_refused():
     ctx.sync()
     assert bool((buf.points == SENTINEL).all())
     masked, mask = ctx.filter_batch(sc.depth)                           # the context still filters
-    assert np.array_equal(mask, sc.expected(0)[1])
+    assert np.array_equal(mask, filter_expected(sc, 0)[1])
     ctx.close()
 
 
@@ -346,14 +259,14 @@ def test_width_that_is_no_multiple_of_4_is_refused():
                          ids=["one_lane", "three_lanes", "two_kernel_flag", "two_pipelines"])
 def test_lanes_flags_and_pipelines(kw):
     sc = scene("soup_160x120")
-    ctx = context(sc, **kw)
+    ctx = cloud_context(sc, **kw)
     for r in (0, 2):
         set_radius(ctx, sc, r, **kw)
         for u16 in (False, True):
             device_forms(ctx, sc, expect("soup_160x120", r, u16), u16, "%s r=%d u16=%s" % (kw, r, u16))
     if "flags" in kw:                             # the context filters in two-kernel mode as before, and the cloud again behind it
         masked, mask = ctx.filter_batch(sc.depth)
-        assert np.array_equal(mask, sc.expected(2)[1])
+        assert np.array_equal(mask, filter_expected(sc, 2)[1])
         device_forms(ctx, sc, expect("soup_160x120", 2), False, "behind a two-kernel filter batch")
     ctx.close()
 
@@ -361,7 +274,7 @@ def test_lanes_flags_and_pipelines(kw):
 @gpu
 def test_partial_batch_leaves_the_other_streams_alone():
     sc = scene("soup_160x120")
-    ctx = context(sc)
+    ctx = cloud_context(sc)
     ex = expect("soup_160x120")
     org, comp = device_forms(ctx, sc, ex, False, "2 of 3 streams", n=2, total=3)
     assert bool((org.points[2] == SENTINEL).all()) and bool((comp.points[2] == SENTINEL).all())
@@ -372,7 +285,7 @@ def test_partial_batch_leaves_the_other_streams_alone():
 @gpu
 def test_several_launch_groups():
     sc = scene("soup_160x120")
-    ctx = context(sc, max_inflight_streams=1, raster_lanes=3)
+    ctx = cloud_context(sc, max_inflight_streams=1, raster_lanes=3)
     device_forms(ctx, sc, expect("soup_160x120"), False, "three groups")
     assert ctx.stats()["groups_last_batch"] == 3
     ctx.close()
@@ -381,12 +294,12 @@ def test_several_launch_groups():
 @gpu
 def test_two_batches_in_flight_with_outputs_of_their_own():
     sc = scene("soup_160x120")
-    ctx = context(sc)
+    ctx = cloud_context(sc)
     ctx.filter_batch(sc.depth)
     d, d16 = upload(sc.depth), upload(depth_f32_to_u16(sc.depth))
-    a, b = Buffers(sc, sc.n), Buffers(sc, sc.n, 8000)
-    enqueue(ctx, d, sc.n, a)
-    enqueue(ctx, d16, sc.n, b, u16=True)
+    a, b = CloudBuffers(sc, sc.n), CloudBuffers(sc, sc.n, 8000)
+    cloud_enqueue(ctx, d, sc.n, a)
+    cloud_enqueue(ctx, d16, sc.n, b, u16=True)
     ctx.sync()
     check_org(a.host()[0], expect("soup_160x120"), "first in flight")
     p, i, c = b.host()
@@ -397,17 +310,17 @@ def test_two_batches_in_flight_with_outputs_of_their_own():
 @gpu
 def test_regrown_bins_rerun_rewrites_counts_and_points():
     sc = scene("soup_160x120")
-    ctx = context(sc, bin_capacity=1, silhouette_dilation_px=2)
+    ctx = cloud_context(sc, bin_capacity=1, silhouette_dilation_px=2)
     d = upload(sc.depth)
-    org, comp = Buffers(sc, sc.n), Buffers(sc, sc.n, sc.W * sc.H)
-    enqueue(ctx, d, sc.n, comp)
+    org, comp = CloudBuffers(sc, sc.n), CloudBuffers(sc, sc.n, sc.W * sc.H)
+    cloud_enqueue(ctx, d, sc.n, comp)
     ctx.sync()
     st = ctx.stats()
     assert st["regrowths"] >= 1 and st["batch_reruns"] >= 1 and st["batch_status"] != 0, st
     ex = expect("soup_160x120", 2)
     p, i, c = comp.host()
     check_comp(p, i, c, ex, sc.W * sc.H, "re-run")
-    enqueue(ctx, d, sc.n, org)                    # the next batch is final at once
+    cloud_enqueue(ctx, d, sc.n, org)                    # the next batch is final at once
     ctx.sync()
     assert ctx.stats()["batch_status"] == 0
     check_org(org.host()[0], ex, "after the re-run")
@@ -417,7 +330,7 @@ def test_regrown_bins_rerun_rewrites_counts_and_points():
 @gpu
 def test_regrown_bins_rerun_host_planes():
     sc = scene("soup_160x120")
-    ctx = context(sc, bin_capacity=1)
+    ctx = cloud_context(sc, bin_capacity=1)
     p, i, c = ctx.cloud_compact_batch(sc.depth, sc.W * sc.H)
     assert ctx.stats()["batch_reruns"] >= 1
     check_comp(p, i, c, expect("soup_160x120"), sc.W * sc.H, "re-run, host planes")
@@ -428,11 +341,11 @@ def test_regrown_bins_rerun_host_planes():
 def test_graph_replay_follows_the_sensor():
     """One raster lane, pipelines = 2, one stream: small batches replay a captured graph, the cloud kernels included.  The
     same buffers every time; sensor plane and poses change in between."""
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = scene("soup_160x120")
-    ctx = context(sc, n=1, max_streams=1, raster_lanes=1, pipelines=2)
+    ctx = cloud_context(sc, n=1, max_streams=1, raster_lanes=1, pipelines=2)
     d = torch.empty((1, sc.H, sc.W), dtype=torch.float32, device=dev)
-    org, comp = Buffers(sc, 1), Buffers(sc, 1, 9000)
+    org, comp = CloudBuffers(sc, 1), CloudBuffers(sc, 1, 9000)
     for i in range(15):
         s = i % sc.n
         ctx.set_cameras(0, sc.wl.projection[s:s + 1], sc.wl.offset_inv[s:s + 1], sc.wl.cam_tf[s:s + 1])
@@ -441,11 +354,11 @@ def test_graph_replay_follows_the_sensor():
         torch.cuda.synchronize()
         ex = expect("soup_160x120", 0, False, (s,))
         if i % 5 == 4:
-            enqueue(ctx, d, 1, org)
+            cloud_enqueue(ctx, d, 1, org)
             ctx.sync()
             check_org(org.host()[0], ex, "replay %d" % i)
         else:
-            enqueue(ctx, d, 1, comp)
+            cloud_enqueue(ctx, d, 1, comp)
             ctx.sync()
             p, ix, c = comp.host()
             check_comp(p, ix, c, ex, 9000, "replay %d" % i)
@@ -457,12 +370,12 @@ def test_graph_replay_follows_the_sensor():
 @gpu
 def test_status_word_is_zero_behind_a_final_cloud_batch():
     sc = scene("soup_160x120")
-    ctx = context(sc)
+    ctx = cloud_context(sc)
     ctx.filter_batch(sc.depth)                    # (bins sized)
     d = upload(sc.depth)
-    comp = Buffers(sc, sc.n, sc.W * sc.H)
+    comp = CloudBuffers(sc, sc.n, sc.W * sc.H)
     user = Consumer(ctx)
-    enqueue(ctx, d, sc.n, comp)
+    cloud_enqueue(ctx, d, sc.n, comp)
     word, early_points, early_counts, _ = user.read(comp.points, comp.counts)
     assert word == 0, hex(word)
     ex = expect("soup_160x120")
@@ -477,16 +390,16 @@ def test_status_word_is_zero_behind_a_final_cloud_batch():
 @gpu
 def test_counts_shrink_when_the_second_call_keeps_fewer_pixels():
     sc = scene("soup_160x120")
-    ctx = context(sc)
+    ctx = cloud_context(sc)
     d = upload(sc.depth)
-    comp = Buffers(sc, sc.n, sc.W * sc.H)
-    enqueue(ctx, d, sc.n, comp)
+    comp = CloudBuffers(sc, sc.n, sc.W * sc.H)
+    cloud_enqueue(ctx, d, sc.n, comp)
     ctx.sync()
     p, i, c = comp.host()
     first = expect("soup_160x120")
     check_comp(p, i, c, first, sc.W * sc.H, "first call")
     set_radius(ctx, sc, 2)
-    enqueue(ctx, d, sc.n, comp)
+    cloud_enqueue(ctx, d, sc.n, comp)
     ctx.sync()
     p, i, c = comp.host()
     second = expect("soup_160x120", 2)
@@ -498,7 +411,7 @@ def test_counts_shrink_when_the_second_call_keeps_fewer_pixels():
 @gpu
 def test_scratch_is_counted_in_device_bytes_and_timings_land_in_ms_compare():
     sc = scene("soup_160x120")
-    ctx = context(sc)
+    ctx = cloud_context(sc)
     ctx.filter_batch(sc.depth)
     before = ctx.stats()["device_bytes"]
     ctx.enable_timing(2)

@@ -11,142 +11,26 @@ import pytest
 import scenes as S
 import realtime_urdf_filter_amd as R
 from bench_support import workloads as WL
-from bench_support.dilation_check import drawn_z, shade, window_min
-from oracle import bindings as O
-from realtime_urdf_filter_amd.filter import depth_f32_to_u16, depth_u16_to_f32
-from test_batch_status_gpu import bits_equal, params
+from bench_support.dilation_check import window_min
+from gpu_support import (DeviceWord, OracleScene, bits_equal, border_scene, cached, centred_projection, compare_labels, compare_planes, filter_expected, neighbour_scene,
+                         pack_bits, params, quad, set_radius, soup_scene, undrawn_at, undrawn_scene, workload_of)
+from realtime_urdf_filter_amd.filter import depth_f32_to_u16
 
 RADII = (1, 2, 5, 16)
 STATUS_UNCOVERED = 1 << 20
 gpu = pytest.mark.gpu
 
 
-# ---- expectation --------------------------------------------------------------------------------------------------------
-
-def pack_bits(mask):
-    H, W = mask.shape
-    words = (W + 31) // 32
-    m = np.zeros((H, words * 32), np.uint8)
-    m[:, :W] = mask > 0
-    return np.packbits(m, axis=1, bitorder="little").view("<u4").reshape(H, words).reshape(-1)
-
-
-class Scene:
-    """A batch of streams with its oracle planes; `workload` is a bench_support Workload (one model or several)."""
-
-    def __init__(self, name, wl, depth):
-        self.name, self.wl, self.depth = name, wl, np.ascontiguousarray(depth, np.float32)
-        self.W, self.H, self.n = wl.width, wl.height, wl.n_streams
-        self.oracle = []
-        for s in range(self.n):
-            om, ok, zwin, prim, _ = O.filter_frame(self.depth[s], wl.projection[s], wl.oracle_draws(s), wl.offset_inv[s], wl.cam_tf[s],
-                                                   z_near=wl.near, z_far=wl.far, max_diff=wl.max_diff, replace_value=wl.replace_value,
-                                                   want_debug=True)
-            self.oracle.append((om, ok, drawn_z(zwin, prim)))
-        self._exp = {}
-
-    def zprime(self, s, r):
-        return window_min(self.oracle[s][2], r)
-
-    def expected(self, r, u16=False):
-        """(masked [n,H,W], mask [n,H,W]) at radius r; 16UC1: the sensor goes through convertTo both ways."""
-        key = (r, u16)
-        if key not in self._exp:
-            out = []
-            for s in range(self.n):
-                sensor = depth_u16_to_f32(depth_f32_to_u16(self.depth[s])) if u16 else self.depth[s]
-                m, k = shade(self.zprime(s, r), sensor, self.wl.near, self.wl.far, self.wl.max_diff, self.wl.replace_value)
-                out.append((depth_f32_to_u16(m) if u16 else m, k))
-            self._exp[key] = (np.stack([o[0] for o in out]), np.stack([o[1] for o in out]))
-        return self._exp[key]
-
-    def undrawn_at(self, r):
-        return any(np.isnan(self.zprime(s, r)).any() for s in range(self.n))
-
-    def context(self, max_streams=None, **kw):
-        p = params(replace=self.wl.replace_value, max_diff=self.wl.max_diff, **kw)
-        p.near_plane, p.far_plane = self.wl.near, self.wl.far
-        ctx = R.Context(self.W, self.H, max_streams or self.n, 0, p)
-        ids = self.wl.load_into(ctx)
-        self.wl.stage(ctx, ids, n=min(self.n, max_streams or self.n))
-        return ctx
-
-
-class _Draw:
-    def __init__(self, pre_op, op, verts, tris):
-        self.pre_op, self.op, self.verts, self.tris = pre_op, op, verts, tris
-
-
-def _workload(name, W, H, geo, link_tf, projection, offset_inv=None, cam_tf=None):
-    n = link_tf.shape[0]
-    wl = WL.Workload(name, W, H, n)
-    wl.models = [[[_Draw(*g)] for g in geo]]
-    wl.link_tf = [np.ascontiguousarray(link_tf, np.float64)]
-    wl.projection = np.ascontiguousarray(projection, np.float64)
-    wl.offset_inv = np.tile(S.gl(np.eye(4)), (n, 1)) if offset_inv is None else np.ascontiguousarray(offset_inv, np.float64)
-    wl.cam_tf = np.tile(S.gl(np.eye(4)), (n, 1)) if cam_tf is None else np.ascontiguousarray(cam_tf, np.float64)
-    return wl
-
-
-def _centred(W, H, f=None):
-    f = f or 262.5 * W / 320.0
-    return S.projection(f, f, (W - 1) / 2.0, (H - 1) / 2.0, W, H)
-
-
-def soup_scene(seed, W, H, n=3):
-    rng = np.random.default_rng(seed)
-    geo = S.soup_geometry(rng, n_links=6, tris_per_link=40)
-    tfs = np.stack([np.stack(S.random_link_poses(rng, len(geo), near=bool(s & 1))) for s in range(n)])
-    cams = [S.random_camera(rng, small=True) for _ in range(n)]
-    wl = _workload("soup%d_%dx%d" % (seed, W, H), W, H, geo, tfs, np.tile(_centred(W, H), (n, 1)),
-                   np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
-    return Scene(wl.name, wl, np.stack([S.sensor_depth(W, H, 0.37 * s + 0.1 * seed) for s in range(n)]))
-
-
-def _quad(x0, x1, y0, y1, z):
-    v = np.array([[x0, y0, z], [x1, y0, z], [x1, y1, z], [x0, y1, z]], np.float32)
-    return (0, [0.0, 0.0, 0.0], v, np.array([[0, 1, 2], [0, 2, 3]], np.uint32))
-
-
-def border_scene(W=160, H=120):
-    """Four bars, each crossing one image border (frustum half extents at z = 1: 0.61 x 0.46)."""
-    geo = [_quad(-0.9, -0.5, -0.7, 0.7, 1.0), _quad(0.5, 0.9, -0.7, 0.7, 1.1), _quad(-0.9, 0.9, -0.7, -0.38, 1.2),
-           _quad(-0.9, 0.9, 0.38, 0.7, 1.3)]
-    wl = _workload("borders_%dx%d" % (W, H), W, H, geo, np.tile(S.gl(np.eye(4)), (1, len(geo), 1)), _centred(W, H)[None])
-    return Scene(wl.name, wl, S.sensor_depth(W, H, 0.3)[None] * np.float32(0.6))
-
-
-def neighbour_scene(W=160, H=120):
-    """Streams 0 and 2 have a bar along their top and bottom edges, stream 1 between them sees nothing: a window that
-    crossed into a neighbouring plane would filter stream 1's first or last rows (sensor 2 m everywhere)."""
-    geo = [_quad(-0.9, 0.9, -0.7, -0.42, 1.0), _quad(-0.9, 0.9, 0.42, 0.7, 1.0)]
-    away = np.eye(4)
-    away[2, 3] = -5.0                          # behind the camera
-    tfs = np.stack([np.tile(S.gl(np.eye(4)), (len(geo), 1)), np.tile(S.gl(away), (len(geo), 1)), np.tile(S.gl(np.eye(4)), (len(geo), 1))])
-    wl = _workload("neighbours_%dx%d" % (W, H), W, H, geo, tfs, np.tile(_centred(W, H), (3, 1)))
-    return Scene(wl.name, wl, np.full((3, H, W), 2.0, np.float32))
-
-
-def undrawn_scene(W=160, H=120):
-    """A projection the background quad does not cover (clip-space x shifted): the left part of the image stays at the clear
-    colour, and geometry on its edge turns some of it into drawn pixels once dilated."""
-    P = _centred(W, H)
-    P[12] = 160.0
-    rng = np.random.default_rng(11)
-    geo = S.soup_geometry(rng, n_links=4, tris_per_link=30, scale_lo=0.05, scale_hi=0.3)
-    tfs = np.stack([np.stack(S.random_link_poses(rng, len(geo)))])
-    wl = _workload("undrawn_%dx%d" % (W, H), W, H, geo, tfs, P[None])
-    return Scene(wl.name, wl, S.sensor_depth(W, H, 0.9)[None])
-
+# ---- scenes (the expectation at radius r is gpu_support.filter_expected: point clouds and clearance tables expect it too) ----------
 
 def example_scene():
     wl = WL.example_workload(640, 480)
-    return Scene("example_urdf_640x480", wl, wl.depth_batch())
+    return OracleScene(wl, wl.depth_batch(), "example_urdf_640x480")
 
 
 def pr2_scene():
     wl = WL.pr2_workload(3, 640, 480, near_arm=True, walls=True)
-    return Scene("pr2_near_arm_walls_3x640x480", wl, wl.depth_batch())
+    return OracleScene(wl, wl.depth_batch(), "pr2_near_arm_walls_3x640x480")
 
 
 BUILDERS = {
@@ -158,31 +42,18 @@ BUILDERS = {
     "neighbours_160x120": neighbour_scene,
     "undrawn_160x120": undrawn_scene,
 }
-_cache = {}
 
 
+@cached
 def scene(name):
-    if name not in _cache:
-        _cache[name] = BUILDERS[name]()
-    return _cache[name]
+    return BUILDERS[name]()
 
 
 def check(sc, r, masked, mask, u16=False, what=""):
-    em, ek = sc.expected(r, u16)
+    em, ek = filter_expected(sc, r, u16)
     if mask is not None:
-        bad = int((np.asarray(mask) != ek).sum())
-        assert bad == 0, "%s r=%d %s: %d mask pixels differ" % (sc.name, r, what, bad)
-    if u16:
-        assert np.array_equal(np.asarray(masked), em), "%s r=%d %s: 16UC1 masked depth differs in %d px" % (sc.name, r, what, int((np.asarray(masked) != em).sum()))
-    else:
-        assert bits_equal(masked, em), "%s r=%d %s: masked depth differs in %d px" % (
-            sc.name, r, what, int((np.asarray(masked, np.float32).view(np.uint32) != em.view(np.uint32)).sum()))
-
-
-def set_radius(ctx, sc, r, **kw):
-    p = params(replace=sc.wl.replace_value, max_diff=sc.wl.max_diff, silhouette_dilation_px=r, **kw)
-    p.near_plane, p.far_plane = sc.wl.near, sc.wl.far
-    ctx.set_params(p)
+        compare_labels(mask, ek, "%s r=%d %s" % (sc.name, r, what), "mask")
+    compare_planes(masked, em, "%s r=%d %s" % (sc.name, r, what), "16UC1 masked depth" if u16 else "masked depth")
 
 
 # ---- the expectation itself -------------------------------------------------------------------------------------------
@@ -190,14 +61,14 @@ def set_radius(ctx, sc, r, **kw):
 @pytest.mark.parametrize("name", sorted(BUILDERS))
 def test_expectation_reproduces_the_oracle_at_r0(name):
     sc = scene(name)
-    em, ek = sc.expected(0)
+    em, ek = filter_expected(sc, 0)
     for s in range(sc.n):
-        om, ok, _ = sc.oracle[s]
+        om, ok = sc.masked[s], sc.mask[s]
         assert np.array_equal(ok, ek[s]), "%s stream %d: %d mask px" % (name, s, int((ok != ek[s]).sum()))
         assert bits_equal(om, em[s]), name
     if name in ("soup_160x120", "pr2_640x480", "borders_160x120", "neighbours_160x120"):
         # the scenes are not trivial for the dilation: the mask grows
-        assert (sc.expected(1)[1] > 0).sum() > (ek > 0).sum(), name
+        assert (filter_expected(sc, 1)[1] > 0).sum() > (ek > 0).sum(), name
 
 
 def test_window_min_clips_instead_of_padding():
@@ -252,7 +123,7 @@ def test_dilated_outputs_match_the_expectation(name, two_kernel, lanes):
             with pytest.raises(R.RtufError):          # the rule stays: no mask bits under RTUF_FLAG_TWO_KERNEL
                 ctx.filter_batch_bits_async(sc.depth, np.zeros((sc.n, words), np.uint32))
             continue
-        undrawn = sc.undrawn_at(r)
+        undrawn = undrawn_at(sc, r)
         for u16 in (False, True):
             bits = np.zeros((sc.n, words), np.uint32)
             ctx.filter_batch_bits_async(depth16 if u16 else sc.depth, bits)
@@ -263,7 +134,7 @@ def test_dilated_outputs_match_the_expectation(name, two_kernel, lanes):
                 assert ctx.stats()["batch_status"] & STATUS_UNCOVERED
                 continue
             ctx.sync()
-            em, ek = sc.expected(r, u16)
+            em, ek = filter_expected(sc, r, u16)
             for s in range(sc.n):
                 assert np.array_equal(bits[s], pack_bits(ek[s])), "%s r=%d bits (u16=%s) stream %d" % (name, r, u16, s)
                 xm, xk = R.expand_mask_bits(depth16[s] if u16 else sc.depth[s], bits[s], sc.wl.replace_value)
@@ -315,7 +186,7 @@ def test_regrown_bins_rerun_the_batch_with_its_radius(bits):
         ctx.filter_batch_bits_async(sc.depth, out)
         ctx.sync()
         for s in range(sc.n):
-            assert np.array_equal(out[s], pack_bits(sc.expected(5)[1][s]))
+            assert np.array_equal(out[s], pack_bits(filter_expected(sc, 5)[1][s]))
     else:
         masked, mask = ctx.filter_batch(sc.depth)
         check(sc, 5, masked, mask, what="re-run")
@@ -340,7 +211,7 @@ def test_graph_replay_follows_the_radius():
         ctx.set_cameras(0, sc.wl.projection[s:s + 1], sc.wl.offset_inv[s:s + 1], sc.wl.cam_tf[s:s + 1])
         ctx.set_link_poses_batch(0, 0, sc.wl.link_tf[0][s:s + 1])
         masked, mask = ctx.filter_batch(sc.depth[s:s + 1])
-        em, ek = sc.expected(r)
+        em, ek = filter_expected(sc, r)
         assert np.array_equal(mask[0], ek[s]), "batch %d (r=%d): %d mask px" % (i, r, int((mask[0] != ek[s]).sum()))
         assert bits_equal(masked[0], em[s]), "batch %d (r=%d)" % (i, r)
     st = ctx.stats()
@@ -359,13 +230,13 @@ def test_back_to_zero_is_the_unmodified_filter():
     set_radius(ctx, sc, 0)
     masked, mask = ctx.filter_batch(sc.depth)
     for s in range(sc.n):
-        om, ok, _ = sc.oracle[s]
+        om, ok = sc.masked[s], sc.mask[s]
         assert np.array_equal(mask[s], ok) and bits_equal(masked[s], om)
     bits = np.zeros((sc.n, ctx.mask_bits_words()), np.uint32)
     ctx.filter_batch_bits_async(sc.depth, bits)
     ctx.sync()
     for s in range(sc.n):
-        assert np.array_equal(bits[s], pack_bits(sc.oracle[s][1]))
+        assert np.array_equal(bits[s], pack_bits(sc.mask[s]))
     ctx.close()
 
 
@@ -389,7 +260,6 @@ def test_radius_above_16_is_refused_and_the_previous_params_stay():
 @gpu
 def test_status_word_of_final_dilated_batches_is_zero():
     import torch
-    from test_batch_status_gpu import _DeviceWord
     sc = scene("soup_160x120")
     ctx = sc.context(silhouette_dilation_px=3)
     dev = torch.device("cuda:0")
@@ -399,7 +269,7 @@ def test_status_word_of_final_dilated_batches_is_zero():
     for _ in range(3):
         ctx.filter_batch_device(sc.n, d.data_ptr(), m.data_ptr(), None)
         ctx.sync()
-        word = torch.as_tensor(_DeviceWord(ctx.batch_status_device()), device=dev)
+        word = torch.as_tensor(DeviceWord(ctx.batch_status_device()), device=dev)
         assert int(word.cpu().numpy()[0]) == 0
         assert ctx.stats()["batch_status"] == 0
     check(sc, 3, m.cpu().numpy(), None)
@@ -425,8 +295,8 @@ def test_square_on_a_plane_grows_by_r_pixels_and_keeps_the_occluder():
     A block of sensor pixels at 0.5 m (in front of the square, nearer than its depth minus the threshold) across the
     square's right edge stays unfiltered at every r."""
     W, H = 160, 128
-    P = _centred(W, H)
-    wl = _workload("square", W, H, [_quad(-0.15, 0.15, -0.12, 0.12, 1.0)], np.tile(S.gl(np.eye(4)), (1, 1, 1)), P[None])
+    P = centred_projection(W, H)
+    wl = workload_of("square", W, H, [quad(-0.15, 0.15, -0.12, 0.12, 1.0)], np.tile(S.gl(np.eye(4)), (1, 1, 1)), P[None])
     depth = np.full((1, H, W), 1.5, np.float32)
     ctx = R.Context(W, H, 1, 0, params(replace=5.0, max_diff=0.05))
     ids = wl.load_into(ctx)

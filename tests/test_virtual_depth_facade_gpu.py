@@ -11,9 +11,9 @@ import golden_io
 from bench_support import workloads as WL
 from bench_support.labels_check import expected_labels
 from bench_support.virtual_check import bits_equal_f32, expected_virtual, metres_to_u16
+from gpu_support import example_facade, info
 from oracle import bindings as O
-from realtime_urdf_filter_amd import urdf
-from realtime_urdf_filter_amd.filter import CameraInfo, FilterParameters, RealtimeURDFFilter
+from realtime_urdf_filter_amd.filter import RealtimeURDFFilter
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -66,14 +66,8 @@ int main(int argc, char** argv)
 
 
 def python_facade():
-    tf = urdf.StaticTransformProvider()
-    tf.set_frames(urdf.forward_kinematics(urdf.Model.from_string(WL.EXAMPLE_URDF)), "/EXAMPLE/")
-    tf.frames["/world"] = urdf.Transform()
-    tf.frames["/cam"] = urdf.Transform(np.array([[1.0, 0, 0], [0, 0, 1.0], [0, -1.0, 0]]), (0, 0, 0))
-    prm = FilterParameters("/world", "/cam", [{"model": "d", "tf_prefix": "/EXAMPLE", "geometry_type": "visual"}], 0.05, filter_replace_value=5.0)
-    f = RealtimeURDFFilter(prm, tf, {"d": WL.EXAMPLE_URDF}, labels=True)
-    info = CameraInfo(640, 480, [FX, 0, CX, 0, 0, FY, CY, 0, 0, 0, 1, 0])
-    P = f.getProjectionMatrix(info)
+    f, tf = example_facade(labels=True)
+    P = f.getProjectionMatrix(info(intr=(FX, FY, CX, CY)))
     assert f.getVirtualDepth() is None
     f.render(P, 640, 480, empty_value=EMPTY)
     return f, P, tf

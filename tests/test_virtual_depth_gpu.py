@@ -18,14 +18,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if __name__ == "__main__":
     sys.path.insert(0, ROOT)
 
-import golden_io
 import realtime_urdf_filter_amd as R
 from bench_support import configs as CF
-from bench_support.labels_check import expected_labels, share_draws, workload_draws
+from bench_support.labels_check import expected_labels, share_draws
 from bench_support.virtual_check import bits_equal_f32, expected_virtual, metres_to_u16
-from oracle import bindings as O
-from test_batch_status_gpu import Consumer, bits_equal, params
-from test_silhouette_dilation_gpu import _quad, _workload, undrawn_scene
+from gpu_support import (Consumer, OracleScene, bits_equal, compare_labels, fixture_scene, label_planes, oracle_frames, params, quad, same_planes,
+                         share_frames, tie_scene, torch_device, undrawn_scene, virtual_planes)
 
 pytestmark = pytest.mark.gpu
 INVALID, STATE = -1, -6
@@ -35,90 +33,13 @@ FIXTURES = ["soup_seed11_160x120", "soup_seed12_160x120", "soup_seed13_160x120",
             "near_range_ties_160x120", "far_plane_covers_160x120", "far_plane_covers_background_160x120", "near_large_shapes_517x389"]
 
 
-def _torch():
-    import torch
-    return torch, torch.device("cuda:0")
-
-
-# ---- scenes and expectations -----------------------------------------------------------------------------------------------
-
-class VScene:
-    """A Workload with the oracle's planes of every stream: mask / masked of the filter, zwin and prim."""
-
-    def __init__(self, wl, depth):
-        self.wl, self.name = wl, wl.name
-        self.W, self.H, self.n = wl.width, wl.height, wl.n_streams
-        self.depth = np.ascontiguousarray(depth, np.float32)
-        prep = [O.PreparedFrame(self.depth[s], wl.projection[s], wl.oracle_draws(s), wl.offset_inv[s], wl.cam_tf[s], z_near=wl.near,
-                                z_far=wl.far, max_diff=wl.max_diff, replace_value=wl.replace_value, want_debug=True) for s in range(self.n)]
-        O.run_prepared(prep, O.usable_threads())
-        self.masked, self.mask = np.stack([f.masked for f in prep]), np.stack([f.mask for f in prep])
-        self.zwin, self.prim = np.stack([f.zwin for f in prep]), np.stack([f.prim for f in prep])
-
-    def virtual(self, empty=0.0, u16=False):
-        v = expected_virtual(self.zwin, self.prim, self.wl.near, self.wl.far, empty)
-        return metres_to_u16(v) if u16 else v
-
-    def labels(self, link_label=None):
-        lab, nt = workload_draws(self.wl, link_label)
-        return np.stack([expected_labels(self.prim[s], lab, nt) for s in range(self.n)])
-
-    def context(self, max_streams=None, n=None, **kw):
-        p = params(replace=self.wl.replace_value, max_diff=self.wl.max_diff, **kw)
-        p.near_plane, p.far_plane = self.wl.near, self.wl.far
-        ctx = R.Context(self.W, self.H, max_streams or self.n, 0, p)
-        self.ids = self.wl.load_into(ctx)
-        self.wl.stage(ctx, self.ids, n=n or min(self.n, max_streams or self.n))
-        return ctx
-
-
-def fixture_scene(name, n=3):
-    """A golden fixture as n streams: one link per draw, stream s looks from 2 cm * s to the side of the fixture's camera."""
-    fx = golden_io.Fixture(name)
-    geo = [(pre, op, v, t) for _, pre, op, v, t in fx.draws]
-    tfs = np.tile(np.stack([np.asarray(d[0], np.float64).reshape(16) for d in fx.draws])[None], (n, 1, 1))
-    cams = np.tile(np.asarray(fx.cam_tf, np.float64).reshape(16), (n, 1))
-    cams[:, 12] += 0.02 * np.arange(n)
-    wl = _workload(name, fx.width, fx.height, geo, tfs, np.tile(np.asarray(fx.projection, np.float64).reshape(16), (n, 1)),
-                   np.tile(np.asarray(fx.offset_inv, np.float64).reshape(16), (n, 1)), cams)
-    wl.near, wl.far, wl.max_diff, wl.replace_value = fx.z_near, fx.z_far, fx.max_diff, fx.replace_value
-    return VScene(wl, np.tile(fx.depth[None], (n, 1, 1)))
-
-
-_scenes = {}
-
-
 def scene(name):
-    if name not in _scenes:
-        if name == "undrawn":
-            sc = undrawn_scene()
-            _scenes[name] = VScene(sc.wl, sc.depth)
-        else:
-            _scenes[name] = fixture_scene(name)
-    return _scenes[name]
-
-
-def check_virtual(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    if got.dtype == np.float32:
-        bad = ~((got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want)))
-    else:
-        bad = got != want
-    if bad.any():
-        s, y, x = np.argwhere(bad)[0]
-        raise AssertionError("%s: %d virtual depth pixels differ (first: stream %d y %d x %d: %r instead of %r)"
-                             % (what, int(bad.sum()), s, y, x, got[s, y, x], want[s, y, x]))
-
-
-def check_labels(got, want, what):
-    bad = np.asarray(got) != want
-    assert not bad.any(), "%s: %d label pixels differ" % (what, int(bad.sum()))
+    return undrawn_scene() if name == "undrawn" else fixture_scene(name, 3)
 
 
 def planes(sc, total=None, u16=False, labels=True):
     """Device planes of `total` streams with their sentinel fill."""
-    torch, dev = _torch()
+    torch, dev = torch_device()
     shape = (total or sc.n, sc.H, sc.W)
     v = torch.full(shape, 0x5a5a, dtype=torch.int16, device=dev) if u16 else torch.full(shape, SENTINEL, dtype=torch.float32, device=dev)
     lab = torch.full(shape, 0x5a5a, dtype=torch.int16, device=dev) if labels else None
@@ -143,19 +64,19 @@ def render_device(ctx, sc, empty=0.0, u16=False, labels=True, n=None, total=None
 def route_checks(name, lanes):
     sc = scene(name)
     ctx = sc.context(raster_lanes=lanes)
-    want_lab = sc.labels()
+    want_lab = label_planes(sc)
     for rep in range(2):                       # (the second round runs after the cover pass has gone to sleep where no tile has a cover)
         for u16 in ((False, True) if sc.W % 4 == 0 else (False,)):
             for labels in (True, False):
                 what = "%s lanes %d %s labels %d" % (name, lanes, "16UC1" if u16 else "f32", labels)
                 v, lab = render_device(ctx, sc, empty=-1.5 if u16 else 0.25, u16=u16, labels=labels)
-                check_virtual(v, sc.virtual(-1.5 if u16 else 0.25, u16), what + " device")
+                same_planes(v, virtual_planes(sc, -1.5 if u16 else 0.25, u16), what + " device")
                 if labels:
-                    check_labels(lab, want_lab, what + " device")
+                    compare_labels(lab, want_lab, what + " device")
                 v, lab = ctx.render_batch(sc.n, 3.0, labels=labels, u16=u16)
-                check_virtual(v, sc.virtual(3.0, u16), what + " host")
+                same_planes(v, virtual_planes(sc, 3.0, u16), what + " host")
                 if labels:
-                    check_labels(lab, want_lab, what + " host")
+                    compare_labels(lab, want_lab, what + " host")
         assert ctx.stats()["batch_status"] == 0
     st = ctx.stats()
     if name.startswith("near_range_ties"):
@@ -193,7 +114,7 @@ def test_empty_values(name):
     for e in (0.0, -1.5, float("inf"), float("nan")):
         for u16 in (False, True):
             v, _ = render_device(ctx, sc, empty=e, u16=u16, labels=False)
-            check_virtual(v, sc.virtual(e, u16), "%s empty %r u16 %d" % (name, e, u16))
+            same_planes(v, virtual_planes(sc, e, u16), "%s empty %r u16 %d" % (name, e, u16))
             want_e = metres_to_u16(np.float32(e)) if u16 else np.float32(e)
             got_e = v[~drawn]
             assert (np.isnan(got_e).all() if (not u16 and np.isnan(e)) else (got_e == want_e).all()), (e, u16)
@@ -206,16 +127,15 @@ def test_empty_values(name):
 
 def far_quad_scene():
     """Two links in front of a third: a quad at 0.99 * far, the depth of the background quad, which is drawn first."""
-    from test_link_labels_gpu import _tie_workload
     far = float(np.float32(0.99) * np.float32(8.0))
-    tie = _tie_workload([[_quad(-0.5, -0.3, -0.3, 0.3, 1.2), _quad(-0.2, 0.2, -0.15, 0.15, 1.0), _quad(-20.0, 20.0, -20.0, 20.0, far)]])
+    tie = tie_scene([[quad(-0.5, -0.3, -0.3, 0.3, 1.2), quad(-0.2, 0.2, -0.15, 0.15, 1.0), quad(-20.0, 20.0, -20.0, 20.0, far)]])
     depth = np.linspace(0.5, 9.0, tie.W * tie.H, dtype=np.float32).reshape(1, tie.H, tie.W)
-    return VScene(tie.wl, depth)
+    return OracleScene(tie.wl, depth)
 
 
 @pytest.mark.parametrize("far_quad", [False, True])
 def test_agrees_with_the_filter_on_the_same_context(far_quad):
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = far_quad_scene() if far_quad else scene("soup_seed12_160x120")
     ctx = sc.context()
     d = torch.from_numpy(sc.depth).to(dev)
@@ -225,8 +145,8 @@ def test_agrees_with_the_filter_on_the_same_context(far_quad):
     v, lab = render_device(ctx, sc, empty=float("nan"))
     flab, mask = flab.cpu().numpy().view(np.uint16), k.cpu().numpy()
     assert np.array_equal(flab, lab)
-    check_labels(lab, sc.labels(), "labels")
-    check_virtual(v, sc.virtual(float("nan")), "virtual")
+    compare_labels(lab, label_planes(sc), "labels")
+    same_planes(v, virtual_planes(sc, float("nan")), "virtual")
     assert np.isnan(v[sc.prim < 0]).all()      # the background quad, drawn by the library or met at its own depth, reads the empty value
     with np.errstate(invalid="ignore"):
         robot = (lab > 0) & (sc.depth > v - np.float32(sc.wl.max_diff))
@@ -240,17 +160,16 @@ def test_agrees_with_the_filter_on_the_same_context(far_quad):
 
 @pytest.mark.parametrize("case", ["links", "models", "cover_links", "cover_models", "near_links", "near_models"])
 def test_ties_go_to_the_earlier_draw(case):
-    from test_link_labels_gpu import _tie_workload
     if case.startswith("cover"):
-        q = _quad(-3.0, 3.0, -3.0, 3.0, 1.5)
+        q = quad(-3.0, 3.0, -3.0, 3.0, 1.5)
     elif case.startswith("near"):
-        q = _quad(-0.02, 0.02, -0.015, 0.015, 0.100003)
+        q = quad(-0.02, 0.02, -0.015, 0.015, 0.100003)
     else:
-        q = _quad(-0.2, 0.2, -0.15, 0.15, 1.0)
-    other = _quad(-0.5, -0.3, -0.3, 0.3, 1.2)
+        q = quad(-0.2, 0.2, -0.15, 0.15, 1.0)
+    other = quad(-0.5, -0.3, -0.3, 0.3, 1.2)
     geo = [[other, q], [q]] if case.endswith("models") else [[other, q, q]]
-    tie = _tie_workload(geo)
-    sc = VScene(tie.wl, tie.depth)
+    tie = tie_scene(geo)
+    sc = OracleScene(tie.wl, tie.depth)
     ctx = sc.context()
     labels = [5, 7, 3]
     if case.endswith("models"):
@@ -258,12 +177,12 @@ def test_ties_go_to_the_earlier_draw(case):
         ctx.set_link_labels(sc.ids[1], np.array(labels[2:], np.uint16))
     else:
         ctx.set_link_labels(sc.ids[0], np.array(labels, np.uint16))
-    want = sc.labels(np.array(labels))
+    want = label_planes(sc, np.array(labels))
     assert (want == 7).sum() > 50 and not (want == 3).any()
     for u16 in (False, True):
         v, lab = render_device(ctx, sc, empty=0.0, u16=u16)
-        check_virtual(v, sc.virtual(0.0, u16), case)
-        check_labels(lab, want, case)
+        same_planes(v, virtual_planes(sc, 0.0, u16), case)
+        compare_labels(lab, want, case)
     st = ctx.stats()
     assert not case.startswith("near") or st["exact_tiles"] > 0, st
     assert not case.startswith("cover") or st["cover_tiles"] > 0, st
@@ -277,14 +196,14 @@ def test_partial_batch_leaves_the_other_planes_alone():
     ctx = sc.context(max_streams=5, n=3)
     for u16 in (False, True):
         v, lab = render_device(ctx, sc, empty=1.0, u16=u16, n=3, total=5)
-        check_virtual(v[:3], sc.virtual(1.0, u16), "partial")
-        check_labels(lab[:3], sc.labels(), "partial")
+        same_planes(v[:3], virtual_planes(sc, 1.0, u16), "partial")
+        compare_labels(lab[:3], label_planes(sc), "partial")
         assert (v[3:] == (0x5a5a if u16 else np.float32(SENTINEL))).all() and (lab[3:] == 0x5a5a).all()
     ctx.close()
 
 
 def test_pipelines_render_and_filter_batches_alternate():
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = scene("soup_seed13_160x120")
     ctx = sc.context(pipelines=2)
     d = torch.from_numpy(sc.depth).to(dev)
@@ -297,8 +216,8 @@ def test_pipelines_render_and_filter_batches_alternate():
         rounds.append((v, lab, m, k))
     ctx.sync()
     for i, (v, lab, m, k) in enumerate(rounds):
-        check_virtual(v.cpu().numpy(), sc.virtual(float(i)), "round %d" % i)
-        check_labels(lab.cpu().numpy().view(np.uint16), sc.labels(), "round %d" % i)
+        same_planes(v.cpu().numpy(), virtual_planes(sc, float(i)), "round %d" % i)
+        compare_labels(lab.cpu().numpy().view(np.uint16), label_planes(sc), "round %d" % i)
         assert np.array_equal(k.cpu().numpy(), sc.mask) and bits_equal(m.cpu().numpy(), sc.masked), i
     ctx.close()
 
@@ -312,10 +231,10 @@ def test_regrown_bins_rerun_the_render_batch():
     st = ctx.stats()
     assert st["regrowths"] > 0 and st["batch_reruns"] > 0 and st["batch_status"] != 0, st
     v, lab = host(v, lab)
-    check_virtual(v, sc.virtual(-1.5), "re-run")
-    check_labels(lab, sc.labels(), "re-run")
+    same_planes(v, virtual_planes(sc, -1.5), "re-run")
+    compare_labels(lab, label_planes(sc), "re-run")
     v, _ = ctx.render_batch(sc.n, 2.0, u16=True)
-    check_virtual(v, sc.virtual(2.0, True), "after the re-run")
+    same_planes(v, virtual_planes(sc, 2.0, True), "after the re-run")
     ctx.close()
 
 
@@ -324,7 +243,7 @@ def test_graph_replay_picks_up_a_new_empty_value_and_new_buffers():
     another empty value or buffer must capture anew and never write the old buffer."""
     sc = scene("primitives_160x120")
     ctx = sc.context(max_streams=1, n=1, raster_lanes=1, pipelines=2)
-    want_lab = sc.labels()[:1]
+    want_lab = label_planes(sc)[:1]
     va, la = planes(sc, 1)
     vb, lb = planes(sc, 1)
 
@@ -332,8 +251,8 @@ def test_graph_replay_picks_up_a_new_empty_value_and_new_buffers():
         ctx.render_batch_device(1, v.data_ptr(), lab.data_ptr(), e)
         ctx.sync()
         gv, gl = host(v, lab)
-        check_virtual(gv, sc.virtual(e)[:1], what)
-        check_labels(gl, want_lab, what)
+        same_planes(gv, virtual_planes(sc, e)[:1], what)
+        compare_labels(gl, want_lab, what)
     for i in range(6):
         run(va, la, 0.5, "repeat %d" % i)
     run(va, la, 4.0, "new empty value")
@@ -360,8 +279,8 @@ def test_status_word_is_zero_behind_a_final_render_batch():
     ctx.render_batch_device(sc.n, v.data_ptr(), lab.data_ptr(), 0.0)
     word, early_v, early_lab, word_t = user.read(v, lab)
     assert word == 0, hex(word)
-    check_virtual(early_v, sc.virtual(0.0), "behind the batch")
-    check_labels(early_lab.view(np.uint16), sc.labels(), "behind the batch")
+    same_planes(early_v, virtual_planes(sc, 0.0), "behind the batch")
+    compare_labels(early_lab.view(np.uint16), label_planes(sc), "behind the batch")
     ctx.sync()
     st = ctx.stats()
     assert st["batch_status"] == 0 and st["batch_reruns"] == 0, st
@@ -381,7 +300,7 @@ def test_timings_land_in_ms_raster():
 # ---- refusals, and contexts whose filter batches take other routes ---------------------------------------------------------
 
 def test_refusals_write_nothing_and_leave_the_context_usable():
-    torch, dev = _torch()
+    torch, dev = torch_device()
     sc = scene("soup_seed12_160x120")
     p = params(replace=sc.wl.replace_value, max_diff=sc.wl.max_diff)
     p.near_plane, p.far_plane = sc.wl.near, sc.wl.far
@@ -411,8 +330,8 @@ def test_refusals_write_nothing_and_leave_the_context_usable():
     p.silhouette_dilation_px = 0
     ctx.set_params(p)
     gv, gl = render_device(ctx, sc, empty=0.0)
-    check_virtual(gv, sc.virtual(0.0), "after the refusals")
-    check_labels(gl, sc.labels(), "after the refusals")
+    same_planes(gv, virtual_planes(sc, 0.0), "after the refusals")
+    compare_labels(gl, label_planes(sc), "after the refusals")
     masked, mask = ctx.filter_batch(sc.depth)
     assert np.array_equal(mask, sc.mask) and bits_equal(masked, sc.masked)
     ctx.close()
@@ -430,10 +349,10 @@ def test_contexts_with_other_filter_routes_render_and_filter_as_before(kind):
         assert np.array_equal(before[1], sc.mask) and bits_equal(before[0], sc.masked)
     for u16 in (False, True):
         v, lab = render_device(ctx, sc, empty=0.0, u16=u16)
-        check_virtual(v, sc.virtual(0.0, u16), kind)
-        check_labels(lab, sc.labels(), kind)
+        same_planes(v, virtual_planes(sc, 0.0, u16), kind)
+        compare_labels(lab, label_planes(sc), kind)
     v, lab = ctx.render_batch(sc.n, 1.0, labels=True)
-    check_virtual(v, sc.virtual(1.0), kind + " host")
+    same_planes(v, virtual_planes(sc, 1.0), kind + " host")
     if zs is not None:                         # the z-surface still shows the last filter batch
         assert bits_equal_f32(ctx.read_zsurface(sc.n), zs)
     after = ctx.filter_batch(sc.depth)
@@ -450,24 +369,20 @@ def test_config3_256_streams():
     ctx = R.Context(share.width, share.height, n, 0, params(replace=wl0.replace_value, max_diff=wl0.max_diff))
     share.load(ctx)
     share.stage(ctx, 0)
-    torch, dev = _torch()
+    torch, dev = torch_device()
     v = torch.full((n, share.height, share.width), SENTINEL, dtype=torch.float32, device=dev)
     lab = torch.full((n, share.height, share.width), 0x5a5a, dtype=torch.int16, device=dev)
     ctx.render_batch_device(n, v.data_ptr(), lab.data_ptr(), -1.0)
     ctx.sync()                                 # (a context's first batch sizes its bins: the planes are final once it is retired)
-    link_dev, cam_dev = ctx.read_poses(n, share.n_links_total)
     sample = [0, 1, 85, 170, n - 1]
     depth = np.ascontiguousarray(share.depth_host(0), np.float32)
-    prep = []
-    for s in sample:
-        P, draws, off, cam = share.oracle_frame(0, s, link_dev, cam_dev)
-        prep.append(O.PreparedFrame(depth[s], P, draws, off, cam, z_near=wl0.near, z_far=wl0.far, want_debug=True))
-    O.run_prepared(prep, O.usable_threads())
+    frames = share_frames(share, ctx, n)
+    zwin, prim = oracle_frames([frames[s] for s in sample], depth[sample])
     gv, gl = v[sample].cpu().numpy(), lab[sample].cpu().numpy().view(np.uint16)
-    want_v = np.stack([expected_virtual(f.zwin, f.prim, wl0.near, wl0.far, -1.0) for f in prep])
-    want_l = np.stack([expected_labels(f.prim, *share_draws(share, s)) for f, s in zip(prep, sample)])
-    check_virtual(gv, want_v, "C3")
-    check_labels(gl, want_l, "C3")
+    want_v = expected_virtual(zwin, prim, wl0.near, wl0.far, -1.0)
+    want_l = np.stack([expected_labels(p, *share_draws(share, s)) for p, s in zip(prim, sample)])
+    same_planes(gv, want_v, "C3")
+    compare_labels(gl, want_l, "C3")
     assert (want_l > 0).any() and (want_v == -1.0).any()
     ctx.close()
 
