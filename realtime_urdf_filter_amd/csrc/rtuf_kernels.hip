@@ -64,8 +64,12 @@ enum {
   // histogram of the tile kernel's bin records (live = records): by quad trips of the lane-per-triangle walk (1, 2, 3, 4, 5, 6,
   // 7-8, 9-12, 13-16, 17-24, 25+), quarter-wave class, larger, nothing in this tile; and how many records have a WHOLE box of
   // at most 8 x 8 / 8 x 4 (or 4 x 8) pixel centres inside one tile (what a larger fragment class of the set-up kernel would take)
-  kLaneHist = 24, kLaneHistQuarter = kLaneHist + 11, kLaneHistLarge, kLaneHistNone, kLaneHist8x8, kLaneHist8x4, kLaneHistEnd
+  kLaneHist = 24, kLaneHistQuarter = kLaneHist + 11, kLaneHistLarge, kLaneHistNone, kLaneHist8x8, kLaneHist8x4, kLaneHistEnd,
+  // the same two set-up loops again, counting only the trips of waves that hold a live lane at all (RTUF_LANES_LIVE: a wave
+  // without one skips the body and costs next to nothing, but fills the counts above with empty slots)
+  kLaneSetupVertLive = kLaneHistEnd, kLaneSetupSmallLive, kLaneEnd
 };
+static_assert(kLaneEnd <= kLaneLoops, "CounterShard holds kLaneLoops pairs");
 static_assert(kLaneHistEnd <= kLaneLoops, "CounterShard holds kLaneLoops pairs");
 static_assert(kLaneCount <= kLaneLoops, "CounterShard holds kLaneLoops pairs");
 #ifdef RTUF_LANECOUNT
@@ -74,6 +78,14 @@ __device__ __forceinline__ uint32_t* lane_words() { __shared__ uint32_t s_lw[2 *
   do {                                                                                                                \
     const unsigned long long act_ = __ballot(true), m_ = __ballot(pred);                                              \
     if ((int)(threadIdx.x & 63) == __ffsll((long long)act_) - 1) {                                                    \
+      atomicAdd(&lane_words()[2 * (id)], 64u);                                                                        \
+      atomicAdd(&lane_words()[2 * (id) + 1], (uint32_t)__popcll(m_));                                                 \
+    }                                                                                                                 \
+  } while (0)
+#define RTUF_LANES_LIVE(id, pred)                                                                                     \
+  do {                                                                                                                \
+    const unsigned long long act_ = __ballot(true), m_ = __ballot(pred);                                              \
+    if (m_ && (int)(threadIdx.x & 63) == __ffsll((long long)act_) - 1) {                                              \
       atomicAdd(&lane_words()[2 * (id)], 64u);                                                                        \
       atomicAdd(&lane_words()[2 * (id) + 1], (uint32_t)__popcll(m_));                                                 \
     }                                                                                                                 \
@@ -90,6 +102,7 @@ __device__ __forceinline__ uint32_t* lane_words() { __shared__ uint32_t s_lw[2 *
   } while (0)
 #else
 #define RTUF_LANES(id, pred) ((void)0)
+#define RTUF_LANES_LIVE(id, pred) ((void)0)
 #define RTUF_LANES_INIT() ((void)0)
 #define RTUF_LANES_FLUSH(shard) ((void)0)
 #endif
@@ -958,6 +971,11 @@ __global__ __launch_bounds__(kBlock) void cull_kernel(SetupArgs a)
 // <= 256 triangles of one draw call with its own <= kMaxChunkVerts vertex list, so each vertex is transformed
 // once per stream (into LDS) instead of once per incident triangle, and the chunk's geometry is loaded
 // once for all streams of the item.
+// The three survivor lists' counters are fields of ONE LDS word (list_counts, rtuf_numerics.h): a wave reserves in all
+// three with one atomic per stream.  (Built with it, measured and taken out again: phase 1 over one index space of all live
+// streams' vertices, and the two box classes as one index space -- docs/experiments.md R7.1, docs/patches/setup-dense-experiment.patch.)
+static_assert(kStreamsPerBlock * kBlock <= (int)kListFieldMask, "list_counts (rtuf_numerics.h): every list fits its field");
+
 template <bool STRIDED>
 __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t item_base)
 {
@@ -966,7 +984,7 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
   __shared__ uint32_t s_packed[kBlock];                         // the chunk's triangles
   __shared__ uint16_t s_list[kStreamsPerBlock * kBlock];        // survivors binned as records: stream k << 8 | triangle
   __shared__ uint16_t s_list2[kStreamsPerBlock * kBlock];       // survivors resolved to fragments: 4x4 boxes from the bottom, 2x2 from the top
-  __shared__ uint32_t s_nlist, s_ntiny, s_nsmall;
+  __shared__ uint32_t s_counts;                                 // list_counts(records, 2x2 boxes, 4x4 boxes): the lists' fill
   __shared__ uint32_t s_stat[3];
   __shared__ float s_mvp[kStreamsPerBlock][16];
   __shared__ uint32_t s_on[kStreamsPerBlock];
@@ -987,9 +1005,7 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
   // it takes everything)
   if (blockIdx.x == 0 && tid == 0) a.counters->work.grid = STRIDED ? 0xffffffffu : gridDim.x;
   for (uint32_t item_id = item_base + blockIdx.x; item_id < n_items; item_id += gridDim.x) {
-  if (tid == 3) s_nlist = 0;
-  if (tid == 4) s_ntiny = 0;
-  if (tid == 5) s_nsmall = 0;
+  if (tid == 3) s_counts = 0;
   // the item carries the chunk's ranges, so the geometry loads depend on it alone
   struct { uint32_t tri_begin, vert_begin, draw, tri_count, vert_count; } ch;
   uint32_t slots01, slots23;
@@ -1043,6 +1059,7 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
     // (phase 1 of all three streams before ONE barrier, then phase 2 of all three: measured, no difference)
     // phase 1
     RTUF_LANES(kLaneSetupVert, have_vert);
+    RTUF_LANES_LIVE(kLaneSetupVertLive, have_vert);
     if (have_vert) {
       float M[16];
 #pragma unroll
@@ -1104,26 +1121,14 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
     // (<= 4x4 single-tile boxes from the bottom, <= 2x2 boxes from the top)
     const bool rec = survive && !tiny && !small;
     const unsigned long long sm = __ballot(rec), tm = __ballot(tiny), qm = __ballot(small);
-    if (sm) {
-      const int leader = __ffsll((long long)sm) - 1;
+    if (sm | tm | qm) {      // ONE reservation in all three lists: an LDS round trip per wave and stream instead of up to three
+      const unsigned long long below = (1ull << lane) - 1ull;
       uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(&s_nlist, (uint32_t)__popcll(sm));
-      base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-      if (rec) s_list[base + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = (uint16_t)((k << 8) | tid);
-    }
-    if (tm) {
-      const int leader = __ffsll((long long)tm) - 1;
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(&s_ntiny, (uint32_t)__popcll(tm));
-      base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-      if (tiny) s_list2[kStreamsPerBlock * kBlock - 1 - (base + (uint32_t)__popcll(tm & ((1ull << lane) - 1ull)))] = (uint16_t)((k << 8) | tid);
-    }
-    if (qm) {
-      const int leader = __ffsll((long long)qm) - 1;
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(&s_nsmall, (uint32_t)__popcll(qm));
-      base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-      if (small) s_list2[base + (uint32_t)__popcll(qm & ((1ull << lane) - 1ull))] = (uint16_t)((k << 8) | tid);
+      if (lane == 0) base = atomicAdd(&s_counts, list_counts((uint32_t)__popcll(sm), (uint32_t)__popcll(tm), (uint32_t)__popcll(qm)));
+      base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+      if (rec) s_list[list_count_rec(base) + (uint32_t)__popcll(sm & below)] = (uint16_t)((k << 8) | tid);
+      if (tiny) s_list2[kStreamsPerBlock * kBlock - 1 - (list_count_tiny(base) + (uint32_t)__popcll(tm & below))] = (uint16_t)((k << 8) | tid);
+      if (small) s_list2[list_count_small(base) + (uint32_t)__popcll(qm & below)] = (uint16_t)((k << 8) | tid);
     }
   }
   __syncthreads();
@@ -1131,8 +1136,9 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
   // phase 3a/3b: tiny (2x2) and small (4x4, single tile) survivors -> coverage of their box positions
   // -> 8-byte fragments; the z plane (one division) is only evaluated for triangles that actually
   // cover a pixel centre
-  const uint32_t ntiny = s_ntiny, nsmall = s_nsmall;
-  if (tid == 0 && (ntiny | nsmall | s_nlist) == 0u) atomicAdd(&shard.zero_items, 1u);      // (statistics: an item the cull pass could have spared)
+  const uint32_t counts = s_counts;
+  const uint32_t ntiny = list_count_tiny(counts), nsmall = list_count_small(counts);
+  if (tid == 0 && counts == 0u) atomicAdd(&shard.zero_items, 1u);      // (statistics: an item the cull pass could have spared)
 #pragma unroll
   for (int cls = 0; cls < 2; cls++) {
     const uint32_t ncls = cls == 0 ? ntiny : nsmall;
@@ -1145,6 +1151,7 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
       bool near = false;
       uint32_t ent = 0;
       RTUF_LANES(kLaneSetupSmall, j < ncls);
+      RTUF_LANES_LIVE(kLaneSetupSmallLive, j < ncls);
       if (j < ncls) {
         Win v0, v1, v2;
         const uint32_t e = s_list2[cls == 0 ? kStreamsPerBlock * kBlock - 1 - j : j];
@@ -1173,8 +1180,8 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
           near = !(zmin >= 0.51f);      // (a NaN anywhere in the plane makes zmin NaN: counts as near)
         }
       }
-      if (near) {      // rare: hand the triangle to the record pass below (one LDS append)
-        s_list[atomicAdd(&s_nlist, 1u)] = (uint16_t)ent;
+      if (near) {      // rare: hand the triangle to the record pass below (one LDS append: the record field is the packed word's lowest)
+        s_list[list_count_rec(atomicAdd(&s_counts, 1u))] = (uint16_t)ent;
         mask = 0;
       }
       RTUF_LANES(kLaneSetupSmallHit, mask != 0);
@@ -1188,7 +1195,7 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
   __syncthreads();        // appends of the fragment pass to the record list
   // phase 3c: dense set-up + binning of the larger survivors as 32-byte records (the tile kernel
   // rebuilds the edge functions, so only orientation, bounding box and z plane are needed here)
-  const uint32_t nlist = s_nlist;
+  const uint32_t nlist = list_count_rec(s_counts);
   for (uint32_t base = 0; base < nlist; base += kBlock) {
     const uint32_t j = base + tid;
     bool have = false;

@@ -1,8 +1,8 @@
 // rtuf_numerics.h -- the arithmetic whose exact bits the results depend on and that something besides the kernels checks or
 // shares: the 24-bit depth and its bit-pattern forms, the depth keys' encoding of a near fragment's float z, the set-up's
 // 32-bit edge constants, the key format's host-side rules, the compare threshold's constants, division core and the rule
-// that admits that core, the pixel classes of the link residual tables, the point of a filtered point cloud, and the sphere centres and
-// point-to-sphere clearances of the link clearance tables.
+// that admits that core, the pixel classes of the link residual tables, the point of a filtered point cloud, the sphere centres and
+// point-to-sphere clearances of the link clearance tables, and the set-up kernel's packed list counters.
 //
 // Included by the kernels (rtuf_kernels.hip, device and host pass), the host API (rtuf_api.cpp), scripts/fdiv_check.hip (which
 // holds div_core against the IEEE division on the GPU) and the CPU checks (tests/fast_class_check.cpp, tests/near_key_check.cpp:
@@ -241,6 +241,21 @@ RTUF_NUMERIC_HD uint32_t clearance_order_bits(float c)
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 RTUF_NUMERIC_HD uint32_t clearance_bits_of_order(uint32_t o) { return (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o; }
+
+// ---------------------------------------------------------------------------------------
+// set-up kernel: the list counters of a work item (tests/setup_lists_check.cpp)
+// ---------------------------------------------------------------------------------------
+
+// The three survivor lists of an item (records, <= 2x2 boxes, <= 4x4 boxes) hold at most 3 x 256 = 768 entries TOGETHER, so
+// their three counters are 10-bit fields of one word and one addition reserves in all three; no field can carry into the next.
+constexpr uint32_t kListFieldBits = 10u, kListFieldMask = (1u << kListFieldBits) - 1u;
+RTUF_NUMERIC_HD uint32_t list_counts(uint32_t nrec, uint32_t ntiny, uint32_t nsmall)
+{
+  return nrec | (ntiny << kListFieldBits) | (nsmall << (2u * kListFieldBits));
+}
+RTUF_NUMERIC_HD uint32_t list_count_rec(uint32_t w) { return w & kListFieldMask; }
+RTUF_NUMERIC_HD uint32_t list_count_tiny(uint32_t w) { return (w >> kListFieldBits) & kListFieldMask; }
+RTUF_NUMERIC_HD uint32_t list_count_small(uint32_t w) { return (w >> (2u * kListFieldBits)) & kListFieldMask; }
 
 #ifdef __HIP__
 // The IEEE division without the instructions that only matter for operands near the ends of the exponent range: the compiler

@@ -6,9 +6,12 @@
 here="$(cd "$(dirname "$0")/.." && pwd)"
 lib=$here/realtime_urdf_filter_amd/lib/variants/librtuf_lanes.so
 src=$here/realtime_urdf_filter_amd/csrc
-# (always rebuilt: 20 s, and a library that travelled to the box keeps no usable time stamp; LANE_FLAGS adds -D switches)
+# (rebuilt unless LANE_LIB names an instrumented library built beforehand: a library that travelled to the box keeps no usable
+# time stamp; LANE_FLAGS adds -D switches, e.g. -DRTUF_SETUP_FLAT_VERTS=0)
+if [ -n "$LANE_LIB" ]; then lib=$LANE_LIB; else
 (cd $here/realtime_urdf_filter_amd/csrc && mkdir -p ../lib/variants && hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -I../../include -I. \
    -Wno-unused-value -Wno-unused-result -DRTUF_LANECOUNT -DRTUF_COUNT $LANE_FLAGS rtuf_kernels.hip rtuf_api.cpp -o $lib) || exit 1
+fi
 RTUF_LIB=$lib python - "$@" <<'PY'
 import ctypes, json, sys, os
 sys.path.insert(0, os.getcwd())
@@ -46,7 +49,8 @@ for key, kw in cases:
     slots = (ctypes.c_uint64 * 48)(); live = (ctypes.c_uint64 * 48)()
     lib.rtuf_debug_lane_counts(ctx._h, slots, live, 48)
     rows = {}
-    for i, name in enumerate(NAMES):
+    # (slots 40, 41: the same two loops, counting only the trips of waves that hold a live lane)
+    for i, name in list(enumerate(NAMES)) + [(40, "setup: phase 1 vertices, waves with a live lane"), (41, "setup: small boxes (coverage), waves with a live lane")]:
         if slots[i]:
             rows[name] = {"wave_trips": int(slots[i]) // 64, "live_lanes": int(live[i]), "live_fraction": round(live[i] / slots[i], 4)}
     hist_names = ["1", "2", "3", "4", "5", "6", "7-8", "9-12", "13-16", "17-24", "25+", "quarter-wave class", "larger", "nothing in this tile",
