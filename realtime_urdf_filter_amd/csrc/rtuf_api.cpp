@@ -21,6 +21,7 @@
 #include "rtuf_device.h"
 #include "rtuf_groups.h"
 #include "rtuf_numerics.h"
+#include "rtuf_routes.h"
 
 
 using namespace rtuf;
@@ -65,9 +66,9 @@ struct HostModel { std::vector<HostLink> links; int link_base = 0; Kinematics ki
                    std::vector<int32_t> sph_link; std::vector<float> sph_xyzr; };
 
 // One batch as its caller asked for it: the kind, and the device buffers and scalars that kind has (the rest stays nullptr / 0).
-// A slot keeps the record of its batch (Batch::rq) for re-runs; what a kind does is written down in the predicates before the hot path.
+// A slot keeps the record of its batch (Batch::rq) for re-runs; which kernels a kind runs is route_of's to say (rtuf_routes.h).
 struct BatchRequest {
-  enum class Kind { Filter, Bits, Render, Residual, Cloud, Clearance };
+  using Kind = BatchKind;
   Kind kind; int n; bool u16;               // (u16: the sensor / masked / virtual planes are 16UC1)
   bool wait_upload = false;                 // host planes: the lanes wait for the slot's `uploaded` event before the first kernel that reads them
   const float* depth = nullptr;             // sensor planes (every kind but Render)
@@ -214,7 +215,8 @@ struct rtuf_context {
   struct Batch {
     bool active = false;
     BatchRequest rq;                         // what the caller asked for (submit_batch); every run of the batch reads it
-    const float* order_thr = nullptr;        // per-link thresholds: the draw order -> threshold table, or nullptr (set when first enqueued)
+    Route route{};                           // the kernels it runs (route_of, when it is first enqueued; kept for re-runs): the tile variant -- cover pass
+                                             // and per-link thresholds among its fields -- and what runs behind the tile kernel
     // cloud batches: the slot's own bits buffer and row scratch ([2][max_streams][H]: row counts, row starts), allocated on the
     // slot's first (compacted) cloud batch for max_streams, so that captured graphs keep their addresses
     uint32_t* cl_bits = nullptr; uint32_t* cl_rows = nullptr;
@@ -242,8 +244,7 @@ struct rtuf_context {
     struct { uint64_t hash = 0; hipGraphExec_t exec = nullptr; } graphs[kGraphs];
     int graph_next = 0;
     std::vector<uint32_t> setup_grid;        // per launch group: work items its set-up launch covered (0xffffffff = the worst case)
-    bool cover_pass = true;                  // this batch runs the cover pass (decided when it is first enqueued, kept for re-runs)
-    int dilation = 0;                        // silhouette dilation radius of this batch (set when it is first enqueued, kept for re-runs)
+    int dilation = 0;                        // Post::Dilate: the radius (set when the batch is first enqueued, kept for re-runs)
     int timing = 0;                          // event timing of this batch: 0 none, 1 every stage, 2 tile/compare kernel only
     // Host-plane batches (submit_host_planes): grow-only device staging of this slot (ensure_staging; `have` in the units its
     // user counts in: streams, table rows, floats, words), the caller's planes of an asynchronous download, and the events
@@ -1393,24 +1394,16 @@ int rtuf_debug_read_poses(rtuf_context* c, int n, double* link_tf_out, double* c
   return RTUF_OK;
 }
 
-// ---- what a batch of each kind does (everything below decides by kind through these; a new kind answers them here) ----
+// ---- what a batch of each kind does ----
+// Which kernels it runs is its route (route_of in rtuf_routes.h, asked once by enqueue_batch; a new kind starts there).  The
+// predicates below are what is asked BEFORE a batch has a route: by the calls' checks and when a slot's buffers are allocated.
 // the batches of this context write the z-surface: two-kernel mode, or a silhouette dilation radius
 static bool uses_zsurface(const rtuf_context* c) { return (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 || c->params.silhouette_dilation_px > 0; }
-// RTUF_FLAG_TWO_KERNEL: full planes only (the mask-bits calls refuse the flag; render, residual and cloud batches are always one tile kernel)
-static bool takes_two_kernel(const BatchRequest& r) { return r.kind == Kind::Filter; }
-// silhouette dilation: dilate_compare_kernel makes every output form from the z-surface, mask bits and so clouds included (the render and residual calls refuse it; clearance batches follow the clouds)
-static bool honours_dilation(const BatchRequest& r) { return r.kind != Kind::Render && r.kind != Kind::Residual; }
-// the per-link threshold table (a render batch compares nothing: no thresholds; a residual batch honours them)
-static bool reads_thresholds(const BatchRequest& r) { return r.kind != Kind::Render; }
-// the table draw order -> label: a label plane beside the outputs, or the rows of a residual table
-static bool reads_label_table(const BatchRequest& r) { return r.labels != nullptr || r.kind == Kind::Residual; }
-// may write the z-surface, and so needs d_zsurface and moves last_lane (render and residual batches leave it alone)
-static bool may_write_zsurface(const BatchRequest& r) { return takes_two_kernel(r) || honours_dilation(r); }
+// may write the z-surface, and so needs d_zsurface and moves last_lane (render and residual batches never take that route and leave it alone)
+static bool may_write_zsurface(const BatchRequest& r) { return r.kind != Kind::Render && r.kind != Kind::Residual; }
 // refused while per-link thresholds meet the z-surface route (check_thresh_route).  Render and residual batches never take that
 // route; a cloud batch takes it for dilation only, which check_cloud_call refuses with thresholds
 static bool subject_to_thresh_route(const BatchRequest& r) { return r.kind == Kind::Filter || r.kind == Kind::Bits; }
-// retire_oldest fills ms_compare: a kernel runs behind the tile kernel (compare, dilate + compare, or the cloud kernels)
-static bool fills_ms_compare(const rtuf_context* c, const rtuf_context::Batch& b) { return ((c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && takes_two_kernel(b.rq)) || b.dilation > 0 || b.rq.kind == Kind::Cloud || b.rq.kind == Kind::Clearance; }
 
 // ---- the hot path ---------------------------------------------------------------------
 static hipEvent_t get_event(rtuf_context::Batch& b, size_t i)
@@ -1427,10 +1420,10 @@ static hipEvent_t get_event(rtuf_context::Batch& b, size_t i)
 struct BatchPlan {
   std::vector<FkArgs> fks;
   PoseArgs pa{};
-  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; CloudArgs cl{}; ClearanceArgs cr{}; bool compare = false, dilate = false, cloud = false, clearance = false; int lane = 0; };
+  // (ca, da, cl, cr: filled and read where the route's post / tail has that kernel)
+  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; CloudArgs cl{}; ClearanceArgs cr{}; int lane = 0; };
   std::vector<Group> groups;
-  bool cover_pass = true;
-  bool zroute = false;          // the tile kernel writes the z-surface (two-kernel mode, or silhouette dilation)
+  Route route{};                // the batch's (Batch::route): every group runs the same kernels
   uint64_t hash() const
   {
     uint64_t h = 1469598103934665603ull;
@@ -1438,12 +1431,15 @@ struct BatchPlan {
     for (const FkArgs& f : fks) mix(&f, sizeof f);
     mix(&pa, sizeof pa);
     for (const Group& g : groups) {
-      mix(&g.sa, sizeof g.sa); mix(&g.ta, sizeof g.ta); if (g.compare) mix(&g.ca, sizeof g.ca); if (g.dilate) mix(&g.da, sizeof g.da);
-      if (g.cloud) mix(&g.cl, sizeof g.cl);
-      if (g.clearance) mix(&g.cr, sizeof g.cr);
+      mix(&g.sa, sizeof g.sa); mix(&g.ta, sizeof g.ta);
+      if (route.post == Post::Compare) mix(&g.ca, sizeof g.ca);
+      if (route.post == Post::Dilate) mix(&g.da, sizeof g.da);
+      if (route.tail == Tail::Cloud) mix(&g.cl, sizeof g.cl);
+      if (route.tail == Tail::Clearance) mix(&g.cr, sizeof g.cr);
       mix(&g.lane, sizeof g.lane);
     }
-    return h ^ (uint64_t)fks.size() << 56 ^ (uint64_t)groups.size() << 48 ^ (uint64_t)cover_pass << 47 ^ (uint64_t)zroute << 46;
+    // (the route too: equal argument blocks on another route are other kernels)
+    return h ^ (uint64_t)fks.size() << 56 ^ (uint64_t)groups.size() << 48 ^ (uint64_t)route_index(route) << 32;
   }
 };
 
@@ -1459,7 +1455,7 @@ enum { kEvStart = 0, kEvPoseEnd = 1, kEvLaneEnd = 2, kEvGroup0 = 2 + kMaxLanes, 
 // group still belongs to the pose stage (it then runs under the previous batch's raster kernels).
 static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& plan, hipStream_t sp, bool worst_case_grid)
 {
-  const bool two = plan.zroute;
+  const Route& rt = plan.route;
   worst_case_grid = worst_case_grid || c->force_worst_grid || (c->params.flags & RTUF_FLAG_STRICT_GRID) != 0;
   auto mark = [&](size_t i, hipStream_t s) { hipEventRecord(get_event(b, i), s); };
   if (b.timing) (void)get_event(b, kEvGroup0 + kEvPerGroup * plan.groups.size() - 1);      // (all of the batch's events exist)
@@ -1506,22 +1502,22 @@ static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& 
     b.setup_grid[g] = worst_case_grid ? 0xffffffffu : grid;
     if (b.timing >= 2) mark(e0 + 1, st);
     launch_clip(gr.sa, st);
-    launch_bigrec(gr.sa, plan.cover_pass, st);      // appends the many-tile records the two kernels above listed (after the cover pass, if it is on)
+    launch_bigrec(gr.sa, rt.tile.cover, st);      // appends the many-tile records the two kernels above listed (after the cover pass, if it is on)
     if (b.timing) mark(e0 + 2, st);
     // a residual batch: the group's rows of the table are contiguous and start from zero on every run (timed with the tile
     // kernel: ms_raster)
-    if (gr.ta.resid_table)
+    if (rt.tile.out == TileOut::Residual)
       launch_zero_residual_rows(gr.ta.resid_table + (size_t)gr.ta.group_base * (size_t)gr.ta.n_labels * 8u,
                                 (size_t)gr.ta.group_size * (size_t)gr.ta.n_labels * 8u, st);
-    launch_tile(gr.ta, two, plan.cover_pass, st);
+    if (!launch_tile(gr.ta, rt.tile, st)) return c->fail(RTUF_ERR_STATE, "internal: the tile kernel has no variant %d", tile_variant_index(rt.tile));
     if (b.timing) mark(e0 + 3, st);
-    if (gr.compare) { launch_compare(gr.ca, st); if (b.timing) mark(e0 + 4, st); }
-    if (gr.dilate) { launch_dilate_compare(gr.da, st); if (b.timing && !gr.cloud && !gr.clearance) mark(e0 + 4, st); }
-    // a cloud batch: the group's points from the bits the kernel above wrote, before the lane publishes its counters (timed
-    // as ms_compare, with the dilate kernel where there is one)
-    if (gr.cloud) { launch_cloud(gr.cl, st); if (b.timing) mark(e0 + 4, st); }
-    // a clearance batch: the group's rows of the table, in the same place and timed the same way
-    if (gr.clearance) { launch_clearance(gr.cr, st); if (b.timing) mark(e0 + 4, st); }
+    // behind it: the outputs from the z-surface, then what reads the mask bits (a cloud batch: the group's points; a clearance
+    // batch: the group's rows of the table) before the lane publishes its counters -- timed together as ms_compare
+    if (rt.post == Post::Compare) launch_compare(gr.ca, st);
+    if (rt.post == Post::Dilate) launch_dilate_compare(gr.da, st);
+    if (rt.tail == Tail::Cloud) launch_cloud(gr.cl, st);
+    if (rt.tail == Tail::Clearance) launch_clearance(gr.cr, st);
+    if (b.timing && runs_behind_tile(rt)) mark(e0 + 4, st);
   }
   // every lane publishes the counter blocks of its own groups
   const int ng = (int)plan.groups.size();
@@ -1542,7 +1538,6 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   const float* d_depth = r.depth; float* d_masked = r.masked; uint8_t* d_mask = r.mask;
   const bool io_u16 = r.u16;
   const size_t esz = io_u16 ? sizeof(uint16_t) : sizeof(float);
-  const bool two = (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 && takes_two_kernel(r);
   // Launch groups: as many as the lanes' bins ask for, alternating between the lanes; a batch that is not split takes one
   // lane, the next such batch the other.
   const int n_groups = groups_for(c, n);
@@ -1552,7 +1547,15 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     return c->fail(RTUF_ERR_STATE, "internal: %d launch groups for %d streams, but counter blocks for %d", n_groups, n, c->max_groups);
   if ((n + per_group - 1) / per_group != n_groups)
     return c->fail(RTUF_ERR_STATE, "internal: %d launch groups planned, %d made (the status word counts the former down)", n_groups, (n + per_group - 1) / per_group);
+  // The kernels of this batch, decided here and nowhere else; a re-run takes what its first run took.  (A combination that is
+  // not ok has been refused by the call's checks: none gets here.)
+  const Route route = rerun ? b.route
+                            : route_of({r.kind, r.u16, r.labels != nullptr, c->thresh_models > 0, (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0,
+                                        (int)c->params.silhouette_dilation_px, c->cover_on});
+  if (!route.ok) return c->fail(RTUF_ERR_STATE, "internal: no kernel route for a batch of kind %d (tile variant %d)", (int)r.kind, tile_variant_index(route.tile));
   if (!rerun) {
+    b.route = route;
+    b.dilation = route.post == Post::Dilate ? (int)c->params.silhouette_dilation_px : 0;
     b.lanes_used = 0;
     if (n_groups == 1) { b.lanes_used = 1u << c->next_lane; c->next_lane = (c->next_lane + 1) % c->n_lanes; }
     else for (int l = 0; l < std::min(c->n_lanes, n_groups); l++) b.lanes_used |= 1u << l;
@@ -1594,12 +1597,8 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   b.uploaded_streams = std::max(b.uploaded_streams, n);
   c->mask_uploaded_streams = std::max(c->mask_uploaded_streams, n);
   BatchPlan plan;
-  if (!rerun) b.cover_pass = c->cover_on;
-  plan.cover_pass = b.cover_pass;
-  if (!rerun) b.dilation = honours_dilation(r) ? (int)c->params.silhouette_dilation_px : 0;
-  if (!rerun) b.order_thr = c->thresh_models > 0 && reads_thresholds(r) ? c->d_order_thr : nullptr;
-  const int dil = b.dilation;
-  plan.zroute = dil > 0 || two;
+  plan.route = route;
+  const TileVariant& tv = route.tile;
   // on-device forward kinematics overwrites the link matrices (and camera) of the streams that use it
   for (HostModel& m : c->models) {
     Kinematics& k = m.kin;
@@ -1673,30 +1672,26 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     ta.io_u16 = io_u16 ? 1 : 0;
     ta.key_shift = c->key_shift;
     ta.fast_div = fast_div;
-    ta.bits = dil ? nullptr : r.bits;
-    ta.labels = r.labels;                    // (the label calls refuse silhouette dilation and mask bits)
-    ta.order_labels = reads_label_table(r) ? c->d_order_labels : nullptr;
-    ta.order_thr = b.order_thr;              // (batches with per-link thresholds never take the z-surface route: check_thresh_route)
+    ta.bits = tv.out == TileOut::Bits ? r.bits : nullptr;
+    ta.labels = r.labels;
+    ta.order_labels = tv.labels || tv.out == TileOut::Residual ? c->d_order_labels : nullptr;      // a label plane beside the outputs, or the rows of a residual table
+    ta.order_thr = tv.thresh ? c->d_order_thr : nullptr;      // (allocated once, rewritten in place: a re-run finds the same table)
     ta.virtual_out = r.virt; ta.empty_value = r.empty_value;
     ta.resid_table = reinterpret_cast<unsigned long long*>(r.resid); ta.n_labels = r.n_labels;
-    gr.compare = two && !dil;
-    gr.dilate = dil > 0;
-    if (gr.dilate) {
+    if (route.post == Post::Dilate) {
       DilateArgs& da = gr.da;
       da.depth = d_depth; da.zsurface = ln.d_zsurface; da.masked = d_masked; da.mask = d_mask; da.bits = r.bits; da.counters = d_counters;
-      da.group_base = base; da.group_size = gs; da.width = c->width; da.height = c->height; da.radius = dil;
+      da.group_base = base; da.group_size = gs; da.width = c->width; da.height = c->height; da.radius = b.dilation;
       da.max_diff = ta.max_diff; da.replace_value = ta.replace_value; da.sc_num = sc_num; da.sc_off = sc_off;
       da.io_u16 = io_u16 ? 1 : 0; da.fast_div = fast_div;
     }
-    gr.cloud = r.kind == Kind::Cloud;
-    if (gr.cloud) {
+    if (route.tail == Tail::Cloud) {
       CloudArgs& cl = gr.cl;
       cl.depth = d_depth; cl.bits = r.bits; cl.intr = c->d_cloud_intr; cl.points = r.points; cl.index = r.index; cl.counts = r.counts;
       cl.row_count = b.cl_rows; cl.row_start = b.cl_rows ? b.cl_rows + (size_t)c->max_streams * c->height : nullptr;
       cl.group_base = base; cl.group_size = gs; cl.width = c->width; cl.height = c->height; cl.capacity = r.capacity; cl.io_u16 = io_u16 ? 1 : 0;
     }
-    gr.clearance = r.kind == Kind::Clearance;
-    if (gr.clearance) {
+    if (route.tail == Tail::Clearance) {
       ClearanceArgs& cr = gr.cr;
       // (the spheres of labels below n_labels: the list is sorted by label)
       int used = 0, slots = 0;
@@ -1708,7 +1703,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
       cr.n_spheres = used; cr.n_slots = slots; cr.n_links = (int)L; cr.n_labels = r.n_labels;
       cr.group_base = base; cr.group_size = gs; cr.width = c->width; cr.height = c->height; cr.max_distance = r.max_distance; cr.io_u16 = io_u16 ? 1 : 0;
     }
-    if (gr.compare) {
+    if (route.post == Post::Compare) {
       CompareArgs& ca = gr.ca;
       ca.depth = reinterpret_cast<const float*>(reinterpret_cast<const char*>(d_depth) + (size_t)base * plane * esz); ca.zsurface = ln.d_zsurface;
       ca.masked = reinterpret_cast<float*>(reinterpret_cast<char*>(d_masked) + (size_t)base * plane * esz);
@@ -1892,7 +1887,7 @@ static int retire_oldest(rtuf_context* c)
     c->stats.occluded_entries = k.occluded; c->stats.cover_tiles = k.cover_tiles; c->stats.exact_tiles = k.exact_tiles;
     c->stats.work_items = (uint32_t)std::min<unsigned long long>(k.work_items, 0xffffffffu); c->stats.zero_survivor_items = k.zero_items;
     c->stats.raster_atomics = k.raster_atomics; c->stats.drawn_pixels = k.drawn_pixels;
-    c->stats.cover_pass = b.cover_pass ? 1u : 0u;
+    c->stats.cover_pass = b.route.tile.cover ? 1u : 0u;
     c->stats.groups_last_batch = (uint32_t)b.n_groups;
     const bool bin_over = k.max_bin_fill > c->capacity || k.max_fbin_fill > c->fcapacity;
     const bool clip_over = k.clip_overflow != 0;
@@ -1909,7 +1904,7 @@ static int retire_oldest(rtuf_context* c)
       if (b.timing && b.events.size() >= (size_t)(kEvGroup0 + kEvPerGroup * b.n_groups)) {
         // per launch group E0 .. E4 (see issue_plan).  With several lanes the kernels of different groups overlap: the sums
         // below add up per-launch durations, they are not wall time.
-        const bool two = fills_ms_compare(c, b);
+        const bool behind = runs_behind_tile(b.route);      // ms_compare: whatever ran behind the tile kernel
         auto el = [&](size_t i, size_t j) { float ms = 0; hipEventElapsedTime(&ms, b.events[i], b.events[j]); return ms; };
         c->stats.ms_pose = c->stats.ms_setup = c->stats.ms_clip = c->stats.ms_raster = c->stats.ms_compare = c->stats.ms_total = 0;
         for (int g = 0; g < b.n_groups; g++) {
@@ -1921,7 +1916,7 @@ static int retire_oldest(rtuf_context* c)
             c->stats.ms_clip += el(e0 + 1, e0 + 2);
           }
           c->stats.ms_raster += el(e0 + 2, e0 + 3);
-          if (two) c->stats.ms_compare += el(e0 + 3, e0 + 4);
+          if (behind) c->stats.ms_compare += el(e0 + 3, e0 + 4);
         }
         if (b.timing == 1) {
           c->stats.ms_pose = el(kEvStart, kEvPoseEnd);
@@ -1935,7 +1930,7 @@ static int retire_oldest(rtuf_context* c)
         c->stats.sum_ms_pose = c->acc_ms[0]; c->stats.sum_ms_setup = c->acc_ms[1]; c->stats.sum_ms_raster = c->acc_ms[2];
         c->stats.sum_ms_compare = c->acc_ms[3]; c->stats.sum_ms_total = c->acc_ms[4]; c->stats.sum_ms_clip = c->acc_ms[5];
       }
-      if (b.cover_pass) {
+      if (b.route.tile.cover) {
         if (k.cover_tiles) c->cover_idle = 0;
         else if (++c->cover_idle >= 3) { c->cover_on = false; c->cover_sleep = 64; c->cover_idle = 2; }      // (idle = 2: one empty probe sends it back to sleep)
       } else if (--c->cover_sleep <= 0) {

@@ -28,6 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rtuf_routes.h"
+
 namespace rtuf {
 
 // Timing experiments (scripts/ablate_*.sh) skip work and produce WRONG images.  They exist only in a library
@@ -320,16 +322,17 @@ struct TileArgs {
   int io_u16;                    // 16UC1 in/out fused into the kernel (src/urdf_filter.cpp:287-288, :309-312)
   int key_shift;                 // depth keys: draw order << key_shift in the low word, the float z's low bits below it (KeyFmt)
   int fast_div;                  // the threshold's division may run without its scaling / fix-up instructions (host: fast_div_admitted, rtuf_numerics.h)
-  // link labels (appended: the fields above keep their kernarg offsets).  labels != nullptr selects tile_labels_kernel.
+  // Which kernel reads the fields below is the launch's TileVariant (rtuf_routes.h), never their nullness.
+  // link labels (appended: the fields above keep their kernarg offsets): variants with `labels` (tile_labels_kernel & co.)
   uint16_t* labels;              // [n][H][W] link label of every pixel's winner, 8-byte aligned; nullptr = none
   const uint16_t* order_labels;  // [n_tris + 1] label of every draw order (entry 0, background / no fragment: 0)
-  // per-link depth thresholds (appended).  order_thr != nullptr selects tile_thresh_kernel (fused route only).
+  // per-link depth thresholds (appended): variants with `thresh` (tile_thresh_kernel, tile_resid_kernel; never the z-surface route)
   const float* order_thr;        // [n_tris + 1] threshold of every draw order's link (entry 0, the background quad: max_diff)
-  // virtual depth planes (appended).  virtual_out != nullptr selects tile_render_kernel: depth, masked, mask, bits unused.
+  // virtual depth planes (appended): TileOut::Render (tile_render_kernel); depth, masked, mask, bits unused.
   float* virtual_out;            // [n][H][W] virtual depth of every pixel's winner (f32 metres or, with io_u16, uint16 millimetres)
   float empty_value;             // ... and what a pixel holds where the background quad won or nothing was drawn
-  // link residual tables (appended).  resid_table != nullptr selects tile_resid_kernel: masked, mask, bits, labels unused;
-  // order_labels is always set, order_thr as for a filter batch.
+  // link residual tables (appended): TileOut::Residual (tile_resid_kernel); masked, mask, bits, labels unused; order_labels is
+  // always set, order_thr as for a filter batch.
   unsigned long long* resid_table;   // [n][n_labels] rows of eight 64-bit sums (rtuf_link_residuals), zeroed before the kernel
   int n_labels;
 };
@@ -438,14 +441,15 @@ void launch_cull(const SetupArgs& a, hipStream_t st);
 uint32_t launch_setup(const SetupArgs& a, uint32_t items_hint, bool sweep, hipStream_t st);    // returns the main grid size
 void launch_clip(const SetupArgs& a, hipStream_t st);
 size_t clip_spill_bytes(uint32_t clip_capacity);
-void launch_bigrec(const SetupArgs& a, bool cover_pass, hipStream_t st);      // cover_pass: bigrec_kernel<0> runs first (and launch_tile gets the same flag)
+void launch_bigrec(const SetupArgs& a, bool cover_pass, hipStream_t st);      // cover_pass: bigrec_kernel<0> runs first (and launch_tile gets a variant with `cover`)
 void launch_init_headers(BinHeader* hdr, size_t n_bins, hipStream_t st);
 // copies the counter blocks first, first + stride, ... (count of them) of a batch to the same places of the pinned host array
 // ... and folds what they say about overflows into the batch's status word (PublishLimits: the capacities they are held against)
 struct PublishLimits { uint32_t capacity, fcapacity, big_capacity; };
 void launch_publish_counters(const Counters* src, Counters* host_dst, int first, int stride, int count, uint32_t* status, PublishLimits lim, hipStream_t st);
 void launch_zero_residual_rows(unsigned long long* rows, size_t n_words, hipStream_t st);      // n_words 64-bit words from rows on
-void launch_tile(const TileArgs& a, bool two_kernel, bool cover_pass, hipStream_t st);   // a.io_u16 selects the 16UC1 variant
+// the variant's instantiation for the launch's size; false, and nothing launched: there is none (tile_variant_legal(v) fails)
+bool launch_tile(const TileArgs& a, TileVariant v, hipStream_t st);
 void launch_compare(const CompareArgs& a, hipStream_t st);
 void launch_dilate_compare(const DilateArgs& a, hipStream_t st);     // a.bits selects the mask-only variant, a.io_u16 the 16UC1 one
 void launch_cloud(const CloudArgs& a, hipStream_t st);               // a.capacity selects the compacted form (count, scan, emit), a.io_u16 the 16UC1 variants

@@ -32,6 +32,7 @@
 
 #include "rtuf_device.h"
 #include "rtuf_numerics.h"
+#include "rtuf_routes.h"
 
 namespace rtuf {
 
@@ -1588,6 +1589,10 @@ __device__ __forceinline__ unsigned long long resolved_key(unsigned long long ke
 }
 // draw order of a resolved key (keep_order)
 __device__ __forceinline__ uint32_t resolved_order(unsigned long long k) { return (uint32_t)(k >> 32) & 0x7fffffffu; }
+// The winner's draw order: the key's, or -- after the exact-z pass -- the one resolved_key kept above the float z.  0 is "no
+// fragment" (kNoFragment), whose label table entry is 0, and the background quad drawn as geometry, whose threshold table entry
+// is max_diff.
+__device__ __forceinline__ uint32_t winner_order(unsigned long long k, const KeyFmt& kf) { return (k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift; }
 
 // One depth test of a fragment whose window z is already evaluated (`order`: the draw order shifted into place).
 // Issue classes (profiles/valu_peak.json: gfx950 issues v_fma/mul/add_f32, v_add/sub_u32, v_and/or/xor_b32 and the right shifts
@@ -2258,19 +2263,23 @@ __device__ __forceinline__ void resid_reduce(const uint32_t (&cls)[4], const uin
 
 // COVER: the batch ran the cover pass (bigrec_kernel<0>), so a bin's header may name a cover.  Without it (the host skips the
 // pass while no scene has triangles that cover whole tiles) the cover code is compiled out: it costs the headline workload 3 %.
-// LABELS: the kernel also writes the link label plane (a.labels, a.order_labels: rtuf_filter_batch*_labels); never with BITS.
+// LABELS: the kernel also writes the link label plane (a.labels, a.order_labels: rtuf_filter_batch*_labels).
 // THRESH: a drawn pixel is compared with its winner's link threshold (a.order_thr: rtuf_set_link_thresholds) instead of
-// max_diff; the background plane keeps thr_bg.  Fused route only (never with TWO_KERNEL).
-// RENDER: no sensor plane, no compare: the only outputs are the virtual depth plane (a.virtual_out: shade_virtual of every
+// max_diff; the background plane keeps thr_bg.
+// OUT (rtuf_routes.h, where tile_variant_legal says which of LABELS and THRESH each output may carry):
+// Planes: the masked plane and the byte mask, compared here.  ZSurface (TWO_KERNEL below): the winners' window z for the
+// kernel behind this one.  Bits: the mask only, one bit per pixel.
+// Render: no sensor plane, no compare: the only outputs are the virtual depth plane (a.virtual_out: shade_virtual of every
 // winner's z, a.empty_value where the background quad won or nothing was drawn; U16: both through metres_to_u16) and, with
-// LABELS, the label plane (rtuf_render_batch*).  Never with TWO_KERNEL, BITS or THRESH.
-// RESID: no output plane at all: every pixel of the image is classified against the sensor plane (link_residual_class:
-// virtual depth, the winner's threshold -- a.order_thr's with THRESH, max_diff without -- and label) and counted in its
-// label's row of the stream's table (a.resid_table: rtuf_link_residuals_batch*; resid_reduce).  Never with TWO_KERNEL, BITS,
-// LABELS or RENDER.
-template <bool TWO_KERNEL, bool U16, bool BITS, bool COVER, int NT, bool LABELS = false, bool THRESH = false, bool RENDER = false, bool RESID = false>
+// LABELS, the label plane (rtuf_render_batch*).
+// Residual (RESID below): no output plane at all: every pixel of the image is classified against the sensor plane
+// (link_residual_class: virtual depth, the winner's threshold -- a.order_thr's with THRESH, max_diff without -- and label) and
+// counted in its label's row of the stream's table (a.resid_table: rtuf_link_residuals_batch*; resid_reduce).
+template <TileOut OUT, bool U16, bool COVER, int NT, bool LABELS = false, bool THRESH = false>
 __device__ __forceinline__ void tile_body(const TileArgs& a)
 {
+  static_assert(tile_variant_legal(TileVariant{OUT, LABELS, THRESH, U16, COVER}), "no such variant of the tile kernel (rtuf_routes.h)");
+  constexpr bool TWO_KERNEL = OUT == TileOut::ZSurface, BITS = OUT == TileOut::Bits, RENDER = OUT == TileOut::Render, RESID = OUT == TileOut::Residual;
   __shared__ unsigned long long keys[kKeyCount];
   __shared__ uint32_t s_huge[2 + kHugeMax];        // raster_bin's list of whole-tile triangles (+ count in front, area threshold behind)
   __shared__ uint32_t s_winners[kWinnerWords];     // exact-z pass: filter of the draw-order keys that won a pixel in need
@@ -2365,17 +2374,26 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   uint32_t cov_label = 0;                    // LABELS: the cover's link label, one lookup per tile
   float cov_thr = 0.0f;                      // THRESH: the cover's link threshold, one lookup per tile
   bool cov_robot = true;                     // RENDER: the cover is a link's triangle, not the background quad drawn as geometry
+  // the cover's z plane and draw order, from the record the bin's header points to
+  struct CoverPlane { float a0, dzdx, dzdy; uint32_t order; };
+  auto cover_plane = [&]() {
+    const uint4 pl = reinterpret_cast<const uint4*>(a.big_list + cover_idx)[1];       // {a0, dzdx, dzdy, order}: same address in every lane
+    CoverPlane c;
+    c.a0 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.x));
+    c.dzdx = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.y));
+    c.dzdy = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.z));
+    c.order = (uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask;
+    return c;
+  };
   if constexpr (COVER) {
     cover_only = has_cover && n == 0 && nf == 0 && !empty;
     if (cover_only) {
       if (!RENDER) request_sensor();
-      const uint4 pl = reinterpret_cast<const uint4*>(a.big_list + cover_idx)[1];       // {a0, dzdx, dzdy, order}: same address in every lane
-      cov_a0 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.x));
-      cov_dzdx = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.y));
-      cov_dzdy = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.z));
-      if (LABELS || RESID) cov_label = a.order_labels[(uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask];
-      if (THRESH) cov_thr = a.order_thr[(uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask];
-      if (RENDER) cov_robot = ((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask) != 0u;
+      const CoverPlane c = cover_plane();
+      cov_a0 = c.a0; cov_dzdx = c.dzdx; cov_dzdy = c.dzdy;
+      if (LABELS || RESID) cov_label = a.order_labels[c.order];
+      if (THRESH) cov_thr = a.order_thr[c.order];
+      if (RENDER) cov_robot = c.order != 0u;
 #ifdef RTUF_COUNT
       if (tid < 2) count_words()[tid] = 0u;
 #endif
@@ -2393,16 +2411,6 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
     // evaluated per pixel exactly as fragment() would (same two fused multiply-adds, same 24-bit conversion, its draw
     // order), but written instead of min'ed: it is the first thing the tile sees, and bigrec_kernel<1> left it out of the bin.
     // (the plane is fetched again by the rare exact-z pass below rather than kept in registers across the rasterisation)
-    struct CoverPlane { float a0, dzdx, dzdy; uint32_t order; };
-    auto cover_plane = [&]() {
-      const uint4 pl = reinterpret_cast<const uint4*>(a.big_list + cover_idx)[1];       // {a0, dzdx, dzdy, order}: same address in every lane
-      CoverPlane c;
-      c.a0 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.x));
-      c.dzdx = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.y));
-      c.dzdy = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)pl.z));
-      c.order = (uint32_t)__builtin_amdgcn_readfirstlane((int)pl.w) & kOrderMask;
-      return c;
-    };
     // Ask for the first things this lane will need from the bins BEFORE the key tile is initialised: its first record and
     // its first fragments (their latency then passes under the initialisation and the barrier instead of after it).
     uint4 first_rec0 = make_uint4(0u, 0u, 0u, 0u), first_rec1 = make_uint4(0u, 0u, 0u, 0u);
@@ -2691,23 +2699,20 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
               }
             }
             if (!TWO_KERNEL && !THRESH && !RENDER && !RESID) thr[j] = shade_threshold(z[j], sc);
-            // the winner's draw order: the key's (or, after the exact-z pass, kept above the float z: resolved_key); 0 is
-            // "no fragment" (kNoFragment), whose table entry is label 0 -- and the background quad drawn as geometry, whose
-            // threshold entry is max_diff
-            if (LABELS && !THRESH) lab[j] = a.order_labels[(k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift];
+            // what the tables say of the winner's draw order (winner_order)
+            if (LABELS && !THRESH) lab[j] = a.order_labels[winner_order(k, kf)];
             if (RESID) {                             // the winner's label, threshold and virtual depth
-              const uint32_t ord = (k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift;
+              const uint32_t ord = winner_order(k, kf);
               lab[j] = a.order_labels[ord];
               thr[j] = THRESH ? a.order_thr[ord] : a.max_diff;
               z[j] = shade_virtual(z[j], sc);
             } else if (THRESH) {
-              const uint32_t ord = (k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift;
+              const uint32_t ord = winner_order(k, kf);
               thr[j] = shade_threshold(z[j], sc, a.order_thr[ord]);
               if (LABELS) lab[j] = a.order_labels[ord];
             }
             if (RENDER) {                            // (draw order 0: the background quad drawn as geometry is background too)
-              const uint32_t ord = (k & kResolvedBit) ? resolved_order(k) : (uint32_t)k >> kf.shift;
-              z[j] = ord ? shade_virtual(z[j], sc) : a.empty_value;
+              z[j] = winner_order(k, kf) ? shade_virtual(z[j], sc) : a.empty_value;
             }
           }
         }
@@ -2766,23 +2771,23 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
 // stage 42 -> 23 us, 14.2 k -> 17.6 k frames/s; eight streams 98 k -> 109 k; profiles/r05_experiment_tile_threads.txt).
 constexpr int kTileThreadsSmall = 1024;
 template <bool TWO_KERNEL, bool U16, bool COVER, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(COVER ? RTUF_TILE_WAVES_COVER : RTUF_TILE_WAVES))) void tile_kernel(TileArgs a) { tile_body<TWO_KERNEL, U16, false, COVER, NT>(a); }
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(COVER ? RTUF_TILE_WAVES_COVER : RTUF_TILE_WAVES))) void tile_kernel(TileArgs a) { tile_body<TWO_KERNEL ? TileOut::ZSurface : TileOut::Planes, U16, COVER, NT>(a); }
 // mask-only output, one bit per pixel (rtuf_filter_batch_bits*): 4 (2) B/pixel in, 1/8 B/pixel out
 template <bool U16, bool COVER, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(COVER ? RTUF_TILE_WAVES_COVER : RTUF_TILE_WAVES))) void tile_bits_kernel(TileArgs a) { tile_body<false, U16, true, COVER, NT>(a); }
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(COVER ? RTUF_TILE_WAVES_COVER : RTUF_TILE_WAVES))) void tile_bits_kernel(TileArgs a) { tile_body<TileOut::Bits, U16, COVER, NT>(a); }
 // link labels beside the planes (rtuf_filter_batch*_labels): the variants of tile_kernel, plus 2 B/pixel out
 #ifndef RTUF_TILE_WAVES_LABELS
 #define RTUF_TILE_WAVES_LABELS 7
 #endif
 template <bool TWO_KERNEL, bool U16, bool COVER, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_LABELS))) void tile_labels_kernel(TileArgs a) { tile_body<TWO_KERNEL, U16, false, COVER, NT, true>(a); }
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_LABELS))) void tile_labels_kernel(TileArgs a) { tile_body<TWO_KERNEL ? TileOut::ZSurface : TileOut::Planes, U16, COVER, NT, true>(a); }
 // per-link depth thresholds (rtuf_set_link_thresholds): the fused tile_kernel, tile_bits_kernel and tile_labels_kernel with
 // one more gather (4 B, from the draw order -> threshold table) per drawn pixel
 #ifndef RTUF_TILE_WAVES_THRESH
 #define RTUF_TILE_WAVES_THRESH 7
 #endif
 template <bool U16, bool BITS, bool LABELS, bool COVER, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_THRESH))) void tile_thresh_kernel(TileArgs a) { tile_body<false, U16, BITS, COVER, NT, LABELS, true>(a); }
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_THRESH))) void tile_thresh_kernel(TileArgs a) { tile_body<BITS ? TileOut::Bits : TileOut::Planes, U16, COVER, NT, LABELS, true>(a); }
 // virtual depth planes (rtuf_render_batch*): no sensor plane in, 4 (2) B/pixel out, plus 2 B/pixel with labels.
 // Without the sensor registers the variants take 71 or 72 VGPRs and spill none at 7 waves/SIMD (the label variants' setting).
 // More cannot help the 256-thread kernels: seven key tiles fill the CU's LDS, and seven workgroups of four waves are 7 per SIMD.
@@ -2790,7 +2795,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WA
 #define RTUF_TILE_WAVES_RENDER 7
 #endif
 template <bool U16, bool LABELS, bool COVER, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_RENDER))) void tile_render_kernel(TileArgs a) { tile_body<false, U16, false, COVER, NT, LABELS, false, true>(a); }
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WAVES_RENDER))) void tile_render_kernel(TileArgs a) { tile_body<TileOut::Render, U16, COVER, NT, LABELS>(a); }
 // link residual tables (rtuf_link_residuals_batch*): 4 (2) B/pixel in, no plane out; 64 bytes per (stream, label) by atomics.
 // 72 VGPRs without spills at 7 waves/SIMD for the 256-thread variants.  A 1,024-thread workgroup is four waves per SIMD and a
 // second one would need eight, which 72 registers do not allow: those variants ask for 5 (up to 96 VGPRs) and lose nothing,
@@ -2799,7 +2804,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RTUF_TILE_WA
 #define RTUF_TILE_WAVES_RESID 7
 #endif
 template <bool U16, bool THRESH, bool COVER, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT > 256 ? 5 : RTUF_TILE_WAVES_RESID))) void tile_resid_kernel(TileArgs a) { tile_body<false, U16, false, COVER, NT, false, THRESH, false, true>(a); }
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT > 256 ? 5 : RTUF_TILE_WAVES_RESID))) void tile_resid_kernel(TileArgs a) { tile_body<TileOut::Residual, U16, COVER, NT, false, THRESH>(a); }
 
 // ---------------------------------------------------------------------------------------
 // compare_kernel (two-kernel mode): streaming, 13 B/pixel (4 sensor + 4 z + 4 masked + 1 mask)
@@ -3140,52 +3145,49 @@ static long long small_launch_threshold()
   static const long long t = [] { const char* e = getenv("RTUF_SMALL_LAUNCH"); return e && *e ? atoll(e) : (long long)RTUF_SMALL_LAUNCH; }();
   return t;
 }
+// A variant's instantiation, for one workgroup size and with or without the cover code: every legal variant (rtuf_routes.h) is
+// one case below, once -- the compiler refuses a second -- and anything else is no kernel.  V's arguments read as TileVariant's
+// fields: output, labels, thresh, u16.
+using TileKernel = void (*)(TileArgs);
 template <bool COVER, int NT>
-static void launch_tile_variant(const TileArgs& a, bool two_kernel, hipStream_t st)
+static TileKernel tile_kernel_for(TileVariant v)
 {
-  const dim3 grid(a.tiles_x, a.tiles_y, a.group_size);
-  if (a.resid_table) {                       // (a residual batch stores no plane and has no z-surface route)
-    if (a.order_thr) {
-      if (a.io_u16) hipLaunchKernelGGL((tile_resid_kernel<true, true, COVER, NT>), grid, dim3(NT), 0, st, a);
-      else hipLaunchKernelGGL((tile_resid_kernel<false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
-    } else if (a.io_u16) hipLaunchKernelGGL((tile_resid_kernel<true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((tile_resid_kernel<false, false, COVER, NT>), grid, dim3(NT), 0, st, a);
-  } else if (a.virtual_out) {                       // (a render batch has neither thresholds nor a z-surface route)
-    if (a.labels) {
-      if (a.io_u16) hipLaunchKernelGGL((tile_render_kernel<true, true, COVER, NT>), grid, dim3(NT), 0, st, a);
-      else hipLaunchKernelGGL((tile_render_kernel<false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
-    } else if (a.io_u16) hipLaunchKernelGGL((tile_render_kernel<true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((tile_render_kernel<false, false, COVER, NT>), grid, dim3(NT), 0, st, a);
-  } else if (a.order_thr) {                         // (the host refuses per-link thresholds in two-kernel mode)
-    if (a.labels) {
-      if (a.io_u16) hipLaunchKernelGGL((tile_thresh_kernel<true, false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
-      else hipLaunchKernelGGL((tile_thresh_kernel<false, false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
-    } else if (a.bits) {
-      if (a.io_u16) hipLaunchKernelGGL((tile_thresh_kernel<true, true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
-      else hipLaunchKernelGGL((tile_thresh_kernel<false, true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
-    } else if (a.io_u16) hipLaunchKernelGGL((tile_thresh_kernel<true, false, false, COVER, NT>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((tile_thresh_kernel<false, false, false, COVER, NT>), grid, dim3(NT), 0, st, a);
-  } else if (a.labels) {
-    if (two_kernel) hipLaunchKernelGGL((tile_labels_kernel<true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
-    else if (a.io_u16) hipLaunchKernelGGL((tile_labels_kernel<false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((tile_labels_kernel<false, false, COVER, NT>), grid, dim3(NT), 0, st, a);
-  } else if (a.bits) {
-    if (a.io_u16) hipLaunchKernelGGL((tile_bits_kernel<true, COVER, NT>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((tile_bits_kernel<false, COVER, NT>), grid, dim3(NT), 0, st, a);
-  } else if (two_kernel) hipLaunchKernelGGL((tile_kernel<true, false, COVER, NT>), grid, dim3(NT), 0, st, a);
-  else if (a.io_u16) hipLaunchKernelGGL((tile_kernel<false, true, COVER, NT>), grid, dim3(NT), 0, st, a);
-  else hipLaunchKernelGGL((tile_kernel<false, false, COVER, NT>), grid, dim3(NT), 0, st, a);
+  using O = TileOut;
+  constexpr auto V = [](TileOut out, bool labels, bool thresh, bool u16) { return tile_variant_index(TileVariant{out, labels, thresh, u16, COVER}); };
+  switch (tile_variant_index(TileVariant{v.out, v.labels, v.thresh, v.u16, COVER})) {
+    case V(O::Residual, false, true, true): return tile_resid_kernel<true, true, COVER, NT>;
+    case V(O::Residual, false, true, false): return tile_resid_kernel<false, true, COVER, NT>;
+    case V(O::Residual, false, false, true): return tile_resid_kernel<true, false, COVER, NT>;
+    case V(O::Residual, false, false, false): return tile_resid_kernel<false, false, COVER, NT>;
+    case V(O::Render, true, false, true): return tile_render_kernel<true, true, COVER, NT>;
+    case V(O::Render, true, false, false): return tile_render_kernel<false, true, COVER, NT>;
+    case V(O::Render, false, false, true): return tile_render_kernel<true, false, COVER, NT>;
+    case V(O::Render, false, false, false): return tile_render_kernel<false, false, COVER, NT>;
+    case V(O::Planes, true, true, true): return tile_thresh_kernel<true, false, true, COVER, NT>;
+    case V(O::Planes, true, true, false): return tile_thresh_kernel<false, false, true, COVER, NT>;
+    case V(O::Bits, false, true, true): return tile_thresh_kernel<true, true, false, COVER, NT>;
+    case V(O::Bits, false, true, false): return tile_thresh_kernel<false, true, false, COVER, NT>;
+    case V(O::Planes, false, true, true): return tile_thresh_kernel<true, false, false, COVER, NT>;
+    case V(O::Planes, false, true, false): return tile_thresh_kernel<false, false, false, COVER, NT>;
+    case V(O::ZSurface, true, false, false): return tile_labels_kernel<true, false, COVER, NT>;
+    case V(O::Planes, true, false, true): return tile_labels_kernel<false, true, COVER, NT>;
+    case V(O::Planes, true, false, false): return tile_labels_kernel<false, false, COVER, NT>;
+    case V(O::Bits, false, false, true): return tile_bits_kernel<true, COVER, NT>;
+    case V(O::Bits, false, false, false): return tile_bits_kernel<false, COVER, NT>;
+    case V(O::ZSurface, false, false, false): return tile_kernel<true, false, COVER, NT>;
+    case V(O::Planes, false, false, true): return tile_kernel<false, true, COVER, NT>;
+    case V(O::Planes, false, false, false): return tile_kernel<false, false, COVER, NT>;
+    default: return nullptr;
+  }
 }
-void launch_tile(const TileArgs& a, bool two_kernel, bool cover_pass, hipStream_t st)
+bool launch_tile(const TileArgs& a, TileVariant v, hipStream_t st)
 {
   const bool small = (long long)a.tiles_x * a.tiles_y * a.group_size < small_launch_threshold();
-  if (small) {
-    if (cover_pass) launch_tile_variant<true, kTileThreadsSmall>(a, two_kernel, st);
-    else launch_tile_variant<false, kTileThreadsSmall>(a, two_kernel, st);
-  } else {
-    if (cover_pass) launch_tile_variant<true, kTileThreads>(a, two_kernel, st);
-    else launch_tile_variant<false, kTileThreads>(a, two_kernel, st);
-  }
+  const TileKernel kernel = small ? (v.cover ? tile_kernel_for<true, kTileThreadsSmall>(v) : tile_kernel_for<false, kTileThreadsSmall>(v))
+                                  : (v.cover ? tile_kernel_for<true, kTileThreads>(v) : tile_kernel_for<false, kTileThreads>(v));
+  if (!kernel) return false;
+  hipLaunchKernelGGL(kernel, dim3(a.tiles_x, a.tiles_y, a.group_size), dim3(small ? kTileThreadsSmall : kTileThreads), 0, st, a);
+  return true;
 }
 // A launch group's rows of a residual table start from zero on every run.  (A kernel, not hipMemsetAsync: the memset node a
 // stream capture makes of it filled the rows with other values when the graph was replayed.)

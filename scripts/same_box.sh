@@ -8,10 +8,16 @@ Q="--cpu-seconds 0 --host-copy-seconds 0 --min-seconds 3 --check-frames 8 --isol
 full() { grep -q '"--full"' "$1/bench.py" && echo --full; }      # (checkouts from before --full run every leg by default)
 line() { python -c "
 import sys,json
-d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
-print('%9.0f frames/s  tile %.4f ms  mem %.2f GB  mismatches %s  %s' % (d['value'], r['avg_launch_ms'], d['device_memory_bytes']/1e9, d['parity']['mismatching_values'], d.get('step_ms')))"; }
+d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d.get('roofline') or {}
+print('%9.0f frames/s  tile %.4f ms  mem %.2f GB  mismatches %s  %s' % (d['value'], r.get('avg_launch_ms', float('nan')), d['device_memory_bytes']/1e9, (d.get('parity') or {}).get('mismatching_values'), d.get('step_ms')))"; }
+# one bench line of the tree in $2, under a time limit of its own; a leg that fails (or faults the GPU) ends the comparison there
+set -o pipefail
+leg() {
+  printf "%-10s " "$1"; local dir=$2; shift 2
+  (cd $dir && timeout -k 10 300 python bench.py $Q "$@" 2>/dev/null | line) || { echo "leg failed: stopping"; exit 1; }
+}
 for rep in 1 2; do
-  printf "%-10s " other; (cd $other && python bench.py $Q $(full $other) "$@" 2>/dev/null | line)
-  printf "%-10s " this;  (cd $here && python bench.py $Q --full "$@" 2>/dev/null | line)
-  printf "%-10s " this-v2; (cd $here && python bench.py $Q --full --variants 2 "$@" 2>/dev/null | line)
+  leg other $other $(full $other) "$@"
+  leg this $here --full "$@"
+  leg this-v2 $here --full --variants 2 "$@"
 done

@@ -1,0 +1,71 @@
+"""CPU (-m "not gpu"): which kernels a batch runs -- its route -- is decided in one header, rtuf_routes.h.
+
+tests/routes_check.cpp holds the library's own route_of and tile_variant_legal against a table written out by hand, for all
+384 combinations of batch kind, 16UC1, label plane, per-link thresholds, two-kernel flag, dilation and cover pass, and the
+variants the routes reach against the 22 x 2 instantiations of the tile kernel the launcher names (see its head comment).
+The source checks below keep the host API and the launcher from growing a second copy of the rule."""
+import os
+import re
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(HERE, "..", "realtime_urdf_filter_amd", "csrc")
+
+
+@pytest.fixture(scope="module")
+def check(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("routes") / "routes_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I", CSRC, "-o", exe, os.path.join(HERE, "routes_check.cpp")])
+    return exe
+
+
+def test_route_of_is_the_table_for_every_combination(check):
+    r = subprocess.run([check], capture_output=True, text=True, timeout=60)
+    print(r.stdout.strip())
+    assert r.returncode == 0 and r.stdout.split() == ["ok", "384", "44", "88"], r.stdout
+
+
+def _body(src, head):
+    """The text of the function that starts with `head`, up to the closing brace in column 0."""
+    start = src.index(head)
+    return src[start:src.index("\n}\n", start)]
+
+
+def test_the_kernels_and_the_host_take_the_route_from_the_header():
+    api = open(os.path.join(CSRC, "rtuf_api.cpp")).read()
+    dev = open(os.path.join(CSRC, "rtuf_kernels.hip")).read()
+    hdr = open(os.path.join(CSRC, "rtuf_device.h")).read()
+    for src in (api, dev, hdr):
+        assert '#include "rtuf_routes.h"' in src
+    routes = open(os.path.join(CSRC, "rtuf_routes.h")).read()
+    assert "#include <hip" not in routes and "__device__" not in routes      # plain C++: the CPU check compiles it
+
+    # the host asks once, before anything of the context or the slot changes, and a re-run takes the stored route
+    assert api.count("route_of(") == 1
+    enqueue = _body(api, "static int enqueue_batch(")
+    ask = enqueue.index("route_of(")
+    assert "rerun ? b.route" in enqueue[:ask] and enqueue.index("if (!route.ok) return c->fail(RTUF_ERR_STATE") > ask
+    assert all(ask < enqueue.index(m) for m in ("b.lanes_used = 0;", "c->next_lane", "c->timing_seq++", "c->last_slot =", "hipMemcpyAsync"))
+    # ... and keeps no second encoding of it: the plan's flags, the slot's saved pieces, the predicates the route replaced
+    for gone in ("zroute", "b.cover_pass", "b.order_thr", "gr.compare", "gr.dilate", "gr.cloud", "gr.clearance", "takes_two_kernel",
+                 "honours_dilation", "reads_thresholds", "fills_ms_compare", "enum class Kind"):
+        assert gone not in api, gone
+    assert "(uint64_t)route_index(route) << 32" in api      # equal argument blocks, another route: another graph
+    # no stage of the host learns the kind of a batch from a pointer of the tile kernel's argument block
+    issue = _body(api, "static int issue_plan(")
+    assert not re.search(r"if \((!)?gr\.ta\.\w+\)", issue)
+    assert "launch_tile(gr.ta, rt.tile, st)" in issue
+
+    # the launcher goes from the variant to the kernel, and decodes no pointer
+    launch = dev[dev.index("static TileKernel tile_kernel_for("):dev.index("void launch_zero_residual_rows(")]
+    for gone in ("a.resid_table) {", "a.virtual_out) {", "a.order_thr) {", "a.labels) {", "a.bits) {", "a.io_u16", "two_kernel"):
+        assert gone not in launch, gone
+    assert "launch_tile_variant" not in dev
+    cases = re.findall(r"case V\(O::(\w+), (true|false), (true|false), (true|false)\): return (tile_\w*kernel)<", launch)
+    assert len(cases) == 22 and len(set(c[:4] for c in cases)) == 22
+    assert sorted(set(c[4] for c in cases)) == ["tile_bits_kernel", "tile_kernel", "tile_labels_kernel", "tile_render_kernel", "tile_resid_kernel", "tile_thresh_kernel"]
+    assert "default: return nullptr;" in launch and "if (!kernel) return false;" in launch
+    # the kernel body refuses an instantiation the header does not admit
+    assert "static_assert(tile_variant_legal(TileVariant{OUT, LABELS, THRESH, U16, COVER})" in _body(dev, "__device__ __forceinline__ void tile_body(")
