@@ -148,6 +148,7 @@ class URDFRenderer {
  public:
   std::unordered_set<std::string> link_names;    // every link of the URDF, ignored ones included
   std::map<std::string, double> link_thresholds; // URDF link name -> depth threshold of its own (RealtimeURDFFilter::loadModels)
+  std::map<std::string, double> link_padding;    // URDF link name -> padding in metres (RealtimeURDFFilter::loadModels)
  protected:
   std::string camera_frame_, fixed_frame_;
   const TransformProvider& tf_;
@@ -166,6 +167,10 @@ struct ModelParameter {
   // name.  Every renderable of the link takes the value, the model's other links the global depth_distance_threshold; a name
   // that is no link of the model's URDF is an error at load, a link on the ignore list is accepted and has no effect.
   std::vector<std::pair<std::string, double>> link_depth_distance_thresholds;
+  // New, beyond the reference: link padding (include/rtuf.h, LINK PADDING), keyed by URDF link name like the thresholds: a margin
+  // in metres around the silhouette of every renderable of the link, none for the model's other links.  Needs the intrinsics
+  // of getProjectionMatrix before the first frame; not together with thresholds, link_labels or silhouette_dilation_px > 0.
+  std::vector<std::pair<std::string, double>> link_padding;
 };
 struct FilterParameters {
   std::string fixed_frame, camera_frame;
@@ -216,6 +221,11 @@ class RealtimeURDFFilter {
         if (!renderers_.back()->link_names.count(lt.first))
           throw std::runtime_error("link_depth_distance_thresholds of model " + elem.model + ": no link '" + lt.first + "' in its URDF");
         renderers_.back()->link_thresholds[lt.first] = lt.second;
+      }
+      for (const auto& lp : elem.link_padding) {
+        if (!renderers_.back()->link_names.count(lp.first))
+          throw std::runtime_error("link_padding of model " + elem.model + ": no link '" + lp.first + "' in its URDF");
+        renderers_.back()->link_padding[lp.first] = lp.second;
       }
     }
   }
@@ -277,6 +287,19 @@ class RealtimeURDFFilter {
     }
     applied_threshold_ = depth_distance_threshold_;
     apply_link_thresholds();
+    // link padding, in loadModels order: every renderable of a listed URDF link takes its margin, the model's other links none
+    padded_ = false;
+    for (size_t i = 0; i < renderers_.size(); i++) {
+      const URDFRenderer* rd = renderers_[i];
+      if (rd->link_padding.empty() || rd->renderables_.empty()) continue;
+      std::vector<float> pad;
+      for (const auto& r : rd->renderables_) {
+        auto it = rd->link_padding.find(r->urdf_link);
+        pad.push_back(it != rd->link_padding.end() ? (float)it->second : 0.0f);
+      }
+      check(rtuf_set_link_padding(ctx_, model_ids_[i], pad.data(), (int)pad.size()));
+      padded_ = true;
+    }
     labels_.assign(want_labels_ ? (size_t)width_ * height_ : 0, 0);
     masked_depth_ = nullptr;
     mask_ = nullptr;
@@ -363,11 +386,7 @@ class RealtimeURDFFilter {
     if (!depth || !points_out) throw std::runtime_error("cloud_into: needs depth and points_out");
     if (!have_cloud_intr_) throw std::runtime_error("cloud_into: no intrinsics yet (getProjectionMatrix sets them)");
     if (renderers_.empty() || !stage_frame(glTf, timestamp)) return false;
-    if (!cloud_intr_sent_ || std::memcmp(cloud_intr_given_, cloud_intr_, sizeof cloud_intr_) != 0) {
-      check(rtuf_set_cloud_intrinsics(ctx_, 0, 1, cloud_intr_));
-      cloud_intr_sent_ = true;
-      std::memcpy(cloud_intr_given_, cloud_intr_, sizeof cloud_intr_);
-    }
+    send_cloud_intrinsics();
     const void* in = depth;
     if (!count_out) {
       if (is_16uc1) check(rtuf_cloud_batch_u16(ctx_, 1, reinterpret_cast<const uint16_t* const*>(&in), &points_out));
@@ -422,11 +441,7 @@ class RealtimeURDFFilter {
     if (!depth || !table_out) throw std::runtime_error("clearance_into: needs depth and table_out");
     if (!have_cloud_intr_) throw std::runtime_error("clearance_into: no intrinsics yet (getProjectionMatrix sets them)");
     if (renderers_.empty() || !stage_frame(glTf, timestamp)) return false;
-    if (!cloud_intr_sent_ || std::memcmp(cloud_intr_given_, cloud_intr_, sizeof cloud_intr_) != 0) {
-      check(rtuf_set_cloud_intrinsics(ctx_, 0, 1, cloud_intr_));
-      cloud_intr_sent_ = true;
-      std::memcpy(cloud_intr_given_, cloud_intr_, sizeof cloud_intr_);
-    }
+    send_cloud_intrinsics();
     if (!spheres_sent_) {
       for (const auto& kv : link_spheres_)
         check(rtuf_set_link_spheres(ctx_, kv.first, kv.second.first.data(), kv.second.second.data(), (int)kv.second.first.size()));
@@ -564,6 +579,10 @@ class RealtimeURDFFilter {
     camera_transform.o.x += down.x * camera_ty_; camera_transform.o.y += down.y * camera_ty_; camera_transform.o.z += down.z * camera_ty_;
     camera_transform.opengl_matrix(cam);
     check(rtuf_set_camera(ctx_, 0, camera_projection_matrix, off, cam));
+    if (padded_) {                                  // link padding projects its margins with the stream's focal lengths
+      if (!have_cloud_intr_) throw std::runtime_error("link padding: no intrinsics yet (getProjectionMatrix sets them)");
+      send_cloud_intrinsics();
+    }
     for (size_t i = 0; i < renderers_.size(); i++) {
       URDFRenderer* rd = renderers_[i];
       rd->update_link_transforms(timestamp);
@@ -640,6 +659,15 @@ class RealtimeURDFFilter {
     }
   }
   double applied_threshold_ = 0.0;                   // the global threshold apply_link_thresholds last used
+  // the context gets the intrinsics of the last getProjectionMatrix, when it has not got them yet
+  void send_cloud_intrinsics()
+  {
+    if (cloud_intr_sent_ && std::memcmp(cloud_intr_given_, cloud_intr_, sizeof cloud_intr_) == 0) return;
+    check(rtuf_set_cloud_intrinsics(ctx_, 0, 1, cloud_intr_));
+    cloud_intr_sent_ = true;
+    std::memcpy(cloud_intr_given_, cloud_intr_, sizeof cloud_intr_);
+  }
+  bool padded_ = false;                              // some model entry gave a link a padding (initGL)
   bool want_labels_;                                 // FilterParameters::link_labels
   std::vector<uint16_t> labels_;                     // label plane of the last frame (getLabels)
   std::vector<float> virtual_depth_;                 // virtual depth plane of the last render_into (getVirtualDepth)

@@ -584,6 +584,47 @@ int rtuf_link_clearance_batch(rtuf_context *ctx, int n_streams, const float *con
 int rtuf_link_clearance_batch_u16(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in, rtuf_link_clearance *table_out,
                                   int n_labels, float max_distance);
 
+/* LINK PADDING.  New, beyond the reference: a margin in metres around every link's silhouette, per link -- what
+ * robot_self_filter's padding and MoveIt's padding_offset give.  rtuf_set_link_thresholds pads a link ALONG the ray;
+ * silhouette_dilation_px pads across it, but by one radius in pixels for the whole image.  Padding is across the ray, metric
+ * and per link: a drawn pixel of link g at depth d spreads its depth over the disc of pad[g] * f / d pixels around it, the
+ * projection of a ball of pad[g] metres at that depth, so the margin shrinks with distance as the robot's image does.
+ * Definition (every float operation single precision and rounded on its own), per stream:
+ *   f      = (float)max(fx, fy) of rtuf_set_cloud_intrinsics (the larger one: the margin is never under-stated)
+ *   Z(q)   = the window z of the fragment that won pixel q (GL_LESS on the 24-bit depth, ties to the earlier draw), NaN where
+ *            nothing was drawn
+ *   S(q)   = 0 where the background quad won or nothing was drawn, else 1 + the context-global number of the winner's link
+ *   pad[s] = the padding of the link of slot s in metres, pad[0] = 0
+ *   d(q)   = num / (Z(q) - off)                   the shader's to_linear_depth, IEEE division
+ *   rho    = fminf((pad[S(q)] * f) / d(q), 16)    product, then IEEE division; 16 = RTUF_MAX_LINK_PADDING_PX
+ *   R2(q)  = (uint32_t)(rho * rho)                truncated; 0 where Z(q) is NaN, S(q) is 0 or the pad is 0
+ *   z'(p)  = the smallest Z(q) over the pixels q of the image with Z(q) not NaN and (px-qx)^2 + (py-qy)^2 <= R2(q), in
+ *            integers; NaN when there is none.  p itself always qualifies when it is drawn.
+ * and pixel p is shaded as silhouette dilation shades: the global depth_distance_threshold against z'(p), the GL clear colour
+ * where z'(p) is NaN (for mask bits: the "uncovered" state).  z' is a minimum of input values: no order of execution enters.
+ * THE CLAMP at RTUF_MAX_LINK_PADDING_PX = 16 pixels is part of the definition: nearer than d = pad * f / 16 the margin stops
+ * growing in the image -- a 2 cm margin reaches 16 pixels at d = f / 800 (0.66 m at f = 525).
+ * rtuf_set_link_padding sets the paddings of one model's links (n_links = rtuf_num_links(model)), each finite and >= 0;
+ * rtuf_clear_link_padding removes them.  Both wait for the batches in flight and take effect with the next batch enqueued; a
+ * bad model id, a wrong n_links, a NULL array, a negative, NaN or infinite value, or a context of more than 65,534 links fail
+ * with RTUF_ERR_INVALID and change nothing.  The draw-order -> slot table (2 bytes per triangle) and the slot -> padding table
+ * are allocated by the first rtuf_set_link_padding, a 2-byte slot plane per lane and stream of the launch group by the first
+ * padded batch.
+ * Padding is IN EFFECT while some model holds a non-zero value.  Then
+ *   - every filter batch (device, host-plane, asynchronous, f32 and 16UC1), mask-bits batch, cloud batch and clearance batch
+ *     honours it -- so filtered point clouds and link clearance tables hold neither the robot nor its halo.  They all take the
+ *     z-surface route whatever RTUF_FLAG_TWO_KERNEL says (the mask-bits calls still refuse that flag), one batch in flight at a
+ *     time, as with dilation;
+ *   - the link label calls, render batches, residual batches, any batch with silhouette_dilation_px > 0 and any batch while
+ *     per-link thresholds are in effect (equal depths of two links would make "the winner's threshold" ambiguous) fail with
+ *     RTUF_ERR_INVALID before anything is enqueued: not supported yet;
+ *   - a batch with a stream that has no intrinsics fails with RTUF_ERR_STATE.
+ * While it is not -- after the last rtuf_clear_link_padding too -- nothing differs from a context that never used it: batches
+ * take the routes and kernels they always took. */
+#define RTUF_MAX_LINK_PADDING_PX 16
+int rtuf_set_link_padding(rtuf_context *ctx, int model, const float *padding_m, int n_links);
+int rtuf_clear_link_padding(rtuf_context *ctx, int model);
+
 /* Counters of the last batch and kernel timings measured with HIP events on the context's
  * stream (replaces the wall-clock statistics of src/urdf_filter.cpp:239-266). */
 typedef struct {

@@ -40,7 +40,7 @@ SYMBOLS = [
     "rtuf_set_cloud_intrinsics", "rtuf_cloud_batch_device", "rtuf_cloud_batch_device_u16", "rtuf_cloud_compact_batch_device",
     "rtuf_cloud_compact_batch_device_u16", "rtuf_cloud_batch", "rtuf_cloud_batch_u16", "rtuf_cloud_compact_batch", "rtuf_cloud_compact_batch_u16",
     "rtuf_set_link_spheres", "rtuf_link_clearance_batch_device", "rtuf_link_clearance_batch_device_u16", "rtuf_link_clearance_batch",
-    "rtuf_link_clearance_batch_u16",
+    "rtuf_link_clearance_batch_u16", "rtuf_set_link_padding", "rtuf_clear_link_padding",
 ]
 
 # rtuf_link_residuals (include/rtuf.h, LINK RESIDUAL TABLES): one 64-byte row per (stream, label)
@@ -214,6 +214,8 @@ def load_library(path=None):
     lib.rtuf_link_clearance_batch_u16.argtypes = [vp, ci, vp, vp, ci, ctypes.c_float]
     lib.rtuf_set_link_thresholds.argtypes = [vp, ci, vp, ci]
     lib.rtuf_clear_link_thresholds.argtypes = [vp, ci]
+    lib.rtuf_set_link_padding.argtypes = [vp, ci, vp, ci]
+    lib.rtuf_clear_link_padding.argtypes = [vp, ci]
     if path is None:
         _lib = lib
     return lib
@@ -419,6 +421,17 @@ class Context:
     def clear_link_thresholds(self, model):
         """Model `model`'s links follow params.depth_distance_threshold again."""
         self._check(self._lib.rtuf_clear_link_thresholds(self._h, model))
+
+    # link padding (include/rtuf.h, LINK PADDING)
+    def set_link_padding(self, model, padding_m):
+        """Margins in metres (finite, >= 0) around the silhouettes of model `model`'s links, one per link in rtuf_add_link order.
+        The streams need their intrinsics (set_cloud_intrinsics): a margin is projected with max(fx, fy)."""
+        a = np.ascontiguousarray(padding_m, np.float32).reshape(-1)
+        self._check(self._lib.rtuf_set_link_padding(self._h, model, _ptr(a), len(a)))
+
+    def clear_link_padding(self, model):
+        """Model `model`'s links have no padding again."""
+        self._check(self._lib.rtuf_clear_link_padding(self._h, model))
 
     # virtual depth (include/rtuf.h, VIRTUAL DEPTH)
     def render_batch(self, n, empty_value=0.0, labels=False, u16=False):

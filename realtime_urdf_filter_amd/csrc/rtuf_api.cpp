@@ -62,8 +62,9 @@ struct Kinematics {               // on-device forward kinematics of one model
 // labels: rtuf_set_link_labels's labels of the model's links (empty: the default, 1 + link_base + link)
 // thresholds: rtuf_set_link_thresholds's depth thresholds of the model's links (empty: rtuf_params.depth_distance_threshold)
 // sph_link / sph_xyzr: rtuf_set_link_spheres's list of the model (the link and x, y, z, r of every sphere)
+// padding: rtuf_set_link_padding's margins of the model's links in metres (empty: none)
 struct HostModel { std::vector<HostLink> links; int link_base = 0; Kinematics kin; std::vector<uint16_t> labels; std::vector<float> thresholds;
-                   std::vector<int32_t> sph_link; std::vector<float> sph_xyzr; };
+                   std::vector<int32_t> sph_link; std::vector<float> sph_xyzr; std::vector<float> padding; };
 
 // One batch as its caller asked for it: the kind, and the device buffers and scalars that kind has (the rest stays nullptr / 0).
 // A slot keeps the record of its batch (Batch::rq) for re-runs; which kernels a kind runs is route_of's to say (rtuf_routes.h).
@@ -89,6 +90,7 @@ char g_create_error[512] = "";
 
 constexpr uint32_t kKnownFlags = RTUF_FLAG_TWO_KERNEL | RTUF_FLAG_STRICT_GRID;
 static bool dilation_valid(const rtuf_params* p) { return p->silhouette_dilation_px <= (uint32_t)kMaxDilation; }
+static_assert(kMaxLinkPaddingPx == RTUF_MAX_LINK_PADDING_PX, "the header's clamp is the kernels'");
 inline bool flags_valid(uint32_t flags)
 {
 #ifdef RTUF_ABLATE
@@ -134,6 +136,14 @@ struct rtuf_context {
   // rewritten in place after that (captured graphs keep its address), and which streams have been given theirs.
   CloudIntrinsics* d_cloud_intr = nullptr;
   std::vector<uint8_t> cloud_intr_set;
+  // Link padding: the device tables draw order -> link slot, [n_tris + 1] (entry 0 = 0; a link's slot is 1 + its context-global
+  // number), slot -> padding in metres, [n_links + 1] (entry 0 = 0), and stream -> (float)max(fx, fy), [max_streams], allocated
+  // by the first rtuf_set_link_padding and rewritten in place after that (captured graphs keep their addresses).  The kernels
+  // read them only while pad_models > 0 (models that hold a non-zero padding).  focal: the host's copy, kept since the first
+  // rtuf_set_cloud_intrinsics.
+  uint16_t* d_order_slot = nullptr; float* d_slot_pad = nullptr; float* d_pad_focal = nullptr;
+  std::vector<float> focal;
+  int pad_models = 0;
   // Link clearance tables: the spheres of every model sorted by label (label 0 left out) with their label slots, rebuilt on
   // the host when the lists or the labels changed (clr_dirty) and uploaded before the next clearance batch; the device
   // arrays are allocated once for the most a context can hold (captured graphs keep their addresses).
@@ -177,6 +187,7 @@ struct rtuf_context {
                                                                  // batch slot: the cull of a lane's first group runs in the batch's pose
                                                                  // stage, under the set-up kernel of the batch before it
     float* d_zsurface = nullptr;
+    uint16_t* d_slots = nullptr;                                 // link padding: the link slot plane beside the z-surface, [G][H][W]
   };
   Lane lane[kMaxLanes];
   int n_lanes = 1;
@@ -682,7 +693,7 @@ static void free_frame_buffers(rtuf_context* c)
   for (auto& b : c->batch) { dev_free(c, b.d_cams); dev_free(c, b.d_link_tf); dev_free(c, b.d_mvp); dev_free(c, b.d_bg); dev_free(c, b.d_counters); dev_free(c, b.d_status); }
   for (auto& ln : c->lane) {
     dev_free(c, ln.d_bins); dev_free(c, ln.d_bin_hdr); dev_free(c, ln.d_fbins); dev_free(c, ln.d_fbin_count); dev_free(c, ln.d_clip_list);
-    dev_free(c, ln.d_clip_spill); dev_free(c, ln.d_big_list); dev_free(c, ln.d_zsurface);
+    dev_free(c, ln.d_clip_spill); dev_free(c, ln.d_big_list); dev_free(c, ln.d_zsurface); dev_free(c, ln.d_slots);
     for (auto*& it : ln.d_items) dev_free(c, it);
   }
   for (auto& b : c->batch) for (auto& st : b.st) { dev_free(c, st.p); st.have = 0; }
@@ -715,6 +726,7 @@ void rtuf_destroy(rtuf_context* c)
   free_frame_buffers(c);
   dev_free(c, c->d_cverts); dev_free(c, c->d_ctris); dev_free(c, c->d_corder); dev_free(c, c->d_chunks); dev_free(c, c->d_draws);
   dev_free(c, c->d_order_labels);
+  dev_free(c, c->d_order_slot); dev_free(c, c->d_slot_pad); dev_free(c, c->d_pad_focal);
   dev_free(c, c->d_order_thr);
   dev_free(c, c->d_cloud_intr);
   dev_free(c, c->d_clr_spheres); dev_free(c, c->d_clr_slot_label);
@@ -1397,8 +1409,8 @@ int rtuf_debug_read_poses(rtuf_context* c, int n, double* link_tf_out, double* c
 // ---- what a batch of each kind does ----
 // Which kernels it runs is its route (route_of in rtuf_routes.h, asked once by enqueue_batch; a new kind starts there).  The
 // predicates below are what is asked BEFORE a batch has a route: by the calls' checks and when a slot's buffers are allocated.
-// the batches of this context write the z-surface: two-kernel mode, or a silhouette dilation radius
-static bool uses_zsurface(const rtuf_context* c) { return (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 || c->params.silhouette_dilation_px > 0; }
+// the batches of this context write the z-surface: two-kernel mode, a silhouette dilation radius, or link padding in effect
+static bool uses_zsurface(const rtuf_context* c) { return (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 || c->params.silhouette_dilation_px > 0 || c->pad_models > 0; }
 // may write the z-surface, and so needs d_zsurface and moves last_lane (render and residual batches never take that route and leave it alone)
 static bool may_write_zsurface(const BatchRequest& r) { return r.kind != Kind::Render && r.kind != Kind::Residual; }
 // refused while per-link thresholds meet the z-surface route (check_thresh_route).  Render and residual batches never take that
@@ -1420,8 +1432,8 @@ static hipEvent_t get_event(rtuf_context::Batch& b, size_t i)
 struct BatchPlan {
   std::vector<FkArgs> fks;
   PoseArgs pa{};
-  // (ca, da, cl, cr: filled and read where the route's post / tail has that kernel)
-  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; CloudArgs cl{}; ClearanceArgs cr{}; int lane = 0; };
+  // (ca, da, pd, cl, cr: filled and read where the route's post / tail has that kernel)
+  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; PadArgs pd{}; CloudArgs cl{}; ClearanceArgs cr{}; int lane = 0; };
   std::vector<Group> groups;
   Route route{};                // the batch's (Batch::route): every group runs the same kernels
   uint64_t hash() const
@@ -1434,6 +1446,7 @@ struct BatchPlan {
       mix(&g.sa, sizeof g.sa); mix(&g.ta, sizeof g.ta);
       if (route.post == Post::Compare) mix(&g.ca, sizeof g.ca);
       if (route.post == Post::Dilate) mix(&g.da, sizeof g.da);
+      if (route.post == Post::Pad) mix(&g.pd, sizeof g.pd);
       if (route.tail == Tail::Cloud) mix(&g.cl, sizeof g.cl);
       if (route.tail == Tail::Clearance) mix(&g.cr, sizeof g.cr);
       mix(&g.lane, sizeof g.lane);
@@ -1515,6 +1528,7 @@ static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& 
     // batch: the group's rows of the table) before the lane publishes its counters -- timed together as ms_compare
     if (rt.post == Post::Compare) launch_compare(gr.ca, st);
     if (rt.post == Post::Dilate) launch_dilate_compare(gr.da, st);
+    if (rt.post == Post::Pad) launch_pad_compare(gr.pd, st);
     if (rt.tail == Tail::Cloud) launch_cloud(gr.cl, st);
     if (rt.tail == Tail::Clearance) launch_clearance(gr.cr, st);
     if (b.timing && runs_behind_tile(rt)) mark(e0 + 4, st);
@@ -1551,7 +1565,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   // not ok has been refused by the call's checks: none gets here.)
   const Route route = rerun ? b.route
                             : route_of({r.kind, r.u16, r.labels != nullptr, c->thresh_models > 0, (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0,
-                                        (int)c->params.silhouette_dilation_px, c->cover_on});
+                                        (int)c->params.silhouette_dilation_px, c->cover_on, c->pad_models > 0});
   if (!route.ok) return c->fail(RTUF_ERR_STATE, "internal: no kernel route for a batch of kind %d (tile variant %d)", (int)r.kind, tile_variant_index(route.tile));
   if (!rerun) {
     b.route = route;
@@ -1646,7 +1660,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     const int gs = std::min(per_group, n - base);
     plan.groups.emplace_back();
     BatchPlan::Group& gr = plan.groups.back();
-    memset(&gr.sa, 0, sizeof gr.sa); memset(&gr.ta, 0, sizeof gr.ta); memset(&gr.ca, 0, sizeof gr.ca); memset(&gr.da, 0, sizeof gr.da);
+    memset(&gr.sa, 0, sizeof gr.sa); memset(&gr.ta, 0, sizeof gr.ta); memset(&gr.ca, 0, sizeof gr.ca); memset(&gr.da, 0, sizeof gr.da); memset(&gr.pd, 0, sizeof gr.pd);
     memset(&gr.cl, 0, sizeof gr.cl); memset(&gr.cr, 0, sizeof gr.cr);
     gr.lane = n_groups == 1 ? lane0 : g % c->n_lanes;
     const rtuf_context::Lane& ln = c->lane[gr.lane];
@@ -1675,6 +1689,18 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     ta.bits = tv.out == TileOut::Bits ? r.bits : nullptr;
     ta.labels = r.labels;
     ta.order_labels = tv.labels || tv.out == TileOut::Residual ? c->d_order_labels : nullptr;      // a label plane beside the outputs, or the rows of a residual table
+    if (route.post == Post::Pad) {
+      // link padding: the "label" of a winner is its link slot, and the plane is the lane's own, laid out like the z-surface
+      // (slot 0 = stream `base`) where the tile kernel indexes its label plane by batch stream: biased by the group's base
+      ta.order_labels = c->d_order_slot;
+      ta.labels = ln.d_slots - (ptrdiff_t)base * (ptrdiff_t)plane;
+      PadArgs& pd = gr.pd;
+      pd.depth = d_depth; pd.zsurface = ln.d_zsurface; pd.slots = ln.d_slots; pd.slot_pad = c->d_slot_pad; pd.focal = c->d_pad_focal;
+      pd.masked = d_masked; pd.mask = d_mask; pd.bits = r.bits; pd.counters = d_counters;
+      pd.group_base = base; pd.group_size = gs; pd.width = c->width; pd.height = c->height;
+      pd.max_diff = ta.max_diff; pd.replace_value = ta.replace_value; pd.sc_num = sc_num; pd.sc_off = sc_off;
+      pd.io_u16 = io_u16 ? 1 : 0; pd.fast_div = fast_div;
+    }
     ta.order_thr = tv.thresh ? c->d_order_thr : nullptr;      // (allocated once, rewritten in place: a re-run finds the same table)
     ta.virtual_out = r.virt; ta.empty_value = r.empty_value;
     ta.resid_table = reinterpret_cast<unsigned long long*>(r.resid); ta.n_labels = r.n_labels;
@@ -2009,6 +2035,21 @@ static int check_thresh_route(rtuf_context* c)
   return RTUF_OK;
 }
 
+// While link padding is in effect every batch goes over the z-surface with the link slots beside it (rtuf_routes.h): what has
+// no such route is refused before anything is staged or enqueued, and every stream of the batch needs its focal length.
+static int check_pad_route(rtuf_context* c, const BatchRequest& r, bool labels)
+{
+  if (c->pad_models <= 0) return RTUF_OK;
+  if (labels) return c->fail(RTUF_ERR_INVALID, "link labels are not supported with link padding yet");
+  if (r.kind == Kind::Render) return c->fail(RTUF_ERR_INVALID, "virtual depth is not supported with link padding yet");
+  if (r.kind == Kind::Residual) return c->fail(RTUF_ERR_INVALID, "link residual tables are not supported with link padding yet");
+  if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "silhouette dilation is not supported with link padding yet");
+  if (c->thresh_models > 0) return c->fail(RTUF_ERR_INVALID, "per-link depth thresholds are not supported with link padding yet");
+  for (int s = 0; s < r.n; s++)
+    if (!c->d_cloud_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
+  return RTUF_OK;
+}
+
 static int check_u16_width(rtuf_context* c, bool u16) { return u16 && (c->width & 3) ? c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4") : RTUF_OK; }
 // What every batch call checks first: the models are final, n is in range and the arrays the call cannot do without are there
 // (have_args) and -- u16: the filter calls; the kinds that test something of their own first call check_u16_width after it -- the 16UC1 width.
@@ -2052,6 +2093,9 @@ static int submit_batch(rtuf_context* c, rtuf_context::Batch& b, const BatchRequ
   if (uses_zsurface(c) && may_write_zsurface(rq))
     for (int l = 0; l < c->n_lanes; l++)
       if (!c->lane[l].d_zsurface) HIP_TRY(c, dev_alloc(c, &c->lane[l].d_zsurface, (size_t)c->group * c->width * c->height * sizeof(float)));
+  if (c->pad_models > 0 && may_write_zsurface(rq))
+    for (int l = 0; l < c->n_lanes; l++)
+      if (!c->lane[l].d_slots) HIP_TRY(c, dev_alloc(c, &c->lane[l].d_slots, (size_t)c->group * c->width * c->height * sizeof(uint16_t)));
   b.rq = rq;
   if (rq.kind == Kind::Cloud || rq.kind == Kind::Clearance) b.rq.bits = b.cl_bits;
   b.host_io = false;
@@ -2063,6 +2107,7 @@ static int submit_batch(rtuf_context* c, rtuf_context::Batch& b, const BatchRequ
 // a batch on the caller's device buffers
 static int submit_device(rtuf_context* c, const BatchRequest& rq)
 {
+  { const int rc = check_pad_route(c, rq, rq.labels != nullptr); if (rc != RTUF_OK) return rc; }
   if (subject_to_thresh_route(rq)) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
   rtuf_context::Batch* b = nullptr;
   const int rc = take_slot(c, b);
@@ -2274,7 +2319,8 @@ static int submit_host_planes(rtuf_context* c, BatchRequest rq, const HostPlanes
   for (int s = 0; s < n; s++)
     if ((hp.depth && !hp.depth[s]) || (hp.out && !hp.out[s]) || (hp.labels && !hp.labels[s]) || (hp.index && !hp.index[s]))
       return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
-  if (subject_to_thresh_route(rq)) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }      // (before the planes are staged)
+  { const int rc = check_pad_route(c, rq, hp.labels != nullptr); if (rc != RTUF_OK) return rc; }      // (before the planes are staged)
+  if (subject_to_thresh_route(rq)) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
   B* slot = nullptr;
   { const int rc = take_slot(c, slot); if (rc != RTUF_OK) return rc; }
   B& b = *slot;
@@ -2548,6 +2594,77 @@ int rtuf_clear_link_thresholds(rtuf_context* c, int model)
   return rc;
 }
 
+// ---- link padding --------------------------------------------------------------------------------------
+// The draw order once more, turned into the winner's link slot (1 + its context-global number; 0: the background quad), and
+// the slots' paddings: the tile kernel writes the slot of every pixel's winner beside the z-surface, pad_compare_kernel reads
+// both (rtuf_device.h, PadArgs).  Padding is in effect while some model holds a non-zero value.
+static int build_pad_tables(rtuf_context* c)
+{
+  std::vector<float> slot_pad((size_t)c->n_links + 1, 0.0f);
+  int with = 0;
+  for (const HostModel& m : c->models) {
+    bool any = false;
+    for (size_t l = 0; l < m.padding.size(); l++) { slot_pad[1 + (size_t)m.link_base + l] = m.padding[l]; any = any || m.padding[l] > 0.0f; }
+    with += any ? 1 : 0;
+  }
+  hipSetDevice(c->device);
+  if (!c->d_order_slot) {
+    std::vector<uint16_t> table((size_t)c->n_tris + 1, 0);
+    for (size_t d = 0, first = 1; d < c->draw_link.size(); d++) {
+      for (size_t o = first; o <= c->draw_last_order[d]; o++) table[o] = (uint16_t)(1u + c->draw_link[d]);
+      first = (size_t)c->draw_last_order[d] + 1;
+    }
+    HIP_TRY(c, dev_alloc(c, &c->d_order_slot, table.size() * sizeof(uint16_t)));
+    HIP_TRY(c, hipMemcpy(c->d_order_slot, table.data(), table.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  }
+  if (!c->d_slot_pad) HIP_TRY(c, dev_alloc(c, &c->d_slot_pad, slot_pad.size() * sizeof(float)));
+  if (!c->d_pad_focal) {
+    c->focal.resize((size_t)c->max_streams, 0.0f);
+    HIP_TRY(c, dev_alloc(c, &c->d_pad_focal, (size_t)c->max_streams * sizeof(float)));
+    HIP_TRY(c, hipMemcpy(c->d_pad_focal, c->focal.data(), (size_t)c->max_streams * sizeof(float), hipMemcpyHostToDevice));
+  }
+  // (no batch in flight reads the table: every caller waited for them, and a new table has never been read)
+  HIP_TRY(c, hipMemcpy(c->d_slot_pad, slot_pad.data(), slot_pad.size() * sizeof(float), hipMemcpyHostToDevice));
+  c->pad_models = with;
+  return RTUF_OK;
+}
+
+int rtuf_set_link_padding(rtuf_context* c, int model, const float* padding_m, int n_links)
+{
+  KIDS_ALL(c, rtuf_set_link_padding(k, model, padding_m, n_links));
+  if (!c) return RTUF_ERR_INVALID;
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (model < 0 || model >= (int)c->models.size()) return c->fail(RTUF_ERR_INVALID, "bad model id %d", model);
+  HostModel& m = c->models[model];
+  if (!padding_m || n_links != (int)m.links.size())
+    return c->fail(RTUF_ERR_INVALID, "model %d has %d links (got %d paddings)", model, (int)m.links.size(), n_links);
+  for (int l = 0; l < n_links; l++)
+    if (!(std::isfinite(padding_m[l]) && padding_m[l] >= 0.0f)) return c->fail(RTUF_ERR_INVALID, "link %d: the padding must be finite and >= 0 (got %g)", l, (double)padding_m[l]);
+  if (c->n_links > 65534) return c->fail(RTUF_ERR_INVALID, "link padding is limited to 65534 links in the context (it has %d)", c->n_links);
+  WAIT_IF_PENDING(c);
+  std::vector<float> keep = m.padding;
+  m.padding.assign(padding_m, padding_m + n_links);      // (a model without links stays without)
+  const int rc = build_pad_tables(c);
+  if (rc != RTUF_OK) m.padding = keep;
+  return rc;
+}
+
+int rtuf_clear_link_padding(rtuf_context* c, int model)
+{
+  KIDS_ALL(c, rtuf_clear_link_padding(k, model));
+  if (!c) return RTUF_ERR_INVALID;
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (model < 0 || model >= (int)c->models.size()) return c->fail(RTUF_ERR_INVALID, "bad model id %d", model);
+  WAIT_IF_PENDING(c);
+  HostModel& m = c->models[model];
+  if (m.padding.empty()) return RTUF_OK;
+  std::vector<float> keep;
+  keep.swap(m.padding);
+  const int rc = build_pad_tables(c);
+  if (rc != RTUF_OK) m.padding.swap(keep);
+  return rc;
+}
+
 // ---- virtual depth ---------------------------------------------------------------------------------
 // A render batch is a batch like any other (Kind::Render) whose tile kernel stores the winners' virtual depth instead of
 // comparing a sensor plane with it.  Parameters of the compare do not enter, and the z-surface is never used.
@@ -2687,6 +2804,10 @@ int rtuf_set_cloud_intrinsics(rtuf_context* c, int first, int n, const double* f
   }
   WAIT_IF_PENDING(c);
   hipSetDevice(c->device);
+  // link padding projects a margin with the larger focal length (never under-stated); its device copy exists once padding was set
+  c->focal.resize((size_t)c->max_streams, 0.0f);
+  for (int s = 0; s < n; s++) c->focal[(size_t)(first + s)] = (float)std::max(fx_fy_cx_cy[4 * s], fx_fy_cx_cy[4 * s + 1]);
+  if (c->d_pad_focal) HIP_TRY(c, hipMemcpy(c->d_pad_focal + first, c->focal.data() + first, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
   if (!c->d_cloud_intr) {
     HIP_TRY(c, dev_alloc(c, &c->d_cloud_intr, (size_t)c->max_streams * sizeof(CloudIntrinsics)));
     c->cloud_intr_set.assign((size_t)c->max_streams, 0);

@@ -23,7 +23,8 @@
 //                                                                    record bin holds a near record, see KeyFmt)
 //     clip_list ClipItem[shards][clip_capacity]   triangles that cross a frustum plane (set-up kernel -> clip kernel)
 //     big_list  BigRec[shards][big_capacity]      records over more than 4 tiles (set-up / clip kernel -> bigrec_kernel)
-//     zsurface  f32[G][H][W]                       two-kernel mode and silhouette dilation only
+//     zsurface  f32[G][H][W]                       two-kernel mode, silhouette dilation and link padding only
+//     slots     u16[G][H][W]                       link padding only: the link slot of every pixel's winner, beside the z-surface
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -369,6 +370,29 @@ struct DilateArgs {
   int fast_div;
 };
 
+// Link padding (include/rtuf.h, LINK PADDING; rtuf_set_link_padding): pad_compare_kernel takes the place of compare_kernel.
+// The tile kernel left the z-surface and, in its label plane, the link slot of every pixel's winner (0: background or nothing
+// drawn, else 1 + the context-global link).  A source pixel q spreads its z over the disc of R2(q) = link_padding_reach2
+// (rtuf_numerics.h) around it; per pixel the kernel shades with the smallest z that reaches it (NaN when none does) and
+// writes the outputs dilate_compare_kernel would.
+struct PadArgs {
+  const float* depth;     // [n][H][W] sensor planes (f32 metres or, with io_u16, uint16 millimetres): the whole batch
+  const float* zsurface;  // [G][H][W] the lane's z-surface (slot 0 = stream group_base)
+  const uint16_t* slots;  // [G][H][W] the lane's link slot plane, laid out like the z-surface
+  const float* slot_pad;  // [n_links + 1] padding of every link slot in metres (entry 0: 0)
+  const float* focal;     // [max_streams] (float)max(fx, fy) of every stream
+  float* masked;          // [n][H][W] same element type as depth; unused with bits
+  uint8_t* mask;          // [n][H][W] or nullptr; unused with bits
+  uint32_t* bits;         // mask-only output (rtuf_mask_bits_words layout) or nullptr
+  Counters* counters;     // the launch group's block: BITS sets a shard's `uncovered`
+  int group_base, group_size;
+  int width, height;
+  float max_diff, replace_value;
+  float sc_num, sc_off;
+  int io_u16;
+  int fast_div;
+};
+
 // Filtered point clouds (include/rtuf.h, FILTERED POINT CLOUDS): the cloud kernels of one launch group.  They run behind the
 // group's tile (or dilate) kernel on its lane and read the mask bits that kernel wrote; streams are batch-absolute.
 struct CloudIntrinsics;
@@ -452,6 +476,7 @@ void launch_zero_residual_rows(unsigned long long* rows, size_t n_words, hipStre
 bool launch_tile(const TileArgs& a, TileVariant v, hipStream_t st);
 void launch_compare(const CompareArgs& a, hipStream_t st);
 void launch_dilate_compare(const DilateArgs& a, hipStream_t st);     // a.bits selects the mask-only variant, a.io_u16 the 16UC1 one
+void launch_pad_compare(const PadArgs& a, hipStream_t st);           // as launch_dilate_compare
 void launch_cloud(const CloudArgs& a, hipStream_t st);               // a.capacity selects the compacted form (count, scan, emit), a.io_u16 the 16UC1 variants
 void launch_clearance(const ClearanceArgs& a, hipStream_t st);       // spheres, zero, clearance, finish: the group's rows of the table, a.io_u16 selects the 16UC1 variant
 void launch_spin(unsigned long long ticks, hipStream_t st);      // a one-wave kernel that idles for `ticks` of the 100 MHz clock

@@ -22,6 +22,10 @@
 //   dilate_compare_kernel  silhouette dilation only (new, beyond the       (none: the reference has no dilation)
 //                   reference): (2r+1)^2 window minimum of the z-surface,
 //                   then compare_kernel's shading (or the mask bits)
+//   pad_compare_kernel  link padding only (new as well): every drawn        (none: the reference has no padding)
+//                   pixel spreads its z over the disc its link's padding
+//                   projects to; the smallest z that reaches a pixel,
+//                   then compare_kernel's shading (or the mask bits)
 //
 // Exactness: results must equal the reference's GLSL running on Mesa llvmpipe bit for bit
 // (see oracle/rtuf_oracle.c for what that pins).  Every float operation whose rounding matters
@@ -2897,68 +2901,14 @@ static_assert((kDilH + 2 * kMaxDilation) * (kDilW + 2 * dilate_r4(kMaxDilation) 
 
 __device__ __forceinline__ float4 fmin4(float4 a, float4 b) { return make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z), fminf(a.w, b.w)); }
 
-template <bool U16, bool BITS>
-__global__ __launch_bounds__(kDilThreads) void dilate_compare_kernel(DilateArgs a)
+// The last step of dilate_compare_kernel and pad_compare_kernel (Args: DilateArgs or PadArgs): lane tid holds the window's z
+// of tile rows ly and ly + 1, columns lx .. lx + 3, and shades exactly as compare_kernel does, with that z in place of the
+// pixel's own.
+template <bool U16, bool BITS, class Args>
+__device__ __forceinline__ void shade_window_tile(const Args& a, const float4 (&zd)[2], int stream, int x0, int y0)
 {
-  extern __shared__ float dil_lds[];
-  const int r = a.radius, R4 = dilate_r4(r);
-  const int in_w = kDilW + 2 * R4;            // halo tile columns: image x = x0 - R4 + column
-  const int rows = kDilH + 2 * r;             // halo tile rows:    image y = y0 - r + row
-  float* zin = dil_lds;                       // [rows][in_w]
-  float* rmin = dil_lds + rows * in_w;        // [rows][kDilW]  minimum over the row window of every output column
-  const int tid = threadIdx.x;
-  const int slot = blockIdx.z, stream = a.group_base + slot;
-  const int x0 = blockIdx.x * kDilW, y0 = blockIdx.y * kDilH;
-  const int W = a.width, H = a.height;
-  const float nan = __uint_as_float(0x7fc00000u);
-  const float* zs = a.zsurface + (size_t)slot * ((size_t)H * W);
-
-  // 1. the halo tile (the window is clipped to the image, never padded: NaN is what the minimum ignores)
-  if ((W & 3) == 0) {
-    const int in_w4 = in_w >> 2;
-    for (int i = tid; i < rows * in_w4; i += kDilThreads) {
-      const int row = i / in_w4, c4 = i - row * in_w4;
-      const int y = y0 - r + row, x = x0 - R4 + 4 * c4;
-      float4 v = make_float4(nan, nan, nan, nan);
-      if (y >= 0 && y < H && x >= 0 && x < W) v = *reinterpret_cast<const float4*>(zs + (size_t)y * W + x);      // (x < W: x + 3 < W)
-      *reinterpret_cast<float4*>(zin + row * in_w + 4 * c4) = v;
-    }
-  } else {
-    for (int i = tid; i < rows * in_w; i += kDilThreads) {
-      const int row = i / in_w, c = i - row * in_w;
-      const int y = y0 - r + row, x = x0 - R4 + c;
-      float v = nan;
-      if (y >= 0 && y < H && x >= 0 && x < W) v = zs[(size_t)y * W + x];
-      zin[i] = v;
-    }
-  }
-  __syncthreads();
-
-  // 2. rows: outputs c .. c + 3 of a halo row; output c + j's window is p[j .. j + 2r]
-  for (int i = tid; i < rows * (kDilW / 4); i += kDilThreads) {
-    const int row = i >> 4, c = (i & 15) * 4;
-    const float* p = zin + row * in_w + c + R4 - r;
-    float core = nan;
-    for (int k = 3; k <= 2 * r; k++) core = fminf(core, p[k]);
-    const float e0 = p[0], e1 = p[1], e2 = p[2], f0 = p[2 * r + 1], f1 = p[2 * r + 2], f2 = p[2 * r + 3];
-    *reinterpret_cast<float4*>(rmin + row * kDilW + c) =
-        make_float4(fminf(core, fminf(e0, fminf(e1, e2))), fminf(core, fminf(e1, fminf(e2, f0))),
-                    fminf(core, fminf(e2, fminf(f0, f1))), fminf(core, fminf(f0, fminf(f1, f2))));
-  }
-  __syncthreads();
-
-  // 3. columns: tile rows ly and ly + 1, columns lx .. lx + 3; tile row y's window is halo rows y .. y + 2r
+  const int tid = threadIdx.x, W = a.width, H = a.height;
   const int lx = (tid & 15) * 4, ly = (tid >> 4) * 2;
-  float4 zd[2];
-  {
-    const float* q = rmin + ly * kDilW + lx;
-    float4 core = make_float4(nan, nan, nan, nan);
-    for (int k = 1; k <= 2 * r; k++) core = fmin4(core, *reinterpret_cast<const float4*>(q + k * kDilW));
-    zd[0] = fmin4(core, *reinterpret_cast<const float4*>(q));
-    zd[1] = fmin4(core, *reinterpret_cast<const float4*>(q + (2 * r + 1) * kDilW));
-  }
-
-  // 4. shade exactly as compare_kernel does, with the window's z in place of the pixel's own
   ShadeConsts sc;
   sc.num = a.sc_num; sc.off = a.sc_off; sc.max_diff = a.max_diff; sc.replace_value = a.replace_value; sc.core = a.fast_div != 0;
   const bool vec = (W & 3) == 0;
@@ -3026,6 +2976,179 @@ __global__ __launch_bounds__(kDilThreads) void dilate_compare_kernel(DilateArgs 
     const int bin = ((int)blockIdx.z * (int)gridDim.y + (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x;
     if (__syncthreads_or(uncovered) && tid == 0) a.counters->shard[bin % kCounterShards].uncovered = 1u;
   }
+}
+
+template <bool U16, bool BITS>
+__global__ __launch_bounds__(kDilThreads) void dilate_compare_kernel(DilateArgs a)
+{
+  extern __shared__ float dil_lds[];
+  const int r = a.radius, R4 = dilate_r4(r);
+  const int in_w = kDilW + 2 * R4;            // halo tile columns: image x = x0 - R4 + column
+  const int rows = kDilH + 2 * r;             // halo tile rows:    image y = y0 - r + row
+  float* zin = dil_lds;                       // [rows][in_w]
+  float* rmin = dil_lds + rows * in_w;        // [rows][kDilW]  minimum over the row window of every output column
+  const int tid = threadIdx.x;
+  const int slot = blockIdx.z, stream = a.group_base + slot;
+  const int x0 = blockIdx.x * kDilW, y0 = blockIdx.y * kDilH;
+  const int W = a.width, H = a.height;
+  const float nan = __uint_as_float(0x7fc00000u);
+  const float* zs = a.zsurface + (size_t)slot * ((size_t)H * W);
+
+  // 1. the halo tile (the window is clipped to the image, never padded: NaN is what the minimum ignores)
+  if ((W & 3) == 0) {
+    const int in_w4 = in_w >> 2;
+    for (int i = tid; i < rows * in_w4; i += kDilThreads) {
+      const int row = i / in_w4, c4 = i - row * in_w4;
+      const int y = y0 - r + row, x = x0 - R4 + 4 * c4;
+      float4 v = make_float4(nan, nan, nan, nan);
+      if (y >= 0 && y < H && x >= 0 && x < W) v = *reinterpret_cast<const float4*>(zs + (size_t)y * W + x);      // (x < W: x + 3 < W)
+      *reinterpret_cast<float4*>(zin + row * in_w + 4 * c4) = v;
+    }
+  } else {
+    for (int i = tid; i < rows * in_w; i += kDilThreads) {
+      const int row = i / in_w, c = i - row * in_w;
+      const int y = y0 - r + row, x = x0 - R4 + c;
+      float v = nan;
+      if (y >= 0 && y < H && x >= 0 && x < W) v = zs[(size_t)y * W + x];
+      zin[i] = v;
+    }
+  }
+  __syncthreads();
+
+  // 2. rows: outputs c .. c + 3 of a halo row; output c + j's window is p[j .. j + 2r]
+  for (int i = tid; i < rows * (kDilW / 4); i += kDilThreads) {
+    const int row = i >> 4, c = (i & 15) * 4;
+    const float* p = zin + row * in_w + c + R4 - r;
+    float core = nan;
+    for (int k = 3; k <= 2 * r; k++) core = fminf(core, p[k]);
+    const float e0 = p[0], e1 = p[1], e2 = p[2], f0 = p[2 * r + 1], f1 = p[2 * r + 2], f2 = p[2 * r + 3];
+    *reinterpret_cast<float4*>(rmin + row * kDilW + c) =
+        make_float4(fminf(core, fminf(e0, fminf(e1, e2))), fminf(core, fminf(e1, fminf(e2, f0))),
+                    fminf(core, fminf(e2, fminf(f0, f1))), fminf(core, fminf(f0, fminf(f1, f2))));
+  }
+  __syncthreads();
+
+  // 3. columns: tile rows ly and ly + 1, columns lx .. lx + 3; tile row y's window is halo rows y .. y + 2r
+  const int lx = (tid & 15) * 4, ly = (tid >> 4) * 2;
+  float4 zd[2];
+  {
+    const float* q = rmin + ly * kDilW + lx;
+    float4 core = make_float4(nan, nan, nan, nan);
+    for (int k = 1; k <= 2 * r; k++) core = fmin4(core, *reinterpret_cast<const float4*>(q + k * kDilW));
+    zd[0] = fmin4(core, *reinterpret_cast<const float4*>(q));
+    zd[1] = fmin4(core, *reinterpret_cast<const float4*>(q + (2 * r + 1) * kDilW));
+  }
+
+  // 4. shade exactly as compare_kernel does, with the window's z in place of the pixel's own
+  shade_window_tile<U16, BITS>(a, zd, stream, x0, y0);
+}
+
+// ---------------------------------------------------------------------------------------
+// pad_compare_kernel (link padding, rtuf_set_link_padding): z-surface + link slots -> per pixel the smallest z whose source
+// reaches it -> the compare kernel's outputs, or the bit-packed mask
+// ---------------------------------------------------------------------------------------
+// One workgroup per (64x32 output tile, stream of the launch group), like dilate_compare_kernel.  The radius belongs to the
+// SOURCE pixel here (R2 = link_padding_reach2 of its z and its link's padding), so the window is not separable into rows and
+// columns; the kernel gathers, and keeps the cost proportional to what actually spreads:
+//   1. the tile with a halo of kMaxLinkPaddingPx pixels goes to LDS as {z, R2} pairs, R2 computed once per halo pixel ({NaN, 0}
+//      outside the image); a wave takes whole halo rows, so one ballot per row segment says whether the row holds a source
+//      that spreads at all, and the waves reduce the halo's largest R2;
+//   2. lane c of wave w owns column c of tile rows 8 w .. 8 w + 7, which start as their own z.  The wave walks the halo rows
+//      within m = floor(sqrt(largest R2)) of its rows -- not 16 -- and skips those the ballots found empty; in a row its lanes
+//      read neighbouring 8-byte pairs (one ds_read_b64 each, no two lanes of a half-wave on one bank) at the 2 m + 1 column
+//      offsets, and a pair with R2 = 0 is tested against nothing (a wave whose 64 pairs are all 0 branches over the tests).
+//      dx^2 + dy^2 <= R2 in integers; fminf keeps the other operand of a NaN.  A tile whose halo holds no R2 > 0 -- most of the
+//      image -- has m = 0 and writes its own z straight through;
+//   3. the minima go back to LDS (over the halo, which is dead by then) so that step 4 finds them in the layout it stores from;
+//   4. shade_window_tile, as in dilate_compare_kernel.
+constexpr int kPadR = kMaxLinkPaddingPx;
+constexpr int kPadW = kDilW + 2 * kPadR, kPadH = kDilH + 2 * kPadR;      // the halo tile: image (x0 - kPadR + column, y0 - kPadR + row)
+constexpr int kPadWaves = kDilThreads / 64, kPadRowsPerWave = kDilH / kPadWaves;
+static_assert(kDilW == 64 && kDilH % kPadWaves == 0, "gather: a lane per tile column, a wave per strip of rows");
+static_assert(kPadW * kPadH * 8 <= 49152 && kPadW * kPadH * 8 >= kDilW * kDilH * 4, "three workgroups per CU; the minima fit over the halo");
+
+template <bool U16, bool BITS>
+__global__ __launch_bounds__(kDilThreads) void pad_compare_kernel(PadArgs a)
+{
+  __shared__ uint2 halo[kPadH * kPadW];          // {bits of z, R2}
+  __shared__ uint32_t row_spreads[kPadH];        // the halo row holds a pair with R2 > 0
+  __shared__ uint32_t wave_max[kPadWaves];       // largest R2 of the rows a wave loaded
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int slot = blockIdx.z, stream = a.group_base + slot;
+  const int x0 = blockIdx.x * kDilW, y0 = blockIdx.y * kDilH;
+  const int W = a.width, H = a.height;
+  const float* zs = a.zsurface + (size_t)slot * ((size_t)H * W);
+  const uint16_t* ss = a.slots + (size_t)slot * ((size_t)H * W);
+  const float focal = a.focal[stream];
+
+  // 1. the halo tile
+  uint32_t mine = 0;
+  for (int row = wave; row < kPadH; row += kPadWaves) {
+    const int y = y0 - kPadR + row;
+    bool spreads = false;
+    for (int c0 = 0; c0 < kPadW; c0 += 64) {
+      const int c = c0 + lane, x = x0 - kPadR + c;
+      float z = __uint_as_float(0x7fc00000u);
+      uint32_t r2 = 0;
+      if (c < kPadW && y >= 0 && y < H && x >= 0 && x < W) {
+        const size_t o = (size_t)y * W + x;
+        z = zs[o];
+        const uint32_t s = ss[o];
+        if (s) r2 = link_padding_reach2(z, a.slot_pad[s], focal, a.sc_num, a.sc_off);
+      }
+      if (c < kPadW) halo[row * kPadW + c] = make_uint2(__float_as_uint(z), r2);
+      spreads = spreads || __ballot(r2 != 0) != 0;
+      mine = max(mine, r2);
+    }
+    if (lane == 0) row_spreads[row] = spreads ? 1u : 0u;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine = max(mine, (uint32_t)__shfl_xor((int)mine, o));
+  if (lane == 0) wave_max[wave] = mine;
+  __syncthreads();
+  uint32_t max_r2 = 0;
+#pragma unroll
+  for (int w = 0; w < kPadWaves; w++) max_r2 = max(max_r2, wave_max[w]);
+  int m = 0;
+  while ((uint32_t)((m + 1) * (m + 1)) <= max_r2) m++;      // (at most kPadR trips: R2 <= kPadR^2)
+
+  // 2. gather: tile pixel (lane, ry0 + i) is halo pair (lane + kPadR, ry0 + i + kPadR)
+  const int ry0 = wave * kPadRowsPerWave;
+  float zmin[kPadRowsPerWave];
+#pragma unroll
+  for (int i = 0; i < kPadRowsPerWave; i++) zmin[i] = __uint_as_float(halo[(ry0 + i + kPadR) * kPadW + lane + kPadR].x);
+  if (m > 0) {
+    for (int sy = ry0 + kPadR - m; sy <= ry0 + kPadRowsPerWave - 1 + kPadR + m; sy++) {
+      if (!row_spreads[sy]) continue;
+      const uint2* src = halo + sy * kPadW + lane + kPadR;
+      const int dy0 = sy - (ry0 + kPadR);          // to the strip's first row; row i: dy0 - i
+      for (int dx = -m; dx <= m; dx++) {
+        const uint2 v = src[dx];
+        if (v.y) {
+          const float z = __uint_as_float(v.x);
+          const int dx2 = dx * dx;
+#pragma unroll
+          for (int i = 0; i < kPadRowsPerWave; i++)
+            if ((uint32_t)(dx2 + (dy0 - i) * (dy0 - i)) <= v.y) zmin[i] = fminf(zmin[i], z);
+        }
+      }
+    }
+  }
+
+  // 3. the minima, as a [kDilH][kDilW] tile
+  __syncthreads();                                 // (every wave is done with the halo)
+  float* zout = reinterpret_cast<float*>(halo);
+#pragma unroll
+  for (int i = 0; i < kPadRowsPerWave; i++) zout[(ry0 + i) * kDilW + lane] = zmin[i];
+  __syncthreads();
+  const int lx = (tid & 15) * 4, ly = (tid >> 4) * 2;
+  float4 zd[2];
+  zd[0] = *reinterpret_cast<const float4*>(zout + ly * kDilW + lx);
+  zd[1] = *reinterpret_cast<const float4*>(zout + (ly + 1) * kDilW + lx);
+
+  // 4. shade exactly as compare_kernel does, with the reaching z in place of the pixel's own
+  shade_window_tile<U16, BITS>(a, zd, stream, x0, y0);
 }
 
 // A batch's counters (one block per launch group) go to pinned host memory with plain stores from a tiny kernel, one
@@ -3217,6 +3340,15 @@ void launch_dilate_compare(const DilateArgs& a, hipStream_t st)
     else hipLaunchKernelGGL((dilate_compare_kernel<false, true>), grid, dim3(kDilThreads), lds, st, a);
   } else if (a.io_u16) hipLaunchKernelGGL((dilate_compare_kernel<true, false>), grid, dim3(kDilThreads), lds, st, a);
   else hipLaunchKernelGGL((dilate_compare_kernel<false, false>), grid, dim3(kDilThreads), lds, st, a);
+}
+void launch_pad_compare(const PadArgs& a, hipStream_t st)
+{
+  const dim3 grid((unsigned)((a.width + kDilW - 1) / kDilW), (unsigned)((a.height + kDilH - 1) / kDilH), (unsigned)a.group_size);
+  if (a.bits) {
+    if (a.io_u16) hipLaunchKernelGGL((pad_compare_kernel<true, true>), grid, dim3(kDilThreads), 0, st, a);
+    else hipLaunchKernelGGL((pad_compare_kernel<false, true>), grid, dim3(kDilThreads), 0, st, a);
+  } else if (a.io_u16) hipLaunchKernelGGL((pad_compare_kernel<true, false>), grid, dim3(kDilThreads), 0, st, a);
+  else hipLaunchKernelGGL((pad_compare_kernel<false, false>), grid, dim3(kDilThreads), 0, st, a);
 }
 
 // ---- filtered point clouds (include/rtuf.h, FILTERED POINT CLOUDS) ------------------------------------------------------

@@ -2,7 +2,8 @@
 // shares: the 24-bit depth and its bit-pattern forms, the depth keys' encoding of a near fragment's float z, the set-up's
 // 32-bit edge constants, the key format's host-side rules, the compare threshold's constants, division core and the rule
 // that admits that core, the pixel classes of the link residual tables, the point of a filtered point cloud, the sphere centres and
-// point-to-sphere clearances of the link clearance tables, and the set-up kernel's packed list counters.
+// point-to-sphere clearances of the link clearance tables, the reach of a padded link's pixel, and the set-up kernel's packed
+// list counters.
 //
 // Included by the kernels (rtuf_kernels.hip, device and host pass), the host API (rtuf_api.cpp), scripts/fdiv_check.hip (which
 // holds div_core against the IEEE division on the GPU) and the CPU checks (tests/fast_class_check.cpp, tests/near_key_check.cpp:
@@ -34,6 +35,7 @@ namespace rtuf {
 inline float __fmul_rn(float a, float b) { return a * b; }
 inline float __fadd_rn(float a, float b) { return a + b; }
 inline float __fsub_rn(float a, float b) { return a - b; }
+inline float __fdiv_rn(float a, float b) { return a / b; }
 inline int __float2int_rn(float x)      // (round half to even: the default rounding mode; saturating, NaN -> 0: v_cvt_i32_f32)
 {
   if (!(x == x)) return 0;
@@ -241,6 +243,25 @@ RTUF_NUMERIC_HD uint32_t clearance_order_bits(float c)
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 RTUF_NUMERIC_HD uint32_t clearance_bits_of_order(uint32_t o) { return (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o; }
+
+// ---------------------------------------------------------------------------------------
+// link padding (include/rtuf.h, LINK PADDING): how far a drawn pixel of a padded link spreads its depth
+// ---------------------------------------------------------------------------------------
+
+// The squared reach, in pixels, of a source pixel with window z `z` whose link has `pad` metres of padding, seen through a
+// focal length of f pixels: d = num / (z - off) is the shader's to_linear_depth (IEEE division, as shade_threshold's),
+// rho = min((pad * f) / d, 16) the projected radius of a ball of `pad` metres at that depth, and the result rho * rho
+// truncated -- every operation a single float operation on its own.  The clamp at kMaxLinkPaddingPx = 16 pixels is part of
+// the definition: a 2 cm margin reaches it at d = f / 800.  0 where nothing was drawn (NaN) or the pad is 0 (the background's
+// slot included).  (tests/link_padding_check.cpp against a numpy form, bit for bit.)
+constexpr int kMaxLinkPaddingPx = 16;
+RTUF_NUMERIC uint32_t link_padding_reach2(float z, float pad, float f, float num, float off)
+{
+  if (!(z == z) || !(pad > 0.0f)) return 0u;
+  const float d = __fdiv_rn(num, __fsub_rn(z, off));
+  const float rho = fminf(__fdiv_rn(__fmul_rn(pad, f), d), (float)kMaxLinkPaddingPx);
+  return (uint32_t)__fmul_rn(rho, rho);
+}
 
 // ---------------------------------------------------------------------------------------
 // set-up kernel: the list counters of a work item (tests/setup_lists_check.cpp)

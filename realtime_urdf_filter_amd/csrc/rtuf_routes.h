@@ -16,7 +16,8 @@ enum class BatchKind { Filter, Bits, Render, Residual, Cloud, Clearance };
 
 // What the tile kernel leaves behind for every pixel:
 //   Planes    masked depth plane + optional byte mask, compared in the kernel (the fused route)        tile_kernel & co.
-//   ZSurface  the winners' window z, for compare_kernel or dilate_compare_kernel behind it            tile_kernel<true>, tile_labels_kernel<true>
+//   ZSurface  the winners' window z, for compare_kernel, dilate_compare_kernel or pad_compare_kernel  tile_kernel<true>, tile_labels_kernel<true>
+//             behind it (link padding: with `labels`, the plane then holds the winners' link slots)
 //   Bits      one mask bit per pixel                                                                  tile_bits_kernel, tile_thresh_kernel
 //   Render    the virtual depth plane, no sensor plane read                                           tile_render_kernel
 //   Residual  no plane: per-label sums in a table                                                     tile_resid_kernel
@@ -51,12 +52,13 @@ constexpr int tile_variant_index(TileVariant v)
 
 // What runs behind the tile kernel on the launch group's lane: first the kernel that makes the outputs from the z-surface
 // (Post), then the kernels that read the mask bits (Tail).
-enum class Post { None, Compare, Dilate };
+enum class Post { None, Compare, Dilate, Pad };
+constexpr int kPosts = 4;
 enum class Tail { None, Cloud, Clearance };
 
 struct Route { TileVariant tile; Post post; Tail tail; bool ok; };      // ok == false: a combination the API refuses
 constexpr bool runs_behind_tile(const Route& r) { return r.post != Post::None || r.tail != Tail::None; }
-constexpr int route_index(const Route& r) { return tile_variant_index(r.tile) + kTileVariantSlots * ((int)r.post + 3 * (int)r.tail); }
+constexpr int route_index(const Route& r) { return tile_variant_index(r.tile) + kTileVariantSlots * ((int)r.post + kPosts * (int)r.tail); }
 
 // The facts a route follows from.
 struct RouteFacts {
@@ -67,12 +69,14 @@ struct RouteFacts {
   bool two_kernel;    // the context's RTUF_FLAG_TWO_KERNEL
   int dilation;       // the context's silhouette dilation radius
   bool cover;         // the cover pass is on
+  bool padded;        // link padding is in effect in the context (some model holds a non-zero padding); last: older brace lists leave it false
 };
 
 //   batch                                      tile output   modifiers              behind it
 //   Filter                                     Planes        labels, thresh, u16    -
 //   Filter, two-kernel flag                    ZSurface      labels                 Compare
 //   Filter / Bits / Cloud / Clearance, dilated ZSurface      -                      Dilate (then Cloud / Clearance)
+//   Filter / Bits / Cloud / Clearance, padded  ZSurface      labels (link slots)    Pad (then Cloud / Clearance)
 //   Bits                                       Bits          thresh, u16            -
 //   Render                                     Render        labels, u16            -
 //   Residual                                   Residual      thresh, u16            -
@@ -80,7 +84,9 @@ struct RouteFacts {
 //   Clearance                                  Bits          thresh, u16            Clearance
 // The two-kernel flag is for full planes: the mask-bits calls refuse it, the other kinds run as if it were not set.
 // Thresholds do not enter a render batch.  Refused: a label plane beside anything but a filter or render batch, or with
-// dilation; dilation with a render or residual batch; thresholds on the z-surface route.
+// dilation; dilation with a render or residual batch; thresholds on the z-surface route.  Link padding goes over the
+// z-surface whatever the two-kernel flag says, and the plane beside it belongs to the link slots: refused with a label plane,
+// a render or residual batch, dilation or thresholds.
 constexpr Route route_of(const RouteFacts& f)
 {
   const bool filter = f.kind == BatchKind::Filter, bits = f.kind == BatchKind::Bits;
@@ -88,7 +94,11 @@ constexpr Route route_of(const RouteFacts& f)
   const bool dilated = f.dilation > 0, two = f.two_kernel && filter, thresh = f.thresh && !render;
   bool ok = !(f.labels && !filter && !render) && !(dilated && (f.labels || render || residual)) && !(f.two_kernel && bits);
   Route r{};
-  if (dilated || two) {
+  if (f.padded) {
+    ok = ok && !f.labels && !render && !residual && !dilated && !f.thresh;
+    r.tile = TileVariant{TileOut::ZSurface, true, false, false, f.cover};
+    r.post = Post::Pad;
+  } else if (dilated || two) {
     ok = ok && !thresh;
     r.tile = TileVariant{TileOut::ZSurface, f.labels, false, false, f.cover};
     r.post = dilated ? Post::Dilate : Post::Compare;

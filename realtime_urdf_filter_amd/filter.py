@@ -101,6 +101,7 @@ class URDFRenderer:
         self.renderables_ = []
         self.link_names_ = []                     # every link of the URDF, ignored ones included
         self.link_thresholds_ = {}                # URDF link name -> depth threshold of its own (RealtimeURDFFilter.loadModels)
+        self.link_padding_ = {}                   # URDF link name -> padding in metres (RealtimeURDFFilter.loadModels)
         self.initURDFModel()
 
     def initURDFModel(self):
@@ -173,7 +174,8 @@ class FilterParameters:
         self.fixed_frame = fixed_frame
         self.camera_frame = camera_frame
         self.models = models                 # list of dicts: model, tf_prefix, geometry_type, [scale], [ignore],
-        #                                      [link_depth_distance_thresholds: [{"link": URDF link name, "threshold": metres}]]
+        #                                      [link_depth_distance_thresholds: [{"link": URDF link name, "threshold": metres,
+        #                                        "padding": metres}]] (either value or both: include/rtuf.h, LINK PADDING)
         self.depth_distance_threshold = float(depth_distance_threshold)
         self.camera_offset_translation = tuple(camera_offset_translation)
         self.camera_offset_rotation = tuple(camera_offset_rotation)     # x y z w
@@ -226,6 +228,7 @@ class RealtimeURDFFilter:
         self._ctx = None
         self.link_spheres_ = {}                     # setLinkSpheres: {model: (link, xyzr)}, kept across contexts
         self._spheres_given_ = False                # the context holds link_spheres_ (cleared by initGL and setLinkSpheres)
+        self._padded_ = False                       # some model entry gave a link a "padding" (initGL)
         self._model_ids = []
         self._batch_masked = None
         self._batch_mask = None
@@ -258,12 +261,17 @@ class RealtimeURDFFilter:
                                                 self.tf_, elem.get("geometry_type", ""), elem.get("scale", 1.0),
                                                 ignore, self.mesh_loader))
             # new, beyond the reference: per-link depth thresholds [{"link": <URDF link name>, "threshold": <metres>}, ...]
+            # and, beside or instead of "threshold", a link's "padding": <metres> (include/rtuf.h, LINK PADDING)
             rd = self.renderers_[-1]
             rd.link_thresholds_ = {}
+            rd.link_padding_ = {}
             for e in elem.get("link_depth_distance_thresholds", []) or []:
                 if e["link"] not in rd.link_names_:
                     raise ValueError("link_depth_distance_thresholds of model %r: no link %r in its URDF" % (description_param, e["link"]))
-                rd.link_thresholds_[e["link"]] = float(e["threshold"])
+                if "padding" in e:
+                    rd.link_padding_[e["link"]] = float(e["padding"])
+                if "threshold" in e or "padding" not in e:
+                    rd.link_thresholds_[e["link"]] = float(e["threshold"])
 
     def initGL(self):
         """src/urdf_filter.cpp:386-436 without GL: create the device context for width_ x height_,
@@ -278,6 +286,7 @@ class RealtimeURDFFilter:
         if self._ctx is not None:
             self._ctx.close()
         self._cloud_intr_given_ = None              # (the new context has no cloud intrinsics: cloud() gives them again)
+        self._pad_intr_given_ = None
         self._spheres_given_ = False                # (... and no link spheres: clearance() gives them again)
         self._ctx = _capi.Context(self.width_, self.height_, self.max_streams, self.device, p)
         self.loadModels()
@@ -307,8 +316,27 @@ class RealtimeURDFFilter:
             if rd.link_thresholds_ and rd.renderables_:
                 self._ctx.set_link_thresholds(m, [rd.link_thresholds_.get(r.urdf_link, self.depth_distance_threshold_)
                                                   for r in rd.renderables_])
+        # link padding, in loadModels order: every renderable of a listed URDF link takes its margin, the model's other links none
+        self._padded_ = False
+        for rd, m in zip(self.renderers_, self._model_ids):
+            if rd.link_padding_ and rd.renderables_:
+                self._ctx.set_link_padding(m, [rd.link_padding_.get(r.urdf_link, 0.0) for r in rd.renderables_])
+                self._padded_ = True
         self.masked_depth_ = np.zeros((self.height_, self.width_), np.float32)
         self.mask_ = np.zeros((self.height_, self.width_), np.uint8)
+
+    def _give_padding_intrinsics(self, n):
+        """Link padding projects its margins with the streams' focal lengths: streams 0 .. n-1 get the intrinsics of the last
+        getProjectionMatrix() before a padded batch (initGL clears the record with every new context)."""
+        if not self._padded_:
+            return
+        intr = getattr(self, "cloud_intrinsics_", None)
+        if intr is None:
+            raise RuntimeError("link padding: no intrinsics yet (getProjectionMatrix sets them)")
+        if getattr(self, "_pad_intr_given_", None) != (intr, n):
+            self._ctx.set_cloud_intrinsics(0, [intr] * n)
+            self._pad_intr_given_ = (intr, n)
+            self._cloud_intr_given_ = intr
 
     # ---- camera --------------------------------------------------------------------------
     def getProjectionMatrix(self, info):
@@ -362,6 +390,7 @@ class RealtimeURDFFilter:
         except Exception as e:                      # noqa: BLE001 - ROS_ERROR + return (quirk Q6)
             log.error("%s", e)
             return
+        self._give_padding_intrinsics(1)
         depth = np.frombuffer(buffer, np.float32, width * height) if not isinstance(buffer, np.ndarray) else buffer
         d = np.asarray(depth, np.float32).reshape(1, height, width)
         if self.want_labels_:
@@ -533,6 +562,7 @@ class RealtimeURDFFilter:
             except Exception as e:                  # noqa: BLE001
                 log.error("stream %d: %s", s, e)
                 failed.append(s)
+        self._give_padding_intrinsics(n)
         masked, mask = self._ctx.filter_batch(depths, want_mask=want_mask)
         if self._batch_masked is None or self._batch_masked.shape != masked.shape:
             self._batch_masked = np.zeros_like(masked)

@@ -120,6 +120,7 @@ def build(tag):
     text("link residual tables on c3: residual batches beside the plain fused filter", ["README.md", "DESIGN.md 4"], "link_residuals_rate_c3.txt", "the last line")
     text("filtered point clouds on c3: cloud batches beside the mask-bits batch and beside filter + torch ops", ["README.md", "DESIGN.md 4"], "cloud_rate_c3.txt", "the last line")
     text("link clearance tables on c3: clearance batches beside the mask-bits batch and beside compacted cloud + torch ops", ["README.md", "DESIGN.md 4"], "clearance_rate_c3.txt", "the last line")
+    text("link padding on c3: padded mask-bits and cloud batches beside the dilated leg of the same run", ["README.md", "DESIGN.md 4"], "link_padding_rate_c3.txt", "the last line")
     f = "link_residuals_kernel_stats.txt"
     if os.path.exists(os.path.join(PROFILES, f)):
         v = {}
