@@ -16,7 +16,7 @@ from bench_support.labels_check import expected_labels
 from bench_support.labels_check import workload_draws as label_draws
 from bench_support.link_thresholds_check import workload_draws as thr_draws
 from bench_support.residuals_check import ROW, expected_table, tables_equal, u16_to_metres
-from bench_support.virtual_check import expected_virtual, metres_to_u16
+from bench_support.virtual_check import bits_equal_f32, expected_virtual, metres_to_u16
 from oracle import bindings as O
 from realtime_urdf_filter_amd import urdf
 from realtime_urdf_filter_amd.filter import CameraInfo, FilterParameters, RealtimeURDFFilter, depth_f32_to_u16, depth_u16_to_f32
@@ -352,6 +352,52 @@ def label_planes(sc, link_label=None):
 def virtual_planes(sc, empty=0.0, u16=False):
     v = expected_virtual(sc.zwin, sc.prim, sc.wl.near, sc.wl.far, empty)
     return metres_to_u16(v) if u16 else v
+
+
+# ---- every kind of batch on a scene with label planes (the fill-rule and the clipper tests) ---------------------------------------
+
+def filter_routes(g, ctx, n, what, two_kernel=False, check_labels=None):
+    """Every kind of batch of one context on the first n streams of g, each batch twice (the cover pass has made up its mind
+    by the second), every output against the oracle's: plain f32 (in a two-kernel context with the z-surface), 16UC1, mask
+    bits, labels, render_batch f32 and 16UC1 with labels, link_residuals_batch pixel counts.  g is an OracleScene whose
+    sensor is in whole millimetres, with mm ([n,H,W] uint16), labels, n_labels and zsurface set.  In a two-kernel context the
+    mask bits are left out (the API refuses them there); a labelled filter batch takes the z-surface + labels route and the
+    compare kernel there, render and residual batches run as in any context.  check_labels(label planes, what), if given,
+    sees the label planes of every labelled filter batch.  Returns the statistics of the second plain batch."""
+    for rep in range(2):
+        w = "%s %s batch %d" % (g.name, what, rep)
+        masked, mask = ctx.filter_batch(g.depth[:n])
+        same_planes(mask, g.mask[:n], w + ": mask")
+        assert bits_equal(masked, g.masked[:n]), w + ": masked depth"
+        if two_kernel:
+            assert bits_equal_f32(ctx.read_zsurface(n), g.zsurface[:n]), w + ": z surface"
+    stats = ctx.stats()
+    for rep in range(2):
+        w = "%s %s batch %d" % (g.name, what, rep)
+        masked, mask = ctx.filter_batch_u16(g.mm[:n])
+        same_planes(mask, g.mask[:n], w + ": 16UC1 mask")
+        same_planes(masked, depth_f32_to_u16(g.masked[:n]), w + ": 16UC1 masked depth")
+        if not two_kernel:
+            bits = np.zeros((n, ctx.mask_bits_words()), np.uint32)
+            ctx.filter_batch_bits_async(g.depth[:n], bits)
+            ctx.sync()
+            for s in range(n):
+                assert np.array_equal(bits[s], pack_bits(g.mask[s])), "%s: mask bits, stream %d" % (w, s)
+        masked, mask, lab = ctx.filter_batch_labels(g.depth[:n])
+        same_planes(lab, g.labels[:n], w + ": labels")
+        same_planes(mask, g.mask[:n], w + ": mask beside the labels")
+        assert bits_equal(masked, g.masked[:n]), w + ": masked depth beside the labels"
+        if check_labels is not None:
+            check_labels(np.asarray(lab), w)
+        for u16 in (False, True):
+            v, lab = ctx.render_batch(n, -1.5, labels=True, u16=u16)
+            same_planes(v, virtual_planes(g, -1.5, u16)[:n], w + ": virtual depth%s" % (" 16UC1" if u16 else ""))
+            same_planes(lab, g.labels[:n], w + ": rendered labels")
+        table = ctx.link_residuals_batch(g.depth[:n], g.n_labels)
+        for s in range(n):
+            want = np.bincount(g.labels[s].reshape(-1), minlength=g.n_labels)
+            assert np.array_equal(table[s]["pixels"], want), "%s: residual table pixels, stream %d: %s instead of %s" % (w, s, table[s]["pixels"], want)
+    return stats
 
 
 # ---- residual tables ------------------------------------------------------------------------------------------------------------

@@ -27,8 +27,7 @@ if __name__ == "__main__":
 
 import lattice_scenes as L
 import realtime_urdf_filter_amd as R
-from bench_support.virtual_check import bits_equal_f32
-from gpu_support import OracleScene, bits_equal, label_planes, pack_bits, same_planes, virtual_planes
+from gpu_support import OracleScene, filter_routes, label_planes
 from realtime_urdf_filter_amd.filter import depth_f32_to_u16, depth_u16_to_f32
 
 pytestmark = pytest.mark.gpu
@@ -65,44 +64,6 @@ def gscene(name, reverse=False):
     if (name, reverse) not in _scenes:
         _scenes[(name, reverse)] = build(name, reverse)
     return _scenes[(name, reverse)]
-
-
-def filter_routes(g, ctx, n, what, two_kernel=False):
-    """Every route of one context, each batch twice (the cover pass has made up its mind by the second); returns the
-    statistics of the second plain batch."""
-    for rep in range(2):
-        w = "%s %s batch %d" % (g.name, what, rep)
-        masked, mask = ctx.filter_batch(g.depth[:n])
-        same_planes(mask, g.mask[:n], w + ": mask")
-        assert bits_equal(masked, g.masked[:n]), w + ": masked depth"
-        if two_kernel:
-            assert bits_equal_f32(ctx.read_zsurface(n), g.zsurface[:n]), w + ": z surface"
-    stats = ctx.stats()
-    for rep in range(2):
-        w = "%s %s batch %d" % (g.name, what, rep)
-        masked, mask = ctx.filter_batch_u16(g.mm[:n])
-        same_planes(mask, g.mask[:n], w + ": 16UC1 mask")
-        same_planes(masked, depth_f32_to_u16(g.masked[:n]), w + ": 16UC1 masked depth")
-        if two_kernel:          # (the other kinds of batch take the fused kernels in such a context too: met below)
-            continue
-        bits = np.zeros((n, ctx.mask_bits_words()), np.uint32)
-        ctx.filter_batch_bits_async(g.depth[:n], bits)
-        ctx.sync()
-        for s in range(n):
-            assert np.array_equal(bits[s], pack_bits(g.mask[s])), "%s: mask bits, stream %d" % (w, s)
-        masked, mask, lab = ctx.filter_batch_labels(g.depth[:n])
-        same_planes(lab, g.labels[:n], w + ": labels")
-        same_planes(mask, g.mask[:n], w + ": mask beside the labels")
-        assert bits_equal(masked, g.masked[:n]), w + ": masked depth beside the labels"
-        for u16 in (False, True):
-            v, lab = ctx.render_batch(n, -1.5, labels=True, u16=u16)
-            same_planes(v, virtual_planes(g, -1.5, u16)[:n], w + ": virtual depth%s" % (" 16UC1" if u16 else ""))
-            same_planes(lab, g.labels[:n], w + ": rendered labels")
-        table = ctx.link_residuals_batch(g.depth[:n], g.n_labels)
-        for s in range(n):
-            want = np.bincount(g.labels[s].reshape(-1), minlength=g.n_labels)
-            assert np.array_equal(table[s]["pixels"], want), "%s: residual table pixels, stream %d: %s instead of %s" % (w, s, table[s]["pixels"], want)
-    return stats
 
 
 def path_checks(name, g, st, n):

@@ -43,6 +43,7 @@ def planes(sc, total=None, u16=False, labels=True):
     shape = (total or sc.n, sc.H, sc.W)
     v = torch.full(shape, 0x5a5a, dtype=torch.int16, device=dev) if u16 else torch.full(shape, SENTINEL, dtype=torch.float32, device=dev)
     lab = torch.full(shape, 0x5a5a, dtype=torch.int16, device=dev) if labels else None
+    torch.cuda.synchronize()          # the fills run on torch's stream, which the library's streams do not wait for: a late one would overwrite a batch's pixels
     return v, lab
 
 
