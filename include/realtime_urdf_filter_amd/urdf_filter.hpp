@@ -190,6 +190,10 @@ struct FilterParameters {
   // New, beyond the reference: also produce the link label plane (include/rtuf.h, LINK LABELS; getLabels(), linkLabels()).
   // Off by default: filter() then costs what it did.  Not together with silhouette_dilation_px > 0.
   bool link_labels = false;
+  // New, beyond the reference: scene planes (include/rtuf.h, SCENE PLANES).  scene_margin >= 0 (metres) enables scene filtering
+  // with the margins {scene_margin, scene_margin_rel in [0, 1)}; negative (the default): a scene can be learned and set, but
+  // filters nothing.
+  double scene_margin = -1.0, scene_margin_rel = 0.0;
 };
 
 // ---- urdf_filter.h --------------------------------------------------------------------------
@@ -303,6 +307,7 @@ class RealtimeURDFFilter {
     labels_.assign(want_labels_ ? (size_t)width_ * height_ : 0, 0);
     masked_depth_ = nullptr;
     mask_ = nullptr;
+    enable_scene();
   }
 
   // compute Projection matrix from CameraInfo message (src/urdf_filter.cpp:459-501)
@@ -452,6 +457,42 @@ class RealtimeURDFFilter {
     else check(rtuf_link_clearance_batch(ctx_, 1, reinterpret_cast<const float* const*>(&in), table_out, n_labels, max_distance));
     return true;
   }
+  // ---- scene planes (include/rtuf.h, SCENE PLANES) ----
+  // Lowers the scene plane to the readings of every pixel the robot filter keeps, for the camera and link poses filter_into
+  // would use: call it for a few frames of the empty cell while the robot moves, with link padding in the model entries so
+  // that the arm's halo is not learned.  Returns false when the camera transform is not available (nothing was learned).
+  bool learnScene(const void* depth, bool is_16uc1, double* glTf, int width, int height, double timestamp = 0.0)
+  {
+    prepare(width, height);
+    if (!depth) throw std::runtime_error("learnScene: needs depth");
+    if (renderers_.empty() || !stage_frame(glTf, timestamp)) return false;
+    const void* in = depth;
+    if (is_16uc1) check(rtuf_learn_scene_batch_u16(ctx_, 1, reinterpret_cast<const uint16_t* const*>(&in)));
+    else check(rtuf_learn_scene_batch(ctx_, 1, reinterpret_cast<const float* const*>(&in)));
+    return true;
+  }
+  // The scene plane: width x height floats in metres, +inf or NaN where unknown (a context of another size is replaced, as by
+  // filter()).
+  void setScene(const float* plane, int width, int height)
+  {
+    prepare(width, height);
+    check(rtuf_set_scene_planes(ctx_, 0, 1, &plane));
+  }
+  // false before the first frame (no context yet: nothing is written)
+  bool getScene(float* plane_out)
+  {
+    if (!ctx_) return false;
+    check(rtuf_get_scene_planes(ctx_, 0, 1, &plane_out));
+    return true;
+  }
+  // the plane back to unknown; the parameters' margins stay in force for the next scene
+  void clearScene()
+  {
+    if (!ctx_) return;
+    check(rtuf_clear_scene(ctx_, 0, 1));
+    enable_scene();
+  }
+
   // rows a link_residuals_into table needs: one more than the largest label in effect (0 before the models are loaded)
   int numLinkResidualRows() const
   {
@@ -659,6 +700,14 @@ class RealtimeURDFFilter {
     }
   }
   double applied_threshold_ = 0.0;                   // the global threshold apply_link_thresholds last used
+  // scene filtering with the parameters' margins (a new context's plane is all unknown: nothing is filtered until a scene is
+  // learned or set)
+  void enable_scene()
+  {
+    if (params_.scene_margin < 0.0) return;
+    const float abs_rel[2] = {(float)params_.scene_margin, (float)params_.scene_margin_rel};
+    check(rtuf_set_scene_margins(ctx_, 0, 1, abs_rel));
+  }
   // the context gets the intrinsics of the last getProjectionMatrix, when it has not got them yet
   void send_cloud_intrinsics()
   {

@@ -625,6 +625,63 @@ int rtuf_link_clearance_batch_u16(rtuf_context *ctx, int n_streams, const uint16
 int rtuf_set_link_padding(rtuf_context *ctx, int model, const float *padding_m, int n_links);
 int rtuf_clear_link_padding(rtuf_context *ctx, int model);
 
+/* SCENE PLANES.  New, beyond the reference: also filter the static scene -- the pedestal, the table, the fence, the floor --
+ * from a per-stream depth plane of the empty cell, which can be set or LEARNED from the camera's own frames while the robot
+ * moves in front of it.  With a scene in effect a link clearance table measures the distance from the robot to an intruder, not
+ * to the table, and a filtered point cloud holds only what is new in the cell.  ("Background" already names the far-plane quad
+ * here; this is the scene.)
+ * Per stream the context holds one float plane scene[H][W] in metres, whatever the element type of the batches; every pixel
+ * is +inf until it is set or learned, and +inf and NaN mean "unknown".  It also holds two margins, abs_m >= 0 and rel in
+ * [0, 1), and a switch.  Definition (every float operation single precision and rounded on its own), per pixel p:
+ *   thr(p)            = scene(p) - (abs_m + rel * scene(p))
+ *   scene_filtered(p) = s(p) > thr(p)         s: the sensor value in metres (16UC1: float(u) * 0.001f, as everywhere)
+ * The comparison is strict and ordered: a NaN sensor value is never scene-filtered, and an unknown scene pixel never filters
+ * anything (thr is NaN for every legal margin; nothing is special-cased).  For a stream whose scene filtering is
+ * enabled
+ *   filtered(p) = the robot filter's verdict (exactly today's, with dilation, thresholds and padding as configured)
+ *                 OR scene_filtered(p)
+ *   masked(p)   = filtered(p) ? filter_replace_value : sensor(p)     (16UC1: the value the robot filter writes there)
+ * in every filter batch (device, host-plane, asynchronous, f32 and 16UC1, with or without a byte mask or a label plane),
+ * mask-bits batch, cloud batch and clearance batch; mask byte 255 and mask bit 1 mean filtered, as ever.  Label planes are
+ * untouched (a scene-filtered pixel no link won keeps label 0); render and residual batches compare nothing against the
+ * scene.  Nothing is refused because of a scene: labels, RTUF_FLAG_TWO_KERNEL, dilation, thresholds and padding keep working.
+ * A masked plane that aliases the sensor plane stays legal wherever it is today.
+ *   rtuf_set_scene_planes / _device   set the planes of streams first_stream .. first_stream + n_streams - 1 from n_streams
+ *                                     host pointers / one packed device array [n_streams][H][W]; any float value is accepted
+ *   rtuf_get_scene_planes / _device   read them back (+inf everywhere for a context that never held a scene)
+ *   rtuf_set_scene_margins            abs_rel = [n_streams][2] {abs_m, rel}: sets the margins and ENABLES scene filtering for
+ *                                     those streams; NULL disables it for them and keeps their planes and margins
+ *   rtuf_clear_scene                  disables filtering, resets the planes to +inf and the margins to 0
+ *   rtuf_learn_scene_batch*           streams 0 .. n_streams - 1: for every pixel the ROBOT filter keeps (its bits honour
+ *                                     dilation, thresholds and padding, never the scene) and whose reading carries a point
+ *                                     (positive and finite), scene = min(scene, s); a NaN scene value counts as unknown and is
+ *                                     replaced.  Every other pixel is left alone; no output plane is written.  Learn with link
+ *                                     padding on, so that the arm's halo is not learned.  A running minimum of input values:
+ *                                     idempotent, and independent of the frames' order.
+ * The setters wait for the batches in flight and take effect with the next batch enqueued, like rtuf_set_link_padding.  The
+ * learn calls are a calibration phase, not the hot path: they are synchronous -- they wait for the batches in flight, run a
+ * mask-bits batch into a buffer of the context, let the host retire it INCLUDING its re-run after a bin overflow, and only
+ * then update the planes, so provisional bits never reach them.  They inherit the mask-bits calls' conditions (a width that
+ * is a multiple of 4, the background quad covers the image, RTUF_FLAG_TWO_KERNEL refused) and report them the same way.
+ * A stream range outside 0 .. max_streams, a NULL plane or array, a negative, NaN or infinite margin or rel >= 1 fail with
+ * RTUF_ERR_INVALID and change nothing; a context that is not finalized fails with RTUF_ERR_STATE.  The planes (max_streams *
+ * H * W * 4 bytes), the streams' table and learning's scratch are allocated by the first call that needs them and counted in
+ * rtuf_stats.device_bytes.
+ * A scene is IN EFFECT in the context while some stream has filtering enabled: then every batch of the kinds above runs one
+ * more streaming kernel per launch group (scene_apply_planes_kernel or scene_apply_bits_kernel), which
+ * skips the streams that have it disabled.  While none has -- and after rtuf_clear_scene cleared the last stream that was ever
+ * touched, when the memory is returned too -- nothing differs from a context that never used a scene. */
+int rtuf_set_scene_planes(rtuf_context *ctx, int first_stream, int n_streams, const float *const *planes);
+int rtuf_set_scene_planes_device(rtuf_context *ctx, int first_stream, int n_streams, const float *d_planes);
+int rtuf_get_scene_planes(rtuf_context *ctx, int first_stream, int n_streams, float *const *out);
+int rtuf_get_scene_planes_device(rtuf_context *ctx, int first_stream, int n_streams, float *d_out);
+int rtuf_set_scene_margins(rtuf_context *ctx, int first_stream, int n_streams, const float *abs_rel);
+int rtuf_clear_scene(rtuf_context *ctx, int first_stream, int n_streams);
+int rtuf_learn_scene_batch(rtuf_context *ctx, int n_streams, const float *const *depth_in);
+int rtuf_learn_scene_batch_u16(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in);
+int rtuf_learn_scene_batch_device(rtuf_context *ctx, int n_streams, const float *d_depth);
+int rtuf_learn_scene_batch_device_u16(rtuf_context *ctx, int n_streams, const uint16_t *d_depth);
+
 /* Counters of the last batch and kernel timings measured with HIP events on the context's
  * stream (replaces the wall-clock statistics of src/urdf_filter.cpp:239-266). */
 typedef struct {

@@ -41,6 +41,9 @@ SYMBOLS = [
     "rtuf_cloud_compact_batch_device_u16", "rtuf_cloud_batch", "rtuf_cloud_batch_u16", "rtuf_cloud_compact_batch", "rtuf_cloud_compact_batch_u16",
     "rtuf_set_link_spheres", "rtuf_link_clearance_batch_device", "rtuf_link_clearance_batch_device_u16", "rtuf_link_clearance_batch",
     "rtuf_link_clearance_batch_u16", "rtuf_set_link_padding", "rtuf_clear_link_padding",
+    "rtuf_set_scene_planes", "rtuf_set_scene_planes_device", "rtuf_get_scene_planes", "rtuf_get_scene_planes_device",
+    "rtuf_set_scene_margins", "rtuf_clear_scene", "rtuf_learn_scene_batch", "rtuf_learn_scene_batch_u16",
+    "rtuf_learn_scene_batch_device", "rtuf_learn_scene_batch_device_u16",
 ]
 
 # rtuf_link_residuals (include/rtuf.h, LINK RESIDUAL TABLES): one 64-byte row per (stream, label)
@@ -216,6 +219,16 @@ def load_library(path=None):
     lib.rtuf_clear_link_thresholds.argtypes = [vp, ci]
     lib.rtuf_set_link_padding.argtypes = [vp, ci, vp, ci]
     lib.rtuf_clear_link_padding.argtypes = [vp, ci]
+    lib.rtuf_set_scene_planes.argtypes = [vp, ci, ci, vp]
+    lib.rtuf_set_scene_planes_device.argtypes = [vp, ci, ci, vp]
+    lib.rtuf_get_scene_planes.argtypes = [vp, ci, ci, vp]
+    lib.rtuf_get_scene_planes_device.argtypes = [vp, ci, ci, vp]
+    lib.rtuf_set_scene_margins.argtypes = [vp, ci, ci, vp]
+    lib.rtuf_clear_scene.argtypes = [vp, ci, ci]
+    lib.rtuf_learn_scene_batch.argtypes = [vp, ci, vp]
+    lib.rtuf_learn_scene_batch_u16.argtypes = [vp, ci, vp]
+    lib.rtuf_learn_scene_batch_device.argtypes = [vp, ci, vp]
+    lib.rtuf_learn_scene_batch_device_u16.argtypes = [vp, ci, vp]
     if path is None:
         _lib = lib
     return lib
@@ -432,6 +445,62 @@ class Context:
     def clear_link_padding(self, model):
         """Model `model`'s links have no padding again."""
         self._check(self._lib.rtuf_clear_link_padding(self._h, model))
+
+    # scene planes (include/rtuf.h, SCENE PLANES)
+    def set_scene_planes(self, first_stream, planes):
+        """The scene planes of streams first_stream ..: [n,H,W] float32 metres (any value; +inf and NaN mean unknown)."""
+        a = np.ascontiguousarray(planes, np.float32).reshape(-1, self.height, self.width)
+        PP = ctypes.c_void_p * max(len(a), 1)
+        pin = PP(*[a[i].ctypes.data for i in range(len(a))])
+        self._check(self._lib.rtuf_set_scene_planes(self._h, first_stream, len(a), pin))
+
+    def set_scene_planes_device(self, first_stream, n, d_planes):
+        """Device pointer (int): [n,H,W] float32, packed."""
+        self._check(self._lib.rtuf_set_scene_planes_device(self._h, first_stream, n, ctypes.c_void_p(d_planes) if d_planes else None))
+
+    def get_scene_planes(self, first_stream=0, n=None):
+        """-> [n,H,W] float32: the scene planes of streams first_stream .. (all of them by default)."""
+        n = self.max_streams - first_stream if n is None else n
+        out = np.empty((max(n, 0), self.height, self.width), np.float32)
+        PP = ctypes.c_void_p * max(n, 1)
+        pout = PP(*[out[i].ctypes.data for i in range(max(n, 0))])
+        self._check(self._lib.rtuf_get_scene_planes(self._h, first_stream, n, pout))
+        return out
+
+    def get_scene_planes_device(self, first_stream, n, d_out):
+        self._check(self._lib.rtuf_get_scene_planes_device(self._h, first_stream, n, ctypes.c_void_p(d_out) if d_out else None))
+
+    def set_scene_margins(self, first_stream, abs_rel, n=None):
+        """abs_rel: [n,2] (or one row of 2) floats {abs_m >= 0, 0 <= rel < 1}: sets the margins and enables scene filtering for
+        streams first_stream ..; abs_rel=None disables it for n streams and keeps their planes."""
+        if abs_rel is None:
+            self._check(self._lib.rtuf_set_scene_margins(self._h, first_stream, self.max_streams - first_stream if n is None else n, None))
+            return
+        a = np.ascontiguousarray(abs_rel, np.float32).reshape(-1, 2)
+        self._check(self._lib.rtuf_set_scene_margins(self._h, first_stream, len(a), _ptr(a)))
+
+    def clear_scene(self, first_stream=0, n=None):
+        """Streams first_stream .. (all by default): filtering off, planes back to +inf, margins back to 0."""
+        self._check(self._lib.rtuf_clear_scene(self._h, first_stream, self.max_streams - first_stream if n is None else n))
+
+    def learn_scene_batch(self, depth):
+        """Lowers the scene planes of streams 0 .. n-1 to the readings of every pixel the robot filter keeps: depth [n,H,W]
+        float32 metres (or uint16 millimetres: the 16UC1 form).  Synchronous."""
+        u16 = np.asarray(depth).dtype == np.uint16
+        d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32).reshape(-1, self.height, self.width)
+        n = d.shape[0]
+        PP = ctypes.c_void_p * max(n, 1)
+        din = PP(*[d[i].ctypes.data for i in range(n)])
+        fn = self._lib.rtuf_learn_scene_batch_u16 if u16 else self._lib.rtuf_learn_scene_batch
+        self._check(fn(self._h, n, din))
+
+    def learn_scene_batch_u16(self, depth_mm):
+        self.learn_scene_batch(np.ascontiguousarray(depth_mm, np.uint16))
+
+    def learn_scene_batch_device(self, n, d_depth, u16=False):
+        """Device pointer (int): d_depth [n,H,W] float32 (uint16 with u16).  Synchronous."""
+        fn = self._lib.rtuf_learn_scene_batch_device_u16 if u16 else self._lib.rtuf_learn_scene_batch_device
+        self._check(fn(self._h, n, ctypes.c_void_p(d_depth) if d_depth else None))
 
     # virtual depth (include/rtuf.h, VIRTUAL DEPTH)
     def render_batch(self, n, empty_value=0.0, labels=False, u16=False):

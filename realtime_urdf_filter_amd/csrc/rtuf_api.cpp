@@ -71,6 +71,7 @@ struct HostModel { std::vector<HostLink> links; int link_base = 0; Kinematics ki
 struct BatchRequest {
   using Kind = BatchKind;
   Kind kind; int n; bool u16;               // (u16: the sensor / masked / virtual planes are 16UC1)
+  bool robot_only = false;                  // rtuf_learn_scene_batch*'s mask-bits batch: the robot's bits alone, whatever scene is in effect
   bool wait_upload = false;                 // host planes: the lanes wait for the slot's `uploaded` event before the first kernel that reads them
   const float* depth = nullptr;             // sensor planes (every kind but Render)
   float* masked = nullptr; uint8_t* mask = nullptr;      // Filter (mask may be nullptr)
@@ -151,6 +152,18 @@ struct rtuf_context {
   std::vector<uint32_t> clr_slot_label;
   ClearanceSphere* d_clr_spheres = nullptr; uint32_t* d_clr_slot_label = nullptr;
   bool clr_dirty = true;
+  // Scene planes (include/rtuf.h, SCENE PLANES): one float plane per stream, [max_streams][H][W], +inf until set or learned, and
+  // the streams' margins and switches (scene_streams: the host's copy), allocated by the first scene call that needs them and
+  // rewritten in place after that (captured graphs keep their addresses).  The scene kernels run only while scene_enabled > 0
+  // (streams with filtering enabled).  scene_touched: streams whose plane, margins or switch may differ from a fresh
+  // context's; when rtuf_clear_scene clears the last of them everything here is returned.  d_scene_bits / d_scene_stage:
+  // learning's scratch -- the robot's mask bits of a learn call, [max_streams] bits planes, and the sensor planes of a
+  // host-plane learn call, [max_streams][H][W] floats.
+  float* d_scene = nullptr; SceneStream* d_scene_streams = nullptr;
+  std::vector<SceneStream> scene_streams;
+  std::vector<uint8_t> scene_touched;
+  int scene_enabled = 0;
+  uint32_t* d_scene_bits = nullptr; float* d_scene_stage = nullptr;
 
   // per-frame pose staging
   // Cameras and link matrices are staged in a ring of kMaxInflight + 1 pinned sets, like the joint positions: every
@@ -730,6 +743,7 @@ void rtuf_destroy(rtuf_context* c)
   dev_free(c, c->d_order_thr);
   dev_free(c, c->d_cloud_intr);
   dev_free(c, c->d_clr_spheres); dev_free(c, c->d_clr_slot_label);
+  dev_free(c, c->d_scene); dev_free(c, c->d_scene_streams); dev_free(c, c->d_scene_bits); dev_free(c, c->d_scene_stage);
   for (auto& b : c->batch) {
     for (hipEvent_t ev : b.events) hipEventDestroy(ev);
     for (hipEvent_t ev : b.done) if (ev) hipEventDestroy(ev);
@@ -1432,8 +1446,8 @@ static hipEvent_t get_event(rtuf_context::Batch& b, size_t i)
 struct BatchPlan {
   std::vector<FkArgs> fks;
   PoseArgs pa{};
-  // (ca, da, pd, cl, cr: filled and read where the route's post / tail has that kernel)
-  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; PadArgs pd{}; CloudArgs cl{}; ClearanceArgs cr{}; int lane = 0; };
+  // (ca, da, pd, sc, cl, cr: filled and read where the route's post / scene stage / tail has that kernel)
+  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; PadArgs pd{}; SceneArgs sc{}; CloudArgs cl{}; ClearanceArgs cr{}; int lane = 0; };
   std::vector<Group> groups;
   Route route{};                // the batch's (Batch::route): every group runs the same kernels
   uint64_t hash() const
@@ -1447,6 +1461,7 @@ struct BatchPlan {
       if (route.post == Post::Compare) mix(&g.ca, sizeof g.ca);
       if (route.post == Post::Dilate) mix(&g.da, sizeof g.da);
       if (route.post == Post::Pad) mix(&g.pd, sizeof g.pd);
+      if (route.scene) mix(&g.sc, sizeof g.sc);
       if (route.tail == Tail::Cloud) mix(&g.cl, sizeof g.cl);
       if (route.tail == Tail::Clearance) mix(&g.cr, sizeof g.cr);
       mix(&g.lane, sizeof g.lane);
@@ -1529,6 +1544,7 @@ static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& 
     if (rt.post == Post::Compare) launch_compare(gr.ca, st);
     if (rt.post == Post::Dilate) launch_dilate_compare(gr.da, st);
     if (rt.post == Post::Pad) launch_pad_compare(gr.pd, st);
+    if (rt.scene) launch_scene_apply(gr.sc, st);      // the scene's verdict on top of the outputs or bits, before anything reads the bits
     if (rt.tail == Tail::Cloud) launch_cloud(gr.cl, st);
     if (rt.tail == Tail::Clearance) launch_clearance(gr.cr, st);
     if (b.timing && runs_behind_tile(rt)) mark(e0 + 4, st);
@@ -1565,7 +1581,8 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   // not ok has been refused by the call's checks: none gets here.)
   const Route route = rerun ? b.route
                             : route_of({r.kind, r.u16, r.labels != nullptr, c->thresh_models > 0, (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0,
-                                        (int)c->params.silhouette_dilation_px, c->cover_on, c->pad_models > 0});
+                                        (int)c->params.silhouette_dilation_px, c->cover_on, c->pad_models > 0,
+                                        c->scene_enabled > 0 && !r.robot_only});
   if (!route.ok) return c->fail(RTUF_ERR_STATE, "internal: no kernel route for a batch of kind %d (tile variant %d)", (int)r.kind, tile_variant_index(route.tile));
   if (!rerun) {
     b.route = route;
@@ -1661,7 +1678,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     plan.groups.emplace_back();
     BatchPlan::Group& gr = plan.groups.back();
     memset(&gr.sa, 0, sizeof gr.sa); memset(&gr.ta, 0, sizeof gr.ta); memset(&gr.ca, 0, sizeof gr.ca); memset(&gr.da, 0, sizeof gr.da); memset(&gr.pd, 0, sizeof gr.pd);
-    memset(&gr.cl, 0, sizeof gr.cl); memset(&gr.cr, 0, sizeof gr.cr);
+    memset(&gr.cl, 0, sizeof gr.cl); memset(&gr.cr, 0, sizeof gr.cr); memset(&gr.sc, 0, sizeof gr.sc);
     gr.lane = n_groups == 1 ? lane0 : g % c->n_lanes;
     const rtuf_context::Lane& ln = c->lane[gr.lane];
     Counters* const d_counters = b.d_counters + g;
@@ -1710,6 +1727,18 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
       da.group_base = base; da.group_size = gs; da.width = c->width; da.height = c->height; da.radius = b.dilation;
       da.max_diff = ta.max_diff; da.replace_value = ta.replace_value; da.sc_num = sc_num; da.sc_off = sc_off;
       da.io_u16 = io_u16 ? 1 : 0; da.fast_div = fast_div;
+    }
+    if (route.scene) {
+      SceneArgs& sc = gr.sc;
+      const bool planes_out = r.kind == Kind::Filter;
+      sc.depth = d_depth; sc.scene = c->d_scene; sc.streams = c->d_scene_streams;
+      sc.masked = planes_out ? d_masked : nullptr; sc.mask = planes_out ? d_mask : nullptr; sc.bits = planes_out ? nullptr : r.bits;
+      sc.group_base = base; sc.group_size = gs; sc.width = c->width; sc.height = c->height;
+      sc.replace_value = c->params.filter_replace_value; sc.io_u16 = io_u16 ? 1 : 0;
+      // 16-byte accesses: every stream's plane (the planes form) or row (the bits form) starts on a 16-byte boundary
+      const size_t per_lane = io_u16 ? 8u : 4u;
+      auto aligned = [](const void* q, uintptr_t to) { return (reinterpret_cast<uintptr_t>(q) & (to - 1u)) == 0u; };
+      sc.wide = aligned(d_depth, 16) && (planes_out ? plane % per_lane == 0 && aligned(d_masked, 16) && aligned(d_mask, 8) : (size_t)c->width % per_lane == 0) ? 1 : 0;
     }
     if (route.tail == Tail::Cloud) {
       CloudArgs& cl = gr.cl;
@@ -2663,6 +2692,231 @@ int rtuf_clear_link_padding(rtuf_context* c, int model)
   const int rc = build_pad_tables(c);
   if (rc != RTUF_OK) m.padding.swap(keep);
   return rc;
+}
+
+// ---- scene planes ---------------------------------------------------------------------------------------
+// include/rtuf.h, SCENE PLANES.  The planes, the streams' table and the scratch live in the context and keep their addresses
+// from the first call that needs them until the last touched stream is cleared; the batches find the scene through their
+// route (RouteFacts::scene: some stream has filtering enabled) and their SceneArgs.
+static int check_scene_range(rtuf_context* c, int first, int n)
+{
+  if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
+  if (first < 0 || n <= 0 || first > c->max_streams || n > c->max_streams - first)
+    return c->fail(RTUF_ERR_INVALID, "bad stream range [%d, %d) (max_streams = %d)", first, first + n, c->max_streams);
+  return RTUF_OK;
+}
+
+static int ensure_scene(rtuf_context* c)
+{
+  if (c->d_scene) return RTUF_OK;
+  hipSetDevice(c->device);
+  const size_t plane = (size_t)c->width * c->height;
+  c->scene_streams.assign((size_t)c->max_streams, SceneStream{0.0f, 0.0f, 0u, 0u});
+  c->scene_touched.assign((size_t)c->max_streams, 0);
+  c->scene_enabled = 0;
+  HIP_TRY(c, dev_alloc(c, &c->d_scene_streams, (size_t)c->max_streams * sizeof(SceneStream)));
+  HIP_TRY(c, dev_alloc(c, &c->d_scene, (size_t)c->max_streams * plane * sizeof(float)));
+  HIP_TRY(c, hipMemcpy(c->d_scene_streams, c->scene_streams.data(), (size_t)c->max_streams * sizeof(SceneStream), hipMemcpyHostToDevice));
+  launch_fill_f32(c->d_scene, (size_t)c->max_streams * plane, INFINITY, c->lane[0].stream);
+  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
+  return RTUF_OK;
+}
+
+// (no batch in flight reads the table: every caller waited for them)
+static int upload_scene_streams(rtuf_context* c)
+{
+  int on = 0;
+  for (const SceneStream& s : c->scene_streams) on += s.enabled ? 1 : 0;
+  HIP_TRY(c, hipMemcpy(c->d_scene_streams, c->scene_streams.data(), c->scene_streams.size() * sizeof(SceneStream), hipMemcpyHostToDevice));
+  c->scene_enabled = on;
+  return RTUF_OK;
+}
+
+int rtuf_set_scene_planes(rtuf_context* c, int first, int n, const float* const* planes)
+{
+  KIDS_ALL(c, rtuf_set_scene_planes(k, first, n, planes));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = check_scene_range(c, first, n); if (rc != RTUF_OK) return rc; }
+  if (!planes) return c->fail(RTUF_ERR_INVALID, "null plane array");
+  for (int s = 0; s < n; s++) if (!planes[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", first + s);
+  WAIT_IF_PENDING(c);
+  { const int rc = ensure_scene(c); if (rc != RTUF_OK) return rc; }
+  const size_t plane = (size_t)c->width * c->height;
+  const int rc = copy_planes(c, c->d_scene + (size_t)first * plane, reinterpret_cast<void* const*>(const_cast<float* const*>(planes)), n, plane * sizeof(float),
+                             hipMemcpyHostToDevice, nullptr);
+  if (rc == RTUF_OK) for (int s = 0; s < n; s++) c->scene_touched[(size_t)(first + s)] = 1;
+  return rc;
+}
+
+int rtuf_set_scene_planes_device(rtuf_context* c, int first, int n, const float* d_planes)
+{
+  KIDS_ALL(c, rtuf_set_scene_planes_device(k, first, n, d_planes));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = check_scene_range(c, first, n); if (rc != RTUF_OK) return rc; }
+  if (!d_planes) return c->fail(RTUF_ERR_INVALID, "null plane array");
+  WAIT_IF_PENDING(c);
+  { const int rc = ensure_scene(c); if (rc != RTUF_OK) return rc; }
+  const size_t plane = (size_t)c->width * c->height;
+  HIP_TRY(c, hipMemcpy(c->d_scene + (size_t)first * plane, d_planes, (size_t)n * plane * sizeof(float), hipMemcpyDeviceToDevice));
+  for (int s = 0; s < n; s++) c->scene_touched[(size_t)(first + s)] = 1;
+  return RTUF_OK;
+}
+
+int rtuf_get_scene_planes(rtuf_context* c, int first, int n, float* const* out)
+{
+  KIDS_ONE(c, 0, rtuf_get_scene_planes(k, first, n, out));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = check_scene_range(c, first, n); if (rc != RTUF_OK) return rc; }
+  if (!out) return c->fail(RTUF_ERR_INVALID, "null plane array");
+  for (int s = 0; s < n; s++) if (!out[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", first + s);
+  WAIT_IF_PENDING(c);
+  const size_t plane = (size_t)c->width * c->height;
+  if (!c->d_scene) {                     // never set, never learned: unknown everywhere
+    for (int s = 0; s < n; s++) std::fill(out[s], out[s] + plane, INFINITY);
+    return RTUF_OK;
+  }
+  hipSetDevice(c->device);
+  return copy_planes(c, c->d_scene + (size_t)first * plane, reinterpret_cast<void* const*>(out), n, plane * sizeof(float), hipMemcpyDeviceToHost, nullptr);
+}
+
+int rtuf_get_scene_planes_device(rtuf_context* c, int first, int n, float* d_out)
+{
+  KIDS_ONE(c, 0, rtuf_get_scene_planes_device(k, first, n, d_out));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = check_scene_range(c, first, n); if (rc != RTUF_OK) return rc; }
+  if (!d_out) return c->fail(RTUF_ERR_INVALID, "null plane array");
+  WAIT_IF_PENDING(c);
+  hipSetDevice(c->device);
+  const size_t plane = (size_t)c->width * c->height;
+  if (!c->d_scene) {
+    launch_fill_f32(d_out, (size_t)n * plane, INFINITY, c->lane[0].stream);
+    HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
+    return RTUF_OK;
+  }
+  HIP_TRY(c, hipMemcpy(d_out, c->d_scene + (size_t)first * plane, (size_t)n * plane * sizeof(float), hipMemcpyDeviceToDevice));
+  return RTUF_OK;
+}
+
+int rtuf_set_scene_margins(rtuf_context* c, int first, int n, const float* abs_rel)
+{
+  KIDS_ALL(c, rtuf_set_scene_margins(k, first, n, abs_rel));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = check_scene_range(c, first, n); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; abs_rel && s < n; s++) {
+    const float a = abs_rel[2 * s], r = abs_rel[2 * s + 1];
+    if (!(std::isfinite(a) && a >= 0.0f)) return c->fail(RTUF_ERR_INVALID, "stream %d: the scene margin must be finite and >= 0 (got %g)", first + s, (double)a);
+    if (!(r >= 0.0f && r < 1.0f)) return c->fail(RTUF_ERR_INVALID, "stream %d: the relative scene margin must lie in [0, 1) (got %g)", first + s, (double)r);
+  }
+  WAIT_IF_PENDING(c);
+  if (!abs_rel && !c->d_scene) return RTUF_OK;      // nothing was ever enabled
+  { const int rc = ensure_scene(c); if (rc != RTUF_OK) return rc; }
+  const std::vector<SceneStream> keep = c->scene_streams;
+  for (int s = 0; s < n; s++) {
+    SceneStream& ss = c->scene_streams[(size_t)(first + s)];
+    if (abs_rel) { ss.abs_m = abs_rel[2 * s]; ss.rel = abs_rel[2 * s + 1]; ss.enabled = 1u; c->scene_touched[(size_t)(first + s)] = 1; }
+    else ss.enabled = 0u;
+  }
+  const int rc = upload_scene_streams(c);
+  if (rc != RTUF_OK) c->scene_streams = keep;
+  return rc;
+}
+
+int rtuf_clear_scene(rtuf_context* c, int first, int n)
+{
+  KIDS_ALL(c, rtuf_clear_scene(k, first, n));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = check_scene_range(c, first, n); if (rc != RTUF_OK) return rc; }
+  WAIT_IF_PENDING(c);
+  if (!c->d_scene) return RTUF_OK;
+  hipSetDevice(c->device);
+  const size_t plane = (size_t)c->width * c->height;
+  for (int s = 0; s < n; s++) { c->scene_streams[(size_t)(first + s)] = SceneStream{0.0f, 0.0f, 0u, 0u}; c->scene_touched[(size_t)(first + s)] = 0; }
+  bool any = false;
+  for (uint8_t t : c->scene_touched) any = any || t != 0;
+  if (!any) {
+    // the last touched stream: as if the context had never held a scene
+    dev_free(c, c->d_scene); dev_free(c, c->d_scene_streams); dev_free(c, c->d_scene_bits); dev_free(c, c->d_scene_stage);
+    c->scene_streams.clear(); c->scene_touched.clear(); c->scene_enabled = 0;
+    return RTUF_OK;
+  }
+  launch_fill_f32(c->d_scene + (size_t)first * plane, (size_t)n * plane, INFINITY, c->lane[0].stream);
+  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
+  return upload_scene_streams(c);
+}
+
+// Learning.  The robot's bits come from a mask-bits batch like any other, but for its route (robot_only: never the scene) and
+// its output, the context's own buffer; rtuf_sync retires it, re-runs after an overflow included, before the planes are touched.
+static int learn_scene_device(rtuf_context* c, int n, const void* d_depth, bool u16)
+{
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  { const int rc = ensure_scene(c); if (rc != RTUF_OK) return rc; }
+  if (!c->d_scene_bits) HIP_TRY(c, dev_alloc(c, &c->d_scene_bits, (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
+  BatchRequest rq = bits_request(n, d_depth, c->d_scene_bits, u16);
+  rq.robot_only = true;
+  { const int rc = submit_device(c, rq); if (rc != RTUF_OK) return rc; }
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  SceneLearnArgs la;
+  la.depth = static_cast<const float*>(d_depth); la.bits = c->d_scene_bits; la.scene = c->d_scene;
+  la.n_streams = n; la.width = c->width; la.height = c->height; la.io_u16 = u16 ? 1 : 0;
+  launch_scene_learn(la, c->lane[0].stream);
+  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
+  HIP_TRY(c, hipGetLastError());
+  for (int s = 0; s < n; s++) c->scene_touched[(size_t)s] = 1;
+  return RTUF_OK;
+}
+
+// the other pipelines take the planes the first one learned (state is replicated)
+static int learn_scene_kids(rtuf_context* c, int n, int rc)
+{
+  if (rc < 0) { c->error = c->kids[0]->error; return rc; }
+  for (size_t i = 1; i < c->kids.size(); i++) {
+    const int rk = rtuf_set_scene_planes_device(c->kids[i], 0, n, c->kids[0]->d_scene);
+    if (rk < 0) { c->error = c->kids[i]->error; return rk; }
+  }
+  return rc;
+}
+
+static int learn_scene_host(rtuf_context* c, int n, const void* const* depth_in, bool u16)
+{
+  { const int rc = check_bits_call(c, n, depth_in, depth_in); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; s < n; s++) if (!depth_in[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  hipSetDevice(c->device);
+  const size_t plane = (size_t)c->width * c->height;
+  if (!c->d_scene_stage) HIP_TRY(c, dev_alloc(c, &c->d_scene_stage, (size_t)c->max_streams * plane * sizeof(float)));
+  { const int rc = copy_planes(c, c->d_scene_stage, const_cast<void* const*>(depth_in), n, plane * (u16 ? sizeof(uint16_t) : sizeof(float)), hipMemcpyHostToDevice, nullptr);
+    if (rc != RTUF_OK) return rc; }
+  return learn_scene_device(c, n, c->d_scene_stage, u16);
+}
+
+int rtuf_learn_scene_batch_device(rtuf_context* c, int n, const float* d_depth)
+{
+  if (c && !c->kids.empty()) return learn_scene_kids(c, n, rtuf_learn_scene_batch_device(c->kids[0], n, d_depth));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_bits_call(c, n, d_depth, d_depth);
+  return rc != RTUF_OK ? rc : learn_scene_device(c, n, d_depth, false);
+}
+
+int rtuf_learn_scene_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth)
+{
+  if (c && !c->kids.empty()) return learn_scene_kids(c, n, rtuf_learn_scene_batch_device_u16(c->kids[0], n, d_depth));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_bits_call(c, n, d_depth, d_depth);
+  return rc != RTUF_OK ? rc : learn_scene_device(c, n, d_depth, true);
+}
+
+int rtuf_learn_scene_batch(rtuf_context* c, int n, const float* const* depth_in)
+{
+  if (c && !c->kids.empty()) return learn_scene_kids(c, n, rtuf_learn_scene_batch(c->kids[0], n, depth_in));
+  if (!c) return RTUF_ERR_INVALID;
+  return learn_scene_host(c, n, reinterpret_cast<const void* const*>(depth_in), false);
+}
+
+int rtuf_learn_scene_batch_u16(rtuf_context* c, int n, const uint16_t* const* depth_in)
+{
+  if (c && !c->kids.empty()) return learn_scene_kids(c, n, rtuf_learn_scene_batch_u16(c->kids[0], n, depth_in));
+  if (!c) return RTUF_ERR_INVALID;
+  return learn_scene_host(c, n, reinterpret_cast<const void* const*>(depth_in), true);
 }
 
 // ---- virtual depth ---------------------------------------------------------------------------------

@@ -444,6 +444,29 @@ struct ClearanceArgs {
   int io_u16;
 };
 
+// Scene planes (include/rtuf.h, SCENE PLANES): per stream one float plane of the empty scene in metres, margins and a switch.
+// The scene kernels of one launch group run behind whatever wrote the group's outputs and in front of the kernels that read
+// its mask bits; streams are batch-absolute, and a stream whose filtering is disabled is skipped.
+struct alignas(16) SceneStream { float abs_m, rel; uint32_t enabled, reserved; };
+struct SceneArgs {
+  const float* depth;            // [n][H][W] sensor planes (f32 metres or, with io_u16, uint16 millimetres): the whole batch
+  const float* scene;            // [max_streams][H][W] the context's scene planes, float whatever the batch's element type
+  const SceneStream* streams;    // [max_streams]
+  float* masked;                 // Filter: [n][H][W], same element type as depth (may alias depth)
+  uint8_t* mask;                 // Filter: [n][H][W] or nullptr
+  uint32_t* bits;                // Bits / Cloud / Clearance: [n][H][ceil(W/32)], ORed into in place
+  int group_base, group_size;
+  int width, height;
+  float replace_value;
+  int io_u16;
+  int wide;                      // every plane of the group starts on a 16-byte boundary and W % 4 == 0 (16UC1: W % 8 == 0): 16-byte accesses
+};
+// Learning: scene = scene_learned(scene, sensor, robot's bit) for streams 0 .. n - 1 (rtuf_numerics.h); bits are final.
+struct SceneLearnArgs {
+  const float* depth; const uint32_t* bits; float* scene;
+  int n_streams, width, height, io_u16;
+};
+
 struct FkArgs {
   const int32_t* parent;        // [F]
   const int32_t* joint_type;    // [F]
@@ -479,6 +502,9 @@ void launch_dilate_compare(const DilateArgs& a, hipStream_t st);     // a.bits s
 void launch_pad_compare(const PadArgs& a, hipStream_t st);           // as launch_dilate_compare
 void launch_cloud(const CloudArgs& a, hipStream_t st);               // a.capacity selects the compacted form (count, scan, emit), a.io_u16 the 16UC1 variants
 void launch_clearance(const ClearanceArgs& a, hipStream_t st);       // spheres, zero, clearance, finish: the group's rows of the table, a.io_u16 selects the 16UC1 variant
+void launch_scene_apply(const SceneArgs& a, hipStream_t st);         // a.bits selects scene_apply_bits_kernel, else scene_apply_planes_kernel; a.io_u16 the 16UC1 variants
+void launch_scene_learn(const SceneLearnArgs& a, hipStream_t st);
+void launch_fill_f32(float* p, size_t n, float v, hipStream_t st);
 void launch_spin(unsigned long long ticks, hipStream_t st);      // a one-wave kernel that idles for `ticks` of the 100 MHz clock
 
 }  // namespace rtuf

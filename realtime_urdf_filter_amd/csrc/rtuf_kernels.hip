@@ -3723,4 +3723,171 @@ void launch_clearance(const ClearanceArgs& a, hipStream_t st)
   else hipLaunchKernelGGL(clearance_finish_kernel<false>, dim3(fblocks), dim3(kBlock), 0, st, a);
 }
 
+// ---- scene planes (include/rtuf.h, SCENE PLANES) --------------------------------------------------------------------------
+// Two streaming kernels that run behind whatever made a launch group's outputs: they read the sensor plane once more and the
+// stream's scene plane, and add the scene's verdict (scene_filtered, rtuf_numerics.h) to outputs that are already complete.
+// Neither needs to know why a pixel was filtered before: masked' = scene_filtered ? replace : masked and mask' =
+// scene_filtered ? 255 : mask touch filtered pixels only, so nothing of the outputs is read and a masked plane that aliases
+// the sensor plane stays legal (a pixel already replaced is rewritten with the same value or left alone).
+//
+// Shape: a lane takes one 16-byte load of sensor values -- 4 float pixels, 8 16UC1 pixels -- and the matching 16 or 32 bytes of
+// the scene plane.  Where all of its pixels are scene-filtered (the common case in a cell with a full scene model: writes are
+// dense) it stores 16 bytes of the replace value and 4 or 8 mask bytes in one instruction each; where none is, nothing; only
+// the lanes on an object's outline fall back to a store per pixel.  Planes that do not start on 16-byte boundaries (an odd
+// image size, a caller's offset pointer) take the one-pixel-per-lane instantiation.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2s __attribute__((ext_vector_type(2)));
+
+// the lane's N sensor values in metres and scene values, from pixel `pix` of the batch / `spix` of the scene planes
+template <bool U16, int N>
+__device__ __forceinline__ void scene_load(const SceneArgs& a, size_t pix, size_t spix, float (&s)[N], float (&sc)[N])
+{
+  if constexpr (N == 1) {
+    s[0] = U16 ? u16_to_metres(reinterpret_cast<const uint16_t*>(a.depth)[pix]) : a.depth[pix];
+    sc[0] = a.scene[spix];
+  } else {
+    const u32x4 q = *reinterpret_cast<const u32x4*>(U16 ? reinterpret_cast<const char*>(a.depth) + pix * 2u : reinterpret_cast<const char*>(a.depth) + pix * 4u);
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (U16) { s[2 * j] = u16_to_metres(w[j] & 0xffffu); s[2 * j + 1] = u16_to_metres(w[j] >> 16); }
+      else s[j] = __uint_as_float(w[j]);
+    }
+#pragma unroll
+    for (int k = 0; k < N / 4; k++) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(a.scene + spix + 4 * k);
+      sc[4 * k] = v.x; sc[4 * k + 1] = v.y; sc[4 * k + 2] = v.z; sc[4 * k + 3] = v.w;
+    }
+  }
+}
+
+// grid: (ceil(H * W / N / kBlock), group_size)
+template <bool U16, bool WIDE>
+__global__ __launch_bounds__(kBlock) void scene_apply_planes_kernel(SceneArgs a)
+{
+  constexpr int N = WIDE ? (U16 ? 8 : 4) : 1;
+  const int stream = a.group_base + (int)blockIdx.y;
+  const SceneStream ss = a.streams[stream];
+  if (!ss.enabled) return;
+  const size_t plane = (size_t)a.width * (size_t)a.height;
+  const size_t p0 = ((size_t)blockIdx.x * kBlock + threadIdx.x) * (size_t)N;
+  if (p0 >= plane) return;                       // (WIDE: N divides the plane)
+  const size_t pix = (size_t)stream * plane + p0;
+  float s[N], sc[N];
+  scene_load<U16, N>(a, pix, pix, s, sc);
+  uint32_t f = 0;
+#pragma unroll
+  for (int j = 0; j < N; j++) f |= (scene_filtered(s[j], sc[j], ss.abs_m, ss.rel) ? 1u : 0u) << j;
+  if (!f) return;
+  uint16_t* const out16 = reinterpret_cast<uint16_t*>(a.masked) + pix;
+  float* const out32 = a.masked + pix;
+  const uint32_t rep16 = U16 ? metres_to_u16(a.replace_value) : 0u;
+  if (WIDE && f == (1u << N) - 1u) {
+    u32x4 o;
+    o.x = o.y = o.z = o.w = U16 ? (rep16 | rep16 << 16) : __float_as_uint(a.replace_value);
+    __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(U16 ? (void*)out16 : (void*)out32));
+    if (a.mask) {
+      if (U16) { u32x2s m; m.x = m.y = 0xffffffffu; __builtin_nontemporal_store(m, reinterpret_cast<u32x2s*>(a.mask + pix)); }
+      else __builtin_nontemporal_store(0xffffffffu, reinterpret_cast<uint32_t*>(a.mask + pix));
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < N; j++) {
+    if (!((f >> j) & 1u)) continue;
+    if (U16) out16[j] = (uint16_t)rep16;
+    else out32[j] = a.replace_value;
+    if (a.mask) a.mask[pix + j] = 255;
+  }
+}
+
+// The mask-bits form: the lane's N verdicts go to its place in the row's bits word, the 32 / N lanes of a word OR theirs
+// together and the first of them ORs the result into the word in place (the only writer of that word; words that gain no bit
+// are not written).  grid: (ceil(H * ceil(W/32) * (32 / N) / kBlock), group_size); a word's lanes never straddle a wave.
+template <bool U16, bool WIDE>
+__global__ __launch_bounds__(kBlock) void scene_apply_bits_kernel(SceneArgs a)
+{
+  constexpr int N = WIDE ? (U16 ? 8 : 4) : 1;
+  constexpr uint32_t kLanesPerWord = 32u / (uint32_t)N;
+  const int stream = a.group_base + (int)blockIdx.y;
+  const SceneStream ss = a.streams[stream];
+  if (!ss.enabled) return;
+  const uint32_t row_words = (uint32_t)(a.width + 31) >> 5, row_lanes = row_words * kLanesPerWord;
+  const uint32_t t = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  const uint32_t v = t / row_lanes, q = t - v * row_lanes;
+  const int u = (int)(q * (uint32_t)N);
+  uint32_t f = 0;
+  if (v < (uint32_t)a.height && u < a.width) {        // (WIDE: N divides W, the lane's pixels are all inside or all outside)
+    const size_t spix = ((size_t)stream * a.height + (size_t)v) * (size_t)a.width + (size_t)u;
+    float s[N], sc[N];
+    scene_load<U16, N>(a, spix, spix, s, sc);
+#pragma unroll
+    for (int j = 0; j < N; j++) f |= (scene_filtered(s[j], sc[j], ss.abs_m, ss.rel) ? 1u : 0u) << j;
+  }
+  uint32_t word = f << ((q & (kLanesPerWord - 1u)) * (uint32_t)N);
+#pragma unroll
+  for (uint32_t o = 1; o < kLanesPerWord; o <<= 1) word |= (uint32_t)__shfl_xor((int)word, (int)o);
+  if ((q & (kLanesPerWord - 1u)) == 0u && word && v < (uint32_t)a.height) {
+    uint32_t* const p = a.bits + ((size_t)stream * a.height + (size_t)v) * (size_t)row_words + (size_t)(q / kLanesPerWord);
+    const uint32_t old = *p;
+    if ((old | word) != old) *p = old | word;
+  }
+}
+
+void launch_scene_apply(const SceneArgs& a, hipStream_t st)
+{
+  const int n = a.wide ? (a.io_u16 ? 8 : 4) : 1;
+  if (a.bits) {
+    const size_t lanes = (size_t)a.height * (size_t)((a.width + 31) >> 5) * (size_t)(32 / n);
+    const dim3 grid((unsigned)((lanes + kBlock - 1) / kBlock), (unsigned)a.group_size);
+    if (a.wide) {
+      if (a.io_u16) hipLaunchKernelGGL((scene_apply_bits_kernel<true, true>), grid, dim3(kBlock), 0, st, a);
+      else hipLaunchKernelGGL((scene_apply_bits_kernel<false, true>), grid, dim3(kBlock), 0, st, a);
+    } else if (a.io_u16) hipLaunchKernelGGL((scene_apply_bits_kernel<true, false>), grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((scene_apply_bits_kernel<false, false>), grid, dim3(kBlock), 0, st, a);
+    return;
+  }
+  const size_t lanes = ((size_t)a.width * (size_t)a.height + (size_t)n - 1) / (size_t)n;
+  const dim3 grid((unsigned)((lanes + kBlock - 1) / kBlock), (unsigned)a.group_size);
+  if (a.wide) {
+    if (a.io_u16) hipLaunchKernelGGL((scene_apply_planes_kernel<true, true>), grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((scene_apply_planes_kernel<false, true>), grid, dim3(kBlock), 0, st, a);
+  } else if (a.io_u16) hipLaunchKernelGGL((scene_apply_planes_kernel<true, false>), grid, dim3(kBlock), 0, st, a);
+  else hipLaunchKernelGGL((scene_apply_planes_kernel<false, false>), grid, dim3(kBlock), 0, st, a);
+}
+
+// Learning (rtuf_learn_scene_batch*): a pixel per lane, the calibration phase's kernel.  The bits are the robot's alone and
+// final (the mask-bits batch that made them has been retired, re-runs included).  grid: (ceil(H * W / kBlock), n).
+template <bool U16>
+__global__ __launch_bounds__(kBlock) void scene_learn_kernel(SceneLearnArgs a)
+{
+  const size_t plane = (size_t)a.width * (size_t)a.height;
+  const size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (p >= plane) return;
+  const int stream = (int)blockIdx.y;
+  const int v = (int)(p / (size_t)a.width), u = (int)(p - (size_t)v * (size_t)a.width);
+  const size_t pix = (size_t)stream * plane + p;
+  const float s = U16 ? u16_to_metres(reinterpret_cast<const uint16_t*>(a.depth)[pix]) : a.depth[pix];
+  const uint32_t w = a.bits[((size_t)stream * a.height + (size_t)v) * (size_t)((a.width + 31) >> 5) + (size_t)(u >> 5)];
+  const float have = a.scene[pix];
+  const float next = scene_learned(have, s, ((w >> (u & 31)) & 1u) != 0u);
+  if (__float_as_uint(next) != __float_as_uint(have)) a.scene[pix] = next;
+}
+void launch_scene_learn(const SceneLearnArgs& a, hipStream_t st)
+{
+  const dim3 grid((unsigned)(((size_t)a.width * a.height + kBlock - 1) / kBlock), (unsigned)a.n_streams);
+  if (a.io_u16) hipLaunchKernelGGL(scene_learn_kernel<true>, grid, dim3(kBlock), 0, st, a);
+  else hipLaunchKernelGGL(scene_learn_kernel<false>, grid, dim3(kBlock), 0, st, a);
+}
+
+__global__ __launch_bounds__(kBlock) void fill_f32_kernel(float* p, size_t n, float v)
+{
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) p[i] = v;
+}
+void launch_fill_f32(float* p, size_t n, float v, hipStream_t st)
+{
+  const size_t blocks = (n + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(fill_f32_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks))), dim3(kBlock), 0, st, p, n, v);
+}
+
 }  // namespace rtuf

@@ -2,8 +2,8 @@
 // shares: the 24-bit depth and its bit-pattern forms, the depth keys' encoding of a near fragment's float z, the set-up's
 // 32-bit edge constants, the key format's host-side rules, the compare threshold's constants, division core and the rule
 // that admits that core, the pixel classes of the link residual tables, the point of a filtered point cloud, the sphere centres and
-// point-to-sphere clearances of the link clearance tables, the reach of a padded link's pixel, and the set-up kernel's packed
-// list counters.
+// point-to-sphere clearances of the link clearance tables, the reach of a padded link's pixel, the scene planes' threshold and
+// learning rule, and the set-up kernel's packed list counters.
 //
 // Included by the kernels (rtuf_kernels.hip, device and host pass), the host API (rtuf_api.cpp), scripts/fdiv_check.hip (which
 // holds div_core against the IEEE division on the GPU) and the CPU checks (tests/fast_class_check.cpp, tests/near_key_check.cpp:
@@ -261,6 +261,29 @@ RTUF_NUMERIC uint32_t link_padding_reach2(float z, float pad, float f, float num
   const float d = __fdiv_rn(num, __fsub_rn(z, off));
   const float rho = fminf(__fdiv_rn(__fmul_rn(pad, f), d), (float)kMaxLinkPaddingPx);
   return (uint32_t)__fmul_rn(rho, rho);
+}
+
+// ---------------------------------------------------------------------------------------
+// scene planes (include/rtuf.h, SCENE PLANES): what lies at or behind a stream's learned depth plane is filtered too
+// ---------------------------------------------------------------------------------------
+
+// thr = scene - (abs_m + rel * scene), every operation a single float operation rounded on its own.  An unknown scene pixel
+// (+inf or NaN) gives NaN for every legal margin (abs_m >= 0 finite, 0 <= rel < 1): rel * inf is inf, or NaN for rel = 0, and
+// inf - (abs_m + inf) = inf - inf = NaN -- no sensor value is above a NaN, so nothing is special-cased.
+// (tests/scene_check.cpp against a numpy form, bit for bit.)
+RTUF_NUMERIC float scene_threshold(float scene, float abs_m, float rel)
+{
+  return __fsub_rn(scene, __fadd_rn(abs_m, __fmul_rn(rel, scene)));
+}
+// Strict and ordered: a NaN sensor value is never scene-filtered.
+RTUF_NUMERIC bool scene_filtered(float s, float scene, float abs_m, float rel) { return s > scene_threshold(scene, abs_m, rel); }
+
+// Learning (rtuf_learn_scene_batch*): a pixel the ROBOT filter keeps and whose reading carries a point lowers the plane to that
+// reading -- a running minimum of input values, so idempotent and independent of the frames' order.  A NaN plane value is
+// "unknown" like +inf: the first such reading replaces it (fminf's rule).
+RTUF_NUMERIC float scene_learned(float scene, float s, bool robot_filtered)
+{
+  return !robot_filtered && cloud_sensor_valid(s) && !(scene <= s) ? s : scene;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -51,14 +51,21 @@ constexpr int tile_variant_index(TileVariant v)
 }
 
 // What runs behind the tile kernel on the launch group's lane: first the kernel that makes the outputs from the z-surface
-// (Post), then the kernels that read the mask bits (Tail).
+// (Post), then -- scene planes in effect (include/rtuf.h, SCENE PLANES) -- the kernel that adds the scene's verdict to those
+// outputs (scene), then the kernels that read the mask bits (Tail).
 enum class Post { None, Compare, Dilate, Pad };
 constexpr int kPosts = 4;
 enum class Tail { None, Cloud, Clearance };
+constexpr int kTails = 3;
 
-struct Route { TileVariant tile; Post post; Tail tail; bool ok; };      // ok == false: a combination the API refuses
-constexpr bool runs_behind_tile(const Route& r) { return r.post != Post::None || r.tail != Tail::None; }
-constexpr int route_index(const Route& r) { return tile_variant_index(r.tile) + kTileVariantSlots * ((int)r.post + kPosts * (int)r.tail); }
+// ok == false: a combination the API refuses.  scene (last: older brace lists leave it false): scene_apply_planes_kernel behind
+// a Filter batch's outputs, scene_apply_bits_kernel behind the mask bits of a Bits, Cloud or Clearance batch.
+struct Route { TileVariant tile; Post post; Tail tail; bool ok; bool scene; };
+constexpr bool runs_behind_tile(const Route& r) { return r.post != Post::None || r.tail != Tail::None || r.scene; }
+constexpr int route_index(const Route& r)
+{
+  return tile_variant_index(r.tile) + kTileVariantSlots * ((int)r.post + kPosts * ((int)r.tail + kTails * (r.scene ? 1 : 0)));
+}
 
 // The facts a route follows from.
 struct RouteFacts {
@@ -69,7 +76,9 @@ struct RouteFacts {
   bool two_kernel;    // the context's RTUF_FLAG_TWO_KERNEL
   int dilation;       // the context's silhouette dilation radius
   bool cover;         // the cover pass is on
-  bool padded;        // link padding is in effect in the context (some model holds a non-zero padding); last: older brace lists leave it false
+  // padded: link padding is in effect in the context (some model holds a non-zero padding).  scene: scene planes are in effect in
+  // the context (some stream has scene filtering enabled).  The two newest facts, scene last: older brace lists leave them false.
+  bool padded; bool scene;
 };
 
 //   batch                                      tile output   modifiers              behind it
@@ -87,6 +96,8 @@ struct RouteFacts {
 // dilation; dilation with a render or residual batch; thresholds on the z-surface route.  Link padding goes over the
 // z-surface whatever the two-kernel flag says, and the plane beside it belongs to the link slots: refused with a label plane,
 // a render or residual batch, dilation or thresholds.
+// Scene planes refuse nothing and change nothing in front of them: a Filter, Bits, Cloud or Clearance batch takes the route it
+// would take without, plus the scene stage between Post and Tail; render and residual batches compare nothing against the scene.
 constexpr Route route_of(const RouteFacts& f)
 {
   const bool filter = f.kind == BatchKind::Filter, bits = f.kind == BatchKind::Bits;
@@ -109,6 +120,7 @@ constexpr Route route_of(const RouteFacts& f)
   }
   r.tail = f.kind == BatchKind::Cloud ? Tail::Cloud : f.kind == BatchKind::Clearance ? Tail::Clearance : Tail::None;
   r.ok = ok && tile_variant_legal(r.tile);
+  r.scene = f.scene && !render && !residual;
   return r;
 }
 

@@ -170,7 +170,8 @@ class FilterParameters:
     def __init__(self, fixed_frame, camera_frame, models, depth_distance_threshold,
                  camera_offset_translation=(0.0, 0.0, 0.0), camera_offset_rotation=(0.0, 0.0, 0.0, 1.0),
                  show_gui=False, filter_replace_value=0.0, use_own_calibration=False,
-                 own_calibration=(585.260, 585.028, 317.387, 239.264), silhouette_dilation_px=0):
+                 own_calibration=(585.260, 585.028, 317.387, 239.264), silhouette_dilation_px=0,
+                 scene_margin=None, scene_margin_rel=0.0):
         self.fixed_frame = fixed_frame
         self.camera_frame = camera_frame
         self.models = models                 # list of dicts: model, tf_prefix, geometry_type, [scale], [ignore],
@@ -187,6 +188,11 @@ class FilterParameters:
         self.own_calibration = tuple(float(np.float32(v)) for v in own_calibration)
         # new, beyond the reference: widen the rendered robot by this many pixels, 0 .. 16 (rtuf_params.silhouette_dilation_px)
         self.silhouette_dilation_px = int(silhouette_dilation_px)
+        # new, beyond the reference: scene planes (include/rtuf.h, SCENE PLANES).  scene_margin (metres, >= 0) enables scene
+        # filtering for every stream with the margins {scene_margin, scene_margin_rel in [0, 1)}; None: a scene can be learned
+        # and set, but filters nothing
+        self.scene_margin = None if scene_margin is None else float(scene_margin)
+        self.scene_margin_rel = float(scene_margin_rel)
 
     @staticmethod
     def from_dict(d):
@@ -195,7 +201,7 @@ class FilterParameters:
                                 off.get("translation", (0.0, 0.0, 0.0)), off.get("rotation", (0.0, 0.0, 0.0, 1.0)),
                                 d.get("show_gui", False), d.get("filter_replace_value", 0.0),
                                 d.get("use_own_calibration", False), d.get("own_calibration", (585.260, 585.028, 317.387, 239.264)),
-                                d.get("silhouette_dilation_px", 0))
+                                d.get("silhouette_dilation_px", 0), d.get("scene_margin"), d.get("scene_margin_rel", 0.0))
 
 
 class RealtimeURDFFilter:
@@ -324,6 +330,13 @@ class RealtimeURDFFilter:
                 self._padded_ = True
         self.masked_depth_ = np.zeros((self.height_, self.width_), np.float32)
         self.mask_ = np.zeros((self.height_, self.width_), np.uint8)
+        self._enable_scene()
+
+    def _enable_scene(self):
+        """Scene filtering for every stream, with the parameters' margins (a new context's planes are all unknown: nothing is
+        filtered until a scene is learned or set)."""
+        if self.params.scene_margin is not None:
+            self._ctx.set_scene_margins(0, [(self.params.scene_margin, self.params.scene_margin_rel)] * self.max_streams)
 
     def _give_padding_intrinsics(self, n):
         """Link padding projects its margins with the streams' focal lengths: streams 0 .. n-1 get the intrinsics of the last
@@ -506,6 +519,60 @@ class RealtimeURDFFilter:
         d = np.asarray(depth)
         d = d.astype(np.uint16 if d.dtype == np.uint16 else np.float32, copy=False).reshape(1, height, width)
         return self._ctx.link_clearance_batch(d, self.numLinkResidualRows(), max_distance)[0]
+
+    # ---- scene planes (include/rtuf.h, SCENE PLANES) ------------------------------------------
+    def learnScene(self, depth, projection_matrix, width, height, timestamp=None):
+        """New, beyond the reference: lowers stream 0's scene plane to the readings of every pixel the robot filter keeps, for the
+        camera and link poses filter() would use -- call it for a few frames of the empty cell while the robot moves, with link
+        padding in the model entries so that the arm's halo is not learned.  depth: [H,W] float32 metres or uint16 millimetres.
+        Returns False where filter() would have returned without a result."""
+        self._ensure_size(width, height)
+        if not self.renderers_:
+            return False
+        try:
+            self._stage_stream(0, projection_matrix, self.tf_, timestamp)
+        except Exception as e:                      # noqa: BLE001 - ROS_ERROR + return (quirk Q6)
+            log.error("%s", e)
+            return False
+        self._give_padding_intrinsics(1)
+        d = np.asarray(depth)
+        d = d.astype(np.uint16 if d.dtype == np.uint16 else np.float32, copy=False).reshape(1, height, width)
+        self._ctx.learn_scene_batch(d)
+        return True
+
+    def learnSceneBatch(self, depths, projections, tfs, timestamp=None):
+        """learnScene for streams 0 .. N-1 at once (the arguments of filter_batch); a stream whose camera lookup fails makes the
+        call fail: a plane must not be learned with stale poses."""
+        depths = np.asarray(depths)
+        depths = np.ascontiguousarray(depths, np.uint16 if depths.dtype == np.uint16 else np.float32)
+        n, height, width = depths.shape
+        self._ensure_size(width, height)
+        projections = np.asarray(projections, np.float64).reshape(-1, 16)
+        for s in range(n):
+            self._stage_stream(s, projections[s if len(projections) > 1 else 0], tfs[s], timestamp)
+        self._give_padding_intrinsics(n)
+        self._ctx.learn_scene_batch(depths)
+
+    def setScene(self, planes, first_stream=0):
+        """The scene planes of streams first_stream ..: [H,W] or [n,H,W] float32 metres, +inf or NaN where unknown.  The image
+        size is the planes' (a context of another size is replaced, as by filter())."""
+        a = np.ascontiguousarray(planes, np.float32)
+        a = a.reshape((-1,) + a.shape[-2:])
+        self._ensure_size(a.shape[2], a.shape[1])
+        self._ctx.set_scene_planes(first_stream, a)
+
+    def getScene(self):
+        """Stream 0's scene plane [H,W] float32 (max_streams > 1: all of them, [n,H,W]); None before the first frame."""
+        if self._ctx is None:
+            return None
+        planes = self._ctx.get_scene_planes()
+        return planes[0] if self.max_streams == 1 else planes
+
+    def clearScene(self):
+        """Every stream's plane back to unknown; the parameters' margins stay in force for the next scene."""
+        if self._ctx is not None:
+            self._ctx.clear_scene()
+            self._enable_scene()
 
     def numLinkResidualRows(self):
         """Rows of a link_residuals() table: one more than the largest label in effect."""

@@ -121,6 +121,14 @@ def build(tag):
     text("filtered point clouds on c3: cloud batches beside the mask-bits batch and beside filter + torch ops", ["README.md", "DESIGN.md 4"], "cloud_rate_c3.txt", "the last line")
     text("link clearance tables on c3: clearance batches beside the mask-bits batch and beside compacted cloud + torch ops", ["README.md", "DESIGN.md 4"], "clearance_rate_c3.txt", "the last line")
     text("link padding on c3: padded mask-bits and cloud batches beside the dilated leg of the same run", ["README.md", "DESIGN.md 4"], "link_padding_rate_c3.txt", "the last line")
+    f = "scene_rate_c3.txt"
+    if os.path.exists(os.path.join(PROFILES, f)):
+        body = open(os.path.join(PROFILES, f)).read().splitlines()
+        v = {"summary": next((l[:400] for l in body if l.startswith("# c3 frames/s")), None),
+             "kernels": [json.loads(l) for l in body if l.startswith('{"kernel"')],
+             "headline_same_box": [l for l in body if l.startswith("other ") or l.startswith("this ")]}
+        add("scene planes on c3: batches with a learned scene in effect beside the plain fused filter, filter + torch ops, and the apply kernels beside compare_kernel",
+            ["README.md", "DESIGN.md 4"], f, "the '# c3 frames/s' line, the kernel rows of the rocprofv3 run, the same-box bench lines of the parent and this tree", v)
     f = "link_residuals_kernel_stats.txt"
     if os.path.exists(os.path.join(PROFILES, f)):
         v = {}
