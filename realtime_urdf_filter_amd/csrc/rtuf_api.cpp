@@ -319,6 +319,7 @@ struct rtuf_context {
   rtuf_stats stats{};
 #ifdef RTUF_LANECOUNT
   unsigned long long lane_slots[kLaneLoops] = {}, lane_live[kLaneLoops] = {};      // of the last retired batch (instrumented build)
+  unsigned long long lane_roles[kLaneRoleWords] = {};
 #endif
   int timing = 0;            // 0 off, 1 every stage, 2 only around the tile (and compare) kernel, 3 = 2 on every fourth batch
   uint32_t timing_seq = 0;
@@ -1907,6 +1908,10 @@ static int retire_oldest(rtuf_context* c)
     for (int g = 0; g < b.n_groups; g++)
       for (int sh = 0; sh < kCounterShards; sh++)
         for (int i = 0; i < kLaneLoops; i++) { c->lane_slots[i] += b.h_counters[g].shard[sh].lane_slots[i]; c->lane_live[i] += b.h_counters[g].shard[sh].lane_live[i]; }
+    for (int i = 0; i < kLaneRoleWords; i++) c->lane_roles[i] = 0;
+    for (int g = 0; g < b.n_groups; g++)
+      for (int sh = 0; sh < kCounterShards; sh++)
+        for (int i = 0; i < kLaneRoleWords; i++) c->lane_roles[i] += b.h_counters[g].shard[sh].lane_roles[i];
 #endif
     for (int g = 0; g < b.n_groups; g++) {
       const Counters& cn = b.h_counters[g];
@@ -3419,6 +3424,15 @@ int rtuf_debug_lane_counts(rtuf_context* c, unsigned long long* slots, unsigned 
   if (!c->kids.empty()) c = c->kids[c->last_kid];
   for (int i = 0; i < n && i < kLaneLoops; i++) { slots[i] = c->lane_slots[i]; live[i] = c->lane_live[i]; }
   return kLaneLoops;
+}
+// ... and which wave did the work (scripts/wave_roles.sh): 4 words per loop (trips with a live lane, by wave role), then
+// kRoleTables tables of 4 x 4 (role against SIMD) for the set-up kernel and as many for the tile kernel
+int rtuf_debug_wave_roles(rtuf_context* c, unsigned long long* words, int n)
+{
+  if (!c || !words) return RTUF_ERR_INVALID;
+  if (!c->kids.empty()) c = c->kids[c->last_kid];
+  for (int i = 0; i < n && i < kLaneRoleWords; i++) words[i] = c->lane_roles[i];
+  return kLaneRoleWords;
 }
 #endif
 

@@ -172,6 +172,10 @@ struct alignas(16) ClipItem {   // one triangle that crosses a frustum plane; se
 #endif
 constexpr int kCounterShards = RTUF_COUNTER_SHARDS;
 constexpr int kLaneLoops = 48;           // instrumented loops (and histogram buckets) of a -DRTUF_LANECOUNT build
+// (same build) per loop four words, then per kernel (set-up, tile) kRoleTables tables of 4 x 4, then two words: see
+// CounterShard::lane_roles
+constexpr int kRoleTables = 2;
+constexpr int kLaneRoleWords = 4 * kLaneLoops + 2 * kRoleTables * 16 + 2;
 struct alignas(128) CounterShard {
   unsigned long long tris_binned;
   unsigned long long bin_entries;
@@ -195,6 +199,10 @@ struct alignas(128) CounterShard {
   // issued (64 per wave and trip) and the lanes that were live in them, see kLane* in rtuf_kernels.hip.
   unsigned long long lane_slots[kLaneLoops];
   unsigned long long lane_live[kLaneLoops];
+  // ... and which wave does the work: per loop and wave index within the workgroup (modulo 4) the trips with a live lane;
+  // then, in shard 0 only, per kernel two tables of 4 x 4 -- waves started, by wave index and hardware SIMD, on the whole chip
+  // and on one CU -- and per kernel the id (+ 1) of that CU
+  unsigned long long lane_roles[kLaneRoleWords];
 #endif
 };
 #ifndef RTUF_LANECOUNT

@@ -78,13 +78,17 @@ static_assert(kLaneEnd <= kLaneLoops, "CounterShard holds kLaneLoops pairs");
 static_assert(kLaneHistEnd <= kLaneLoops, "CounterShard holds kLaneLoops pairs");
 static_assert(kLaneCount <= kLaneLoops, "CounterShard holds kLaneLoops pairs");
 #ifdef RTUF_LANECOUNT
-__device__ __forceinline__ uint32_t* lane_words() { __shared__ uint32_t s_lw[2 * kLaneLoops]; return s_lw; }
+// LDS words of the instrumented build: 2 per loop (slots, live) and 4 per loop (trips with a live lane, by the wave's index in
+// its workgroup modulo 4: the share of every loop's work that a wave gets follows from it, all loops index as base + tid)
+__device__ __forceinline__ uint32_t* lane_words() { __shared__ uint32_t s_lw[6 * kLaneLoops]; return s_lw; }
+__device__ __forceinline__ uint32_t lane_role() { return (threadIdx.x >> 6) & 3u; }
 #define RTUF_LANES(id, pred)                                                                                          \
   do {                                                                                                                \
     const unsigned long long act_ = __ballot(true), m_ = __ballot(pred);                                              \
     if ((int)(threadIdx.x & 63) == __ffsll((long long)act_) - 1) {                                                    \
       atomicAdd(&lane_words()[2 * (id)], 64u);                                                                        \
       atomicAdd(&lane_words()[2 * (id) + 1], (uint32_t)__popcll(m_));                                                 \
+      if (m_) atomicAdd(&lane_words()[2 * kLaneLoops + 4 * (id) + lane_role()], 1u);                                  \
     }                                                                                                                 \
   } while (0)
 #define RTUF_LANES_LIVE(id, pred)                                                                                     \
@@ -93,10 +97,27 @@ __device__ __forceinline__ uint32_t* lane_words() { __shared__ uint32_t s_lw[2 *
     if (m_ && (int)(threadIdx.x & 63) == __ffsll((long long)act_) - 1) {                                              \
       atomicAdd(&lane_words()[2 * (id)], 64u);                                                                        \
       atomicAdd(&lane_words()[2 * (id) + 1], (uint32_t)__popcll(m_));                                                 \
+      atomicAdd(&lane_words()[2 * kLaneLoops + 4 * (id) + lane_role()], 1u);                                          \
     }                                                                                                                 \
   } while (0)
-#define RTUF_LANES_INIT()                                                                                             \
-  do { for (int i_ = threadIdx.x; i_ < 2 * kLaneLoops; i_ += blockDim.x) lane_words()[i_] = 0u; __syncthreads(); } while (0)
+// (kernel: 0 set-up, 1 tile.  The first lane of every wave reads where it runs from the hardware-id register -- id 4: SIMD in
+// bits 5:4, CU / shader array / shader engine in bits 15:8; id 20: the XCD -- and counts the wave in two 4 x 4 tables, wave
+// index against SIMD: one over the whole chip, one for the waves of a single CU, the one that the batch's first wave ran on.
+// A table that is even over the chip could still hide CUs that each keep a placement of their own.)
+#define RTUF_LANES_INIT(kernel)                                                                                       \
+  do {                                                                                                                \
+    for (int i_ = threadIdx.x; i_ < 6 * kLaneLoops; i_ += blockDim.x) lane_words()[i_] = 0u;                          \
+    __syncthreads();                                                                                                  \
+    if ((threadIdx.x & 63u) == 0u) {                                                                                  \
+      const uint32_t simd_ = __builtin_amdgcn_s_getreg(4 | (4 << 6) | (1 << 11)), w_ = (threadIdx.x >> 6) & 3u;       \
+      const uint32_t cu_ = 1u + (__builtin_amdgcn_s_getreg(4 | (8 << 6) | (7 << 11)) | (__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) << 8)); \
+      unsigned long long* t_ = a.counters->shard[0].lane_roles + 4 * kLaneLoops + (kernel) * kRoleTables * 16;        \
+      atomicAdd(&t_[w_ * 4 + simd_], 1ull);                                                                           \
+      unsigned long long* key_ = a.counters->shard[0].lane_roles + kLaneRoleWords - 2 + (kernel);                     \
+      const unsigned long long was_ = atomicCAS(key_, 0ull, (unsigned long long)cu_);                                 \
+      if (was_ == 0ull || was_ == (unsigned long long)cu_) atomicAdd(&t_[16 + w_ * 4 + simd_], 1ull);                 \
+    }                                                                                                                 \
+  } while (0)
 #define RTUF_LANES_FLUSH(shard)                                                                                       \
   do {                                                                                                                \
     __syncthreads();                                                                                                  \
@@ -104,11 +125,13 @@ __device__ __forceinline__ uint32_t* lane_words() { __shared__ uint32_t s_lw[2 *
       atomicAdd(&(shard).lane_slots[threadIdx.x], (unsigned long long)lane_words()[2 * threadIdx.x]);                 \
       atomicAdd(&(shard).lane_live[threadIdx.x], (unsigned long long)lane_words()[2 * threadIdx.x + 1]);              \
     }                                                                                                                 \
+    if ((int)threadIdx.x < 4 * kLaneLoops && lane_words()[2 * kLaneLoops + threadIdx.x])                              \
+      atomicAdd(&(shard).lane_roles[threadIdx.x], (unsigned long long)lane_words()[2 * kLaneLoops + threadIdx.x]);    \
   } while (0)
 #else
 #define RTUF_LANES(id, pred) ((void)0)
 #define RTUF_LANES_LIVE(id, pred) ((void)0)
-#define RTUF_LANES_INIT() ((void)0)
+#define RTUF_LANES_INIT(kernel) ((void)0)
 #define RTUF_LANES_FLUSH(shard) ((void)0)
 #endif
 
@@ -1001,7 +1024,7 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
   CounterShard& shard = a.counters->shard[shard_id];
   const float sx = 0.5f * (float)a.width, sy = 0.5f * (float)a.height;
   uint32_t binned = 0, entries = 0, nfrag = 0;
-  RTUF_LANES_INIT();
+  RTUF_LANES_INIT(0);
   // launch_setup sizes the main grid from the previous batch's work-list length: one item per
   // workgroup (STRIDED = false, no loop: keeps the register count at 8 waves/SIMD).  Items beyond that
   // grid, if the list grew, are swept by a small strided launch of the same code.
@@ -1144,6 +1167,41 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
   const uint32_t counts = s_counts;
   const uint32_t ntiny = list_count_tiny(counts), nsmall = list_count_small(counts);
   if (tid == 0 && counts == 0u) atomicAdd(&shard.zero_items, 1u);      // (statistics: an item the cull pass could have spared)
+  // Dense set-up + binning of one survivor per lane (entry `e` of a work list: stream k << 8 | triangle) as a 32-byte record;
+  // the tile kernel rebuilds the edge functions, so only orientation, bounding box and z plane are needed here.  All lanes
+  // of a wave call it (emit_record_wave is cooperative); `take`: this lane has an entry.
+  auto bin_record = [&](bool take, uint32_t e) {
+    bool have = false;
+    PackedTri pk;
+    uint32_t bbx = 0, bby = 0;
+    int slot = 0;
+    if (take) {
+      const int k = (int)(e >> 8), t = (int)(e & 255u);
+      slot = s_slot[k];
+      const uint32_t order = a.corder[ch.tri_begin + t];      // (asked for early, see below)
+      const uint32_t p = s_packed[t];
+      const uint32_t j0 = p & 1023u, j1 = (p >> 10) & 1023u, j2 = (p >> 20) & 1023u;
+      Win v0, v1, v2;
+      v0.x = s_win[k][0][j0]; v0.y = s_win[k][1][j0]; v0.z = s_win[k][2][j0];
+      v1.x = s_win[k][0][j1]; v1.y = s_win[k][1][j1]; v1.z = s_win[k][2][j1];
+      v2.x = s_win[k][0][j2]; v2.y = s_win[k][1][j2]; v2.z = s_win[k][2][j2];
+      const int2 q0 = s_snap[k][j0], q1 = s_snap[k][j1], q2 = s_snap[k][j2];        // snapped in phase 1 (y << 8 | clip mask)
+      int x0 = q0.x, y0 = q0.y >> 8, x1 = q1.x, y1 = q1.y >> 8, x2 = q2.x, y2 = q2.y >> 8, bx0, bx1, by0, by1;
+      have = orient_and_bound(v0, v1, v2, a.width, a.height, x0, y0, x1, y1, x2, y2, bx0, bx1, by0, by1);
+      if (have) {
+        float a0, dzdx, dzdy;
+        z_plane(v0, v1, v2, a0, dzdx, dzdy);
+        pk = pack_record(x0, y0, x1, y1, x2, y2, a0, dzdx, dzdy, order | near_bit(a0, dzdx, dzdy, bx0, bx1, by0, by1));
+        bbx = (uint32_t)bx0 | ((uint32_t)bx1 << 16);
+        bby = (uint32_t)by0 | ((uint32_t)by1 << 16);
+      }
+    }
+    RTUF_LANES(kLaneSetupRecHit, have);
+    if (__ballot(have) && !RTUF_ABL(a.flags, 0x20000u)) {
+      entries += emit_record_wave(a, list_shard, slot, have, bbx, bby, pk);
+      binned += have ? 1u : 0u;
+    }
+  };
 #pragma unroll
   for (int cls = 0; cls < 2; cls++) {
     const uint32_t ncls = cls == 0 ? ntiny : nsmall;
@@ -1185,7 +1243,8 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
           near = !(zmin >= 0.51f);      // (a NaN anywhere in the plane makes zmin NaN: counts as near)
         }
       }
-      if (near) {      // rare: hand the triangle to the record pass below (one LDS append: the record field is the packed word's lowest)
+      if (near) {      // rare: hand the triangle to the record list (one LDS append: the record field is the packed word's lowest).
+        // It lands BEHIND the entries of phase 2, which the record pass below takes without waiting; the tail pass picks it up.
         s_list[list_count_rec(atomicAdd(&s_counts, 1u))] = (uint16_t)ent;
         mask = 0;
       }
@@ -1197,44 +1256,24 @@ __global__ __launch_bounds__(kBlock) void setup_kernel(SetupArgs a, uint32_t ite
       }
     }
   }
-  __syncthreads();        // appends of the fragment pass to the record list
-  // phase 3c: dense set-up + binning of the larger survivors as 32-byte records (the tile kernel
-  // rebuilds the edge functions, so only orientation, bounding box and z plane are needed here)
-  const uint32_t nlist = list_count_rec(s_counts);
+  // phase 3c: the larger survivors as records.  No barrier in front of it: the record list as phase 2 left it (`counts`) is
+  // complete, and the waves run free.  The list is handed out from the TOP wave downwards: the box passes above fill from
+  // wave 0, so the waves that had few boxes or none take the records while the first waves are still in coverage, and the item
+  // takes the longer of the two passes instead of their sum (docs/experiments.md R8).
+  const uint32_t nlist = list_count_rec(counts);
   for (uint32_t base = 0; base < nlist; base += kBlock) {
-    const uint32_t j = base + tid;
-    bool have = false;
-    PackedTri pk;
-    uint32_t bbx = 0, bby = 0;
-    int slot = 0;
+    const uint32_t j = base + (uint32_t)(tid ^ (kBlock - 64));
     RTUF_LANES(kLaneSetupRec, j < nlist);
-    if (j < nlist) {
-      const uint32_t e = s_list[j];
-      const int k = (int)(e >> 8), t = (int)(e & 255u);
-      slot = s_slot[k];
-      const uint32_t order = a.corder[ch.tri_begin + t];      // (asked for early, see above)
-      const uint32_t p = s_packed[t];
-      const uint32_t j0 = p & 1023u, j1 = (p >> 10) & 1023u, j2 = (p >> 20) & 1023u;
-      Win v0, v1, v2;
-      v0.x = s_win[k][0][j0]; v0.y = s_win[k][1][j0]; v0.z = s_win[k][2][j0];
-      v1.x = s_win[k][0][j1]; v1.y = s_win[k][1][j1]; v1.z = s_win[k][2][j1];
-      v2.x = s_win[k][0][j2]; v2.y = s_win[k][1][j2]; v2.z = s_win[k][2][j2];
-      const int2 q0 = s_snap[k][j0], q1 = s_snap[k][j1], q2 = s_snap[k][j2];        // snapped in phase 1 (y << 8 | clip mask)
-      int x0 = q0.x, y0 = q0.y >> 8, x1 = q1.x, y1 = q1.y >> 8, x2 = q2.x, y2 = q2.y >> 8, bx0, bx1, by0, by1;
-      have = orient_and_bound(v0, v1, v2, a.width, a.height, x0, y0, x1, y1, x2, y2, bx0, bx1, by0, by1);
-      if (have) {
-        float a0, dzdx, dzdy;
-        z_plane(v0, v1, v2, a0, dzdx, dzdy);
-        pk = pack_record(x0, y0, x1, y1, x2, y2, a0, dzdx, dzdy, order | near_bit(a0, dzdx, dzdy, bx0, bx1, by0, by1));
-        bbx = (uint32_t)bx0 | ((uint32_t)bx1 << 16);
-        bby = (uint32_t)by0 | ((uint32_t)by1 << 16);
-      }
-    }
-    RTUF_LANES(kLaneSetupRecHit, have);
-    if (__ballot(have) && !RTUF_ABL(a.flags, 0x20000u)) {
-      entries += emit_record_wave(a, list_shard, slot, have, bbx, bby, pk);
-      binned += have ? 1u : 0u;
-    }
+    bin_record(j < nlist, j < nlist ? (uint32_t)s_list[j] : 0u);
+  }
+  // ... and the tail: what the box passes handed over since (near boxes; none on a robot at arm's length).  The barrier stands
+  // where every wave is done with the item anyway.
+  __syncthreads();
+  const uint32_t nall = list_count_rec(s_counts);
+  for (uint32_t base = nlist; base < nall; base += kBlock) {
+    const uint32_t j = base + tid;
+    RTUF_LANES(kLaneSetupRec, j < nall);
+    bin_record(j < nall, j < nall ? (uint32_t)s_list[j] : 0u);
   }
   if (!STRIDED) break;
   __syncthreads();        // LDS is reused by the next item
@@ -2291,7 +2330,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a)
   __shared__ uint4 s_pmeta[64];                    //     with {class, smallest depth, largest depth if it covers the whole tile}
 
   const int tid = threadIdx.x;
-  RTUF_LANES_INIT();
+  RTUF_LANES_INIT(1);
   const int tiles = a.tiles_x * a.tiles_y;
   // grid = (tiles_x, tiles_y, streams of the group): no integer divisions to find the tile
   const int txi = blockIdx.x, tyi = blockIdx.y, slot = blockIdx.z;

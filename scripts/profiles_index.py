@@ -152,6 +152,10 @@ def build(tag):
                            (T + "_same_box_c4_share_round5_vs_round6.txt", "... C4 share", ["DESIGN.md 4", "docs/experiments.md R6.4"]),
                            (T + "_host_planes.json", "planes in pinned host memory (PCIe-inclusive rates)", ["README.md", "DESIGN.md 5"]),
                            (T + "_lanes.json", "lanes live per trip of every walk / emission loop", ["docs/experiments.md A.5"]),
+                           ("wave_roles_c3.txt", "wave index against SIMD, trips by wave index, and the rotations that were tried (no gain)", ["docs/experiments.md R8"]),
+                           ("wave_roles_same_box.txt", "set-up kernel's phase 3 without its barrier: the parts one by one, and the parent beside the tree on one box", ["DESIGN.md 4", "docs/experiments.md R8"]),
+                           ("wave_roles_kernel_stats_parent.csv", "rocprofv3 --kernel-trace --stats of bench.py --lanes 1, parent of R8", ["docs/experiments.md R8"]),
+                           ("wave_roles_kernel_stats_tree.csv", "... and the tree with R8 (setup_kernel 231.1 -> 221.1 us)", ["DESIGN.md 4", "docs/experiments.md R8"]),
                            ("overdraw.json", "depth tests per drawn pixel", ["bench.py rasteriser.tile.overdraw"]),
                            ("valu_peak.json", "measured VALU issue rates per instruction (two classes)", ["DESIGN.md 4", "docs/experiments.md A.1"]),
                            ("llvmpipe_baseline.json", "the reference's GLSL on llvmpipe at BASELINE sizes (development container)", ["DESIGN.md 2", "BASELINE.md"])):
