@@ -404,6 +404,24 @@ class RealtimeURDFFilter {
     return true;
   }
 
+  // Point list batches (include/rtuf.h, POINT LIST BATCHES): a point list instead of a depth image -- a lidar's points, a cloud
+  // that was cropped or transformed, the compacted output of cloud_into -- for the camera and link poses filter_into would use
+  // and the intrinsics cloud_into would use.  points: count x 3 floats in the camera's optical frame; radius_px 0 .. 4 widens
+  // the robot by that many pixels.  verdict_out: count bytes (0 kept, 1 filtered, 2 outside the image or without a positive
+  // finite z); pixel_out: nullptr or count words (v * width + u, 0xFFFFFFFF where the verdict is 2); summary_out: nullptr or
+  // four words (kept, filtered, outside, count).
+  bool points_into(const float* points, uint32_t count, double* glTf, int width, int height, double timestamp, uint8_t* verdict_out,
+                   uint32_t* pixel_out = nullptr, uint32_t* summary_out = nullptr, int radius_px = 0)
+  {
+    prepare(width, height);
+    if (!points || !verdict_out) throw std::runtime_error("points_into: needs points and verdict_out");
+    if (!have_cloud_intr_) throw std::runtime_error("points_into: no intrinsics yet (getProjectionMatrix sets them)");
+    if (renderers_.empty() || !stage_frame(glTf, timestamp)) return false;
+    send_cloud_intrinsics();
+    check(rtuf_points_batch(ctx_, 1, &points, &count, radius_px, &verdict_out, pixel_out ? &pixel_out : nullptr, summary_out));
+    return true;
+  }
+
   // Link residual tables (include/rtuf.h, LINK RESIDUAL TABLES): per link label, how the sensor image compares with the model
   // for the camera and link poses filter_into would use.  depth: width x height float metres, or uint16 millimetres with
   // is_16uc1; table_out: n_labels rows, at least numLinkResidualRows(); row = label (linkLabels() with

@@ -530,6 +530,66 @@ int rtuf_cloud_compact_batch(rtuf_context *ctx, int n_streams, const float *cons
 int rtuf_cloud_compact_batch_u16(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in, float *const *points_out,
                                  uint32_t *const *index_out, uint32_t *counts_out, int capacity);
 
+/* POINT LIST BATCHES.  New, beyond the reference: filter points instead of planes -- spinning and solid-state lidars, a cloud
+ * that has already been transformed or cropped, the compacted cloud this library itself emits (robot_self_filter's input).
+ * A points batch renders the robot's virtual depth (VIRTUAL DEPTH) into a plane the library owns and judges every point of
+ * every stream against it: a verdict byte per point, optionally the pixel it landed on, and a per-stream summary.  No sensor
+ * plane is read and no image plane is returned.
+ * Definition.  Every float operation is single precision and rounded on its own; divisions are IEEE.
+ * Input, per stream s: count[s] points (x, y, z) in the stream's optical frame -- the frame the cloud calls write in: x right,
+ * y down, z forward, pixel row 0 first.
+ * Intrinsics: those of rtuf_set_cloud_intrinsics, as fx = (float)fx, fy = (float)fy, cx = (float)cx, cy = (float)cy.
+ * Transform, optional and per stream: rtuf_set_point_transforms gives streams first_stream .. first_stream + n_streams - 1 one
+ * column-major matrix each (optical_from_points [n][16]; NULL: none for these streams).  Its 12 used entries m are rounded to
+ * float, and a point becomes p'_r = ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r], r = 0 .. 2.  A stream without a
+ * transform takes its points as given, with no arithmetic at all, so an infinite coordinate does not poison the others.  The
+ * setter waits for the batches in flight and applies to all pipelines, as rtuf_set_cloud_intrinsics does; an entry among the
+ * 12 that is not finite (as a double or once rounded to float) or a stream range outside the context fails with
+ * RTUF_ERR_INVALID and changes nothing.
+ * Pixel of a point (point_pixel in rtuf_numerics.h, the inverse of cloud_point).  The point is JUDGED iff z > 0 && z < +inf
+ * and both range tests below hold:
+ *   a = x / z,   uf = ((a * fx) + cx) + 0.5f,      b = y / z,   vf = ((b * fy) + cy) + 0.5f
+ *   uf >= 0 && uf < (float)W && vf >= 0 && vf < (float)H           (so NaN fails)
+ *   u = (int)uf,  v = (int)vf
+ * The range tests come before the conversions: no out-of-range float is ever converted, no index outside the plane is ever
+ * formed.  Pixel centres sit at integer u, as depth_image_proc puts them: a point cloud_point made from pixel (u, v) lands on
+ * (u, v) again.
+ * Verdict.  V(q) is what rtuf_render_batch_device with empty_value = +inf writes at pixel q, t is
+ * rtuf_params.depth_distance_threshold, r is the call's radius_px, 0 .. 4, and Vmin is the smallest V(q) over the pixels of
+ * the (2r+1)^2 square around (u, v) that lie in this stream's image -- the square is never padded and never reaches into
+ * another stream.  A judged point is FILTERED (verdict 1) iff z > Vmin - t, else KEPT (0); a point that is not judged is
+ * OUTSIDE (2).  Where the square holds nothing drawn by a link, Vmin is +inf and the compare is false for every t: nothing is
+ * special-cased.  The background quad filters nothing here (a point list has no "beyond the far plane" artefact to
+ * reproduce).  to_linear_depth is monotone in the window z, so for r equal to a dilation radius the verdict is the dilated
+ * filter's mask bit for a sensor plane that held z at that pixel, wherever a link, not the background, holds the minimum.
+ * Layout: the compacted cloud's, so the output of rtuf_cloud_compact_batch_device can be fed straight back.  d_points is
+ * [n][capacity][3] float, d_counts [n] uint32 ON THE DEVICE; stream s judges entries j < min(counts[s], capacity), and
+ * everything else in d_verdict ([n][capacity] uint8) and d_pixel (NULL or [n][capacity] uint32) is left untouched.  d_pixel
+ * holds v * W + u, or 0xFFFFFFFF for verdict 2.  d_summary (NULL or [n][4] uint32) holds kept, filtered, outside and
+ * min(count, capacity); it is overwritten by every call and every re-run, and holds integers only, so no order of execution
+ * enters.  1 <= capacity <= 1 << 24.  Alignment is the elements' own; where d_points and d_pixel start on 16-byte boundaries,
+ * d_verdict on a 4-byte one and capacity is a multiple of 4, the kernel takes 16-byte loads and stores.
+ * rtuf_points_batch is the host form, synchronous: points up, results down, capacity = the largest count; verdict_out and
+ * pixel_out (NULL or one array per stream) receive counts[s] entries per stream, summary_out (NULL or [n][4]) the summary.
+ * Refusals, each of which enqueues nothing and writes nothing.  RTUF_ERR_INVALID: a NULL d_points, d_counts or d_verdict; n,
+ * capacity or radius_px out of range; and, not supported yet, silhouette_dilation_px > 0 (radius_px is this batch's own
+ * margin), link padding in effect and per-link thresholds in effect.  RTUF_ERR_STATE: a context that is not finalized, or a
+ * stream without intrinsics.  RTUF_FLAG_TWO_KERNEL and scene planes do not enter.
+ * Otherwise it is a batch like any other: raster lanes, pipelines, launch groups, partial batches, and as many in flight as
+ * render batches, each with outputs of its own (the library keeps one virtual depth plane [max_streams][H][W] per batch
+ * slot, allocated on first use and counted in rtuf_stats.device_bytes); small batches replay captured graphs; a re-run after
+ * a bin regrowth rewrites verdicts, pixels and summary as if the batch had run once; the status word covers the outputs
+ * (the points kernel runs on each launch group's lane before its counters are published; timings: ms_compare), and
+ * rtuf_order_stream_after_batches applies.
+ * Out of scope: a compacted "kept points" output (which verdicts count as kept differs between one camera-like sensor and
+ * several streams used as faces around a 360-degree lidar: compact on the verdict bytes); one list shared by several
+ * streams; honouring padding, dilation and per-link thresholds; a ROS PointCloud2 adapter. */
+int rtuf_set_point_transforms(rtuf_context *ctx, int first_stream, int n_streams, const double *optical_from_points /* [n][16] column-major, NULL = none */);
+int rtuf_points_batch_device(rtuf_context *ctx, int n_streams, const float *d_points, const uint32_t *d_counts, int capacity,
+                             int radius_px, uint8_t *d_verdict, uint32_t *d_pixel, uint32_t *d_summary);
+int rtuf_points_batch(rtuf_context *ctx, int n_streams, const float *const *points_in, const uint32_t *counts /* host */,
+                      int radius_px, uint8_t *const *verdict_out, uint32_t *const *pixel_out, uint32_t *summary_out);
+
 /* LINK CLEARANCE TABLES.  New, beyond the reference: per stream and link label, how close the nearest kept point -- the
  * nearest thing that is not the robot -- is to the link, as a table [n_streams][n_labels] of 16-byte rows with no plane
  * written at all: what speed-and-separation monitors and reactive controllers ask of the filtered cloud.

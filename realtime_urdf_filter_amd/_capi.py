@@ -44,7 +44,12 @@ SYMBOLS = [
     "rtuf_set_scene_planes", "rtuf_set_scene_planes_device", "rtuf_get_scene_planes", "rtuf_get_scene_planes_device",
     "rtuf_set_scene_margins", "rtuf_clear_scene", "rtuf_learn_scene_batch", "rtuf_learn_scene_batch_u16",
     "rtuf_learn_scene_batch_device", "rtuf_learn_scene_batch_device_u16",
+    "rtuf_set_point_transforms", "rtuf_points_batch_device", "rtuf_points_batch",
 ]
+
+# point list batches (include/rtuf.h, POINT LIST BATCHES): the verdict of a point, and the pixel of one that is not judged
+POINT_KEPT, POINT_FILTERED, POINT_OUTSIDE = 0, 1, 2
+POINT_NO_PIXEL = 0xFFFFFFFF
 
 # rtuf_link_residuals (include/rtuf.h, LINK RESIDUAL TABLES): one 64-byte row per (stream, label)
 LINK_RESIDUALS_DTYPE = np.dtype([("pixels", "<u8"), ("invalid", "<u8"), ("filtered", "<u8"), ("in_front", "<u8"), ("behind", "<u8"),
@@ -229,6 +234,9 @@ def load_library(path=None):
     lib.rtuf_learn_scene_batch_u16.argtypes = [vp, ci, vp]
     lib.rtuf_learn_scene_batch_device.argtypes = [vp, ci, vp]
     lib.rtuf_learn_scene_batch_device_u16.argtypes = [vp, ci, vp]
+    lib.rtuf_set_point_transforms.argtypes = [vp, ci, ci, vp]
+    lib.rtuf_points_batch_device.argtypes = [vp, ci, vp, vp, ci, ci, vp, vp, vp]
+    lib.rtuf_points_batch.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -612,6 +620,43 @@ class Context:
 
     def cloud_compact_batch_device_u16(self, n, d_depth_mm, d_points, d_index, d_counts, capacity):
         self.cloud_compact_batch_device(n, d_depth_mm, d_points, d_index, d_counts, capacity, u16=True)
+
+    # point list batches (include/rtuf.h, POINT LIST BATCHES)
+    def set_point_transforms(self, first_stream, optical_from_points, n_streams=None):
+        """optical_from_points: [n,16] (or one row of 16) doubles, column-major, for streams first_stream ..; None takes the
+        transforms of n_streams streams (default: one) away again."""
+        if optical_from_points is None:
+            self._check(self._lib.rtuf_set_point_transforms(self._h, first_stream, 1 if n_streams is None else int(n_streams), None))
+            return
+        a = np.ascontiguousarray(optical_from_points, np.float64).reshape(-1, 16)
+        self._check(self._lib.rtuf_set_point_transforms(self._h, first_stream, len(a), _ptr(a)))
+
+    def points_batch(self, points, radius_px=0, want_pixel=True):
+        """Point lists against the robot's virtual depth: points is a sequence of [count_s,3] float32 arrays, one per stream, in the
+        stream's optical frame -> (verdicts: list of [count_s] uint8 -- 0 kept, 1 filtered, 2 outside --, pixels: list of [count_s]
+        uint32 (v * W + u, 0xFFFFFFFF where the verdict is 2) or None, summary [n,4] uint32: kept, filtered, outside, count).
+        Synchronous."""
+        pts = [np.ascontiguousarray(p, np.float32).reshape(-1, 3) for p in points]
+        n = len(pts)
+        counts = np.array([len(p) for p in pts], np.uint32)
+        verdict = [np.empty(len(p), np.uint8) for p in pts]
+        pixel = [np.empty(len(p), np.uint32) for p in pts] if want_pixel else None
+        summary = np.zeros((n, 4), np.uint32)
+        PP = ctypes.c_void_p * max(n, 1)
+        # (an empty list still hands a valid pointer over: nothing is read or written through it)
+        at = lambda a: a.ctypes.data if a.size else summary.ctypes.data
+        pin = PP(*[at(p) for p in pts])
+        vout = PP(*[at(v) for v in verdict])
+        xout = PP(*[at(x) for x in pixel]) if want_pixel else None
+        self._check(self._lib.rtuf_points_batch(self._h, n, pin, _ptr(counts), int(radius_px), vout, xout, _ptr(summary)))
+        return verdict, pixel, summary
+
+    def points_batch_device(self, n, d_points, d_counts, capacity, radius_px, d_verdict, d_pixel=None, d_summary=None):
+        """Device pointers (ints; d_pixel and d_summary may be None): d_points [n,capacity,3] float32, d_counts [n] uint32,
+        d_verdict [n,capacity] uint8, d_pixel [n,capacity] uint32, d_summary [n,4] uint32; enqueue only; call sync()."""
+        q = lambda v: ctypes.c_void_p(v) if v else None
+        self._check(self._lib.rtuf_points_batch_device(self._h, n, q(d_points), q(d_counts), int(capacity), int(radius_px), q(d_verdict),
+                                                       q(d_pixel), q(d_summary)))
 
     # link clearance tables (include/rtuf.h, LINK CLEARANCE TABLES)
     def set_link_spheres(self, model, link, xyzr):

@@ -83,6 +83,11 @@ struct BatchRequest {
   float* points = nullptr; uint32_t* index = nullptr; uint32_t* counts = nullptr; int capacity = 0;
   // Clearance (a mask-bits batch with the clearance kernels behind it): the table [n][n_labels] and the cutoff
   rtuf_link_clearance* clr = nullptr; float max_distance = 0.0f;
+  // Points (a render batch into the slot's own plane -- virt, set by submit_batch -- with the points kernel behind it): the point
+  // lists [n][capacity][3] with their device counts [n] (capacity: the field above), the window radius, and the outputs:
+  // verdict [n][capacity], pixel [n][capacity] or nullptr, summary [n][4] or nullptr
+  const float* pt_points = nullptr; const uint32_t* pt_counts = nullptr; int pt_radius = 0;
+  uint8_t* pt_verdict = nullptr; uint32_t* pt_pixel = nullptr; uint32_t* pt_summary = nullptr;
   BatchRequest(Kind k = Kind::Filter, int n_ = 0, bool u16_ = false) : kind(k), n(n_), u16(u16_) {}
 };
 using Kind = BatchRequest::Kind;
@@ -137,6 +142,15 @@ struct rtuf_context {
   // rewritten in place after that (captured graphs keep its address), and which streams have been given theirs.
   CloudIntrinsics* d_cloud_intr = nullptr;
   std::vector<uint8_t> cloud_intr_set;
+  // Point list batches: fx, fy, cx, cy of every stream as floats, [max_streams], written beside d_cloud_intr by
+  // rtuf_set_cloud_intrinsics, and the streams' optional transforms (rtuf_set_point_transforms; point_tf: the host's copy),
+  // [max_streams], allocated by the first setter or batch that needs them and rewritten in place after that (captured graphs
+  // keep their addresses).  d_pt_stage / pt_stage_bytes: the host form's grow-only staging (points, counts, verdicts, pixels,
+  // summary: one block).
+  PointIntrinsics* d_point_intr = nullptr;
+  PointTransform* d_point_tf = nullptr;
+  std::vector<PointTransform> point_tf;
+  char* d_pt_stage = nullptr; size_t pt_stage_bytes = 0;
   // Link padding: the device tables draw order -> link slot, [n_tris + 1] (entry 0 = 0; a link's slot is 1 + its context-global
   // number), slot -> padding in metres, [n_links + 1] (entry 0 = 0), and stream -> (float)max(fx, fy), [max_streams], allocated
   // by the first rtuf_set_link_padding and rewritten in place after that (captured graphs keep their addresses).  The kernels
@@ -244,6 +258,10 @@ struct rtuf_context {
     // cloud batches: the slot's own bits buffer and row scratch ([2][max_streams][H]: row counts, row starts), allocated on the
     // slot's first (compacted) cloud batch for max_streams, so that captured graphs keep their addresses
     uint32_t* cl_bits = nullptr; uint32_t* cl_rows = nullptr;
+    // point list batches: the virtual depth plane the slot's batch renders into and its points kernel reads, [max_streams][H][W]
+    // float, allocated on the slot's first such batch (one per slot, not per lane: batches in flight keep planes of their own,
+    // and the launch groups of a batch write disjoint streams of it)
+    float* pt_plane = nullptr;
     // clearance batches: the posed spheres of the slot's batch, [max_streams][clr_posed_have], regrown when the context holds more spheres
     float4* clr_posed = nullptr; size_t clr_posed_have = 0;
     Counters* h_counters = nullptr;          // pinned [max_groups]: one block per launch group, filled by the copies that end the batch
@@ -711,7 +729,7 @@ static void free_frame_buffers(rtuf_context* c)
     for (auto*& it : ln.d_items) dev_free(c, it);
   }
   for (auto& b : c->batch) for (auto& st : b.st) { dev_free(c, st.p); st.have = 0; }
-  for (auto& b : c->batch) { dev_free(c, b.cl_bits); dev_free(c, b.cl_rows); dev_free(c, b.st_counts); dev_free(c, b.clr_posed); }
+  for (auto& b : c->batch) { dev_free(c, b.cl_bits); dev_free(c, b.cl_rows); dev_free(c, b.pt_plane); dev_free(c, b.st_counts); dev_free(c, b.clr_posed); }
   for (auto*& p : c->ring_cams) hfree(p);
   for (auto*& p : c->ring_link_tf) hfree(p);
   c->h_cams = nullptr; c->h_link_tf = nullptr;
@@ -743,6 +761,7 @@ void rtuf_destroy(rtuf_context* c)
   dev_free(c, c->d_order_slot); dev_free(c, c->d_slot_pad); dev_free(c, c->d_pad_focal);
   dev_free(c, c->d_order_thr);
   dev_free(c, c->d_cloud_intr);
+  dev_free(c, c->d_point_intr); dev_free(c, c->d_point_tf); dev_free(c, c->d_pt_stage);
   dev_free(c, c->d_clr_spheres); dev_free(c, c->d_clr_slot_label);
   dev_free(c, c->d_scene); dev_free(c, c->d_scene_streams); dev_free(c, c->d_scene_bits); dev_free(c, c->d_scene_stage);
   for (auto& b : c->batch) {
@@ -1427,7 +1446,7 @@ int rtuf_debug_read_poses(rtuf_context* c, int n, double* link_tf_out, double* c
 // the batches of this context write the z-surface: two-kernel mode, a silhouette dilation radius, or link padding in effect
 static bool uses_zsurface(const rtuf_context* c) { return (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 || c->params.silhouette_dilation_px > 0 || c->pad_models > 0; }
 // may write the z-surface, and so needs d_zsurface and moves last_lane (render and residual batches never take that route and leave it alone)
-static bool may_write_zsurface(const BatchRequest& r) { return r.kind != Kind::Render && r.kind != Kind::Residual; }
+static bool may_write_zsurface(const BatchRequest& r) { return r.kind != Kind::Render && r.kind != Kind::Residual && r.kind != Kind::Points; }
 // refused while per-link thresholds meet the z-surface route (check_thresh_route).  Render and residual batches never take that
 // route; a cloud batch takes it for dilation only, which check_cloud_call refuses with thresholds
 static bool subject_to_thresh_route(const BatchRequest& r) { return r.kind == Kind::Filter || r.kind == Kind::Bits; }
@@ -1447,8 +1466,8 @@ static hipEvent_t get_event(rtuf_context::Batch& b, size_t i)
 struct BatchPlan {
   std::vector<FkArgs> fks;
   PoseArgs pa{};
-  // (ca, da, pd, sc, cl, cr: filled and read where the route's post / scene stage / tail has that kernel)
-  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; PadArgs pd{}; SceneArgs sc{}; CloudArgs cl{}; ClearanceArgs cr{}; int lane = 0; };
+  // (ca, da, pd, sc, cl, cr, pt: filled and read where the route's post / scene stage / tail has that kernel)
+  struct Group { SetupArgs sa{}; TileArgs ta{}; CompareArgs ca{}; DilateArgs da{}; PadArgs pd{}; SceneArgs sc{}; CloudArgs cl{}; ClearanceArgs cr{}; PointsArgs pt{}; int lane = 0; };
   std::vector<Group> groups;
   Route route{};                // the batch's (Batch::route): every group runs the same kernels
   uint64_t hash() const
@@ -1465,6 +1484,7 @@ struct BatchPlan {
       if (route.scene) mix(&g.sc, sizeof g.sc);
       if (route.tail == Tail::Cloud) mix(&g.cl, sizeof g.cl);
       if (route.tail == Tail::Clearance) mix(&g.cr, sizeof g.cr);
+      if (route.tail == Tail::Points) mix(&g.pt, sizeof g.pt);
       mix(&g.lane, sizeof g.lane);
     }
     // (the route too: equal argument blocks on another route are other kernels)
@@ -1548,6 +1568,7 @@ static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& 
     if (rt.scene) launch_scene_apply(gr.sc, st);      // the scene's verdict on top of the outputs or bits, before anything reads the bits
     if (rt.tail == Tail::Cloud) launch_cloud(gr.cl, st);
     if (rt.tail == Tail::Clearance) launch_clearance(gr.cr, st);
+    if (rt.tail == Tail::Points) launch_points(gr.pt, st);      // (reads the plane the group's tile_render_kernel just wrote)
     if (b.timing && runs_behind_tile(rt)) mark(e0 + 4, st);
   }
   // every lane publishes the counter blocks of its own groups
@@ -1679,7 +1700,7 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     plan.groups.emplace_back();
     BatchPlan::Group& gr = plan.groups.back();
     memset(&gr.sa, 0, sizeof gr.sa); memset(&gr.ta, 0, sizeof gr.ta); memset(&gr.ca, 0, sizeof gr.ca); memset(&gr.da, 0, sizeof gr.da); memset(&gr.pd, 0, sizeof gr.pd);
-    memset(&gr.cl, 0, sizeof gr.cl); memset(&gr.cr, 0, sizeof gr.cr); memset(&gr.sc, 0, sizeof gr.sc);
+    memset(&gr.cl, 0, sizeof gr.cl); memset(&gr.cr, 0, sizeof gr.cr); memset(&gr.sc, 0, sizeof gr.sc); memset(&gr.pt, 0, sizeof gr.pt);
     gr.lane = n_groups == 1 ? lane0 : g % c->n_lanes;
     const rtuf_context::Lane& ln = c->lane[gr.lane];
     Counters* const d_counters = b.d_counters + g;
@@ -1758,6 +1779,15 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
       cr.table = reinterpret_cast<unsigned long long*>(r.clr);
       cr.n_spheres = used; cr.n_slots = slots; cr.n_links = (int)L; cr.n_labels = r.n_labels;
       cr.group_base = base; cr.group_size = gs; cr.width = c->width; cr.height = c->height; cr.max_distance = r.max_distance; cr.io_u16 = io_u16 ? 1 : 0;
+    }
+    if (route.tail == Tail::Points) {
+      PointsArgs& pt = gr.pt;
+      pt.points = r.pt_points; pt.counts = r.pt_counts; pt.virt = r.virt; pt.intr = c->d_point_intr; pt.tf = c->d_point_tf;
+      pt.verdict = r.pt_verdict; pt.pixel = r.pt_pixel; pt.summary = r.pt_summary;
+      pt.group_base = base; pt.group_size = gs; pt.width = c->width; pt.height = c->height;
+      pt.capacity = r.capacity; pt.radius = r.pt_radius; pt.threshold = c->params.depth_distance_threshold;
+      auto aligned = [](const void* q, uintptr_t to) { return (reinterpret_cast<uintptr_t>(q) & (to - 1u)) == 0u; };
+      pt.wide = (r.capacity & 3) == 0 && aligned(r.pt_points, 16) && aligned(r.pt_verdict, 4) && (!r.pt_pixel || aligned(r.pt_pixel, 16)) ? 1 : 0;
     }
     if (route.post == Post::Compare) {
       CompareArgs& ca = gr.ca;
@@ -1881,7 +1911,7 @@ static int enqueue_download(rtuf_context* c, rtuf_context::Batch& b)
       rc = down(r.masked, b.h_out, plane * esz);
       if (rc == RTUF_OK) rc = down(r.mask, b.h_mask, plane);
       break;
-    case Kind::Cloud: case Kind::Clearance: break;
+    case Kind::Cloud: case Kind::Clearance: case Kind::Points: break;
   }
   if (rc == RTUF_OK && r.labels) rc = down(r.labels, b.h_labels, plane * sizeof(uint16_t));
   if (rc != RTUF_OK) return rc;
@@ -2124,6 +2154,8 @@ static int submit_batch(rtuf_context* c, rtuf_context::Batch& b, const BatchRequ
       b.clr_posed_have = c->clr_spheres.size();
     }
   }
+  if (rq.kind == Kind::Points && !b.pt_plane)
+    HIP_TRY(c, dev_alloc(c, &b.pt_plane, (size_t)c->max_streams * c->width * c->height * sizeof(float)));
   if (uses_zsurface(c) && may_write_zsurface(rq))
     for (int l = 0; l < c->n_lanes; l++)
       if (!c->lane[l].d_zsurface) HIP_TRY(c, dev_alloc(c, &c->lane[l].d_zsurface, (size_t)c->group * c->width * c->height * sizeof(float)));
@@ -2132,6 +2164,7 @@ static int submit_batch(rtuf_context* c, rtuf_context::Batch& b, const BatchRequ
       if (!c->lane[l].d_slots) HIP_TRY(c, dev_alloc(c, &c->lane[l].d_slots, (size_t)c->group * c->width * c->height * sizeof(uint16_t)));
   b.rq = rq;
   if (rq.kind == Kind::Cloud || rq.kind == Kind::Clearance) b.rq.bits = b.cl_bits;
+  if (rq.kind == Kind::Points) { b.rq.virt = b.pt_plane; b.rq.empty_value = INFINITY; }
   b.host_io = false;
   const int rc = enqueue_batch(c, b, false);
   if (rc == RTUF_OK) { b.active = true; c->pending++; }
@@ -2403,6 +2436,7 @@ static int submit_host_planes(rtuf_context* c, BatchRequest rq, const HostPlanes
       rq.index = hp.index ? reinterpret_cast<uint32_t*>(at(B::kStIndex)) : nullptr; rq.counts = rq.capacity ? b.st_counts : nullptr;
       break;
     case Kind::Clearance: rq.clr = reinterpret_cast<rtuf_link_clearance*>(at(B::kStClearance)); break;
+    case Kind::Points: break;      // (never here: the host form stages for itself, rtuf_points_batch)
   }
   { const int rc = submit_batch(c, b, rq); if (rc != RTUF_OK) return rc; }
   if (cloud) return download_cloud(c, rq, hp);
@@ -3072,6 +3106,14 @@ int rtuf_set_cloud_intrinsics(rtuf_context* c, int first, int n, const double* f
     c->cloud_intr_set.assign((size_t)c->max_streams, 0);
   }
   HIP_TRY(c, hipMemcpy(c->d_cloud_intr + first, h.data(), (size_t)n * sizeof(CloudIntrinsics), hipMemcpyHostToDevice));
+  // point list batches project with the focal lengths themselves: fx, fy rounded to float, beside kx, ky
+  std::vector<PointIntrinsics> hp((size_t)n);
+  for (int s = 0; s < n; s++) hp[(size_t)s] = {(float)fx_fy_cx_cy[4 * s], (float)fx_fy_cx_cy[4 * s + 1], (float)fx_fy_cx_cy[4 * s + 2], (float)fx_fy_cx_cy[4 * s + 3]};
+  if (!c->d_point_intr) {
+    HIP_TRY(c, dev_alloc(c, &c->d_point_intr, (size_t)c->max_streams * sizeof(PointIntrinsics)));
+    HIP_TRY(c, hipMemset(c->d_point_intr, 0, (size_t)c->max_streams * sizeof(PointIntrinsics)));
+  }
+  HIP_TRY(c, hipMemcpy(c->d_point_intr + first, hp.data(), (size_t)n * sizeof(PointIntrinsics), hipMemcpyHostToDevice));
   std::fill(c->cloud_intr_set.begin() + first, c->cloud_intr_set.begin() + first + n, (uint8_t)1);
   return RTUF_OK;
 }
@@ -3175,6 +3217,122 @@ int rtuf_cloud_compact_batch_u16(rtuf_context* c, int n, const uint16_t* const* 
                                  uint32_t* counts_out, int capacity)
 {
   return cloud_host_batch(c, n, reinterpret_cast<const void* const*>(depth_mm_in), points_out, index_out, counts_out, capacity, true, true);
+}
+
+// ---- point list batches ------------------------------------------------------------------------------
+// A points batch (Kind::Points) is a render batch into the slot's own float plane (empty pixels +inf) whose launch groups run
+// the points kernel behind their tile_render_kernel (issue_plan): no sensor plane is read, no image plane returned.
+static int ensure_point_transforms(rtuf_context* c)
+{
+  if (c->d_point_tf) return RTUF_OK;
+  c->point_tf.assign((size_t)c->max_streams, PointTransform{});
+  HIP_TRY(c, dev_alloc(c, &c->d_point_tf, (size_t)c->max_streams * sizeof(PointTransform)));
+  HIP_TRY(c, hipMemset(c->d_point_tf, 0, (size_t)c->max_streams * sizeof(PointTransform)));
+  return RTUF_OK;
+}
+
+int rtuf_set_point_transforms(rtuf_context* c, int first, int n, const double* optical_from_points)
+{
+  KIDS_ALL(c, rtuf_set_point_transforms(k, first, n, optical_from_points));
+  if (!c) return RTUF_ERR_INVALID;
+  if (first < 0 || n <= 0 || n > c->max_streams || first > c->max_streams - n) return c->fail(RTUF_ERR_INVALID, "bad stream range (first=%d, n=%d)", first, n);
+  if (optical_from_points)
+    for (int s = 0; s < n; s++)
+      for (int col = 0; col < 4; col++)
+        for (int r = 0; r < 3; r++)
+          if (!std::isfinite(optical_from_points[16 * s + 4 * col + r]) || !std::isfinite((float)optical_from_points[16 * s + 4 * col + r]))
+            return c->fail(RTUF_ERR_INVALID, "stream %d: the point transform has a non-finite entry (row %d, column %d)", first + s, r, col);
+  WAIT_IF_PENDING(c);
+  hipSetDevice(c->device);
+  if (!optical_from_points && !c->d_point_tf) return RTUF_OK;      // (none was ever set: nothing to take back)
+  { const int rc = ensure_point_transforms(c); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; s < n; s++) {
+    PointTransform t{};
+    if (optical_from_points) {
+      for (int i = 0; i < 16; i++) t.m[i] = (i & 3) == 3 ? 0.0f : (float)optical_from_points[16 * s + i];
+      t.on = 1u;
+    }
+    c->point_tf[(size_t)(first + s)] = t;
+  }
+  HIP_TRY(c, hipMemcpy(c->d_point_tf + first, c->point_tf.data() + first, (size_t)n * sizeof(PointTransform), hipMemcpyHostToDevice));
+  return RTUF_OK;
+}
+
+static int check_points_call(rtuf_context* c, int n, bool have_args, long long capacity, int radius)
+{
+  { const int rc = check_batch_call(c, n, have_args, false); if (rc != RTUF_OK) return rc; }
+  if (capacity < 1 || capacity > (long long)kMaxPointsCapacity) return c->fail(RTUF_ERR_INVALID, "capacity = %lld: 1 .. %d", capacity, kMaxPointsCapacity);
+  if (radius < 0 || radius > kMaxPointsRadius) return c->fail(RTUF_ERR_INVALID, "radius_px = %d: 0 .. %d", radius, kMaxPointsRadius);
+  if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "point list batches are not supported with silhouette dilation yet (radius_px is this batch's own margin)");
+  if (c->pad_models > 0) return c->fail(RTUF_ERR_INVALID, "point list batches are not supported with link padding yet");
+  if (c->thresh_models > 0) return c->fail(RTUF_ERR_INVALID, "point list batches are not supported with per-link depth thresholds yet");
+  for (int s = 0; s < n; s++)
+    if (!c->d_point_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
+  return ensure_point_transforms(c);
+}
+
+static BatchRequest points_request(int n, const float* d_points, const uint32_t* d_counts, int capacity, int radius, uint8_t* d_verdict,
+                                   uint32_t* d_pixel, uint32_t* d_summary)
+{
+  BatchRequest rq(Kind::Points, n, false);
+  rq.pt_points = d_points; rq.pt_counts = d_counts; rq.capacity = capacity; rq.pt_radius = radius;
+  rq.pt_verdict = d_verdict; rq.pt_pixel = d_pixel; rq.pt_summary = d_summary;
+  return rq;
+}
+
+int rtuf_points_batch_device(rtuf_context* c, int n, const float* d_points, const uint32_t* d_counts, int capacity, int radius_px,
+                             uint8_t* d_verdict, uint32_t* d_pixel, uint32_t* d_summary)
+{
+  KIDS_NEXT(c, rtuf_points_batch_device(k, n, d_points, d_counts, capacity, radius_px, d_verdict, d_pixel, d_summary));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_points_call(c, n, d_points && d_counts && d_verdict, capacity, radius_px);
+  return rc != RTUF_OK ? rc : submit_device(c, points_request(n, d_points, d_counts, capacity, radius_px, d_verdict, d_pixel, d_summary));
+}
+
+// host lists, synchronous: the lists go up into one block of the context's (points, counts, verdicts, pixels, summary; every
+// part on a 16-byte boundary), the batch runs on it with capacity = the largest count, and min(count, capacity) = count
+// entries per stream come down once the batch is retired, re-runs included
+int rtuf_points_batch(rtuf_context* c, int n, const float* const* points_in, const uint32_t* counts, int radius_px,
+                      uint8_t* const* verdict_out, uint32_t* const* pixel_out, uint32_t* summary_out)
+{
+  KIDS_NEXT(c, rtuf_points_batch(k, n, points_in, counts, radius_px, verdict_out, pixel_out, summary_out));
+  if (!c) return RTUF_ERR_INVALID;
+  long long cap = 1;
+  if (counts && n > 0 && n <= c->max_streams) for (int s = 0; s < n; s++) cap = std::max<long long>(cap, (long long)counts[s]);
+  { const int rc = check_points_call(c, n, points_in && counts && verdict_out, cap, radius_px); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; s < n; s++)
+    if (counts[s] && (!points_in[s] || !verdict_out[s] || (pixel_out && !pixel_out[s]))) return c->fail(RTUF_ERR_INVALID, "null list for stream %d", s);
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }      // (the block may still be read by an earlier call's batch)
+  hipSetDevice(c->device);
+  const size_t capacity = (size_t)((cap + 3) & ~3ll);                // (a multiple of 4: the kernel's wide path)
+  auto up16 = [](size_t b) { return (b + 15u) & ~(size_t)15u; };
+  const size_t o_points = 0, o_counts = o_points + up16((size_t)n * capacity * 3u * sizeof(float)), o_verdict = o_counts + up16((size_t)n * sizeof(uint32_t));
+  const size_t o_pixel = o_verdict + up16((size_t)n * capacity), o_summary = o_pixel + up16(pixel_out ? (size_t)n * capacity * sizeof(uint32_t) : 0);
+  const size_t bytes = o_summary + up16((size_t)n * 4u * sizeof(uint32_t));
+  if (c->pt_stage_bytes < bytes) {
+    dev_free(c, c->d_pt_stage);
+    c->pt_stage_bytes = 0;
+    HIP_TRY(c, dev_alloc(c, &c->d_pt_stage, bytes));
+    c->pt_stage_bytes = bytes;
+  }
+  char* const d = c->d_pt_stage;
+  for (int s = 0; s < n; s++)
+    if (counts[s]) HIP_TRY(c, hipMemcpy(d + o_points + (size_t)s * capacity * 3u * sizeof(float), points_in[s], (size_t)counts[s] * 3u * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d + o_counts, counts, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  {
+    const int rc = submit_device(c, points_request(n, reinterpret_cast<const float*>(d + o_points), reinterpret_cast<const uint32_t*>(d + o_counts), (int)capacity, radius_px,
+                                                   reinterpret_cast<uint8_t*>(d + o_verdict), pixel_out ? reinterpret_cast<uint32_t*>(d + o_pixel) : nullptr,
+                                                   reinterpret_cast<uint32_t*>(d + o_summary)));
+    if (rc != RTUF_OK) return rc;
+  }
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; s < n; s++) {
+    if (!counts[s]) continue;
+    HIP_TRY(c, hipMemcpy(verdict_out[s], d + o_verdict + (size_t)s * capacity, (size_t)counts[s], hipMemcpyDeviceToHost));
+    if (pixel_out) HIP_TRY(c, hipMemcpy(pixel_out[s], d + o_pixel + (size_t)s * capacity * sizeof(uint32_t), (size_t)counts[s] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  if (summary_out) HIP_TRY(c, hipMemcpy(summary_out, d + o_summary, (size_t)n * 4u * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RTUF_OK;
 }
 
 // ---- link clearance tables ---------------------------------------------------------------------------

@@ -13,6 +13,8 @@
 //     link_tf f64[N][L][16]                                         (two slots: one per batch in flight)
 //     mvp    f32[N][D][16]  written by pose_kernel;  bg BgInfo[N];  items WorkItem[] written by cull_kernel (one list per raster lane)
 //     depth  f32[N][H][W] in, masked f32[N][H][W] + mask u8[N][H][W] out
+//     pt_plane f32[max_streams][H][W]  point list batches only, one per batch slot: the virtual depth the slot's batch renders
+//                                      and its points kernel reads (empty pixels +inf)
 //   rasteriser working set of ONE RASTER LANE (a context has one to three: a lane is a HIP stream plus the arrays below; the
 //   launch groups of a batch alternate between the lanes, so one group's set-up runs under the other's tile kernel),
 //   per stream g of the launch group and screen tile
@@ -452,6 +454,32 @@ struct ClearanceArgs {
   int io_u16;
 };
 
+// Point list batches (include/rtuf.h, POINT LIST BATCHES): the points kernel of one launch group.  It runs behind the group's
+// tile_render_kernel on its lane and reads the virtual depth plane that kernel wrote (the batch slot's own, float, empty
+// pixels +inf); streams are batch-absolute.  PointTransform: the 12 used entries of a stream's column-major matrix as floats
+// (m[4 * c + r]; the last row is not read), on = 0: the stream takes its points as given.
+struct PointIntrinsics;
+struct alignas(16) PointTransform { float m[16]; uint32_t on; uint32_t pad[3]; };
+constexpr int kMaxPointsRadius = 4;
+constexpr int kMaxPointsCapacity = 1 << 24;
+constexpr int kPointsPerThread = 4;
+struct PointsArgs {
+  const float* points;           // [n][capacity][3]
+  const uint32_t* counts;        // [n], on the device: stream s judges entries j < min(counts[s], capacity)
+  const float* virt;             // [max_streams][H][W] the slot's virtual depth plane
+  const PointIntrinsics* intr;   // [max_streams] fx, fy, cx, cy
+  const PointTransform* tf;      // [max_streams]
+  uint8_t* verdict;              // [n][capacity]
+  uint32_t* pixel;               // [n][capacity] v * W + u, 0xffffffff for a point that is not judged; or nullptr
+  uint32_t* summary;             // [n][4] kept, filtered, outside, min(count, capacity); or nullptr.  Zeroed in front of the kernel
+  int group_base, group_size;
+  int width, height;
+  int capacity, radius;
+  float threshold;
+  int wide;                      // points and pixel start on 16-byte boundaries, verdict on a 4-byte one, capacity % 4 == 0: a
+                                 // thread's four points are three 16-byte loads, its verdicts one word, its pixels one 16-byte store
+};
+
 // Scene planes (include/rtuf.h, SCENE PLANES): per stream one float plane of the empty scene in metres, margins and a switch.
 // The scene kernels of one launch group run behind whatever wrote the group's outputs and in front of the kernels that read
 // its mask bits; streams are batch-absolute, and a stream whose filtering is disabled is skipped.
@@ -510,6 +538,7 @@ void launch_dilate_compare(const DilateArgs& a, hipStream_t st);     // a.bits s
 void launch_pad_compare(const PadArgs& a, hipStream_t st);           // as launch_dilate_compare
 void launch_cloud(const CloudArgs& a, hipStream_t st);               // a.capacity selects the compacted form (count, scan, emit), a.io_u16 the 16UC1 variants
 void launch_clearance(const ClearanceArgs& a, hipStream_t st);       // spheres, zero, clearance, finish: the group's rows of the table, a.io_u16 selects the 16UC1 variant
+void launch_points(const PointsArgs& a, hipStream_t st);             // the group's rows of the summary to zero (a.summary), then points_filter_kernel
 void launch_scene_apply(const SceneArgs& a, hipStream_t st);         // a.bits selects scene_apply_bits_kernel, else scene_apply_planes_kernel; a.io_u16 the 16UC1 variants
 void launch_scene_learn(const SceneLearnArgs& a, hipStream_t st);
 void launch_fill_f32(float* p, size_t n, float v, hipStream_t st);

@@ -3919,6 +3919,129 @@ void launch_scene_learn(const SceneLearnArgs& a, hipStream_t st)
   else hipLaunchKernelGGL(scene_learn_kernel<false>, grid, dim3(kBlock), 0, st, a);
 }
 
+// ---- point list batches (include/rtuf.h, POINT LIST BATCHES) -------------------------------------------------------------
+// Behind the launch group's tile_render_kernel on its lane: every point of every stream of the group is projected into its
+// stream's virtual depth plane (point_pixel), compared with the smallest value of its window there (point_verdict) and given
+// a verdict byte.  A latency-bound gather: a thread takes kPointsPerThread consecutive points of one stream, so their window
+// loads are in flight together, a wave's point loads are contiguous 12-byte triples (three 16-byte loads per thread on the
+// wide path) and the verdicts leave as words.  Integers only in the summary: no result depends on the order of execution.
+// grid: (ceil(capacity / (kBlock * kPointsPerThread)), group_size).
+
+__global__ __launch_bounds__(kBlock) void points_zero_summary_kernel(uint32_t* rows, int n_words)
+{
+  const int i = (int)(blockIdx.x * (uint32_t)kBlock + threadIdx.x);
+  if (i < n_words) rows[i] = 0u;
+}
+
+// The smallest value of the (2R + 1)^2 window around (u, v), its rows and columns clamped to the stream's image -- never padded,
+// never in a neighbouring plane; a clamped index reads a pixel of the window a second time, which no minimum notices.  The
+// radius is a template argument so that a row's 2R + 1 loads are issued together.
+template <int R>
+__device__ __forceinline__ float points_window_min(const float* __restrict__ plane, int u, int v, int width, int height)
+{
+  float vmin = INFINITY;
+#pragma unroll 1
+  for (int dy = -R; dy <= R; dy++) {
+    const float* row = plane + (size_t)min(max(v + dy, 0), height - 1) * (size_t)width;
+    float q[2 * R + 1];
+#pragma unroll
+    for (int dx = -R; dx <= R; dx++) q[dx + R] = row[min(max(u + dx, 0), width - 1)];
+#pragma unroll
+    for (int dx = 0; dx <= 2 * R; dx++) vmin = fminf(vmin, q[dx]);
+  }
+  return vmin;
+}
+
+template <int R>
+__global__ __launch_bounds__(kBlock) void points_filter_kernel(PointsArgs a)
+{
+  const int stream = a.group_base + (int)blockIdx.y;
+  const uint32_t capacity = (uint32_t)a.capacity;
+  const uint32_t have = a.counts[stream];
+  const uint32_t m = have < capacity ? have : capacity;
+  if (a.summary && blockIdx.x == 0 && threadIdx.x == 0) a.summary[(size_t)stream * 4u + 3u] = m;
+  const uint32_t t = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  const uint32_t j0 = t * (uint32_t)kPointsPerThread;
+  // (wave-uniform: the wave's first point is its lane 0's; lanes past m stay for the ballots and load nothing)
+  if ((j0 & ~(64u * (uint32_t)kPointsPerThread - 1u)) >= m) return;
+  const size_t base = (size_t)stream * (size_t)capacity + (size_t)j0;
+  const uint32_t live = j0 >= m ? 0u : (m - j0 < (uint32_t)kPointsPerThread ? m - j0 : (uint32_t)kPointsPerThread);
+  const bool whole = a.wide && live == (uint32_t)kPointsPerThread;
+  float p[3 * kPointsPerThread];
+  if (whole) {
+    const float4* src = reinterpret_cast<const float4*>(a.points + base * 3u);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      const float4 q = src[i];
+      p[4 * i] = q.x; p[4 * i + 1] = q.y; p[4 * i + 2] = q.z; p[4 * i + 3] = q.w;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3 * kPointsPerThread; i++) p[i] = (uint32_t)(i / 3) < live ? a.points[base * 3u + (size_t)i] : 0.0f;
+  }
+  const PointIntrinsics k = a.intr[stream];
+  const PointTransform* tf = a.tf + stream;
+  const bool moved = tf->on != 0u;
+  const float* plane = a.virt + (size_t)stream * (size_t)a.width * (size_t)a.height;
+  uint32_t verdict[kPointsPerThread], pixel[kPointsPerThread];
+#pragma unroll
+  for (int i = 0; i < kPointsPerThread; i++) {
+    float x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
+    if (moved) point_transform(tf->m, x, y, z);
+    int u, v;
+    verdict[i] = kPointOutside;
+    pixel[i] = kPointNoPixel;
+    if ((uint32_t)i < live && point_pixel(x, y, z, k, a.width, a.height, u, v)) {
+      verdict[i] = point_verdict(z, points_window_min<R>(plane, u, v, a.width, a.height), a.threshold);
+      pixel[i] = (uint32_t)(v * a.width + u);
+    }
+  }
+  if (whole) {
+    *reinterpret_cast<uint32_t*>(a.verdict + base) = verdict[0] | verdict[1] << 8 | verdict[2] << 16 | verdict[3] << 24;
+    if (a.pixel) *reinterpret_cast<uint4*>(a.pixel + base) = make_uint4(pixel[0], pixel[1], pixel[2], pixel[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < kPointsPerThread; i++)
+      if ((uint32_t)i < live) {
+        a.verdict[base + (size_t)i] = (uint8_t)verdict[i];
+        if (a.pixel) a.pixel[base + (size_t)i] = pixel[i];
+      }
+  }
+  if (a.summary) {
+    // per wave and class: the ballots of the lanes' points, one vector atomic from the wave's first lane
+    uint32_t total[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < kPointsPerThread; i++)
+#pragma unroll
+      for (uint32_t c = 0; c < 3u; c++) total[c] += (uint32_t)__popcll(__ballot((uint32_t)i < live && verdict[i] == c));
+    if ((threadIdx.x & 63u) == 0u)
+#pragma unroll
+      for (int c = 0; c < 3; c++)
+        if (total[c]) atomicAdd(a.summary + (size_t)stream * 4u + (size_t)c, total[c]);
+  }
+}
+static_assert(kPointsPerThread == 4, "points_filter_kernel packs four verdicts into a word and four pixels into a 16-byte store");
+
+void launch_points(const PointsArgs& a, hipStream_t st)
+{
+  if (a.summary) {
+    const int n_words = a.group_size * 4;
+    hipLaunchKernelGGL(points_zero_summary_kernel, dim3((unsigned)((n_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                       a.summary + (size_t)a.group_base * 4u, n_words);
+  }
+  const unsigned per_block = (unsigned)kBlock * (unsigned)kPointsPerThread;
+  const dim3 grid(((unsigned)a.capacity + per_block - 1u) / per_block, (unsigned)a.group_size);
+  switch (a.radius) {      // (0 .. kMaxPointsRadius: the call's checks admit nothing else)
+    case 0: hipLaunchKernelGGL(points_filter_kernel<0>, grid, dim3(kBlock), 0, st, a); break;
+    case 1: hipLaunchKernelGGL(points_filter_kernel<1>, grid, dim3(kBlock), 0, st, a); break;
+    case 2: hipLaunchKernelGGL(points_filter_kernel<2>, grid, dim3(kBlock), 0, st, a); break;
+    case 3: hipLaunchKernelGGL(points_filter_kernel<3>, grid, dim3(kBlock), 0, st, a); break;
+    case 4: hipLaunchKernelGGL(points_filter_kernel<4>, grid, dim3(kBlock), 0, st, a); break;
+    default: break;
+  }
+  static_assert(kMaxPointsRadius == 4, "launch_points names an instantiation per radius");
+}
+
 __global__ __launch_bounds__(kBlock) void fill_f32_kernel(float* p, size_t n, float v)
 {
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) p[i] = v;

@@ -1,9 +1,9 @@
 // rtuf_numerics.h -- the arithmetic whose exact bits the results depend on and that something besides the kernels checks or
 // shares: the 24-bit depth and its bit-pattern forms, the depth keys' encoding of a near fragment's float z, the set-up's
 // 32-bit edge constants, the key format's host-side rules, the compare threshold's constants, division core and the rule
-// that admits that core, the pixel classes of the link residual tables, the point of a filtered point cloud, the sphere centres and
-// point-to-sphere clearances of the link clearance tables, the reach of a padded link's pixel, the scene planes' threshold and
-// learning rule, and the set-up kernel's packed list counters.
+// that admits that core, the pixel classes of the link residual tables, the point of a filtered point cloud, the pixel and
+// verdict of a listed point, the sphere centres and point-to-sphere clearances of the link clearance tables, the reach of a
+// padded link's pixel, the scene planes' threshold and learning rule, and the set-up kernel's packed list counters.
 //
 // Included by the kernels (rtuf_kernels.hip, device and host pass), the host API (rtuf_api.cpp), scripts/fdiv_check.hip (which
 // holds div_core against the IEEE division on the GPU) and the CPU checks (tests/fast_class_check.cpp, tests/near_key_check.cpp:
@@ -194,6 +194,53 @@ RTUF_NUMERIC_HD void cloud_point(int u, int v, float s, const CloudIntrinsics& k
   y = ys * k.ky;
   z = s;
 }
+
+// ---------------------------------------------------------------------------------------
+// point list batches (include/rtuf.h, POINT LIST BATCHES): the pixel a point lands on -- the inverse of cloud_point -- and its
+// verdict.  Products feed sums here: the includers compile with -ffp-contract=off (the library, tests/point_pixel_check.cpp).
+// ---------------------------------------------------------------------------------------
+
+// Per-stream pinhole as the points kernel reads it: fx = (float)fx, fy = (float)fy, cx, cy (beside CloudIntrinsics' kx, ky).
+struct PointIntrinsics { float fx, fy, cx, cy; };
+
+// Verdicts of a point.
+enum : uint32_t { kPointKept = 0u, kPointFiltered = 1u, kPointOutside = 2u };
+constexpr uint32_t kPointNoPixel = 0xffffffffu;
+
+// The optional per-stream transform: m holds the 12 used entries of a column-major matrix as floats, m[4 * c + r] = entry
+// (r, c), r < 3 (the last row is not read).  p'_r = ((m[r] x + m[4 + r] y) + m[8 + r] z) + m[12 + r].
+RTUF_NUMERIC_HD void point_transform(const float* m, float& x, float& y, float& z)
+{
+  float o[3];
+  for (int r = 0; r < 3; r++) {
+    const float a = m[r] * x, b = m[4 + r] * y, c = m[8 + r] * z;
+    o[r] = ((a + b) + c) + m[12 + r];
+  }
+  x = o[0]; y = o[1]; z = o[2];
+}
+
+// Is the point judged, and on which pixel does it land?  uf = ((x / z) * fx + cx) + 0.5f, vf likewise (IEEE division); the
+// range tests come before the conversions, so no out-of-range float (NaN included) is ever converted and no index outside
+// the plane is ever formed.
+RTUF_NUMERIC_HD bool point_pixel(float x, float y, float z, const PointIntrinsics& k, int W, int H, int& u, int& v)
+{
+  u = 0; v = 0;
+  if (!(z > 0.0f && z < INFINITY)) return false;
+#ifdef __HIP_DEVICE_COMPILE__
+  const float a = __fdiv_rn(x, z), b = __fdiv_rn(y, z);
+#else
+  const float a = x / z, b = y / z;
+#endif
+  const float au = a * k.fx, bv = b * k.fy;
+  const float uf = (au + k.cx) + 0.5f, vf = (bv + k.cy) + 0.5f;
+  if (!(uf >= 0.0f && uf < (float)W && vf >= 0.0f && vf < (float)H)) return false;
+  u = (int)uf; v = (int)vf;
+  return true;
+}
+
+// A judged point of depth z against the smallest virtual depth vmin of its window and the threshold t: filtered iff
+// z > vmin - t (one float subtraction; vmin = +inf where no link drew, and then nothing is above it).
+RTUF_NUMERIC_HD uint32_t point_verdict(float z, float vmin, float t) { return z > vmin - t ? kPointFiltered : kPointKept; }
 
 // ---------------------------------------------------------------------------------------
 // link clearance tables (include/rtuf.h, LINK CLEARANCE TABLES): a sphere's centre in the camera frame, and the clearance of

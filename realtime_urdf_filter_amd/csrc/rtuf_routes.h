@@ -12,7 +12,7 @@
 namespace rtuf {
 
 // What a caller can ask for (BatchRequest::kind).
-enum class BatchKind { Filter, Bits, Render, Residual, Cloud, Clearance };
+enum class BatchKind { Filter, Bits, Render, Residual, Cloud, Clearance, Points };
 
 // What the tile kernel leaves behind for every pixel:
 //   Planes    masked depth plane + optional byte mask, compared in the kernel (the fused route)        tile_kernel & co.
@@ -55,8 +55,8 @@ constexpr int tile_variant_index(TileVariant v)
 // outputs (scene), then the kernels that read the mask bits (Tail).
 enum class Post { None, Compare, Dilate, Pad };
 constexpr int kPosts = 4;
-enum class Tail { None, Cloud, Clearance };
-constexpr int kTails = 3;
+enum class Tail { None, Cloud, Clearance, Points };
+constexpr int kTails = 4;
 
 // ok == false: a combination the API refuses.  scene (last: older brace lists leave it false): scene_apply_planes_kernel behind
 // a Filter batch's outputs, scene_apply_bits_kernel behind the mask bits of a Bits, Cloud or Clearance batch.
@@ -91,6 +91,7 @@ struct RouteFacts {
 //   Residual                                   Residual      thresh, u16            -
 //   Cloud                                      Bits          thresh, u16            Cloud
 //   Clearance                                  Bits          thresh, u16            Clearance
+//   Points                                     Render        -                      Points
 // The two-kernel flag is for full planes: the mask-bits calls refuse it, the other kinds run as if it were not set.
 // Thresholds do not enter a render batch.  Refused: a label plane beside anything but a filter or render batch, or with
 // dilation; dilation with a render or residual batch; thresholds on the z-surface route.  Link padding goes over the
@@ -98,10 +99,22 @@ struct RouteFacts {
 // a render or residual batch, dilation or thresholds.
 // Scene planes refuse nothing and change nothing in front of them: a Filter, Bits, Cloud or Clearance batch takes the route it
 // would take without, plus the scene stage between Post and Tail; render and residual batches compare nothing against the scene.
+// A point list batch (include/rtuf.h, POINT LIST BATCHES) is a render batch into a float plane of the library's with the points
+// kernel behind it, whatever the other facts say: the two-kernel flag and the scene do not enter, and dilation, padding and
+// thresholds are refused (they are not honoured yet).
 constexpr Route route_of(const RouteFacts& f)
 {
   const bool filter = f.kind == BatchKind::Filter, bits = f.kind == BatchKind::Bits;
   const bool render = f.kind == BatchKind::Render, residual = f.kind == BatchKind::Residual;
+  if (f.kind == BatchKind::Points) {
+    Route p{};
+    p.tile = TileVariant{TileOut::Render, false, false, false, f.cover};
+    p.post = Post::None;
+    p.tail = Tail::Points;
+    p.ok = !f.labels && f.dilation <= 0 && !f.padded && !f.thresh;
+    p.scene = false;
+    return p;
+  }
   const bool dilated = f.dilation > 0, two = f.two_kernel && filter, thresh = f.thresh && !render;
   bool ok = !(f.labels && !filter && !render) && !(dilated && (f.labels || render || residual)) && !(f.two_kernel && bits);
   Route r{};

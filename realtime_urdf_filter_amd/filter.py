@@ -482,6 +482,31 @@ class RealtimeURDFFilter:
         points, index, counts = self._ctx.cloud_compact_batch(d, width * height)
         return points[0, :counts[0]], index[0, :counts[0]]
 
+    def filter_points(self, points, projection_matrix, width, height, timestamp=None, radius_px=0):
+        """New, beyond the reference: a point list instead of a depth image (include/rtuf.h, POINT LIST BATCHES) -- a lidar's
+        points, a cloud that was cropped or transformed, the compact output of cloud() -- for the camera and link poses filter()
+        would use and the intrinsics of the last getProjectionMatrix(), as cloud() takes them.
+        points: [count,3] float32 in the camera's optical frame (x right, y down, z forward); radius_px 0 .. 4 widens the robot
+        by that many pixels.  Returns (verdict [count] uint8 -- 0 kept, 1 filtered: on the robot, 2 outside the image or without
+        a positive finite z --, pixel [count] uint32 = v * width + u, 0xFFFFFFFF where the verdict is 2, summary [4] uint32: kept,
+        filtered, outside, count); None where filter() would have returned without a result."""
+        self._ensure_size(width, height)
+        if not self.renderers_:
+            return None
+        intr = getattr(self, "cloud_intrinsics_", None)
+        if intr is None:
+            raise RuntimeError("filter_points(): no intrinsics yet (getProjectionMatrix sets them)")
+        try:
+            self._stage_stream(0, projection_matrix, self.tf_, timestamp)
+        except Exception as e:                      # noqa: BLE001 - ROS_ERROR + return (quirk Q6)
+            log.error("%s", e)
+            return None
+        if getattr(self, "_cloud_intr_given_", None) != intr:      # (initGL clears it with every new context)
+            self._ctx.set_cloud_intrinsics(0, intr)
+            self._cloud_intr_given_ = intr
+        verdict, pixel, summary = self._ctx.points_batch([np.asarray(points, np.float32).reshape(-1, 3)], radius_px)
+        return verdict[0], pixel[0], summary[0]
+
     def setLinkSpheres(self, model, link, xyzr):
         """New, beyond the reference: the sphere list of model `model` (index into the loaded models) for clearance(): link [n] =
         renderable index within the model, xyzr [n,4] = centre in the renderable's (link's) frame -- a draw's pre_op applied to its

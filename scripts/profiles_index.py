@@ -121,6 +121,7 @@ def build(tag):
     text("filtered point clouds on c3: cloud batches beside the mask-bits batch and beside filter + torch ops", ["README.md", "DESIGN.md 4"], "cloud_rate_c3.txt", "the last line")
     text("link clearance tables on c3: clearance batches beside the mask-bits batch and beside compacted cloud + torch ops", ["README.md", "DESIGN.md 4"], "clearance_rate_c3.txt", "the last line")
     text("link padding on c3: padded mask-bits and cloud batches beside the dilated leg of the same run", ["README.md", "DESIGN.md 4"], "link_padding_rate_c3.txt", "the last line")
+    text("point list batches on c3: points batches beside the render batch they are built on and beside render + torch ops", ["README.md", "DESIGN.md 4"], "points_rate_c3.txt", "the last line")
     f = "scene_rate_c3.txt"
     if os.path.exists(os.path.join(PROFILES, f)):
         body = open(os.path.join(PROFILES, f)).read().splitlines()
@@ -156,6 +157,7 @@ def build(tag):
                            ("wave_roles_same_box.txt", "set-up kernel's phase 3 without its barrier: the parts one by one, and the parent beside the tree on one box", ["DESIGN.md 4", "docs/experiments.md R8"]),
                            ("wave_roles_kernel_stats_parent.csv", "rocprofv3 --kernel-trace --stats of bench.py --lanes 1, parent of R8", ["docs/experiments.md R8"]),
                            ("wave_roles_kernel_stats_tree.csv", "... and the tree with R8 (setup_kernel 231.1 -> 221.1 us)", ["DESIGN.md 4", "docs/experiments.md R8"]),
+                           ("points_same_box.txt", "the default benchmark on the parent commit's tree and on the tree with point list batches, alternating on one box", ["DESIGN.md 4"]),
                            ("overdraw.json", "depth tests per drawn pixel", ["bench.py rasteriser.tile.overdraw"]),
                            ("valu_peak.json", "measured VALU issue rates per instruction (two classes)", ["DESIGN.md 4", "docs/experiments.md A.1"]),
                            ("llvmpipe_baseline.json", "the reference's GLSL on llvmpipe at BASELINE sizes (development container)", ["DESIGN.md 2", "BASELINE.md"])):
