@@ -1441,15 +1441,50 @@ int rtuf_debug_read_poses(rtuf_context* c, int n, double* link_tf_out, double* c
 }
 
 // ---- what a batch of each kind does ----
-// Which kernels it runs is its route (route_of in rtuf_routes.h, asked once by enqueue_batch; a new kind starts there).  The
-// predicates below are what is asked BEFORE a batch has a route: by the calls' checks and when a slot's buffers are allocated.
+// Which kernels it runs, or why none, is its route (route_of in rtuf_routes.h, asked by check_route for the calls and once by
+// enqueue_batch; a new kind starts there).  The two predicates below are still asked BEFORE a batch has a route -- when a slot is
+// taken (the in-flight limit of one) and when its buffers are allocated (the z-surface and slot planes, last_lane) -- and say
+// more than the route would: a cloud batch under the two-kernel flag never takes the z-surface route, but its context has always
+// allocated the z-surface for it, and rtuf_stats.device_bytes counts it.
 // the batches of this context write the z-surface: two-kernel mode, a silhouette dilation radius, or link padding in effect
 static bool uses_zsurface(const rtuf_context* c) { return (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0 || c->params.silhouette_dilation_px > 0 || c->pad_models > 0; }
 // may write the z-surface, and so needs d_zsurface and moves last_lane (render and residual batches never take that route and leave it alone)
 static bool may_write_zsurface(const BatchRequest& r) { return r.kind != Kind::Render && r.kind != Kind::Residual && r.kind != Kind::Points; }
-// refused while per-link thresholds meet the z-surface route (check_thresh_route).  Render and residual batches never take that
-// route; a cloud batch takes it for dilation only, which check_cloud_call refuses with thresholds
-static bool subject_to_thresh_route(const BatchRequest& r) { return r.kind == Kind::Filter || r.kind == Kind::Bits; }
+
+// The facts the route of a request follows from, as the context stands (r.labels: only whether there is one is asked).
+static RouteFacts route_facts(const rtuf_context* c, const BatchRequest& r)
+{
+  return RouteFacts{r.kind, r.u16, r.labels != nullptr, c->thresh_models > 0, (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0, (int)c->params.silhouette_dilation_px,
+                    c->cover_on, c->pad_models > 0, c->scene_enabled > 0 && !r.robot_only};
+}
+
+// Refuses the request if it has no route, with the reason's message (rtuf_routes.h, enum class Refusal: the rules and their
+// order).  Every batch call asks once, behind the checks of its own arguments and before it builds, allocates, stages or
+// enqueues anything: a refused call leaves the context as it found it.
+static int check_route(rtuf_context* c, const BatchRequest& r)
+{
+  static const char* const text[] = {
+    nullptr,
+    "internal: a label plane for a batch kind that has none",      // (NoLabelPlane: no call has the argument)
+    "link labels are not supported with silhouette dilation yet",
+    "link labels are not supported with link padding yet",
+    "virtual depth is not supported with silhouette dilation yet",
+    "virtual depth is not supported with link padding yet",
+    "link residual tables are not supported with silhouette dilation yet",
+    "link residual tables are not supported with link padding yet",
+    "silhouette dilation is not supported with link padding yet",
+    "per-link depth thresholds are not supported with link padding yet",
+    "per-link depth thresholds are not supported with RTUF_FLAG_TWO_KERNEL or silhouette dilation yet",
+    "per-link depth thresholds are not supported with silhouette dilation yet",
+    "mask-bits output exists in fused mode only (RTUF_FLAG_TWO_KERNEL is set)",
+    "point list batches are not supported with silhouette dilation yet (radius_px is this batch's own margin)",
+    "point list batches are not supported with link padding yet",
+    "point list batches are not supported with per-link depth thresholds yet",
+  };
+  static_assert(sizeof text / sizeof *text == (size_t)Refusal::PointsThresh + 1, "one message per reason, in the enum's order");
+  const Refusal why = route_of(route_facts(c, r)).why;
+  return why == Refusal::None ? RTUF_OK : c->fail(RTUF_ERR_INVALID, "%s", text[(int)why]);
+}
 
 // ---- the hot path ---------------------------------------------------------------------
 static hipEvent_t get_event(rtuf_context::Batch& b, size_t i)
@@ -1599,13 +1634,11 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
     return c->fail(RTUF_ERR_STATE, "internal: %d launch groups for %d streams, but counter blocks for %d", n_groups, n, c->max_groups);
   if ((n + per_group - 1) / per_group != n_groups)
     return c->fail(RTUF_ERR_STATE, "internal: %d launch groups planned, %d made (the status word counts the former down)", n_groups, (n + per_group - 1) / per_group);
-  // The kernels of this batch, decided here and nowhere else; a re-run takes what its first run took.  (A combination that is
-  // not ok has been refused by the call's checks: none gets here.)
-  const Route route = rerun ? b.route
-                            : route_of({r.kind, r.u16, r.labels != nullptr, c->thresh_models > 0, (c->params.flags & RTUF_FLAG_TWO_KERNEL) != 0,
-                                        (int)c->params.silhouette_dilation_px, c->cover_on, c->pad_models > 0,
-                                        c->scene_enabled > 0 && !r.robot_only});
-  if (!route.ok) return c->fail(RTUF_ERR_STATE, "internal: no kernel route for a batch of kind %d (tile variant %d)", (int)r.kind, tile_variant_index(route.tile));
+  // The kernels of this batch, decided here for as long as it lives; a re-run takes what its first run took.  (The call asked
+  // check_route of the same facts: a combination without a route, or with a variant the launcher has no kernel for, is a bug.)
+  const Route route = rerun ? b.route : route_of(route_facts(c, r));
+  if (!route.ok() || !tile_variant_legal(route.tile))
+    return c->fail(RTUF_ERR_STATE, "internal: no kernel route for a batch of kind %d (tile variant %d)", (int)r.kind, tile_variant_index(route.tile));
   if (!rerun) {
     b.route = route;
     b.dilation = route.post == Post::Dilate ? (int)c->params.silhouette_dilation_px : 0;
@@ -2091,25 +2124,11 @@ static int retire_oldest(rtuf_context* c)
 }
 
 // ---- submission -----------------------------------------------------------------------
-// per-link depth thresholds exist in the fused route only: the z-surface does not carry the winning link
-static int check_thresh_route(rtuf_context* c)
+// While link padding is in effect a margin in metres is projected with the stream's focal length: every stream of a batch needs
+// its intrinsics (no rule of the route: asked before anything is staged or enqueued).
+static int need_pad_intrinsics(rtuf_context* c, int n)
 {
-  if (c->thresh_models > 0 && uses_zsurface(c))
-    return c->fail(RTUF_ERR_INVALID, "per-link depth thresholds are not supported with RTUF_FLAG_TWO_KERNEL or silhouette dilation yet");
-  return RTUF_OK;
-}
-
-// While link padding is in effect every batch goes over the z-surface with the link slots beside it (rtuf_routes.h): what has
-// no such route is refused before anything is staged or enqueued, and every stream of the batch needs its focal length.
-static int check_pad_route(rtuf_context* c, const BatchRequest& r, bool labels)
-{
-  if (c->pad_models <= 0) return RTUF_OK;
-  if (labels) return c->fail(RTUF_ERR_INVALID, "link labels are not supported with link padding yet");
-  if (r.kind == Kind::Render) return c->fail(RTUF_ERR_INVALID, "virtual depth is not supported with link padding yet");
-  if (r.kind == Kind::Residual) return c->fail(RTUF_ERR_INVALID, "link residual tables are not supported with link padding yet");
-  if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "silhouette dilation is not supported with link padding yet");
-  if (c->thresh_models > 0) return c->fail(RTUF_ERR_INVALID, "per-link depth thresholds are not supported with link padding yet");
-  for (int s = 0; s < r.n; s++)
+  for (int s = 0; c->pad_models > 0 && s < n; s++)
     if (!c->d_cloud_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
   return RTUF_OK;
 }
@@ -2122,6 +2141,18 @@ static int check_batch_call(rtuf_context* c, int n, bool have_args, bool u16)
   if (!c->finalized) return c->fail(RTUF_ERR_STATE, "call rtuf_finalize_models first");
   if (n <= 0 || n > c->max_streams || !have_args) return c->fail(RTUF_ERR_INVALID, "bad batch arguments (n=%d)", n);
   return check_u16_width(c, u16);
+}
+
+// What every filter call checks, with a label plane (labels: the caller's plane, or its array of planes) or without: the
+// arguments, then the route, and only then the label table is built.
+static int ensure_label_table(rtuf_context* c);
+static int check_filter_call(rtuf_context* c, int n, bool have_args, const void* labels, bool u16)
+{
+  { const int rc = check_batch_call(c, n, have_args, u16); if (rc != RTUF_OK) return rc; }
+  BatchRequest rq(Kind::Filter, n, u16);
+  rq.labels = static_cast<uint16_t*>(const_cast<void*>(labels));
+  { const int rc = check_route(c, rq); if (rc != RTUF_OK) return rc; }
+  return labels ? ensure_label_table(c) : RTUF_OK;
 }
 
 // The slot of the next batch: once the ring has room for it (the oldest batches are retired as needed), the one behind the
@@ -2174,8 +2205,7 @@ static int submit_batch(rtuf_context* c, rtuf_context::Batch& b, const BatchRequ
 // a batch on the caller's device buffers
 static int submit_device(rtuf_context* c, const BatchRequest& rq)
 {
-  { const int rc = check_pad_route(c, rq, rq.labels != nullptr); if (rc != RTUF_OK) return rc; }
-  if (subject_to_thresh_route(rq)) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
+  { const int rc = need_pad_intrinsics(c, rq.n); if (rc != RTUF_OK) return rc; }
   rtuf_context::Batch* b = nullptr;
   const int rc = take_slot(c, b);
   return rc != RTUF_OK ? rc : submit_batch(c, *b, rq);
@@ -2198,7 +2228,7 @@ int rtuf_filter_batch_device(rtuf_context* c, int n, const float* d_depth, float
 {
   KIDS_NEXT(c, rtuf_filter_batch_device(k, n, d_depth, d_masked, d_mask));
   if (!c) return RTUF_ERR_INVALID;
-  const int rc = check_batch_call(c, n, d_depth && d_masked, false);
+  const int rc = check_filter_call(c, n, d_depth && d_masked, nullptr, false);
   return rc != RTUF_OK ? rc : submit_device(c, filter_request(n, d_depth, d_masked, d_mask, nullptr, false));
 }
 
@@ -2206,16 +2236,16 @@ int rtuf_filter_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth
 {
   KIDS_NEXT(c, rtuf_filter_batch_device_u16(k, n, d_depth, d_masked, d_mask));
   if (!c) return RTUF_ERR_INVALID;
-  const int rc = check_batch_call(c, n, d_depth && d_masked, true);
+  const int rc = check_filter_call(c, n, d_depth && d_masked, nullptr, true);
   return rc != RTUF_OK ? rc : submit_device(c, filter_request(n, d_depth, d_masked, d_mask, nullptr, true));
 }
 
-static int check_bits_call(rtuf_context* c, int n, const void* in, const void* out)
+// the mask-bits calls, and the learn-scene calls, whose batch is one
+static int check_bits_call(rtuf_context* c, int n, const void* in, const void* out, bool u16)
 {
   { const int rc = check_batch_call(c, n, in && out, false); if (rc != RTUF_OK) return rc; }
   if (c->width & 3) return c->fail(RTUF_ERR_INVALID, "mask-bits output needs a width that is a multiple of 4");
-  if (c->params.flags & RTUF_FLAG_TWO_KERNEL) return c->fail(RTUF_ERR_INVALID, "mask-bits output exists in fused mode only (RTUF_FLAG_TWO_KERNEL is set)");
-  return RTUF_OK;
+  return check_route(c, BatchRequest(Kind::Bits, n, u16));
 }
 
 size_t rtuf_mask_bits_words(int width, int height)
@@ -2227,7 +2257,7 @@ int rtuf_filter_batch_device_bits(rtuf_context* c, int n, const float* d_depth, 
 {
   KIDS_NEXT(c, rtuf_filter_batch_device_bits(k, n, d_depth, d_bits));
   if (!c) return RTUF_ERR_INVALID;
-  const int rc = check_bits_call(c, n, d_depth, d_bits);
+  const int rc = check_bits_call(c, n, d_depth, d_bits, false);
   return rc != RTUF_OK ? rc : submit_device(c, bits_request(n, d_depth, d_bits, false));
 }
 
@@ -2235,7 +2265,7 @@ int rtuf_filter_batch_device_bits_u16(rtuf_context* c, int n, const uint16_t* d_
 {
   KIDS_NEXT(c, rtuf_filter_batch_device_bits_u16(k, n, d_depth, d_bits));
   if (!c) return RTUF_ERR_INVALID;
-  const int rc = check_bits_call(c, n, d_depth, d_bits);
+  const int rc = check_bits_call(c, n, d_depth, d_bits, true);
   return rc != RTUF_OK ? rc : submit_device(c, bits_request(n, d_depth, d_bits, true));
 }
 
@@ -2386,8 +2416,7 @@ static int submit_host_planes(rtuf_context* c, BatchRequest rq, const HostPlanes
   for (int s = 0; s < n; s++)
     if ((hp.depth && !hp.depth[s]) || (hp.out && !hp.out[s]) || (hp.labels && !hp.labels[s]) || (hp.index && !hp.index[s]))
       return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
-  { const int rc = check_pad_route(c, rq, hp.labels != nullptr); if (rc != RTUF_OK) return rc; }      // (before the planes are staged)
-  if (subject_to_thresh_route(rq)) { const int rc = check_thresh_route(c); if (rc != RTUF_OK) return rc; }
+  { const int rc = need_pad_intrinsics(c, n); if (rc != RTUF_OK) return rc; }      // (before the planes are staged)
   B* slot = nullptr;
   { const int rc = take_slot(c, slot); if (rc != RTUF_OK) return rc; }
   B& b = *slot;
@@ -2450,12 +2479,14 @@ static int submit_host_planes(rtuf_context* c, BatchRequest rq, const HostPlanes
   return enqueue_download(c, b);
 }
 
-// the filter and mask-bits calls on host planes (out: masked planes or bits; labels_out may be nullptr)
+// the filter and mask-bits calls on host planes (out: masked planes or bits; labels_out: nullptr unless want_labels)
 static int filter_host_planes(rtuf_context* c, Kind kind, int n, const void* const* depth_in, void* const* out, void* const* mask_out,
-                              uint16_t* const* labels_out, bool u16)
+                              uint16_t* const* labels_out, bool want_labels, bool u16)
 {
-  { const int rc = check_batch_call(c, n, depth_in && out, u16); if (rc != RTUF_OK) return rc; }
-  if (kind == Kind::Bits) { const int rc = check_bits_call(c, n, depth_in, out); if (rc != RTUF_OK) return rc; }
+  int rc = kind == Kind::Bits ? check_batch_call(c, n, depth_in && out, u16)      // (a 16UC1 call names the 16UC1 width rule, as it always has)
+                              : check_filter_call(c, n, depth_in && out && (!want_labels || labels_out), labels_out, u16);
+  if (rc == RTUF_OK && kind == Kind::Bits) rc = check_bits_call(c, n, depth_in, out, u16);
+  if (rc != RTUF_OK) return rc;
   HostPlanes hp{};
   hp.depth = depth_in; hp.out = out; hp.mask = mask_out; hp.labels = reinterpret_cast<void* const*>(labels_out);
   return submit_host_planes(c, BatchRequest(kind, n, u16), hp);
@@ -2467,7 +2498,7 @@ int rtuf_filter_batch_async(rtuf_context* c, int n, const float* const* depth_in
   KIDS_NEXT(c, rtuf_filter_batch_async(k, n, depth_in, masked_out, mask_out));
   if (!c) return RTUF_ERR_INVALID;
   return filter_host_planes(c, Kind::Filter, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(masked_out),
-                            reinterpret_cast<void* const*>(mask_out), nullptr, false);
+                            reinterpret_cast<void* const*>(mask_out), nullptr, false, false);
 }
 
 int rtuf_filter_batch_u16_async(rtuf_context* c, int n, const uint16_t* const* depth_in, uint16_t* const* masked_out,
@@ -2476,21 +2507,21 @@ int rtuf_filter_batch_u16_async(rtuf_context* c, int n, const uint16_t* const* d
   KIDS_NEXT(c, rtuf_filter_batch_u16_async(k, n, depth_in, masked_out, mask_out));
   if (!c) return RTUF_ERR_INVALID;
   return filter_host_planes(c, Kind::Filter, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(masked_out),
-                            reinterpret_cast<void* const*>(mask_out), nullptr, true);
+                            reinterpret_cast<void* const*>(mask_out), nullptr, false, true);
 }
 
 int rtuf_filter_batch_bits_async(rtuf_context* c, int n, const float* const* depth_in, uint32_t* const* bits_out)
 {
   KIDS_NEXT(c, rtuf_filter_batch_bits_async(k, n, depth_in, bits_out));
   if (!c) return RTUF_ERR_INVALID;
-  return filter_host_planes(c, Kind::Bits, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(bits_out), nullptr, nullptr, false);
+  return filter_host_planes(c, Kind::Bits, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(bits_out), nullptr, nullptr, false, false);
 }
 
 int rtuf_filter_batch_bits_u16_async(rtuf_context* c, int n, const uint16_t* const* depth_in, uint32_t* const* bits_out)
 {
   KIDS_NEXT(c, rtuf_filter_batch_bits_u16_async(k, n, depth_in, bits_out));
   if (!c) return RTUF_ERR_INVALID;
-  return filter_host_planes(c, Kind::Bits, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(bits_out), nullptr, nullptr, true);
+  return filter_host_planes(c, Kind::Bits, n, reinterpret_cast<const void* const*>(depth_in), reinterpret_cast<void* const*>(bits_out), nullptr, nullptr, false, true);
 }
 
 int rtuf_filter_batch(rtuf_context* c, int n, const float* const* depth_in, float* const* masked_out,
@@ -2553,18 +2584,11 @@ int rtuf_set_link_labels(rtuf_context* c, int model, const uint16_t* labels, int
   return ensure_label_table(c);
 }
 
-static int check_labels_call(rtuf_context* c, int n, const void* in, const void* out, const void* labels)
-{
-  { const int rc = check_batch_call(c, n, in && out && labels, false); if (rc != RTUF_OK) return rc; }
-  if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "link labels are not supported with silhouette dilation yet");
-  return ensure_label_table(c);
-}
-
 int rtuf_filter_batch_device_labels(rtuf_context* c, int n, const float* d_depth, float* d_masked, uint8_t* d_mask, uint16_t* d_labels)
 {
   KIDS_NEXT(c, rtuf_filter_batch_device_labels(k, n, d_depth, d_masked, d_mask, d_labels));
   if (!c) return RTUF_ERR_INVALID;
-  const int rc = check_labels_call(c, n, d_depth, d_masked, d_labels);
+  const int rc = check_filter_call(c, n, d_depth && d_masked && d_labels, d_labels, false);
   return rc != RTUF_OK ? rc : submit_device(c, filter_request(n, d_depth, d_masked, d_mask, d_labels, false));
 }
 
@@ -2572,8 +2596,7 @@ int rtuf_filter_batch_device_u16_labels(rtuf_context* c, int n, const uint16_t* 
 {
   KIDS_NEXT(c, rtuf_filter_batch_device_u16_labels(k, n, d_depth, d_masked, d_mask, d_labels));
   if (!c) return RTUF_ERR_INVALID;
-  int rc = check_labels_call(c, n, d_depth, d_masked, d_labels);
-  if (rc == RTUF_OK) rc = check_u16_width(c, true);
+  const int rc = check_filter_call(c, n, d_depth && d_masked && d_labels, d_labels, true);
   return rc != RTUF_OK ? rc : submit_device(c, filter_request(n, d_depth, d_masked, d_mask, d_labels, true));
 }
 
@@ -2582,8 +2605,7 @@ static int filter_batch_labels_async(rtuf_context* c, int n, const void* const* 
 {
   KIDS_NEXT(c, filter_batch_labels_async(k, n, depth_in, masked_out, mask_out, labels_out, u16));
   if (!c) return RTUF_ERR_INVALID;
-  const int rc = check_labels_call(c, n, depth_in, masked_out, labels_out);
-  return rc != RTUF_OK ? rc : filter_host_planes(c, Kind::Filter, n, depth_in, masked_out, reinterpret_cast<void* const*>(mask_out), labels_out, u16);
+  return filter_host_planes(c, Kind::Filter, n, depth_in, masked_out, reinterpret_cast<void* const*>(mask_out), labels_out, true, u16);
 }
 
 int rtuf_filter_batch_labels(rtuf_context* c, int n, const float* const* depth_in, float* const* masked_out, uint8_t* const* mask_out,
@@ -2917,7 +2939,7 @@ static int learn_scene_kids(rtuf_context* c, int n, int rc)
 
 static int learn_scene_host(rtuf_context* c, int n, const void* const* depth_in, bool u16)
 {
-  { const int rc = check_bits_call(c, n, depth_in, depth_in); if (rc != RTUF_OK) return rc; }
+  { const int rc = check_bits_call(c, n, depth_in, depth_in, u16); if (rc != RTUF_OK) return rc; }
   for (int s = 0; s < n; s++) if (!depth_in[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
   { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
   hipSetDevice(c->device);
@@ -2932,7 +2954,7 @@ int rtuf_learn_scene_batch_device(rtuf_context* c, int n, const float* d_depth)
 {
   if (c && !c->kids.empty()) return learn_scene_kids(c, n, rtuf_learn_scene_batch_device(c->kids[0], n, d_depth));
   if (!c) return RTUF_ERR_INVALID;
-  const int rc = check_bits_call(c, n, d_depth, d_depth);
+  const int rc = check_bits_call(c, n, d_depth, d_depth, false);
   return rc != RTUF_OK ? rc : learn_scene_device(c, n, d_depth, false);
 }
 
@@ -2940,7 +2962,7 @@ int rtuf_learn_scene_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_
 {
   if (c && !c->kids.empty()) return learn_scene_kids(c, n, rtuf_learn_scene_batch_device_u16(c->kids[0], n, d_depth));
   if (!c) return RTUF_ERR_INVALID;
-  const int rc = check_bits_call(c, n, d_depth, d_depth);
+  const int rc = check_bits_call(c, n, d_depth, d_depth, true);
   return rc != RTUF_OK ? rc : learn_scene_device(c, n, d_depth, true);
 }
 
@@ -2961,12 +2983,14 @@ int rtuf_learn_scene_batch_u16(rtuf_context* c, int n, const uint16_t* const* de
 // ---- virtual depth ---------------------------------------------------------------------------------
 // A render batch is a batch like any other (Kind::Render) whose tile kernel stores the winners' virtual depth instead of
 // comparing a sensor plane with it.  Parameters of the compare do not enter, and the z-surface is never used.
-static int check_render_call(rtuf_context* c, int n, const void* out, bool want_labels, bool u16)
+// (labels: the caller's label plane or its array of planes, or nullptr)
+static int check_render_call(rtuf_context* c, int n, const void* out, const void* labels, bool u16)
 {
-  { const int rc = check_batch_call(c, n, out != nullptr, false); if (rc != RTUF_OK) return rc; }
-  if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "virtual depth is not supported with silhouette dilation yet");
-  { const int rc = check_u16_width(c, u16); if (rc != RTUF_OK) return rc; }
-  return want_labels ? ensure_label_table(c) : RTUF_OK;
+  { const int rc = check_batch_call(c, n, out != nullptr, u16); if (rc != RTUF_OK) return rc; }
+  BatchRequest rq(Kind::Render, n, u16);
+  rq.labels = static_cast<uint16_t*>(const_cast<void*>(labels));
+  { const int rc = check_route(c, rq); if (rc != RTUF_OK) return rc; }
+  return labels ? ensure_label_table(c) : RTUF_OK;
 }
 
 static BatchRequest render_request(int n, void* d_virtual, uint16_t* d_labels, float empty_value, bool u16)
@@ -2980,7 +3004,7 @@ int rtuf_render_batch_device(rtuf_context* c, int n, float* d_virtual, uint16_t*
 {
   KIDS_NEXT(c, rtuf_render_batch_device(k, n, d_virtual, d_labels, empty_value));
   if (!c) return RTUF_ERR_INVALID;
-  const int rc = check_render_call(c, n, d_virtual, d_labels != nullptr, false);
+  const int rc = check_render_call(c, n, d_virtual, d_labels, false);
   return rc != RTUF_OK ? rc : submit_device(c, render_request(n, d_virtual, d_labels, empty_value, false));
 }
 
@@ -2988,7 +3012,7 @@ int rtuf_render_batch_device_u16(rtuf_context* c, int n, uint16_t* d_virtual, ui
 {
   KIDS_NEXT(c, rtuf_render_batch_device_u16(k, n, d_virtual, d_labels, empty_value));
   if (!c) return RTUF_ERR_INVALID;
-  const int rc = check_render_call(c, n, d_virtual, d_labels != nullptr, true);
+  const int rc = check_render_call(c, n, d_virtual, d_labels, true);
   return rc != RTUF_OK ? rc : submit_device(c, render_request(n, d_virtual, d_labels, empty_value, true));
 }
 
@@ -2997,7 +3021,7 @@ static int render_batch_async(rtuf_context* c, int n, void* const* virtual_out, 
 {
   KIDS_NEXT(c, render_batch_async(k, n, virtual_out, labels_out, empty_value, u16));
   if (!c) return RTUF_ERR_INVALID;
-  { const int rc = check_render_call(c, n, virtual_out, labels_out != nullptr, u16); if (rc != RTUF_OK) return rc; }
+  { const int rc = check_render_call(c, n, virtual_out, labels_out, u16); if (rc != RTUF_OK) return rc; }
   BatchRequest rq(Kind::Render, n, u16);
   rq.empty_value = empty_value;
   HostPlanes hp{};
@@ -3025,8 +3049,8 @@ static int check_residuals_call(rtuf_context* c, int n, const void* in, const vo
 {
   { const int rc = check_batch_call(c, n, in && table, false); if (rc != RTUF_OK) return rc; }
   if (n_labels < 1) return c->fail(RTUF_ERR_INVALID, "a residual table needs at least one row per stream (n_labels=%d)", n_labels);
-  if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "link residual tables are not supported with silhouette dilation yet");
   { const int rc = check_u16_width(c, u16); if (rc != RTUF_OK) return rc; }
+  { const int rc = check_route(c, BatchRequest(Kind::Residual, n, u16)); if (rc != RTUF_OK) return rc; }
   { const int rc = ensure_label_table(c); if (rc != RTUF_OK) return rc; }
   if (c->max_label >= (uint32_t)n_labels) return c->fail(RTUF_ERR_INVALID, "a link has label %u: the table needs n_labels > %u (got %d)", c->max_label, c->max_label, n_labels);
   return RTUF_OK;
@@ -3124,8 +3148,7 @@ static int check_cloud_call(rtuf_context* c, int n, const void* in, const void* 
   if (c->width & 3) return c->fail(RTUF_ERR_INVALID, "point clouds are built on the mask bits: they need a width that is a multiple of 4");
   if (compact && (capacity < 1 || (long long)capacity > (long long)c->width * c->height))
     return c->fail(RTUF_ERR_INVALID, "capacity = %d: 1 .. width * height (%lld)", capacity, (long long)c->width * c->height);
-  if (c->thresh_models > 0 && c->params.silhouette_dilation_px > 0)
-    return c->fail(RTUF_ERR_INVALID, "per-link depth thresholds are not supported with silhouette dilation yet");
+  { const int rc = check_route(c, BatchRequest(Kind::Cloud, n, false)); if (rc != RTUF_OK) return rc; }      // (16UC1 or not: no refusal asks)
   for (int s = 0; s < n; s++)
     if (!c->d_cloud_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
   return RTUF_OK;
@@ -3263,9 +3286,7 @@ static int check_points_call(rtuf_context* c, int n, bool have_args, long long c
   { const int rc = check_batch_call(c, n, have_args, false); if (rc != RTUF_OK) return rc; }
   if (capacity < 1 || capacity > (long long)kMaxPointsCapacity) return c->fail(RTUF_ERR_INVALID, "capacity = %lld: 1 .. %d", capacity, kMaxPointsCapacity);
   if (radius < 0 || radius > kMaxPointsRadius) return c->fail(RTUF_ERR_INVALID, "radius_px = %d: 0 .. %d", radius, kMaxPointsRadius);
-  if (c->params.silhouette_dilation_px > 0) return c->fail(RTUF_ERR_INVALID, "point list batches are not supported with silhouette dilation yet (radius_px is this batch's own margin)");
-  if (c->pad_models > 0) return c->fail(RTUF_ERR_INVALID, "point list batches are not supported with link padding yet");
-  if (c->thresh_models > 0) return c->fail(RTUF_ERR_INVALID, "point list batches are not supported with per-link depth thresholds yet");
+  { const int rc = check_route(c, BatchRequest(Kind::Points, n, false)); if (rc != RTUF_OK) return rc; }
   for (int s = 0; s < n; s++)
     if (!c->d_point_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
   return ensure_point_transforms(c);
@@ -3415,8 +3436,7 @@ static int check_clearance_call(rtuf_context* c, int n, const void* in, const vo
   { const int rc = check_batch_call(c, n, in && table, false); if (rc != RTUF_OK) return rc; }
   if (n_labels < 1) return c->fail(RTUF_ERR_INVALID, "a clearance table needs at least one row per stream (n_labels=%d)", n_labels);
   if (!(max_distance > 0.0f)) return c->fail(RTUF_ERR_INVALID, "max_distance must be > 0 (+inf is allowed; got %g)", (double)max_distance);
-  if (c->thresh_models > 0 && c->params.silhouette_dilation_px > 0)
-    return c->fail(RTUF_ERR_INVALID, "per-link depth thresholds are not supported with silhouette dilation yet");
+  { const int rc = check_route(c, BatchRequest(Kind::Clearance, n, false)); if (rc != RTUF_OK) return rc; }      // (16UC1 or not: no refusal asks)
   for (int s = 0; s < n; s++)
     if (!c->d_cloud_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
   return ensure_clearance_spheres(c);

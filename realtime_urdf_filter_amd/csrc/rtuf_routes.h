@@ -1,9 +1,11 @@
 // rtuf_routes.h -- which kernels a batch runs: the tile kernel's variant, and what runs behind it on the group's lane.
 //
-// The one place that decides it.  enqueue_batch (rtuf_api.cpp) asks route_of once, when a batch is first enqueued, keeps the
-// Route with the batch slot (re-runs take it from there) and hands it to issue_plan; launch_tile (rtuf_kernels.hip) maps its
-// TileVariant to a kernel instantiation, and tile_body asserts that the instantiation is a legal one.  A new batch kind, or a
-// new variant of the tile kernel, starts here.
+// The one place that decides it, and that refuses what has no route.  Every batch call of rtuf_api.cpp asks route_of through
+// check_route, once its own arguments are in order, and returns the reason's message if there is one (enum class Refusal
+// below); enqueue_batch asks route_of of the same facts once, when a batch is first enqueued, keeps the Route with the batch
+// slot (re-runs take it from there) and hands it to issue_plan; launch_tile (rtuf_kernels.hip) maps its TileVariant to a kernel
+// instantiation, and tile_body asserts that the instantiation is a legal one.  A new batch kind, a new variant of the tile
+// kernel, or a new refusal starts here.
 //
 // Included by rtuf_device.h (so by the kernels and the host API) and by the CPU check tests/routes_check.cpp (plain g++, no
 // ROCm headers), which holds route_of against a table written out by hand for every combination of its inputs.  Plain C++17.
@@ -58,9 +60,38 @@ constexpr int kPosts = 4;
 enum class Tail { None, Cloud, Clearance, Points };
 constexpr int kTails = 4;
 
-// ok == false: a combination the API refuses.  scene (last: older brace lists leave it false): scene_apply_planes_kernel behind
-// a Filter batch's outputs, scene_apply_bits_kernel behind the mask bits of a Bits, Cloud or Clearance batch.
-struct Route { TileVariant tile; Post post; Tail tail; bool ok; bool scene; };
+// Why a combination has no route: the API refuses it with this reason's message (check_route in rtuf_api.cpp, which holds the
+// texts), before the call builds, allocates or enqueues anything.  route_of names the first reason that applies, per kind in
+// this order -- the order in which the calls have always named them (L: a label plane is asked for, T: per-link thresholds are
+// in effect, K: the two-kernel flag, D: dilation > 0, P: link padding is in effect):
+//   Filter            L&D LabelsDilation, L&P LabelsPadding, P&D DilationPadding, P&T ThreshPadding, T&(K or D) ThreshZSurface
+//   Bits (learn-scene too)   L NoLabelPlane, K BitsTwoKernel, P&D DilationPadding, P&T ThreshPadding, T&D ThreshZSurface
+//   Render            D RenderDilation, L&P LabelsPadding, P RenderPadding
+//   Residual          L NoLabelPlane, D ResidualDilation, P ResidualPadding
+//   Cloud, Clearance  L NoLabelPlane, T&D ThreshDilation, P&D DilationPadding, P&T ThreshPadding
+//   Points            L NoLabelPlane, D PointsDilation, P PointsPadding, T PointsThresh
+// In words: a label plane goes with a filter or render batch only (NoLabelPlane: no call of the other kinds has the argument;
+// the reason keeps route_of total), and not with dilation; dilation not with a render or residual batch; thresholds not on the
+// z-surface route, which does not carry the winning link (ThreshZSurface and ThreshDilation are one rule with the two texts
+// the calls have for it); the mask-bits calls refuse the two-kernel flag, which is for full planes; with link padding the
+// plane beside the z-surface belongs to the link slots, so no label plane, render or residual batch, dilation or thresholds;
+// a point list batch honours neither dilation nor padding nor thresholds yet.
+// A call that is wrong in several ways at once, only one of them a refusal of this list, reports whichever of its checks comes
+// first: the refusal behind the checks of the call's own arguments (the models are final, n, null arrays, n_labels, capacity,
+// radius_px, max_distance, the width rules), before any check of what the context holds (a stream without cloud intrinsics, a
+// label the table has no row for) and before the alignment of device buffers and the single planes of a host form are looked at.
+enum class Refusal {
+  None, NoLabelPlane, LabelsDilation, LabelsPadding, RenderDilation, RenderPadding, ResidualDilation, ResidualPadding, DilationPadding,
+  ThreshPadding, ThreshZSurface, ThreshDilation, BitsTwoKernel, PointsDilation, PointsPadding, PointsThresh
+};
+
+// why != None: a combination the API refuses; the rest of the route is then what it would be, and nothing runs it.  scene (last:
+// older brace lists leave it false): scene_apply_planes_kernel behind a Filter batch's outputs, scene_apply_bits_kernel behind
+// the mask bits of a Bits, Cloud or Clearance batch.
+struct Route {
+  TileVariant tile; Post post; Tail tail; Refusal why; bool scene;
+  constexpr bool ok() const { return why == Refusal::None; }
+};
 constexpr bool runs_behind_tile(const Route& r) { return r.post != Post::None || r.tail != Tail::None || r.scene; }
 constexpr int route_index(const Route& r)
 {
@@ -92,47 +123,55 @@ struct RouteFacts {
 //   Cloud                                      Bits          thresh, u16            Cloud
 //   Clearance                                  Bits          thresh, u16            Clearance
 //   Points                                     Render        -                      Points
-// The two-kernel flag is for full planes: the mask-bits calls refuse it, the other kinds run as if it were not set.
-// Thresholds do not enter a render batch.  Refused: a label plane beside anything but a filter or render batch, or with
-// dilation; dilation with a render or residual batch; thresholds on the z-surface route.  Link padding goes over the
-// z-surface whatever the two-kernel flag says, and the plane beside it belongs to the link slots: refused with a label plane,
-// a render or residual batch, dilation or thresholds.
+// The two-kernel flag is for full planes: the other kinds run as if it were not set.  Thresholds do not enter a render batch.
+// Link padding goes over the z-surface whatever the two-kernel flag says, and the plane beside it belongs to the link slots.
 // Scene planes refuse nothing and change nothing in front of them: a Filter, Bits, Cloud or Clearance batch takes the route it
 // would take without, plus the scene stage between Post and Tail; render and residual batches compare nothing against the scene.
 // A point list batch (include/rtuf.h, POINT LIST BATCHES) is a render batch into a float plane of the library's with the points
-// kernel behind it, whatever the other facts say: the two-kernel flag and the scene do not enter, and dilation, padding and
-// thresholds are refused (they are not honoured yet).
+// kernel behind it, whatever the other facts say: the two-kernel flag and the scene do not enter.
+// What is refused, and in which order the reasons are named: enum class Refusal above.
 constexpr Route route_of(const RouteFacts& f)
 {
-  const bool filter = f.kind == BatchKind::Filter, bits = f.kind == BatchKind::Bits;
-  const bool render = f.kind == BatchKind::Render, residual = f.kind == BatchKind::Residual;
-  if (f.kind == BatchKind::Points) {
-    Route p{};
-    p.tile = TileVariant{TileOut::Render, false, false, false, f.cover};
-    p.post = Post::None;
-    p.tail = Tail::Points;
-    p.ok = !f.labels && f.dilation <= 0 && !f.padded && !f.thresh;
-    p.scene = false;
-    return p;
+  using R = Refusal;
+  const bool filter = f.kind == BatchKind::Filter, render = f.kind == BatchKind::Render, residual = f.kind == BatchKind::Residual;
+  const bool L = f.labels, T = f.thresh, K = f.two_kernel, D = f.dilation > 0, P = f.padded;
+  R why = R::None;
+  switch (f.kind) {
+    case BatchKind::Filter:
+      why = L && D ? R::LabelsDilation : L && P ? R::LabelsPadding : P && D ? R::DilationPadding : P && T ? R::ThreshPadding : T && (K || D) ? R::ThreshZSurface : R::None;
+      break;
+    case BatchKind::Bits:
+      why = L ? R::NoLabelPlane : K ? R::BitsTwoKernel : P && D ? R::DilationPadding : P && T ? R::ThreshPadding : T && D ? R::ThreshZSurface : R::None;
+      break;
+    case BatchKind::Render: why = D ? R::RenderDilation : L && P ? R::LabelsPadding : P ? R::RenderPadding : R::None; break;
+    case BatchKind::Residual: why = L ? R::NoLabelPlane : D ? R::ResidualDilation : P ? R::ResidualPadding : R::None; break;
+    case BatchKind::Cloud:
+    case BatchKind::Clearance:
+      why = L ? R::NoLabelPlane : T && D ? R::ThreshDilation : P && D ? R::DilationPadding : P && T ? R::ThreshPadding : R::None;
+      break;
+    case BatchKind::Points: why = L ? R::NoLabelPlane : D ? R::PointsDilation : P ? R::PointsPadding : T ? R::PointsThresh : R::None; break;
   }
-  const bool dilated = f.dilation > 0, two = f.two_kernel && filter, thresh = f.thresh && !render;
-  bool ok = !(f.labels && !filter && !render) && !(dilated && (f.labels || render || residual)) && !(f.two_kernel && bits);
   Route r{};
-  if (f.padded) {
-    ok = ok && !f.labels && !render && !residual && !dilated && !f.thresh;
+  r.why = why;
+  if (f.kind == BatchKind::Points) {
+    r.tile = TileVariant{TileOut::Render, false, false, false, f.cover};
+    r.post = Post::None;
+    r.tail = Tail::Points;
+    r.scene = false;
+    return r;
+  }
+  if (P) {
     r.tile = TileVariant{TileOut::ZSurface, true, false, false, f.cover};
     r.post = Post::Pad;
-  } else if (dilated || two) {
-    ok = ok && !thresh;
-    r.tile = TileVariant{TileOut::ZSurface, f.labels, false, false, f.cover};
-    r.post = dilated ? Post::Dilate : Post::Compare;
+  } else if (D || (K && filter)) {
+    r.tile = TileVariant{TileOut::ZSurface, L, false, false, f.cover};
+    r.post = D ? Post::Dilate : Post::Compare;
   } else {
     const TileOut out = filter ? TileOut::Planes : render ? TileOut::Render : residual ? TileOut::Residual : TileOut::Bits;
-    r.tile = TileVariant{out, f.labels, thresh, f.u16, f.cover};
+    r.tile = TileVariant{out, L, T && !render, f.u16, f.cover};
     r.post = Post::None;
   }
   r.tail = f.kind == BatchKind::Cloud ? Tail::Cloud : f.kind == BatchKind::Clearance ? Tail::Clearance : Tail::None;
-  r.ok = ok && tile_variant_legal(r.tile);
   r.scene = f.scene && !render && !residual;
   return r;
 }

@@ -2,7 +2,7 @@
 link_padding_reach2, compiled for the host by tests/link_padding_check.cpp) against the numpy mirror bit for bit, the
 expectation bench_support/link_padding_check.py on cases worked out by hand, the scenes of tests/test_link_padding_gpu.py
 (each must tell padding from no padding AND from the square dilation of its largest reach, or it proves nothing), the
-calls' place in the ABI and the bindings, and the kernel routes with padding in effect (tests/link_padding_routes_check.cpp)."""
+calls' place in the ABI and the bindings, and the kernel routes with padding in effect (the padded rows of tests/routes_check.cpp)."""
 import ctypes
 import os
 import re
@@ -205,10 +205,16 @@ def test_cpp_facade_header_has_the_model_field():
 # ---- routes ---------------------------------------------------------------------------------------------------------------------------
 
 def test_routes_with_padding_in_effect_are_the_table(tmp_path):
-    exe = str(tmp_path / "link_padding_routes_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "link_padding_routes_check.cpp")])
+    exe = str(tmp_path / "routes_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "routes_check.cpp")])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stdout.split() == ["ok", "384", "6"], r.stdout
+    # (the walk's 1,792 combinations hold the 384 with padding in effect this asserted before; field 6: the padded routes, 6 as before)
+    ok = r.stdout.splitlines()[0].split()
+    assert r.returncode == 0 and ok[:2] == ["ok", "1792"] and ok[6] == "6", r.stdout
+    refused = set(r.stdout.splitlines()[1].split()[1:])
+    assert {"Filter:LabelsPadding", "Filter:DilationPadding", "Filter:ThreshPadding", "Bits:DilationPadding", "Bits:ThreshPadding", "Render:LabelsPadding",
+            "Render:RenderPadding", "Residual:ResidualPadding", "Cloud:DilationPadding", "Cloud:ThreshPadding", "Clearance:DilationPadding",
+            "Clearance:ThreshPadding", "Points:PointsPadding"} == {p for p in refused if "Padding" in p}
     routes = open(os.path.join(CSRC, "rtuf_routes.h")).read()
     assert re.search(r"bool padded;[^\n]*\n\};", routes)                 # the last member: older brace lists leave it false
     assert re.search(r"enum class Post \{ None, Compare, Dilate, Pad \};", routes)

@@ -1,7 +1,7 @@
 """CPU (no GPU): point list batches (include/rtuf.h, POINT LIST BATCHES) -- the entry points' place in the ABI, the
 expectation bench_support/points_check.py by hand on ten points, the kernel's own per-point arithmetic (rtuf_numerics.h,
 compiled for the host by tests/point_pixel_check.cpp, plain and under the sanitizers) against that expectation, bit for bit,
-on a sweep of edge values, the new kind's kernel routes (tests/points_routes_check.cpp), and the conditions on the GPU tests'
+on a sweep of edge values, the new kind's kernel routes (the Points rows of tests/routes_check.cpp), and the conditions on the GPU tests'
 inputs: the scenes give enough filtered points, and enough kept points on link pixels, in every stream."""
 import ctypes
 import os
@@ -218,11 +218,15 @@ def test_the_kernels_helper_agrees_with_numpy_bit_for_bit(tmp_path, sweep, sanit
 
 
 def test_points_routes(tmp_path):
-    exe = str(tmp_path / "points_routes_check")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "points_routes_check.cpp")])
+    exe = str(tmp_path / "routes_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "routes_check.cpp")])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and r.stdout.split()[0] == "ok", r.stdout + r.stderr
-    assert r.stdout.split()[1:] == ["256", "2"], r.stdout
+    # (the walk's 1,792 combinations hold the 256 of a points batch this asserted before; field 7: the points routes, 2 as before)
+    ok = r.stdout.splitlines()[0].split()
+    assert ok[1] == "1792" and ok[7] == "2", r.stdout
+    assert {p for p in r.stdout.splitlines()[1].split() if p.startswith("Points:")} == {"Points:NoLabelPlane", "Points:PointsDilation", "Points:PointsPadding",
+                                                                                        "Points:PointsThresh"}
 
 
 # ---- conditions on the GPU tests' inputs -------------------------------------------------------------------------------------

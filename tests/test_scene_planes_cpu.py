@@ -1,7 +1,7 @@
 """CPU (no GPU): scene planes (include/rtuf.h, SCENE PLANES) -- the kernels' own arithmetic (rtuf_numerics.h's scene_threshold,
 scene_filtered and scene_learned, compiled for the host by tests/scene_check.cpp) against the numpy form of
-tests/scene_planes_scenes.py bit for bit, the kernel routes with a scene in effect (tests/scene_routes_check.cpp; the two older
-route checks must still pass as they are), the scenes of tests/test_scene_planes_gpu.py (every stream must hold every class of
+tests/scene_planes_scenes.py bit for bit, the kernel routes with a scene in effect (tests/routes_check.cpp: the scene changes nothing
+but the scene stage), the scenes of tests/test_scene_planes_gpu.py (every stream must hold every class of
 pixel the definition tells apart, or a GPU test on it proves nothing), and the calls' place in the ABI and the bindings."""
 import os
 import re
@@ -67,10 +67,10 @@ def test_scene_check_is_clean_under_the_address_and_undefined_behaviour_sanitize
 
 
 def test_routes_with_a_scene_differ_by_the_scene_stage_only_and_the_older_route_checks_still_pass(tmp_path):
-    out = build_and_run(tmp_path, "scene_routes_check").split()
-    assert out[0] == "ok" and int(out[1]) == 768 and int(out[2]) > 0, out
-    assert build_and_run(tmp_path, "routes_check").startswith("ok 384 ")
-    assert build_and_run(tmp_path, "link_padding_routes_check").startswith("ok 384 6")
+    # One program now: its 1,792 combinations hold the 768 pairs with and without a scene this asserted, and the 384 + 384 of
+    # the two older checks; fields 5, 6 and 8 are their figures: 66 plain and 6 padded routes as before, and 56 > 0 scene routes.
+    out = build_and_run(tmp_path, "routes_check", ("-Wall", "-Werror")).splitlines()[0].split()
+    assert out[:4] == ["ok", "1792", "44", "88"] and int(out[8]) == 56 > 0 and out[5:7] == ["66", "6"], out
 
 
 @pytest.mark.parametrize("W,H,n,pose", [(160, 120, 4, 0), (160, 120, 4, 1), (160, 120, 4, 2), (200, 150, 3, 0), (160, 120, 5, 0)])
