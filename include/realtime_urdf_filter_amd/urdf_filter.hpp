@@ -262,6 +262,7 @@ class RealtimeURDFFilter {
     if (ctx_) { rtuf_destroy(ctx_); ctx_ = nullptr; }
     cloud_intr_sent_ = false;                  // (the new context has no cloud intrinsics: cloud_into gives them again)
     spheres_sent_ = false;                     // (... and no link spheres: clearance_into gives them again)
+    voxel_sent_ = false;                       // (... and no voxel grid: voxel_insert gives it again, empty)
     if (rtuf_create(&ctx_, device_, width_, height_, 1, &p) != RTUF_OK) throw std::runtime_error(std::string("ERROR: could not initialize the GPU context: ") + rtuf_last_error(nullptr));
     this->loadModels();
     if (renderers_.empty()) throw std::runtime_error("Could not load any models for filtering!");
@@ -475,6 +476,44 @@ class RealtimeURDFFilter {
     else check(rtuf_link_clearance_batch(ctx_, 1, reinterpret_cast<const float* const*>(&in), table_out, n_labels, max_distance));
     return true;
   }
+  // ---- voxel occupancy grids (include/rtuf.h, VOXEL OCCUPANCY GRIDS) ----
+  // One world grid that voxel_insert accumulates kept points in: origin and voxel_size in metres, dims = (nx, ny, nz),
+  // world_from_optical nullptr or the camera's column-major 4 x 4 matrix.  The grid belongs to the device context: a new image
+  // size makes a new, empty one.
+  void setVoxelGrid(const double origin[3], double voxel_size, const int dims[3], bool with_counts = true, const double* world_from_optical = nullptr)
+  {
+    std::memcpy(voxel_origin_, origin, sizeof voxel_origin_);
+    std::memcpy(voxel_dims_, dims, sizeof voxel_dims_);
+    voxel_size_ = voxel_size; voxel_counts_ = with_counts; voxel_has_tf_ = world_from_optical != nullptr;
+    if (world_from_optical) std::memcpy(voxel_tf_, world_from_optical, sizeof voxel_tf_);
+    have_voxel_ = true; voxel_sent_ = false;
+  }
+  // Inserts the pixels filter_into would keep -- dilation, thresholds, padding and scene honoured -- for the camera and link
+  // poses filter_into would use and the intrinsics cloud_into would use.  depth: width x height float metres, or uint16
+  // millimetres with is_16uc1; the width must be a multiple of 4.  summary_out: nullptr or four words (inserted, outside the
+  // grid, not kept, total).
+  bool voxel_insert(const void* depth, bool is_16uc1, double* glTf, int width, int height, double timestamp, uint32_t* summary_out = nullptr)
+  {
+    prepare(width, height);
+    if (!depth) throw std::runtime_error("voxel_insert: needs depth");
+    if (!have_cloud_intr_) throw std::runtime_error("voxel_insert: no intrinsics yet (getProjectionMatrix sets them)");
+    if (renderers_.empty() || !stage_frame(glTf, timestamp)) return false;
+    send_cloud_intrinsics();
+    send_voxel_grid();
+    const void* in = depth;
+    if (is_16uc1) check(rtuf_voxel_insert_batch_u16(ctx_, 1, reinterpret_cast<const uint16_t* const*>(&in), summary_out));
+    else check(rtuf_voxel_insert_batch(ctx_, 1, reinterpret_cast<const float* const*>(&in), summary_out));
+    return true;
+  }
+  void voxelClear() { if (ctx_ && voxel_sent_) check(rtuf_voxel_clear(ctx_)); }
+  // bits_out: ceil(nx * ny * nz / 32) words; counts_out: nullptr or nx * ny * nz words.  false before the first insert.
+  bool getVoxelGrid(uint32_t* bits_out, uint32_t* counts_out = nullptr)
+  {
+    if (!ctx_ || !voxel_sent_) return false;
+    check(rtuf_get_voxel_grid(ctx_, bits_out, counts_out));
+    return true;
+  }
+
   // ---- scene planes (include/rtuf.h, SCENE PLANES) ----
   // Lowers the scene plane to the readings of every pixel the robot filter keeps, for the camera and link poses filter_into
   // would use: call it for a few frames of the empty cell while the robot moves, with link padding in the model entries so
@@ -744,6 +783,19 @@ class RealtimeURDFFilter {
   std::map<int, std::pair<std::vector<int32_t>, std::vector<float>>> link_spheres_;      // setLinkSpheres: per model, link and xyzr of every sphere
   bool spheres_sent_ = false;                        // ctx_ holds link_spheres_ (cleared whenever initGL makes a new context)
   bool cloud_intr_sent_ = false;                     // ctx_ holds cloud_intr_given_ (cleared whenever initGL makes a new context)
+  // the context gets the grid of setVoxelGrid, when it has not got it yet
+  void send_voxel_grid()
+  {
+    if (!have_voxel_) throw std::runtime_error("no voxel grid yet (setVoxelGrid)");
+    if (voxel_sent_) return;
+    check(rtuf_set_voxel_grid(ctx_, voxel_origin_, voxel_size_, voxel_dims_, voxel_counts_ ? 1 : 0));
+    check(rtuf_set_voxel_transforms(ctx_, 0, 1, voxel_has_tf_ ? voxel_tf_ : nullptr));
+    voxel_sent_ = true;
+  }
+  double voxel_origin_[3] = {0, 0, 0}, voxel_size_ = 0.0, voxel_tf_[16] = {};      // setVoxelGrid
+  int voxel_dims_[3] = {0, 0, 0};
+  bool have_voxel_ = false, voxel_counts_ = false, voxel_has_tf_ = false;
+  bool voxel_sent_ = false;                          // ctx_ holds the grid (cleared whenever initGL makes a new context)
   std::map<std::pair<int, std::string>, uint16_t> link_labels_;
   std::vector<float> own_masked_;                    // render() with labels: the outputs the library-owned planes hold otherwise
   std::vector<uint8_t> own_mask_;

@@ -590,6 +590,63 @@ int rtuf_points_batch_device(rtuf_context *ctx, int n_streams, const float *d_po
 int rtuf_points_batch(rtuf_context *ctx, int n_streams, const float *const *points_in, const uint32_t *counts /* host */,
                       int radius_px, uint8_t *const *verdict_out, uint32_t *const *pixel_out, uint32_t *summary_out);
 
+/* VOXEL OCCUPANCY GRIDS.  New, beyond the reference: the kept points of ALL streams in one world grid -- which part of the
+ * workspace holds something that is neither robot nor learned scene -- as a bit per voxel and, optionally, a count per voxel:
+ * what a mapper, a planner's collision world or a speed-and-separation monitor asks of a cell with several cameras.  The
+ * context holds one grid; inserts accumulate in it until it is cleared.
+ * Definition.  Every float operation is single precision and rounded on its own.
+ * Grid: rtuf_set_voxel_grid gives the origin o (3 doubles, rounded to float), voxel_size (rounded to float; inv = 1.0f /
+ * voxel_size) and dims = (nx, ny, nz).  Voxel (ix, iy, iz) has index i = (iz * ny + iy) * nx + ix.  The bit grid holds bit
+ * i & 31 of word i >> 5, in ceil(nx * ny * nz / 32) uint32 words; the optional count grid (with_counts != 0) one uint32 per
+ * voxel, which WRAPS modulo 2^32.  Limits: each dimension 1 .. 2048, nx * ny * nz <= 1 << 27; voxel_size as a float finite
+ * and > 0 with a finite inv; a finite origin (as doubles and as floats).  The call allocates and zeroes the grid (both arrays
+ * in multiples of 16 bytes, counted in rtuf_stats.device_bytes); calling it again replaces the grid, dims == NULL frees it.
+ * Transform, optional and per stream: rtuf_set_voxel_transforms gives streams first_stream .. first_stream + n_streams - 1 one
+ * column-major matrix each (world_from_optical [n][16]; NULL: none for these streams).  Its 12 used entries m are rounded to
+ * float and applied exactly as rtuf_set_point_transforms defines: p'_r = ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) +
+ * m[12 + r].  A stream without one takes the point as it is, with no arithmetic.  Validation and waiting as in
+ * rtuf_set_point_transforms.  The transforms outlive the grid.
+ * Voxel of a world point p (voxel_of in rtuf_numerics.h): g_r = (p_r - o_r) * inv; the point is IN iff g_r >= 0 &&
+ * g_r < (float)dims_r for r = 0 .. 2 -- NaN and infinities fail, nothing is special-cased, the grid's high faces are outside
+ * -- and then i_r = (int)g_r.  The range tests come before the conversions, as for the pixel of a listed point.
+ * Plane form (rtuf_voxel_insert_batch*).  A pixel of stream s is KEPT iff its mask bit is 0 and its sensor value carries a
+ * point (positive and finite, as the cloud calls define it).  The mask bit is that of the mask-bits batch the context would
+ * run on these planes: dilation, per-link thresholds, link padding and scene planes are honoured.  The pixel's point is that of
+ * the cloud calls (cloud_point with the intrinsics of rtuf_set_cloud_intrinsics), then the stream's transform.  Every kept
+ * pixel whose voxel is IN sets that voxel's bit and adds 1 to its count.
+ * Point-list form (rtuf_voxel_insert_points_device).  The layout is that of rtuf_points_batch_device: d_points
+ * [n][capacity][3], d_counts [n] on the device, entries j < min(count, capacity).  An entry is taken iff d_verdict is NULL or
+ * its verdict byte is 0 (kept).  Its point first goes through the stream's point transform (rtuf_set_point_transforms, if set),
+ * then through world_from_optical.  So a compacted cloud, and a lidar list judged by a points batch, are inserted as they are.
+ * 16-byte loads where the points batch's alignment rule holds (d_verdict, if given, on a 4-byte boundary).
+ * Summary: d_summary is NULL or [n][4] uint32 per call -- inserted, outside the grid, not kept, total (H * W for the plane
+ * form, min(count, capacity) for the list form).  Every call overwrites it.  Bits are ORed and counts are added: everything is
+ * an integer, so no order of execution enters any output.
+ * Order of an insert.  It is synchronous, as learning a scene is, because an OR cannot be taken back: everything in flight is
+ * retired; the plane form then runs a mask-bits batch into a buffer of the context and retires it INCLUDING its re-run after
+ * a bin regrowth, so provisional bits never reach the grid; then one kernel runs and is waited for.  The list form retires
+ * what is in flight because its input may be a batch's output.  With several pipelines the grid lives in the first one and
+ * inserts run there, as rtuf_learn_scene_batch* does.
+ * rtuf_voxel_clear zeroes bits and counts.  rtuf_voxel_grid_device hands out the device arrays (any of the three out-pointers
+ * may be NULL; valid until the grid is replaced or freed), rtuf_get_voxel_grid copies them to the host (either may be NULL).
+ * Errors, each of which writes nothing and changes no grid.  RTUF_ERR_INVALID: bad arguments (a NULL array, n, capacity, dims,
+ * size or origin out of range), and the mask-bits calls' refusals with their texts (plane form).  RTUF_ERR_STATE: no grid, a
+ * context that is not finalized, a stream without cloud intrinsics (plane form), a count grid asked for -- counts_out, or the
+ * d_counts out-pointer -- when the grid has none.
+ * Out of scope: free-space carving along the rays, log-odds or decay, a threshold on counts, an asynchronous insert, merging
+ * the grids of several GPUs (OR the bit words, add the counts), a ROS OccupancyGrid or octomap adapter, labels per voxel. */
+int rtuf_set_voxel_grid(rtuf_context *ctx, const double origin[3], double voxel_size, const int dims[3], int with_counts);
+int rtuf_set_voxel_transforms(rtuf_context *ctx, int first_stream, int n_streams, const double *world_from_optical /* [n][16] column-major, NULL = none */);
+int rtuf_voxel_clear(rtuf_context *ctx);
+int rtuf_voxel_insert_batch(rtuf_context *ctx, int n_streams, const float *const *depth_in, uint32_t *summary_out);
+int rtuf_voxel_insert_batch_u16(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in, uint32_t *summary_out);
+int rtuf_voxel_insert_batch_device(rtuf_context *ctx, int n_streams, const float *d_depth, uint32_t *d_summary);
+int rtuf_voxel_insert_batch_device_u16(rtuf_context *ctx, int n_streams, const uint16_t *d_depth, uint32_t *d_summary);
+int rtuf_voxel_insert_points_device(rtuf_context *ctx, int n_streams, const float *d_points, const uint32_t *d_counts, int capacity,
+                                    const uint8_t *d_verdict, uint32_t *d_summary);
+int rtuf_voxel_grid_device(rtuf_context *ctx, const uint32_t **d_bits, const uint32_t **d_counts, size_t *n_voxels);
+int rtuf_get_voxel_grid(rtuf_context *ctx, uint32_t *bits_out, uint32_t *counts_out);
+
 /* LINK CLEARANCE TABLES.  New, beyond the reference: per stream and link label, how close the nearest kept point -- the
  * nearest thing that is not the robot -- is to the link, as a table [n_streams][n_labels] of 16-byte rows with no plane
  * written at all: what speed-and-separation monitors and reactive controllers ask of the filtered cloud.

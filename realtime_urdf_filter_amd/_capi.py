@@ -45,6 +45,9 @@ SYMBOLS = [
     "rtuf_set_scene_margins", "rtuf_clear_scene", "rtuf_learn_scene_batch", "rtuf_learn_scene_batch_u16",
     "rtuf_learn_scene_batch_device", "rtuf_learn_scene_batch_device_u16",
     "rtuf_set_point_transforms", "rtuf_points_batch_device", "rtuf_points_batch",
+    "rtuf_set_voxel_grid", "rtuf_set_voxel_transforms", "rtuf_voxel_clear", "rtuf_voxel_insert_batch", "rtuf_voxel_insert_batch_u16",
+    "rtuf_voxel_insert_batch_device", "rtuf_voxel_insert_batch_device_u16", "rtuf_voxel_insert_points_device", "rtuf_voxel_grid_device",
+    "rtuf_get_voxel_grid",
 ]
 
 # point list batches (include/rtuf.h, POINT LIST BATCHES): the verdict of a point, and the pixel of one that is not judged
@@ -237,6 +240,16 @@ def load_library(path=None):
     lib.rtuf_set_point_transforms.argtypes = [vp, ci, ci, vp]
     lib.rtuf_points_batch_device.argtypes = [vp, ci, vp, vp, ci, ci, vp, vp, vp]
     lib.rtuf_points_batch.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp]
+    lib.rtuf_set_voxel_grid.argtypes = [vp, vp, ctypes.c_double, vp, ci]
+    lib.rtuf_set_voxel_transforms.argtypes = [vp, ci, ci, vp]
+    lib.rtuf_voxel_clear.argtypes = [vp]
+    lib.rtuf_voxel_insert_batch.argtypes = [vp, ci, vp, vp]
+    lib.rtuf_voxel_insert_batch_u16.argtypes = [vp, ci, vp, vp]
+    lib.rtuf_voxel_insert_batch_device.argtypes = [vp, ci, vp, vp]
+    lib.rtuf_voxel_insert_batch_device_u16.argtypes = [vp, ci, vp, vp]
+    lib.rtuf_voxel_insert_points_device.argtypes = [vp, ci, vp, vp, ci, vp, vp]
+    lib.rtuf_voxel_grid_device.argtypes = [vp, vp, vp, vp]
+    lib.rtuf_get_voxel_grid.argtypes = [vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -657,6 +670,80 @@ class Context:
         q = lambda v: ctypes.c_void_p(v) if v else None
         self._check(self._lib.rtuf_points_batch_device(self._h, n, q(d_points), q(d_counts), int(capacity), int(radius_px), q(d_verdict),
                                                        q(d_pixel), q(d_summary)))
+
+    # voxel occupancy grids (include/rtuf.h, VOXEL OCCUPANCY GRIDS)
+    def set_voxel_grid(self, origin, voxel_size, dims, with_counts=True):
+        """One world grid for the kept points of all streams: origin [3] and voxel_size in metres, dims (nx, ny, nz).  Allocates
+        and zeroes it (replacing the grid that is there); dims None frees it."""
+        if dims is None:
+            self._check(self._lib.rtuf_set_voxel_grid(self._h, None, 0.0, None, 0))
+            self._voxel_dims = None
+            return
+        o = np.ascontiguousarray(origin, np.float64).reshape(3)
+        d = np.ascontiguousarray(dims, np.int32).reshape(3)
+        self._check(self._lib.rtuf_set_voxel_grid(self._h, _ptr(o), float(voxel_size), _ptr(d), 1 if with_counts else 0))
+        self._voxel_dims = (tuple(int(q) for q in d), bool(with_counts))
+
+    def set_voxel_transforms(self, first_stream, world_from_optical, n_streams=None):
+        """world_from_optical: [n,16] (or one row of 16) doubles, column-major, for streams first_stream ..; None takes the
+        transforms of n_streams streams (default: one) away again."""
+        if world_from_optical is None:
+            self._check(self._lib.rtuf_set_voxel_transforms(self._h, first_stream, 1 if n_streams is None else int(n_streams), None))
+            return
+        a = np.ascontiguousarray(world_from_optical, np.float64).reshape(-1, 16)
+        self._check(self._lib.rtuf_set_voxel_transforms(self._h, first_stream, len(a), _ptr(a)))
+
+    def voxel_clear(self):
+        self._check(self._lib.rtuf_voxel_clear(self._h))
+
+    def voxel_insert_batch(self, depth):
+        """Inserts the kept pixels of depth [n,H,W] float32 metres (or uint16 millimetres: the 16UC1 form) into the grid ->
+        summary [n,4] uint32: inserted, outside the grid, not kept, total.  Synchronous."""
+        u16 = np.asarray(depth).dtype == np.uint16
+        d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32).reshape(-1, self.height, self.width)
+        n = d.shape[0]
+        summary = np.zeros((n, 4), np.uint32)
+        PP = ctypes.c_void_p * max(n, 1)
+        din = PP(*[d[i].ctypes.data for i in range(n)])
+        fn = self._lib.rtuf_voxel_insert_batch_u16 if u16 else self._lib.rtuf_voxel_insert_batch
+        self._check(fn(self._h, n, din, _ptr(summary)))
+        return summary
+
+    def voxel_insert_batch_u16(self, depth_mm):
+        return self.voxel_insert_batch(np.ascontiguousarray(depth_mm, np.uint16))
+
+    def voxel_insert_batch_device(self, n, d_depth, d_summary=None, u16=False):
+        """Device pointers (ints; d_summary may be None): d_depth [n,H,W] float32 (uint16 with u16), d_summary [n,4] uint32.
+        Synchronous."""
+        q = lambda v: ctypes.c_void_p(v) if v else None
+        fn = self._lib.rtuf_voxel_insert_batch_device_u16 if u16 else self._lib.rtuf_voxel_insert_batch_device
+        self._check(fn(self._h, n, q(d_depth), q(d_summary)))
+
+    def voxel_insert_batch_device_u16(self, n, d_depth_mm, d_summary=None):
+        self.voxel_insert_batch_device(n, d_depth_mm, d_summary, u16=True)
+
+    def voxel_insert_points_device(self, n, d_points, d_counts, capacity, d_verdict=None, d_summary=None):
+        """Device pointers (ints; d_verdict and d_summary may be None): d_points [n,capacity,3] float32, d_counts [n] uint32,
+        d_verdict [n,capacity] uint8 (0 = taken), d_summary [n,4] uint32.  Synchronous."""
+        q = lambda v: ctypes.c_void_p(v) if v else None
+        self._check(self._lib.rtuf_voxel_insert_points_device(self._h, n, q(d_points), q(d_counts), int(capacity), q(d_verdict), q(d_summary)))
+
+    def voxel_grid_device(self, want_counts=True):
+        """-> (d_bits, d_counts or None, n_voxels): device pointers (ints) of the grid, valid until it is replaced or freed."""
+        b, k, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._lib.rtuf_voxel_grid_device(self._h, ctypes.byref(b), ctypes.byref(k) if want_counts else None, ctypes.byref(n)))
+        return b.value, (k.value if want_counts else None), int(n.value)
+
+    def voxel_grid(self, want_counts=None):
+        """-> (bits [ceil(n_voxels / 32)] uint32, counts [nz,ny,nx] uint32 or None): host copies of the grid.  want_counts
+        defaults to whether the grid was made with counts."""
+        _, _, n = self.voxel_grid_device(want_counts=False)
+        dims, has = getattr(self, "_voxel_dims", None) or ((n, 1, 1), False)
+        want = has if want_counts is None else bool(want_counts)
+        bits = np.empty((n + 31) // 32, np.uint32)
+        counts = np.empty(n, np.uint32) if want else None
+        self._check(self._lib.rtuf_get_voxel_grid(self._h, _ptr(bits), _ptr(counts) if want else None))
+        return bits, (counts.reshape(dims[2], dims[1], dims[0]) if want else None)
 
     # link clearance tables (include/rtuf.h, LINK CLEARANCE TABLES)
     def set_link_spheres(self, model, link, xyzr):

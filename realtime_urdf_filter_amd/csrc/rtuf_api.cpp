@@ -178,6 +178,18 @@ struct rtuf_context {
   std::vector<uint8_t> scene_touched;
   int scene_enabled = 0;
   uint32_t* d_scene_bits = nullptr; float* d_scene_stage = nullptr;
+  // Voxel occupancy grids (include/rtuf.h, VOXEL OCCUPANCY GRIDS): the grid as the kernels read it (vox_grid; nx = 0: none),
+  // its bit words and optional counts (allocated in multiples of 16 bytes: voxel_clear_kernel's stores), the streams'
+  // world_from_optical transforms (allocated by the first rtuf_set_voxel_transforms; vox_tf: the host's copy), and the inserts'
+  // scratch, allocated by the first insert that needs it: the mask bits of a plane insert, [max_streams] bits planes, and one
+  // block for the host forms -- the sensor planes, [max_streams][H][W] floats, with the summary [max_streams][4] behind them.
+  // With several pipelines all of this lives in the first one.
+  VoxelGrid vox_grid{};
+  size_t vox_voxels = 0, vox_words = 0;
+  uint32_t* d_vox_bits = nullptr; uint32_t* d_vox_counts = nullptr;
+  PointTransform* d_vox_tf = nullptr;
+  std::vector<PointTransform> vox_tf;
+  uint32_t* d_vox_mask_bits = nullptr; float* d_vox_stage = nullptr;
 
   // per-frame pose staging
   // Cameras and link matrices are staged in a ring of kMaxInflight + 1 pinned sets, like the joint positions: every
@@ -764,6 +776,7 @@ void rtuf_destroy(rtuf_context* c)
   dev_free(c, c->d_point_intr); dev_free(c, c->d_point_tf); dev_free(c, c->d_pt_stage);
   dev_free(c, c->d_clr_spheres); dev_free(c, c->d_clr_slot_label);
   dev_free(c, c->d_scene); dev_free(c, c->d_scene_streams); dev_free(c, c->d_scene_bits); dev_free(c, c->d_scene_stage);
+  dev_free(c, c->d_vox_bits); dev_free(c, c->d_vox_counts); dev_free(c, c->d_vox_tf); dev_free(c, c->d_vox_mask_bits); dev_free(c, c->d_vox_stage);
   for (auto& b : c->batch) {
     for (hipEvent_t ev : b.events) hipEventDestroy(ev);
     for (hipEvent_t ev : b.done) if (ev) hipEventDestroy(ev);
@@ -3354,6 +3367,244 @@ int rtuf_points_batch(rtuf_context* c, int n, const float* const* points_in, con
   }
   if (summary_out) HIP_TRY(c, hipMemcpy(summary_out, d + o_summary, (size_t)n * 4u * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return RTUF_OK;
+}
+
+// ---- voxel occupancy grids ---------------------------------------------------------------------------
+// An insert is no batch kind: like learning a scene it is a call of its own that retires what is in flight, runs an ordinary
+// mask-bits batch into a buffer of the context (plane form), retires that too -- re-runs after a bin regrowth included, so the
+// grid never sees provisional bits -- and then runs one kernel on lane 0 and waits for it.  With several pipelines the grid
+// lives in the first one: the front retires every pipeline (a list may be the output of a batch in any of them) and hands on.
+#define KIDS_FIRST_RETIRED(c, expr)                                                        \
+  if ((c) && !(c)->kids.empty()) {                                                         \
+    { const int rs_ = rtuf_sync(c); if (rs_ != RTUF_OK) return rs_; }                      \
+    rtuf_context* k = (c)->kids[0];                                                        \
+    const int rc_ = (expr);                                                                \
+    if (rc_ < 0) (c)->error = k->error;                                                    \
+    return rc_;                                                                            \
+  }
+
+static void free_voxel_grid(rtuf_context* c)
+{
+  dev_free(c, c->d_vox_bits); dev_free(c, c->d_vox_counts);
+  c->vox_grid = VoxelGrid{}; c->vox_voxels = 0; c->vox_words = 0;
+}
+
+static int clear_voxel_grid(rtuf_context* c)
+{
+  launch_voxel_clear(c->d_vox_bits, (c->vox_words + 3u) & ~(size_t)3u, c->lane[0].stream);
+  if (c->d_vox_counts) launch_voxel_clear(c->d_vox_counts, (c->vox_voxels + 3u) & ~(size_t)3u, c->lane[0].stream);
+  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
+  HIP_TRY(c, hipGetLastError());
+  return RTUF_OK;
+}
+
+int rtuf_set_voxel_grid(rtuf_context* c, const double* origin, double voxel_size, const int* dims, int with_counts)
+{
+  KIDS_ONE(c, 0, rtuf_set_voxel_grid(k, origin, voxel_size, dims, with_counts));
+  if (!c) return RTUF_ERR_INVALID;
+  if (!dims) {
+    WAIT_IF_PENDING(c);
+    hipSetDevice(c->device);
+    free_voxel_grid(c);
+    return RTUF_OK;
+  }
+  if (!origin) return c->fail(RTUF_ERR_INVALID, "null origin");
+  long long total = 1;
+  for (int r = 0; r < 3; r++) {
+    if (dims[r] < 1 || dims[r] > kMaxVoxelDim) return c->fail(RTUF_ERR_INVALID, "voxel grid: dims[%d] = %d: 1 .. %d", r, dims[r], kMaxVoxelDim);
+    total *= dims[r];
+    if (!std::isfinite(origin[r]) || !std::isfinite((float)origin[r])) return c->fail(RTUF_ERR_INVALID, "voxel grid: origin[%d] is not finite", r);
+  }
+  if (total > (long long)kMaxVoxels) return c->fail(RTUF_ERR_INVALID, "voxel grid: %lld voxels, at most %u", total, kMaxVoxels);
+  const float size = (float)voxel_size, inv = 1.0f / size;
+  if (!(std::isfinite(size) && size > 0.0f && std::isfinite(inv)))
+    return c->fail(RTUF_ERR_INVALID, "voxel grid: voxel_size must be finite and > 0 as a float, and so must its reciprocal (got %g)", voxel_size);
+  WAIT_IF_PENDING(c);
+  hipSetDevice(c->device);
+  // (the new arrays first: a failed allocation leaves the grid that is there)
+  const size_t words = ((size_t)total + 31u) / 32u;
+  uint32_t* bits = nullptr; uint32_t* counts = nullptr;
+  HIP_TRY(c, dev_alloc(c, &bits, ((words + 3u) & ~(size_t)3u) * sizeof(uint32_t)));
+  if (with_counts) {
+    const hipError_t e = dev_alloc(c, &counts, (((size_t)total + 3u) & ~(size_t)3u) * sizeof(uint32_t));
+    if (e != hipSuccess) { dev_free(c, bits); HIP_TRY(c, e); }
+  }
+  free_voxel_grid(c);
+  c->d_vox_bits = bits; c->d_vox_counts = counts;
+  c->vox_grid = VoxelGrid{(float)origin[0], (float)origin[1], (float)origin[2], inv, dims[0], dims[1], dims[2]};
+  c->vox_voxels = (size_t)total; c->vox_words = words;
+  return clear_voxel_grid(c);
+}
+
+int rtuf_set_voxel_transforms(rtuf_context* c, int first, int n, const double* world_from_optical)
+{
+  KIDS_ONE(c, 0, rtuf_set_voxel_transforms(k, first, n, world_from_optical));
+  if (!c) return RTUF_ERR_INVALID;
+  if (first < 0 || n <= 0 || n > c->max_streams || first > c->max_streams - n) return c->fail(RTUF_ERR_INVALID, "bad stream range (first=%d, n=%d)", first, n);
+  if (world_from_optical)
+    for (int s = 0; s < n; s++)
+      for (int col = 0; col < 4; col++)
+        for (int r = 0; r < 3; r++)
+          if (!std::isfinite(world_from_optical[16 * s + 4 * col + r]) || !std::isfinite((float)world_from_optical[16 * s + 4 * col + r]))
+            return c->fail(RTUF_ERR_INVALID, "stream %d: the voxel transform has a non-finite entry (row %d, column %d)", first + s, r, col);
+  WAIT_IF_PENDING(c);
+  hipSetDevice(c->device);
+  if (!world_from_optical && !c->d_vox_tf) return RTUF_OK;      // (none was ever set: nothing to take back)
+  if (!c->d_vox_tf) {
+    c->vox_tf.assign((size_t)c->max_streams, PointTransform{});
+    HIP_TRY(c, dev_alloc(c, &c->d_vox_tf, (size_t)c->max_streams * sizeof(PointTransform)));
+    HIP_TRY(c, hipMemset(c->d_vox_tf, 0, (size_t)c->max_streams * sizeof(PointTransform)));
+  }
+  for (int s = 0; s < n; s++) {
+    PointTransform t{};
+    if (world_from_optical) {
+      for (int i = 0; i < 16; i++) t.m[i] = (i & 3) == 3 ? 0.0f : (float)world_from_optical[16 * s + i];
+      t.on = 1u;
+    }
+    c->vox_tf[(size_t)(first + s)] = t;
+  }
+  HIP_TRY(c, hipMemcpy(c->d_vox_tf + first, c->vox_tf.data() + first, (size_t)n * sizeof(PointTransform), hipMemcpyHostToDevice));
+  return RTUF_OK;
+}
+
+static int need_voxel_grid(rtuf_context* c) { return c->d_vox_bits ? RTUF_OK : c->fail(RTUF_ERR_STATE, "the context has no voxel grid (rtuf_set_voxel_grid)"); }
+
+int rtuf_voxel_clear(rtuf_context* c)
+{
+  KIDS_ONE(c, 0, rtuf_voxel_clear(k));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = need_voxel_grid(c); if (rc != RTUF_OK) return rc; }
+  WAIT_IF_PENDING(c);
+  hipSetDevice(c->device);
+  return clear_voxel_grid(c);
+}
+
+int rtuf_voxel_grid_device(rtuf_context* c, const uint32_t** d_bits, const uint32_t** d_counts, size_t* n_voxels)
+{
+  KIDS_ONE(c, 0, rtuf_voxel_grid_device(k, d_bits, d_counts, n_voxels));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = need_voxel_grid(c); if (rc != RTUF_OK) return rc; }
+  if (d_counts && !c->d_vox_counts) return c->fail(RTUF_ERR_STATE, "the voxel grid has no counts (rtuf_set_voxel_grid: with_counts)");
+  if (d_bits) *d_bits = c->d_vox_bits;
+  if (d_counts) *d_counts = c->d_vox_counts;
+  if (n_voxels) *n_voxels = c->vox_voxels;
+  return RTUF_OK;
+}
+
+int rtuf_get_voxel_grid(rtuf_context* c, uint32_t* bits_out, uint32_t* counts_out)
+{
+  KIDS_ONE(c, 0, rtuf_get_voxel_grid(k, bits_out, counts_out));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = need_voxel_grid(c); if (rc != RTUF_OK) return rc; }
+  if (counts_out && !c->d_vox_counts) return c->fail(RTUF_ERR_STATE, "the voxel grid has no counts (rtuf_set_voxel_grid: with_counts)");
+  hipSetDevice(c->device);
+  if (bits_out) HIP_TRY(c, hipMemcpy(bits_out, c->d_vox_bits, c->vox_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (counts_out) HIP_TRY(c, hipMemcpy(counts_out, c->d_vox_counts, c->vox_voxels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RTUF_OK;
+}
+
+static void voxel_grid_args(const rtuf_context* c, VoxelArgs& va, int n, uint32_t* d_summary)
+{
+  const VoxelGrid& g = c->vox_grid;
+  va.ox = g.ox; va.oy = g.oy; va.oz = g.oz; va.inv = g.inv; va.nx = g.nx; va.ny = g.ny; va.nz = g.nz;
+  va.grid_bits = c->d_vox_bits; va.grid_counts = c->d_vox_counts; va.world_tf = c->d_vox_tf;
+  va.summary = d_summary; va.n_streams = n;
+}
+
+static int run_voxel_insert(rtuf_context* c, const VoxelArgs& va)
+{
+  launch_voxel_insert(va, c->lane[0].stream);
+  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
+  HIP_TRY(c, hipGetLastError());
+  return RTUF_OK;
+}
+
+// what a plane insert checks before anything is retired or written: the mask-bits calls' conditions, the grid, the intrinsics
+static int check_voxel_call(rtuf_context* c, int n, const void* in, bool u16)
+{
+  { const int rc = check_bits_call(c, n, in, in, u16); if (rc != RTUF_OK) return rc; }
+  { const int rc = need_voxel_grid(c); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; s < n; s++)
+    if (!c->d_cloud_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
+  return RTUF_OK;
+}
+
+static int voxel_insert_device(rtuf_context* c, int n, const void* d_depth, uint32_t* d_summary, bool u16)
+{
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  hipSetDevice(c->device);
+  if (!c->d_vox_mask_bits) HIP_TRY(c, dev_alloc(c, &c->d_vox_mask_bits, (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
+  { const int rc = submit_device(c, bits_request(n, d_depth, c->d_vox_mask_bits, u16)); if (rc != RTUF_OK) return rc; }
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  VoxelArgs va{};
+  voxel_grid_args(c, va, n, d_summary);
+  va.depth = static_cast<const float*>(d_depth); va.bits = c->d_vox_mask_bits; va.intr = c->d_cloud_intr;
+  va.width = c->width; va.height = c->height; va.io_u16 = u16 ? 1 : 0;
+  va.wide = (c->width & 3) == 0 && ((uintptr_t)d_depth & (u16 ? 7u : 15u)) == 0u ? 1 : 0;
+  return run_voxel_insert(c, va);
+}
+
+static int voxel_insert_host(rtuf_context* c, int n, const void* const* depth_in, uint32_t* summary_out, bool u16)
+{
+  { const int rc = check_voxel_call(c, n, depth_in, u16); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; s < n; s++) if (!depth_in[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  hipSetDevice(c->device);
+  const size_t plane = (size_t)c->width * c->height;
+  if (!c->d_vox_stage) HIP_TRY(c, dev_alloc(c, &c->d_vox_stage, (size_t)c->max_streams * (plane + 4u) * sizeof(float)));
+  uint32_t* const d_summary = reinterpret_cast<uint32_t*>(c->d_vox_stage + (size_t)c->max_streams * plane);
+  { const int rc = copy_planes(c, c->d_vox_stage, const_cast<void* const*>(depth_in), n, plane * (u16 ? sizeof(uint16_t) : sizeof(float)), hipMemcpyHostToDevice, nullptr);
+    if (rc != RTUF_OK) return rc; }
+  { const int rc = voxel_insert_device(c, n, c->d_vox_stage, summary_out ? d_summary : nullptr, u16); if (rc != RTUF_OK) return rc; }
+  if (summary_out) HIP_TRY(c, hipMemcpy(summary_out, d_summary, (size_t)n * 4u * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RTUF_OK;
+}
+
+int rtuf_voxel_insert_batch_device(rtuf_context* c, int n, const float* d_depth, uint32_t* d_summary)
+{
+  KIDS_FIRST_RETIRED(c, rtuf_voxel_insert_batch_device(k, n, d_depth, d_summary));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_voxel_call(c, n, d_depth, false);
+  return rc != RTUF_OK ? rc : voxel_insert_device(c, n, d_depth, d_summary, false);
+}
+
+int rtuf_voxel_insert_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth, uint32_t* d_summary)
+{
+  KIDS_FIRST_RETIRED(c, rtuf_voxel_insert_batch_device_u16(k, n, d_depth, d_summary));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_voxel_call(c, n, d_depth, true);
+  return rc != RTUF_OK ? rc : voxel_insert_device(c, n, d_depth, d_summary, true);
+}
+
+int rtuf_voxel_insert_batch(rtuf_context* c, int n, const float* const* depth_in, uint32_t* summary_out)
+{
+  KIDS_FIRST_RETIRED(c, rtuf_voxel_insert_batch(k, n, depth_in, summary_out));
+  if (!c) return RTUF_ERR_INVALID;
+  return voxel_insert_host(c, n, reinterpret_cast<const void* const*>(depth_in), summary_out, false);
+}
+
+int rtuf_voxel_insert_batch_u16(rtuf_context* c, int n, const uint16_t* const* depth_mm_in, uint32_t* summary_out)
+{
+  KIDS_FIRST_RETIRED(c, rtuf_voxel_insert_batch_u16(k, n, depth_mm_in, summary_out));
+  if (!c) return RTUF_ERR_INVALID;
+  return voxel_insert_host(c, n, reinterpret_cast<const void* const*>(depth_mm_in), summary_out, true);
+}
+
+int rtuf_voxel_insert_points_device(rtuf_context* c, int n, const float* d_points, const uint32_t* d_counts, int capacity, const uint8_t* d_verdict,
+                                    uint32_t* d_summary)
+{
+  KIDS_FIRST_RETIRED(c, rtuf_voxel_insert_points_device(k, n, d_points, d_counts, capacity, d_verdict, d_summary));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = check_batch_call(c, n, d_points && d_counts, false); if (rc != RTUF_OK) return rc; }
+  if (capacity < 1 || capacity > kMaxPointsCapacity) return c->fail(RTUF_ERR_INVALID, "capacity = %d: 1 .. %d", capacity, kMaxPointsCapacity);
+  { const int rc = need_voxel_grid(c); if (rc != RTUF_OK) return rc; }
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }      // (the list may be the output of a batch in flight)
+  hipSetDevice(c->device);
+  VoxelArgs va{};
+  voxel_grid_args(c, va, n, d_summary);
+  va.points = d_points; va.counts = d_counts; va.verdict = d_verdict; va.point_tf = c->d_point_tf; va.capacity = capacity;
+  va.wide = ((uintptr_t)d_points & 15u) == 0u && ((uintptr_t)d_verdict & 3u) == 0u && (capacity & 3) == 0 ? 1 : 0;
+  return run_voxel_insert(c, va);
 }
 
 // ---- link clearance tables ---------------------------------------------------------------------------

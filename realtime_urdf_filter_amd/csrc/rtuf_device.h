@@ -503,6 +503,34 @@ struct SceneLearnArgs {
   int n_streams, width, height, io_u16;
 };
 
+// Voxel occupancy grids (include/rtuf.h, VOXEL OCCUPANCY GRIDS): one insert into the context's grid, plane form (depth, bits,
+// intr) or list form (points, counts, verdict).  Both run on lane 0 once everything in flight is retired, so the bits are
+// final; streams 0 .. n_streams - 1.  The grid arrays are allocated in multiples of 16 bytes (voxel_clear_kernel).
+struct VoxelArgs {
+  float ox, oy, oz, inv;         // the grid: VoxelGrid's fields (rtuf_numerics.h)
+  int nx, ny, nz;
+  uint32_t* grid_bits;           // [ceil(n_voxels / 32)] ORed into
+  uint32_t* grid_counts;         // [n_voxels] added to, modulo 2^32; or nullptr
+  const PointTransform* world_tf;// [max_streams] world_from_optical (on = 0: none), or nullptr: no stream has one
+  uint32_t* summary;             // [n][4] inserted, outside the grid, not kept, total; or nullptr.  Zeroed in front of the kernel
+  // plane form
+  const float* depth;            // [n][H][W] sensor planes (f32 metres or, with io_u16, uint16 millimetres)
+  const uint32_t* bits;          // [n][H][ceil(W/32)] the final mask bits of these planes
+  const CloudIntrinsics* intr;   // [max_streams]
+  int width, height, io_u16;
+  // list form
+  const float* points;           // [n][capacity][3]
+  const uint32_t* counts;        // [n] on the device
+  const uint8_t* verdict;        // [n][capacity], 0 = taken; or nullptr: every entry is taken
+  const PointTransform* point_tf;// [max_streams] rtuf_set_point_transforms' (applied first), or nullptr
+  int capacity;
+  int n_streams;
+  int wide;                      // plane form: depth starts on a 16-byte (16UC1: 8-byte) boundary and W % 4 == 0; list form: the points
+                                 // batch's rule (points on a 16-byte boundary, verdict on a 4-byte one, capacity % 4 == 0)
+};
+void launch_voxel_clear(uint32_t* p, size_t n_words, hipStream_t st);      // n_words % 4 == 0, p on a 16-byte boundary
+void launch_voxel_insert(const VoxelArgs& a, hipStream_t st);              // a.points selects the list form
+
 struct FkArgs {
   const int32_t* parent;        // [F]
   const int32_t* joint_type;    // [F]

@@ -4042,6 +4042,212 @@ void launch_points(const PointsArgs& a, hipStream_t st)
   static_assert(kMaxPointsRadius == 4, "launch_points names an instantiation per radius");
 }
 
+// ---- voxel occupancy grids (include/rtuf.h, VOXEL OCCUPANCY GRIDS) ---------------------------------------------------------
+// One insert: every kept pixel (plane form) or taken list entry (list form) of every stream becomes a world point
+// (cloud_point, point_transform), the point a voxel index (voxel_of), and the voxel gets its bit ORed and its count added.
+// Neighbouring pixels mostly share a voxel -- a 5 cm voxel at 1 m is 25 VGA pixels wide -- so one atomic per pixel would
+// serialise on a few addresses of a grid all XCDs share.  A thread holds four consecutive pixels (entries): equal neighbours
+// are merged inside the thread first, then runs of equal index across adjacent lanes of the wave, and the run's first lane
+// issues one atomicOr and one atomicAdd for the whole run (relaxed, agent scope).  Lane order is pixel order, a row's end next
+// to the following row's start: a run may cross rows, its sum is the same.  Integers only: no result depends on the order
+// of execution.
+
+__global__ __launch_bounds__(kBlock) void voxel_clear_kernel(uint4* p, size_t n16)
+{
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n16; i += (size_t)gridDim.x * kBlock) p[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+void launch_voxel_clear(uint32_t* p, size_t n_words, hipStream_t st)
+{
+  const size_t n16 = n_words / 4u, blocks = (n16 + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(voxel_clear_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks))), dim3(kBlock), 0, st, reinterpret_cast<uint4*>(p), n16);
+}
+
+// n points in voxel idx (voxel_of's index: below the grid's size, or kVoxelNone: nothing to do)
+__device__ __forceinline__ void voxel_emit(const VoxelArgs& a, uint32_t idx, uint32_t n)
+{
+  if (idx == kVoxelNone) return;
+  __hip_atomic_fetch_or(a.grid_bits + (idx >> 5), 1u << (idx & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (a.grid_counts) __hip_atomic_fetch_add(a.grid_counts + idx, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The four indices of every lane of the wave, in lane order (every lane of the wave calls this, lanes without work with four
+// kVoxelNone).  A lane's HEAD run holds its entry 0 and what equals it behind, its TAIL run its entry 3 and what equals it in
+// front; a UNIFORM lane is one run of four.  Entries 1 and 2 outside both runs are emitted by the lane itself.  A lane JOINS
+// when its entry 0 equals the previous lane's entry 3: its head run is then part of the chain that previous lane's tail run
+// belongs to, and a uniform lane that joins passes the chain on.  Every other tail run starts a chain: its lane adds the 4s of
+// the uniform joining lanes behind it and the head run of the lane that ends the chain, and emits once.
+__device__ __forceinline__ void voxel_aggregate(const VoxelArgs& a, const uint32_t (&idx)[4])
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool uniform = idx[0] == idx[1] && idx[1] == idx[2] && idx[2] == idx[3];
+  const uint32_t ch = idx[1] != idx[0] ? 1u : (idx[2] != idx[0] ? 2u : 3u);                   // (of a lane that is not uniform: 1 .. 3)
+  const uint32_t ct = uniform ? 4u : (idx[2] != idx[3] ? 1u : (idx[1] != idx[3] ? 2u : 3u));
+  const bool in1 = !uniform && ch == 1u && ct <= 2u, in2 = !uniform && ct == 1u && ch <= 2u;  // entries 1, 2 in neither run
+  if (in1 && in2 && idx[1] == idx[2]) voxel_emit(a, idx[1], 2u);
+  else {
+    if (in1) voxel_emit(a, idx[1], 1u);
+    if (in2) voxel_emit(a, idx[2], 1u);
+  }
+  const uint32_t prev_tail = __shfl_up(idx[3], 1);
+  const bool joins = lane > 0u && idx[0] == prev_tail;
+  const unsigned long long J = __ballot(joins), C = __ballot(joins && uniform);
+  const unsigned long long stop = ((~C) >> 1) >> lane;              // bit i: lane + 1 + i does not pass a chain on
+  const uint32_t m = stop ? lane + 1u + (uint32_t)__builtin_ctzll(stop) : 64u;      // the chain's last lane, if it joins; 64: the wave ends first
+  const uint32_t ch_m = __shfl(ch, (int)(m & 63u));
+  if (!(joins && uniform)) voxel_emit(a, idx[3], ct + 4u * (m - lane - 1u) + (m < 64u && ((J >> m) & 1ull) ? ch_m : 0u));
+  if (!uniform && !joins) voxel_emit(a, idx[0], ch);
+}
+
+// The summary's three counted fields of one stream (row: its four words, zeroed in front of the kernel): per wave a packed
+// add-reduction (at most 4 per lane and field: 256 per wave, 10-bit fields), per workgroup in LDS, then one atomic per
+// workgroup and field.  Every thread of the workgroup calls this.
+__device__ __forceinline__ void voxel_summarise(uint32_t* row, uint32_t inserted, uint32_t outside, uint32_t not_kept)
+{
+  __shared__ uint32_t total[3];
+  if (threadIdx.x < 3u) total[threadIdx.x] = 0u;
+  __syncthreads();
+  uint32_t w = inserted | outside << 10 | not_kept << 20;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) w += (uint32_t)__shfl_xor((int)w, o);
+  if ((threadIdx.x & 63u) == 0u && w) {
+    if (w & 1023u) atomicAdd(&total[0], w & 1023u);
+    if ((w >> 10) & 1023u) atomicAdd(&total[1], (w >> 10) & 1023u);
+    if (w >> 20) atomicAdd(&total[2], w >> 20);
+  }
+  __syncthreads();
+  if (threadIdx.x < 3u && total[threadIdx.x]) atomicAdd(row + threadIdx.x, total[threadIdx.x]);
+}
+
+// Plane form: one thread per four consecutive pixels of a row -- one 16-byte (f32) or 8-byte (16UC1) sensor load on the wide
+// path, scalar loads otherwise (a row's remainder when W % 4 != 0 included), and the pixels' nibble of their bits word.  The
+// stream is the workgroup's (blockIdx.y): intrinsics, matrix and grid are read through uniform addresses.
+// grid: (ceil(H * ceil(W / 4) / kBlock), n).
+template <bool U16>
+__global__ __launch_bounds__(kBlock) void voxel_insert_kernel(VoxelArgs a)
+{
+  const int stream = (int)blockIdx.y;
+  const int w4 = (a.width + 3) >> 2;
+  const uint32_t t = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  uint32_t idx[4] = {kVoxelNone, kVoxelNone, kVoxelNone, kVoxelNone};
+  uint32_t inserted = 0u, outside = 0u, not_kept = 0u;
+  if (t < (uint32_t)w4 * (uint32_t)a.height) {
+    const int v = (int)(t / (uint32_t)w4), u = (int)(t - (uint32_t)v * (uint32_t)w4) * 4;
+    const int nvalid = a.width - u < 4 ? a.width - u : 4;
+    const size_t pix = ((size_t)stream * (size_t)a.height + (size_t)v) * (size_t)a.width + (size_t)u;
+    float s[4];
+    if (a.wide) {
+      if (U16) {
+        const uint2 q = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(a.depth) + pix);
+        s[0] = u16_to_metres(q.x & 0xffffu); s[1] = u16_to_metres(q.x >> 16); s[2] = u16_to_metres(q.y & 0xffffu); s[3] = u16_to_metres(q.y >> 16);
+      } else {
+        const float4 q = *reinterpret_cast<const float4*>(a.depth + pix);
+        s[0] = q.x; s[1] = q.y; s[2] = q.z; s[3] = q.w;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        s[j] = j < nvalid ? (U16 ? u16_to_metres(reinterpret_cast<const uint16_t*>(a.depth)[pix + (size_t)j]) : a.depth[pix + (size_t)j]) : 0.0f;
+    }
+    const int row_words = (a.width + 31) >> 5;
+    const uint32_t nib = a.bits[((size_t)stream * a.height + (size_t)v) * (size_t)row_words + (size_t)(u >> 5)] >> (u & 31);
+    const CloudIntrinsics k = a.intr[stream];
+    const VoxelGrid g = {a.ox, a.oy, a.oz, a.inv, a.nx, a.ny, a.nz};
+    const PointTransform* tf = a.world_tf ? a.world_tf + stream : nullptr;
+    const bool moved = tf && tf->on != 0u;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (j >= nvalid) continue;
+      if (((nib >> j) & 1u) || !cloud_sensor_valid(s[j])) { not_kept++; continue; }
+      float x, y, z;
+      cloud_point(u + j, v, s[j], k, x, y, z);
+      if (moved) point_transform(tf->m, x, y, z);
+      if (voxel_of(x, y, z, g, idx[j])) inserted++;
+      else outside++;
+    }
+  }
+  voxel_aggregate(a, idx);
+  if (a.summary) {
+    if (blockIdx.x == 0u && threadIdx.x == 0u) a.summary[(size_t)stream * 4u + 3u] = (uint32_t)a.width * (uint32_t)a.height;
+    voxel_summarise(a.summary + (size_t)stream * 4u, inserted, outside, not_kept);
+  }
+}
+
+// List form: a thread takes kPointsPerThread consecutive entries of one stream, as points_filter_kernel does (three 16-byte
+// loads and the verdicts' word on the wide path).  grid: (ceil(capacity / (kBlock * kPointsPerThread)), n).
+__global__ __launch_bounds__(kBlock) void voxel_insert_points_kernel(VoxelArgs a)
+{
+  const int stream = (int)blockIdx.y;
+  const uint32_t capacity = (uint32_t)a.capacity;
+  const uint32_t have = a.counts[stream];
+  const uint32_t m = have < capacity ? have : capacity;
+  const uint32_t t = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  const uint32_t j0 = t * (uint32_t)kPointsPerThread;
+  const uint32_t live = j0 >= m ? 0u : (m - j0 < (uint32_t)kPointsPerThread ? m - j0 : (uint32_t)kPointsPerThread);
+  uint32_t idx[4] = {kVoxelNone, kVoxelNone, kVoxelNone, kVoxelNone};
+  uint32_t inserted = 0u, outside = 0u, not_kept = 0u;
+  if (live) {
+    const size_t base = (size_t)stream * (size_t)capacity + (size_t)j0;
+    float p[3 * kPointsPerThread];
+    uint32_t verdict[kPointsPerThread] = {0u, 0u, 0u, 0u};
+    if (a.wide && live == (uint32_t)kPointsPerThread) {
+      const float4* src = reinterpret_cast<const float4*>(a.points + base * 3u);
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        const float4 q = src[i];
+        p[4 * i] = q.x; p[4 * i + 1] = q.y; p[4 * i + 2] = q.z; p[4 * i + 3] = q.w;
+      }
+      if (a.verdict) {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(a.verdict + base);
+#pragma unroll
+        for (int i = 0; i < kPointsPerThread; i++) verdict[i] = (w >> (8 * i)) & 255u;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 3 * kPointsPerThread; i++) p[i] = (uint32_t)(i / 3) < live ? a.points[base * 3u + (size_t)i] : 0.0f;
+      if (a.verdict)
+#pragma unroll
+        for (int i = 0; i < kPointsPerThread; i++) verdict[i] = (uint32_t)i < live ? (uint32_t)a.verdict[base + (size_t)i] : 0u;
+    }
+    const VoxelGrid g = {a.ox, a.oy, a.oz, a.inv, a.nx, a.ny, a.nz};
+    const PointTransform* ptf = a.point_tf ? a.point_tf + stream : nullptr;
+    const PointTransform* wtf = a.world_tf ? a.world_tf + stream : nullptr;
+    const bool moved = ptf && ptf->on != 0u, moved_again = wtf && wtf->on != 0u;
+#pragma unroll
+    for (int i = 0; i < kPointsPerThread; i++) {
+      if ((uint32_t)i >= live) continue;
+      if (verdict[i] != kPointKept) { not_kept++; continue; }
+      float x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
+      if (moved) point_transform(ptf->m, x, y, z);
+      if (moved_again) point_transform(wtf->m, x, y, z);
+      if (voxel_of(x, y, z, g, idx[i])) inserted++;
+      else outside++;
+    }
+  }
+  voxel_aggregate(a, idx);
+  if (a.summary) {
+    if (blockIdx.x == 0u && threadIdx.x == 0u) a.summary[(size_t)stream * 4u + 3u] = m;
+    voxel_summarise(a.summary + (size_t)stream * 4u, inserted, outside, not_kept);
+  }
+}
+static_assert(kPointsPerThread == 4, "voxel_aggregate merges four entries per lane");
+
+void launch_voxel_insert(const VoxelArgs& a, hipStream_t st)
+{
+  if (a.summary) {
+    const int n_words = a.n_streams * 4;
+    hipLaunchKernelGGL(points_zero_summary_kernel, dim3((unsigned)((n_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.summary, n_words);
+  }
+  if (a.points) {
+    const unsigned per_block = (unsigned)kBlock * (unsigned)kPointsPerThread;
+    hipLaunchKernelGGL(voxel_insert_points_kernel, dim3(((unsigned)a.capacity + per_block - 1u) / per_block, (unsigned)a.n_streams), dim3(kBlock), 0, st, a);
+    return;
+  }
+  const size_t lanes = (size_t)a.height * (size_t)((a.width + 3) >> 2);
+  const dim3 grid((unsigned)((lanes + kBlock - 1) / kBlock), (unsigned)a.n_streams);
+  if (a.io_u16) hipLaunchKernelGGL(voxel_insert_kernel<true>, grid, dim3(kBlock), 0, st, a);
+  else hipLaunchKernelGGL(voxel_insert_kernel<false>, grid, dim3(kBlock), 0, st, a);
+}
+
 __global__ __launch_bounds__(kBlock) void fill_f32_kernel(float* p, size_t n, float v)
 {
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) p[i] = v;

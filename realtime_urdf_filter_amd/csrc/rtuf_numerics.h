@@ -2,7 +2,7 @@
 // shares: the 24-bit depth and its bit-pattern forms, the depth keys' encoding of a near fragment's float z, the set-up's
 // 32-bit edge constants, the key format's host-side rules, the compare threshold's constants, division core and the rule
 // that admits that core, the pixel classes of the link residual tables, the point of a filtered point cloud, the pixel and
-// verdict of a listed point, the sphere centres and point-to-sphere clearances of the link clearance tables, the reach of a
+// verdict of a listed point, the voxel of a world point, the sphere centres and point-to-sphere clearances of the link clearance tables, the reach of a
 // padded link's pixel, the scene planes' threshold and learning rule, and the set-up kernel's packed list counters.
 //
 // Included by the kernels (rtuf_kernels.hip, device and host pass), the host API (rtuf_api.cpp), scripts/fdiv_check.hip (which
@@ -241,6 +241,33 @@ RTUF_NUMERIC_HD bool point_pixel(float x, float y, float z, const PointIntrinsic
 // A judged point of depth z against the smallest virtual depth vmin of its window and the threshold t: filtered iff
 // z > vmin - t (one float subtraction; vmin = +inf where no link drew, and then nothing is above it).
 RTUF_NUMERIC_HD uint32_t point_verdict(float z, float vmin, float t) { return z > vmin - t ? kPointFiltered : kPointKept; }
+
+// ---------------------------------------------------------------------------------------
+// voxel occupancy grids (include/rtuf.h, VOXEL OCCUPANCY GRIDS): the voxel a world point falls into.  The point comes from
+// cloud_point (plane form) or a list, optionally through point_transform -- the chain above, shared with the point list
+// batches.  (tests/voxel_check.cpp against a numpy form, index for index.)
+// ---------------------------------------------------------------------------------------
+
+// The grid as the kernels read it: origin and inv = 1.0f / (float)voxel_size as floats, and the dims (each 1 .. 2048, their
+// product at most 1 << 27: every index fits 27 bits).
+struct VoxelGrid { float ox, oy, oz, inv; int nx, ny, nz; };
+constexpr int kMaxVoxelDim = 2048;
+constexpr uint32_t kMaxVoxels = 1u << 27;
+constexpr uint32_t kVoxelNone = 0xffffffffu;
+
+// g_r = (p_r - o_r) * inv; IN iff 0 <= g_r < (float)dims_r for every r (NaN and infinities fail: nothing is special-cased);
+// then i_r = (int)g_r and index = (iz * ny + iy) * nx + ix.  The range tests come before the conversions, as in point_pixel:
+// no out-of-range float is ever converted.  index = kVoxelNone for a point that is not IN.
+RTUF_NUMERIC_HD bool voxel_of(float x, float y, float z, const VoxelGrid& g, uint32_t& index)
+{
+  index = kVoxelNone;
+  const float dx = x - g.ox, dy = y - g.oy, dz = z - g.oz;
+  const float gx = dx * g.inv, gy = dy * g.inv, gz = dz * g.inv;
+  if (!(gx >= 0.0f && gx < (float)g.nx && gy >= 0.0f && gy < (float)g.ny && gz >= 0.0f && gz < (float)g.nz)) return false;
+  const int ix = (int)gx, iy = (int)gy, iz = (int)gz;
+  index = (uint32_t)((iz * g.ny + iy) * g.nx + ix);
+  return true;
+}
 
 // ---------------------------------------------------------------------------------------
 // link clearance tables (include/rtuf.h, LINK CLEARANCE TABLES): a sphere's centre in the camera frame, and the clearance of

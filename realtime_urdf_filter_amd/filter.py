@@ -545,6 +545,61 @@ class RealtimeURDFFilter:
         d = d.astype(np.uint16 if d.dtype == np.uint16 else np.float32, copy=False).reshape(1, height, width)
         return self._ctx.link_clearance_batch(d, self.numLinkResidualRows(), max_distance)[0]
 
+    # ---- voxel occupancy grids (include/rtuf.h, VOXEL OCCUPANCY GRIDS) ------------------------
+    def setVoxelGrid(self, origin, voxel_size, dims, with_counts=True, world_from_optical=None):
+        """New, beyond the reference: one world grid that voxelInsert() accumulates kept points in.  origin [3] and voxel_size
+        in metres, dims (nx, ny, nz); world_from_optical: None or the camera's column-major [16] matrix.  The grid belongs to the
+        device context: a new image size makes a new, empty one.  dims None drops it."""
+        self.voxel_grid_ = None if dims is None else (tuple(float(q) for q in origin), float(voxel_size), tuple(int(q) for q in dims), bool(with_counts),
+                                                      None if world_from_optical is None else np.array(world_from_optical, np.float64).reshape(16))
+        self._voxel_ctx_ = None
+        if dims is None and self._ctx is not None:
+            self._ctx.set_voxel_grid(None, 0.0, None)
+
+    def _give_voxel_grid(self):
+        grid = getattr(self, "voxel_grid_", None)
+        if grid is None:
+            raise RuntimeError("no voxel grid yet (setVoxelGrid)")
+        if getattr(self, "_voxel_ctx_", None) is not self._ctx:      # (a new context holds no grid)
+            self._ctx.set_voxel_grid(grid[0], grid[1], grid[2], grid[3])
+            self._ctx.set_voxel_transforms(0, grid[4])
+            self._voxel_ctx_ = self._ctx
+
+    def voxelInsert(self, depth, projection_matrix, width, height, timestamp=None):
+        """Inserts the pixels filter() would keep -- dilation, thresholds, padding and scene honoured -- into the grid of
+        setVoxelGrid(), for the camera and link poses filter() would use and the intrinsics cloud() would use.  depth: [H,W]
+        float32 metres or uint16 millimetres; the width must be a multiple of 4.  Returns the summary [4] uint32 (inserted,
+        outside the grid, not kept, total); None where filter() would have returned without a result."""
+        self._ensure_size(width, height)
+        if not self.renderers_:
+            return None
+        intr = getattr(self, "cloud_intrinsics_", None)
+        if intr is None:
+            raise RuntimeError("voxelInsert(): no intrinsics yet (getProjectionMatrix sets them)")
+        try:
+            self._stage_stream(0, projection_matrix, self.tf_, timestamp)
+        except Exception as e:                      # noqa: BLE001 - ROS_ERROR + return (quirk Q6)
+            log.error("%s", e)
+            return None
+        if getattr(self, "_cloud_intr_given_", None) != intr:      # (initGL clears it with every new context)
+            self._ctx.set_cloud_intrinsics(0, intr)
+            self._cloud_intr_given_ = intr
+        self._give_voxel_grid()
+        d = np.asarray(depth)
+        d = d.astype(np.uint16 if d.dtype == np.uint16 else np.float32, copy=False).reshape(1, height, width)
+        return self._ctx.voxel_insert_batch(d)[0]
+
+    def voxelClear(self):
+        if self._ctx is not None and getattr(self, "_voxel_ctx_", None) is self._ctx:
+            self._ctx.voxel_clear()
+
+    def voxelGrid(self):
+        """(bits [ceil(nx * ny * nz / 32)] uint32, counts [nz,ny,nx] uint32 or None) of the grid as it stands."""
+        if self._ctx is None:
+            raise RuntimeError("voxelGrid(): no frame yet")
+        self._give_voxel_grid()
+        return self._ctx.voxel_grid()
+
     # ---- scene planes (include/rtuf.h, SCENE PLANES) ------------------------------------------
     def learnScene(self, depth, projection_matrix, width, height, timestamp=None):
         """New, beyond the reference: lowers stream 0's scene plane to the readings of every pixel the robot filter keeps, for the

@@ -122,9 +122,10 @@ def build(tag):
     text("link clearance tables on c3: clearance batches beside the mask-bits batch and beside compacted cloud + torch ops", ["README.md", "DESIGN.md 4"], "clearance_rate_c3.txt", "the last line")
     text("link padding on c3: padded mask-bits and cloud batches beside the dilated leg of the same run", ["README.md", "DESIGN.md 4"], "link_padding_rate_c3.txt", "the last line")
     text("point list batches on c3: points batches beside the render batch they are built on and beside render + torch ops", ["README.md", "DESIGN.md 4"], "points_rate_c3.txt", "the last line")
+    text("voxel occupancy grids on c3: clear + insert cycles beside the mask-bits batch and beside compacted cloud + torch ops", ["README.md", "DESIGN.md 4"], "voxel_rate_c3.txt", "the last line")
     f = "scene_rate_c3.txt"
     if os.path.exists(os.path.join(PROFILES, f)):
-        body = open(os.path.join(PROFILES, f)).read().splitlines()
+        body =open(os.path.join(PROFILES, f)).read().splitlines()
         v = {"summary": next((l[:400] for l in body if l.startswith("# c3 frames/s")), None),
              "kernels": [json.loads(l) for l in body if l.startswith('{"kernel"')],
              "headline_same_box": [l for l in body if l.startswith("other ") or l.startswith("this ")]}
