@@ -514,6 +514,34 @@ class RealtimeURDFFilter {
     return true;
   }
 
+  // ---- voxel free space (include/rtuf.h, VOXEL FREE SPACE) ----
+  // Marks the voxels of setVoxelGrid's grid that the camera sees THROUGH: whose centre lies more than `margin` metres in front
+  // of the smallest valid reading within radius_px pixels of its pixel, with the intrinsics cloud_into would use.  The mask is
+  // not read, no model is posed and glTf is not read.  depth: width x height float metres, or uint16 millimetres with is_16uc1;
+  // any width.  summary_out: nullptr or four words (free, not free, not seen, nx * ny * nz).
+  bool voxel_carve(const void* depth, bool is_16uc1, const double* glTf, int width, int height, double margin, int radius_px = 0, uint32_t* summary_out = nullptr)
+  {
+    (void)glTf;
+    prepare(width, height);
+    if (!depth) throw std::runtime_error("voxel_carve: needs depth");
+    if (!have_cloud_intr_) throw std::runtime_error("voxel_carve: no intrinsics yet (getProjectionMatrix sets them)");
+    if (renderers_.empty()) return false;
+    send_cloud_intrinsics();
+    send_voxel_grid();
+    const void* in = depth;
+    if (is_16uc1) check(rtuf_voxel_carve_batch_u16(ctx_, 1, reinterpret_cast<const uint16_t* const*>(&in), margin, radius_px, summary_out));
+    else check(rtuf_voxel_carve_batch(ctx_, 1, reinterpret_cast<const float* const*>(&in), margin, radius_px, summary_out));
+    return true;
+  }
+  // free_bits: ceil(nx * ny * nz / 32) words; occupied wins over free, a voxel with neither bit is unknown.  false before the
+  // first insert or carve.
+  bool getVoxelFree(uint32_t* free_bits)
+  {
+    if (!ctx_ || !voxel_sent_) return false;
+    check(rtuf_get_voxel_free(ctx_, free_bits));
+    return true;
+  }
+
   // ---- scene planes (include/rtuf.h, SCENE PLANES) ----
   // Lowers the scene plane to the readings of every pixel the robot filter keeps, for the camera and link poses filter_into
   // would use: call it for a few frames of the empty cell while the robot moves, with link padding in the model entries so

@@ -633,7 +633,7 @@ int rtuf_points_batch(rtuf_context *ctx, int n_streams, const float *const *poin
  * size or origin out of range), and the mask-bits calls' refusals with their texts (plane form).  RTUF_ERR_STATE: no grid, a
  * context that is not finalized, a stream without cloud intrinsics (plane form), a count grid asked for -- counts_out, or the
  * d_counts out-pointer -- when the grid has none.
- * Out of scope: free-space carving along the rays, log-odds or decay, a threshold on counts, an asynchronous insert, merging
+ * Out of scope: log-odds or decay, a threshold on counts, an asynchronous insert, merging
  * the grids of several GPUs (OR the bit words, add the counts), a ROS OccupancyGrid or octomap adapter, labels per voxel. */
 int rtuf_set_voxel_grid(rtuf_context *ctx, const double origin[3], double voxel_size, const int dims[3], int with_counts);
 int rtuf_set_voxel_transforms(rtuf_context *ctx, int first_stream, int n_streams, const double *world_from_optical /* [n][16] column-major, NULL = none */);
@@ -646,6 +646,60 @@ int rtuf_voxel_insert_points_device(rtuf_context *ctx, int n_streams, const floa
                                     const uint8_t *d_verdict, uint32_t *d_summary);
 int rtuf_voxel_grid_device(rtuf_context *ctx, const uint32_t **d_bits, const uint32_t **d_counts, size_t *n_voxels);
 int rtuf_get_voxel_grid(rtuf_context *ctx, uint32_t *bits_out, uint32_t *counts_out);
+
+/* VOXEL FREE SPACE.  New, beyond the reference: the third state of the grid above.  A clear occupancy bit is ambiguous: a
+ * camera may have looked THROUGH the voxel and seen further, or no camera can see the voxel at all -- behind the robot, behind
+ * an intruder, outside every frustum, a sensor hole.  A carve marks the first kind in a second bit array, the FREE grid.
+ * Reading: occupied wins; free and not occupied = seen through; neither = unknown, which a speed-and-separation monitor must
+ * treat as occupied and a planner must not drive through.  It is built projectively, voxel by voxel, not ray by ray: every
+ * voxel centre is projected into every stream's sensor plane and compared with what the sensor read there.
+ * Definition.  Every float operation is single precision and rounded on its own; divisions are IEEE.
+ * Free grid: a second bit array beside the occupancy bits with the same indexing (bit i & 31 of word i >> 5), allocated in
+ * multiples of 16 bytes and zeroed on the first carve or the first read and counted in rtuf_stats.device_bytes.
+ * rtuf_voxel_clear zeroes it too; rtuf_set_voxel_grid frees it with the grid, whether the grid is replaced or dims == NULL.
+ * Bits are ORed over calls, as inserts are.  Bits at indices >= nx * ny * nz are always 0.
+ * Voxel centre (voxel_centre in rtuf_numerics.h): size = (float)voxel_size, c_r = o_r + ((float)i_r + 0.5f) * size -- one add
+ * (exact), one product, one add.
+ * Into the optical frame: a stream without a voxel transform takes the centre as it is, with no arithmetic; a stream with one
+ * takes it through optical_from_world, the inverse of the 12 FLOATS the insert uses, computed on the host in double
+ * (voxel_inverse_transform): a(r,c) the floats as doubles, the nine cofactors each p * q - r * s, det = (a00 C00 + a01 C01) +
+ * a02 C02, R = adj / det with one division per entry, t'_r = -((R_r0 t_0 + R_r1 t_1) + R_r2 t_2), each of the 12 results then
+ * rounded to float, and applied exactly as rtuf_set_point_transforms defines.  The table is rebuilt whenever
+ * rtuf_set_voxel_transforms changes a stream.  A stream whose det is 0 or not finite, or one of whose 12 results is not finite
+ * as a float, cannot be carved from (see Errors); inserts are not affected.
+ * Pixel: that of a listed point (point_pixel as it stands: z > 0 && z < inf, the range tests before the conversions) with the
+ * intrinsics of rtuf_set_cloud_intrinsics.  A centre that is not judged is NOT SEEN by that stream.
+ * Free test: s(q) is the sensor value at pixel q (32FC1: the float; 16UC1: float(u16) * 0.001f, as the cloud calls define it),
+ * valid(q) iff it carries a point (positive and finite).  radius_px = r, 0 .. 4: Emin is the smallest s(q) over the VALID
+ * pixels of the (2r + 1)^2 square around (u, v) that lie in this stream's image -- never padded, never in another stream;
+ * invalid neighbours are skipped: an absent ray says nothing.  m = (float)margin.  The voxel is FREE for the stream iff the
+ * centre is judged, the centre pixel is valid and z < Emin - m (one subtraction); NOT FREE iff it is judged and not free.
+ * The mask is NOT read: the space in front of the robot's surface is free, what lies behind it fails z < s by itself, so the
+ * robot's own volume stays unknown.  margin is along the optical axis; at least half the voxel diagonal (0.87 voxel_size) is
+ * recommended, so that a voxel is only freed when all of it lies in front of the reading.
+ * Output: the free bit of voxel i is ORed with "FREE for at least one of the n streams".  d_summary is NULL or [n][4] uint32
+ * per call -- free, not free, not seen, nx * ny * nz -- overwritten by every call.  Integers and one owner per output word: no
+ * order of execution enters any output.
+ * A voxel may be both occupied and free: a point fell into it, yet its centre projects onto a pixel that reads deeper -- an
+ * edge, a slanted surface, another camera.  Both bits stand; occupied wins.
+ * Order: a carve is synchronous, like an insert: everything in flight is retired (the planes may be a batch's output), then one
+ * kernel runs on the first pipeline and is waited for.  It is no batch kind.  The sensor planes are only read.  Any image width
+ * is accepted: no mask-bits batch runs.
+ * rtuf_voxel_free_device hands out the device array (either out-pointer may be NULL; valid until the grid is replaced or
+ * freed), rtuf_get_voxel_free copies its ceil(nx * ny * nz / 32) words to the host.
+ * Errors, each of which writes nothing and changes no grid.  RTUF_ERR_INVALID: a NULL plane array or a NULL plane in it, n
+ * outside 1 .. max_streams, radius_px outside 0 .. 4, a margin that is negative or not finite (as a double or as a float), a
+ * stream among the n whose transform cannot be inverted (the message names the stream).  RTUF_ERR_STATE: no grid, a context
+ * that is not finalized, a stream among the n without cloud intrinsics.
+ * Out of scope: clearing occupied bits along the rays, log-odds, decay; a pixel radius that follows the voxel's projected
+ * size; treating "no return" as free up to a maximum range; marking the robot's own volume from the virtual depth; a count of
+ * seeing cameras per voxel; carving from point lists; an asynchronous carve; merging several GPUs' grids (OR the words). */
+int rtuf_voxel_carve_batch_device(rtuf_context *ctx, int n_streams, const float *d_depth, double margin, int radius_px, uint32_t *d_summary);
+int rtuf_voxel_carve_batch_device_u16(rtuf_context *ctx, int n_streams, const uint16_t *d_depth_mm, double margin, int radius_px, uint32_t *d_summary);
+int rtuf_voxel_carve_batch(rtuf_context *ctx, int n_streams, const float *const *depth_in, double margin, int radius_px, uint32_t *summary_out);
+int rtuf_voxel_carve_batch_u16(rtuf_context *ctx, int n_streams, const uint16_t *const *depth_mm_in, double margin, int radius_px, uint32_t *summary_out);
+int rtuf_voxel_free_device(rtuf_context *ctx, const uint32_t **d_free_bits, size_t *n_voxels);
+int rtuf_get_voxel_free(rtuf_context *ctx, uint32_t *free_out);
 
 /* LINK CLEARANCE TABLES.  New, beyond the reference: per stream and link label, how close the nearest kept point -- the
  * nearest thing that is not the robot -- is to the link, as a table [n_streams][n_labels] of 16-byte rows with no plane

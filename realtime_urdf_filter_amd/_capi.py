@@ -48,6 +48,8 @@ SYMBOLS = [
     "rtuf_set_voxel_grid", "rtuf_set_voxel_transforms", "rtuf_voxel_clear", "rtuf_voxel_insert_batch", "rtuf_voxel_insert_batch_u16",
     "rtuf_voxel_insert_batch_device", "rtuf_voxel_insert_batch_device_u16", "rtuf_voxel_insert_points_device", "rtuf_voxel_grid_device",
     "rtuf_get_voxel_grid",
+    "rtuf_voxel_carve_batch_device", "rtuf_voxel_carve_batch_device_u16", "rtuf_voxel_carve_batch", "rtuf_voxel_carve_batch_u16",
+    "rtuf_voxel_free_device", "rtuf_get_voxel_free",
 ]
 
 # point list batches (include/rtuf.h, POINT LIST BATCHES): the verdict of a point, and the pixel of one that is not judged
@@ -250,6 +252,12 @@ def load_library(path=None):
     lib.rtuf_voxel_insert_points_device.argtypes = [vp, ci, vp, vp, ci, vp, vp]
     lib.rtuf_voxel_grid_device.argtypes = [vp, vp, vp, vp]
     lib.rtuf_get_voxel_grid.argtypes = [vp, vp, vp]
+    lib.rtuf_voxel_carve_batch_device.argtypes = [vp, ci, vp, ctypes.c_double, ci, vp]
+    lib.rtuf_voxel_carve_batch_device_u16.argtypes = [vp, ci, vp, ctypes.c_double, ci, vp]
+    lib.rtuf_voxel_carve_batch.argtypes = [vp, ci, vp, ctypes.c_double, ci, vp]
+    lib.rtuf_voxel_carve_batch_u16.argtypes = [vp, ci, vp, ctypes.c_double, ci, vp]
+    lib.rtuf_voxel_free_device.argtypes = [vp, vp, vp]
+    lib.rtuf_get_voxel_free.argtypes = [vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -744,6 +752,41 @@ class Context:
         counts = np.empty(n, np.uint32) if want else None
         self._check(self._lib.rtuf_get_voxel_grid(self._h, _ptr(bits), _ptr(counts) if want else None))
         return bits, (counts.reshape(dims[2], dims[1], dims[0]) if want else None)
+
+    # voxel free space (include/rtuf.h, VOXEL FREE SPACE)
+    def voxel_carve_batch_device(self, n, d_depth, margin, radius_px=0, d_summary=None, u16=False):
+        """Device pointers (ints; d_summary may be None): d_depth [n,H,W] float32 (uint16 with u16), d_summary [n,4] uint32 (free,
+        not free, not seen, n_voxels).  Marks the voxels whose centre some stream sees in front of its reading by more than
+        `margin` metres, at window radius radius_px (0 .. 4).  Synchronous."""
+        q = lambda v: ctypes.c_void_p(v) if v else None
+        fn = self._lib.rtuf_voxel_carve_batch_device_u16 if u16 else self._lib.rtuf_voxel_carve_batch_device
+        self._check(fn(self._h, n, q(d_depth), float(margin), int(radius_px), q(d_summary)))
+
+    def voxel_carve_batch(self, depth, margin, radius_px=0):
+        """Carves from host planes depth [n,H,W] float32 metres (or uint16 millimetres: the 16UC1 form) -> summary [n,4] uint32:
+        free, not free, not seen, n_voxels.  Synchronous."""
+        u16 = np.asarray(depth).dtype == np.uint16
+        d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32).reshape(-1, self.height, self.width)
+        n = d.shape[0]
+        summary = np.zeros((n, 4), np.uint32)
+        PP = ctypes.c_void_p * max(n, 1)
+        din = PP(*[d[i].ctypes.data for i in range(n)])
+        fn = self._lib.rtuf_voxel_carve_batch_u16 if u16 else self._lib.rtuf_voxel_carve_batch
+        self._check(fn(self._h, n, din, float(margin), int(radius_px), _ptr(summary)))
+        return summary
+
+    def voxel_free_device(self):
+        """-> (d_free_bits, n_voxels): the device pointer (int) of the free words, valid until the grid is replaced or freed."""
+        b, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._lib.rtuf_voxel_free_device(self._h, ctypes.byref(b), ctypes.byref(n)))
+        return b.value, int(n.value)
+
+    def voxel_free(self):
+        """-> [ceil(n_voxels / 32)] uint32: a host copy of the free words (bit i & 31 of word i >> 5)."""
+        _, n = self.voxel_free_device()
+        free = np.empty((n + 31) // 32, np.uint32)
+        self._check(self._lib.rtuf_get_voxel_free(self._h, _ptr(free)))
+        return free
 
     # link clearance tables (include/rtuf.h, LINK CLEARANCE TABLES)
     def set_link_spheres(self, model, link, xyzr):

@@ -186,10 +186,19 @@ struct rtuf_context {
   // With several pipelines all of this lives in the first one.
   VoxelGrid vox_grid{};
   size_t vox_voxels = 0, vox_words = 0;
+  float vox_size = 0.0f;      // (float)voxel_size: the voxel centres of a carve
   uint32_t* d_vox_bits = nullptr; uint32_t* d_vox_counts = nullptr;
   PointTransform* d_vox_tf = nullptr;
   std::vector<PointTransform> vox_tf;
   uint32_t* d_vox_mask_bits = nullptr; float* d_vox_stage = nullptr;
+  // Voxel free space (include/rtuf.h, VOXEL FREE SPACE): the free words beside d_vox_bits (the same indexing and rounding;
+  // allocated and zeroed by the first carve or read, freed with the grid), the host's optical_from_world inverses of vox_tf
+  // (vox_inv, rebuilt by every rtuf_set_voxel_transforms; vox_inv_ok: the stream's matrix could be inverted) and their device
+  // table, allocated by the first carve that finds a transform and freed with the grid.  Host carves share d_vox_stage.
+  uint32_t* d_vox_free = nullptr;
+  PointTransform* d_vox_inv = nullptr;
+  std::vector<PointTransform> vox_inv;
+  std::vector<uint8_t> vox_inv_ok;
 
   // per-frame pose staging
   // Cameras and link matrices are staged in a ring of kMaxInflight + 1 pinned sets, like the joint positions: every
@@ -777,6 +786,7 @@ void rtuf_destroy(rtuf_context* c)
   dev_free(c, c->d_clr_spheres); dev_free(c, c->d_clr_slot_label);
   dev_free(c, c->d_scene); dev_free(c, c->d_scene_streams); dev_free(c, c->d_scene_bits); dev_free(c, c->d_scene_stage);
   dev_free(c, c->d_vox_bits); dev_free(c, c->d_vox_counts); dev_free(c, c->d_vox_tf); dev_free(c, c->d_vox_mask_bits); dev_free(c, c->d_vox_stage);
+  dev_free(c, c->d_vox_free); dev_free(c, c->d_vox_inv);
   for (auto& b : c->batch) {
     for (hipEvent_t ev : b.events) hipEventDestroy(ev);
     for (hipEvent_t ev : b.done) if (ev) hipEventDestroy(ev);
@@ -3386,6 +3396,7 @@ int rtuf_points_batch(rtuf_context* c, int n, const float* const* points_in, con
 static void free_voxel_grid(rtuf_context* c)
 {
   dev_free(c, c->d_vox_bits); dev_free(c, c->d_vox_counts);
+  dev_free(c, c->d_vox_free); dev_free(c, c->d_vox_inv);
   c->vox_grid = VoxelGrid{}; c->vox_voxels = 0; c->vox_words = 0;
 }
 
@@ -3393,6 +3404,7 @@ static int clear_voxel_grid(rtuf_context* c)
 {
   launch_voxel_clear(c->d_vox_bits, (c->vox_words + 3u) & ~(size_t)3u, c->lane[0].stream);
   if (c->d_vox_counts) launch_voxel_clear(c->d_vox_counts, (c->vox_voxels + 3u) & ~(size_t)3u, c->lane[0].stream);
+  if (c->d_vox_free) launch_voxel_clear(c->d_vox_free, (c->vox_words + 3u) & ~(size_t)3u, c->lane[0].stream);
   HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
   HIP_TRY(c, hipGetLastError());
   return RTUF_OK;
@@ -3432,7 +3444,7 @@ int rtuf_set_voxel_grid(rtuf_context* c, const double* origin, double voxel_size
   free_voxel_grid(c);
   c->d_vox_bits = bits; c->d_vox_counts = counts;
   c->vox_grid = VoxelGrid{(float)origin[0], (float)origin[1], (float)origin[2], inv, dims[0], dims[1], dims[2]};
-  c->vox_voxels = (size_t)total; c->vox_words = words;
+  c->vox_voxels = (size_t)total; c->vox_words = words; c->vox_size = size;
   return clear_voxel_grid(c);
 }
 
@@ -3464,6 +3476,19 @@ int rtuf_set_voxel_transforms(rtuf_context* c, int first, int n, const double* w
     c->vox_tf[(size_t)(first + s)] = t;
   }
   HIP_TRY(c, hipMemcpy(c->d_vox_tf + first, c->vox_tf.data() + first, (size_t)n * sizeof(PointTransform), hipMemcpyHostToDevice));
+  // voxel free space: the inverses of the streams that changed (a matrix that cannot be inverted is refused by the carve)
+  c->vox_inv.resize((size_t)c->max_streams, PointTransform{});
+  c->vox_inv_ok.resize((size_t)c->max_streams, (uint8_t)1);
+  for (int s = first; s < first + n; s++) {
+    PointTransform inv{};
+    c->vox_inv_ok[(size_t)s] = 1;
+    if (c->vox_tf[(size_t)s].on) {
+      inv.on = 1u;
+      c->vox_inv_ok[(size_t)s] = voxel_inverse_transform(c->vox_tf[(size_t)s].m, inv.m) ? 1 : 0;
+    }
+    c->vox_inv[(size_t)s] = inv;
+  }
+  if (c->d_vox_inv) HIP_TRY(c, hipMemcpy(c->d_vox_inv + first, c->vox_inv.data() + first, (size_t)n * sizeof(PointTransform), hipMemcpyHostToDevice));
   return RTUF_OK;
 }
 
@@ -3605,6 +3630,128 @@ int rtuf_voxel_insert_points_device(rtuf_context* c, int n, const float* d_point
   va.points = d_points; va.counts = d_counts; va.verdict = d_verdict; va.point_tf = c->d_point_tf; va.capacity = capacity;
   va.wide = ((uintptr_t)d_points & 15u) == 0u && ((uintptr_t)d_verdict & 3u) == 0u && (capacity & 3) == 0 ? 1 : 0;
   return run_voxel_insert(c, va);
+}
+
+// ---- voxel free space ----------------------------------------------------------------------------------
+// A carve is no batch kind either: it retires what is in flight (the planes may be a batch's output), runs one kernel on lane 0
+// of the first pipeline and waits for it.  No mask-bits batch runs, so any width is accepted.
+static int ensure_voxel_free(rtuf_context* c)
+{
+  if (c->d_vox_free) return RTUF_OK;
+  const size_t words = (c->vox_words + 3u) & ~(size_t)3u;
+  HIP_TRY(c, dev_alloc(c, &c->d_vox_free, words * sizeof(uint32_t)));
+  launch_voxel_clear(c->d_vox_free, words, c->lane[0].stream);
+  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
+  HIP_TRY(c, hipGetLastError());
+  return RTUF_OK;
+}
+
+// what a carve checks before anything is retired or written
+static int check_carve_call(rtuf_context* c, int n, const void* in, double margin, int radius_px)
+{
+  { const int rc = check_batch_call(c, n, in != nullptr, false); if (rc != RTUF_OK) return rc; }
+  if (radius_px < 0 || radius_px > kMaxCarveRadius) return c->fail(RTUF_ERR_INVALID, "radius_px = %d: 0 .. %d", radius_px, kMaxCarveRadius);
+  if (!(std::isfinite(margin) && margin >= 0.0 && std::isfinite((float)margin)))
+    return c->fail(RTUF_ERR_INVALID, "the carve margin must be finite and >= 0, as a float too (got %g)", margin);
+  for (int s = 0; s < n; s++)
+    if (!c->vox_inv_ok.empty() && !c->vox_inv_ok[(size_t)s])
+      return c->fail(RTUF_ERR_INVALID, "stream %d: its voxel transform cannot be inverted (rtuf_set_voxel_transforms)", s);
+  { const int rc = need_voxel_grid(c); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; s < n; s++)
+    if (!c->d_point_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
+  return RTUF_OK;
+}
+
+static int voxel_carve_device(rtuf_context* c, int n, const void* d_depth, double margin, int radius_px, uint32_t* d_summary, bool u16)
+{
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  hipSetDevice(c->device);
+  { const int rc = ensure_voxel_free(c); if (rc != RTUF_OK) return rc; }
+  if (c->d_vox_tf && !c->d_vox_inv) {
+    HIP_TRY(c, dev_alloc(c, &c->d_vox_inv, (size_t)c->max_streams * sizeof(PointTransform)));
+    HIP_TRY(c, hipMemcpy(c->d_vox_inv, c->vox_inv.data(), (size_t)c->max_streams * sizeof(PointTransform), hipMemcpyHostToDevice));
+  }
+  const VoxelGrid& g = c->vox_grid;
+  VoxelCarveArgs va{};
+  va.ox = g.ox; va.oy = g.oy; va.oz = g.oz; va.size = c->vox_size; va.nx = g.nx; va.ny = g.ny; va.nz = g.nz;
+  va.n_voxels = (uint32_t)c->vox_voxels; va.free_bits = c->d_vox_free; va.inv_tf = c->d_vox_inv; va.intr = c->d_point_intr;
+  va.depth = static_cast<const float*>(d_depth); va.summary = d_summary; va.margin = (float)margin; va.radius = radius_px;
+  va.width = c->width; va.height = c->height; va.io_u16 = u16 ? 1 : 0; va.n_streams = n;
+  launch_voxel_carve(va, c->lane[0].stream);
+  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
+  HIP_TRY(c, hipGetLastError());
+  return RTUF_OK;
+}
+
+static int voxel_carve_host(rtuf_context* c, int n, const void* const* depth_in, double margin, int radius_px, uint32_t* summary_out, bool u16)
+{
+  { const int rc = check_carve_call(c, n, depth_in, margin, radius_px); if (rc != RTUF_OK) return rc; }
+  for (int s = 0; s < n; s++) if (!depth_in[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  hipSetDevice(c->device);
+  const size_t plane = (size_t)c->width * c->height;
+  if (!c->d_vox_stage) HIP_TRY(c, dev_alloc(c, &c->d_vox_stage, (size_t)c->max_streams * (plane + 4u) * sizeof(float)));
+  uint32_t* const d_summary = reinterpret_cast<uint32_t*>(c->d_vox_stage + (size_t)c->max_streams * plane);
+  { const int rc = copy_planes(c, c->d_vox_stage, const_cast<void* const*>(depth_in), n, plane * (u16 ? sizeof(uint16_t) : sizeof(float)), hipMemcpyHostToDevice, nullptr);
+    if (rc != RTUF_OK) return rc; }
+  { const int rc = voxel_carve_device(c, n, c->d_vox_stage, margin, radius_px, summary_out ? d_summary : nullptr, u16); if (rc != RTUF_OK) return rc; }
+  if (summary_out) HIP_TRY(c, hipMemcpy(summary_out, d_summary, (size_t)n * 4u * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RTUF_OK;
+}
+
+int rtuf_voxel_carve_batch_device(rtuf_context* c, int n, const float* d_depth, double margin, int radius_px, uint32_t* d_summary)
+{
+  KIDS_FIRST_RETIRED(c, rtuf_voxel_carve_batch_device(k, n, d_depth, margin, radius_px, d_summary));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_carve_call(c, n, d_depth, margin, radius_px);
+  return rc != RTUF_OK ? rc : voxel_carve_device(c, n, d_depth, margin, radius_px, d_summary, false);
+}
+
+int rtuf_voxel_carve_batch_device_u16(rtuf_context* c, int n, const uint16_t* d_depth_mm, double margin, int radius_px, uint32_t* d_summary)
+{
+  KIDS_FIRST_RETIRED(c, rtuf_voxel_carve_batch_device_u16(k, n, d_depth_mm, margin, radius_px, d_summary));
+  if (!c) return RTUF_ERR_INVALID;
+  const int rc = check_carve_call(c, n, d_depth_mm, margin, radius_px);
+  return rc != RTUF_OK ? rc : voxel_carve_device(c, n, d_depth_mm, margin, radius_px, d_summary, true);
+}
+
+int rtuf_voxel_carve_batch(rtuf_context* c, int n, const float* const* depth_in, double margin, int radius_px, uint32_t* summary_out)
+{
+  KIDS_FIRST_RETIRED(c, rtuf_voxel_carve_batch(k, n, depth_in, margin, radius_px, summary_out));
+  if (!c) return RTUF_ERR_INVALID;
+  return voxel_carve_host(c, n, reinterpret_cast<const void* const*>(depth_in), margin, radius_px, summary_out, false);
+}
+
+int rtuf_voxel_carve_batch_u16(rtuf_context* c, int n, const uint16_t* const* depth_mm_in, double margin, int radius_px, uint32_t* summary_out)
+{
+  KIDS_FIRST_RETIRED(c, rtuf_voxel_carve_batch_u16(k, n, depth_mm_in, margin, radius_px, summary_out));
+  if (!c) return RTUF_ERR_INVALID;
+  return voxel_carve_host(c, n, reinterpret_cast<const void* const*>(depth_mm_in), margin, radius_px, summary_out, true);
+}
+
+int rtuf_voxel_free_device(rtuf_context* c, const uint32_t** d_free_bits, size_t* n_voxels)
+{
+  KIDS_ONE(c, 0, rtuf_voxel_free_device(k, d_free_bits, n_voxels));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = need_voxel_grid(c); if (rc != RTUF_OK) return rc; }
+  WAIT_IF_PENDING(c);
+  hipSetDevice(c->device);
+  { const int rc = ensure_voxel_free(c); if (rc != RTUF_OK) return rc; }
+  if (d_free_bits) *d_free_bits = c->d_vox_free;
+  if (n_voxels) *n_voxels = c->vox_voxels;
+  return RTUF_OK;
+}
+
+int rtuf_get_voxel_free(rtuf_context* c, uint32_t* free_out)
+{
+  KIDS_ONE(c, 0, rtuf_get_voxel_free(k, free_out));
+  if (!c) return RTUF_ERR_INVALID;
+  { const int rc = need_voxel_grid(c); if (rc != RTUF_OK) return rc; }
+  WAIT_IF_PENDING(c);
+  hipSetDevice(c->device);
+  { const int rc = ensure_voxel_free(c); if (rc != RTUF_OK) return rc; }
+  if (free_out) HIP_TRY(c, hipMemcpy(free_out, c->d_vox_free, c->vox_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RTUF_OK;
 }
 
 // ---- link clearance tables ---------------------------------------------------------------------------

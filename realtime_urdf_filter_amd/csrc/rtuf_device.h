@@ -531,6 +531,24 @@ struct VoxelArgs {
 void launch_voxel_clear(uint32_t* p, size_t n_words, hipStream_t st);      // n_words % 4 == 0, p on a 16-byte boundary
 void launch_voxel_insert(const VoxelArgs& a, hipStream_t st);              // a.points selects the list form
 
+// Voxel free space (include/rtuf.h, VOXEL FREE SPACE): one carve of the context's free grid from the sensor planes of streams
+// 0 .. n_streams - 1.  It runs on lane 0 once everything in flight is retired; the planes are only read.  The free words are
+// allocated in multiples of 16 bytes, so the word pair of every wave of 64 voxels lies inside the array.
+constexpr int kMaxCarveRadius = 4;
+struct VoxelCarveArgs {
+  float ox, oy, oz, size;        // the grid's origin and (float)voxel_size
+  int nx, ny, nz;
+  uint32_t n_voxels;
+  uint32_t* free_bits;           // [ceil(n_voxels / 32)] ORed into, every word by one wave
+  const PointTransform* inv_tf;  // [max_streams] optical_from_world (on = 0: the centre as it is), or nullptr: no stream has one
+  const PointIntrinsics* intr;   // [max_streams] fx, fy, cx, cy
+  const float* depth;            // [n][H][W] sensor planes (f32 metres or, with io_u16, uint16 millimetres)
+  uint32_t* summary;             // [n][4] free, not free, not seen, n_voxels; or nullptr.  Zeroed in front of the kernel
+  float margin;
+  int radius, width, height, io_u16, n_streams;
+};
+void launch_voxel_carve(const VoxelCarveArgs& a, hipStream_t st);
+
 struct FkArgs {
   const int32_t* parent;        // [F]
   const int32_t* joint_type;    // [F]

@@ -4248,6 +4248,124 @@ void launch_voxel_insert(const VoxelArgs& a, hipStream_t st)
   else hipLaunchKernelGGL(voxel_insert_kernel<false>, grid, dim3(kBlock), 0, st, a);
 }
 
+// ---- voxel free space (include/rtuf.h, VOXEL FREE SPACE) -------------------------------------------------------------------
+// One carve, projectively: a thread owns one voxel, consecutive lanes consecutive indices (they run along x, so a wave's
+// gathers fall on neighbouring pixels), and walks the streams: centre (voxel_centre) -> optical frame (point_transform with
+// the stream's inverse) -> pixel (point_pixel) -> the sensor value there and, with a radius, the smallest valid value of its
+// window -> voxel_free_test.  The stream's two records are read through uniform addresses.  A wave none of whose lanes is
+// judged by a stream issues no gather for it.  At the end one 64-bit ballot is the wave's two output words: lane 0 reads, ORs
+// and writes them with ordinary 8-byte accesses -- one owner per word, no atomics on the grid; lanes past n_voxels are never
+// free, so the last word's upper bits stay 0.  SUMMARY: per (wave, stream) the popcounts of two ballots go into a table of the
+// workgroup in LDS, flushed with one atomic per workgroup, stream and field for every kCarveChunk streams; "not seen" and the
+// total are filled in behind the kernel (voxel_carve_finish_kernel).  Without a summary a lane that is free stops gathering
+// and a wave whose live lanes are all free leaves the loop: the bits are the same.
+constexpr int kCarveChunk = 256;
+
+template <bool U16>
+__device__ __forceinline__ float carve_sensor(const float* __restrict__ plane, size_t i)
+{
+  return U16 ? u16_to_metres(reinterpret_cast<const uint16_t*>(plane)[i]) : plane[i];
+}
+
+template <bool U16, bool SUMMARY>
+__global__ __launch_bounds__(kBlock) void voxel_carve_kernel(VoxelCarveArgs a)
+{
+  __shared__ uint32_t tab[SUMMARY ? 2 * kCarveChunk : 1];
+  const uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  const bool live = i < a.n_voxels;
+  const uint32_t lane = threadIdx.x & 63u;
+  float wx = 0.0f, wy = 0.0f, wz = 0.0f;
+  if (live) {
+    const uint32_t row = i / (uint32_t)a.nx, ix = i - row * (uint32_t)a.nx;
+    const uint32_t iz = row / (uint32_t)a.ny, iy = row - iz * (uint32_t)a.ny;
+    wx = voxel_centre((int)ix, a.ox, a.size);
+    wy = voxel_centre((int)iy, a.oy, a.size);
+    wz = voxel_centre((int)iz, a.oz, a.size);
+  }
+  const size_t plane_px = (size_t)a.width * (size_t)a.height;
+  bool free_any = false;
+  for (int s0 = 0; s0 < a.n_streams; s0 += kCarveChunk) {
+    const int s1 = min(s0 + kCarveChunk, a.n_streams);
+    if (SUMMARY) {
+      for (int j = (int)threadIdx.x; j < 2 * (s1 - s0); j += kBlock) tab[j] = 0u;
+      __syncthreads();
+    }
+    for (int s = s0; s < s1; s++) {
+      if (!SUMMARY && __ballot(live && !free_any) == 0ull) break;
+      float x = wx, y = wy, z = wz;
+      if (a.inv_tf && a.inv_tf[s].on != 0u) point_transform(a.inv_tf[s].m, x, y, z);
+      const PointIntrinsics k = a.intr[s];
+      int u, v;
+      const bool judged = live && point_pixel(x, y, z, k, a.width, a.height, u, v);
+      bool free_here = false;
+      if (judged && (SUMMARY || !free_any)) {      // (a wave without such a lane branches round the gathers)
+        const float* __restrict__ plane = U16 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a.depth) + (size_t)s * plane_px)
+                                              : a.depth + (size_t)s * plane_px;
+        const float centre = carve_sensor<U16>(plane, (size_t)v * (size_t)a.width + (size_t)u);
+        if (cloud_sensor_valid(centre)) {
+          float emin = centre;
+          if (a.radius > 0) {
+            const int v0 = max(v - a.radius, 0), v1 = min(v + a.radius, a.height - 1);
+            const int u0 = max(u - a.radius, 0), u1 = min(u + a.radius, a.width - 1);
+            for (int vv = v0; vv <= v1; vv++)
+              for (int uu = u0; uu <= u1; uu++) {
+                const float q = carve_sensor<U16>(plane, (size_t)vv * (size_t)a.width + (size_t)uu);
+                if (cloud_sensor_valid(q)) emin = fminf(emin, q);
+              }
+          }
+          free_here = voxel_free_test(z, emin, a.margin);
+        }
+      }
+      free_any = free_any || free_here;
+      if (SUMMARY) {
+        const unsigned long long bf = __ballot(free_here), bn = __ballot(judged && !free_here);
+        if (lane == 0u) {
+          if (bf) atomicAdd(&tab[2 * (s - s0)], (uint32_t)__popcll(bf));
+          if (bn) atomicAdd(&tab[2 * (s - s0) + 1], (uint32_t)__popcll(bn));
+        }
+      }
+    }
+    if (SUMMARY) {
+      __syncthreads();
+      for (int j = (int)threadIdx.x; j < 2 * (s1 - s0); j += kBlock)
+        if (tab[j]) atomicAdd(a.summary + (size_t)(s0 + (j >> 1)) * 4u + (size_t)(j & 1), tab[j]);
+      __syncthreads();
+    }
+  }
+  const unsigned long long word = __ballot(free_any);
+  if (lane == 0u && word != 0ull) {
+    // (i is a multiple of 64 here: words i / 32 and i / 32 + 1, inside the array's multiple of four words)
+    uint2* const p = reinterpret_cast<uint2*>(a.free_bits + (i >> 5));
+    uint2 w = *p;
+    w.x |= (uint32_t)word; w.y |= (uint32_t)(word >> 32);
+    *p = w;
+  }
+}
+
+// rows [n][4] hold free and not free: not seen = n_voxels - free - not free, total = n_voxels
+__global__ __launch_bounds__(kBlock) void voxel_carve_finish_kernel(uint32_t* rows, int n, uint32_t n_voxels)
+{
+  const int s = (int)(blockIdx.x * (uint32_t)kBlock + threadIdx.x);
+  if (s >= n) return;
+  rows[4 * s + 2] = n_voxels - rows[4 * s] - rows[4 * s + 1];
+  rows[4 * s + 3] = n_voxels;
+}
+
+void launch_voxel_carve(const VoxelCarveArgs& a, hipStream_t st)
+{
+  const dim3 grid((a.n_voxels + (uint32_t)kBlock - 1u) / (uint32_t)kBlock);
+  if (a.summary) {
+    const int n_words = a.n_streams * 4;
+    hipLaunchKernelGGL(points_zero_summary_kernel, dim3((unsigned)((n_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.summary, n_words);
+    if (a.io_u16) hipLaunchKernelGGL((voxel_carve_kernel<true, true>), grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((voxel_carve_kernel<false, true>), grid, dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(voxel_carve_finish_kernel, dim3((unsigned)((a.n_streams + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.summary, a.n_streams, a.n_voxels);
+    return;
+  }
+  if (a.io_u16) hipLaunchKernelGGL((voxel_carve_kernel<true, false>), grid, dim3(kBlock), 0, st, a);
+  else hipLaunchKernelGGL((voxel_carve_kernel<false, false>), grid, dim3(kBlock), 0, st, a);
+}
+
 __global__ __launch_bounds__(kBlock) void fill_f32_kernel(float* p, size_t n, float v)
 {
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) p[i] = v;

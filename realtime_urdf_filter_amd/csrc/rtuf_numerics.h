@@ -2,7 +2,7 @@
 // shares: the 24-bit depth and its bit-pattern forms, the depth keys' encoding of a near fragment's float z, the set-up's
 // 32-bit edge constants, the key format's host-side rules, the compare threshold's constants, division core and the rule
 // that admits that core, the pixel classes of the link residual tables, the point of a filtered point cloud, the pixel and
-// verdict of a listed point, the voxel of a world point, the sphere centres and point-to-sphere clearances of the link clearance tables, the reach of a
+// verdict of a listed point, the voxel of a world point, a voxel's centre, inverse transform and free test, the sphere centres and point-to-sphere clearances of the link clearance tables, the reach of a
 // padded link's pixel, the scene planes' threshold and learning rule, and the set-up kernel's packed list counters.
 //
 // Included by the kernels (rtuf_kernels.hip, device and host pass), the host API (rtuf_api.cpp), scripts/fdiv_check.hip (which
@@ -266,6 +266,63 @@ RTUF_NUMERIC_HD bool voxel_of(float x, float y, float z, const VoxelGrid& g, uin
   if (!(gx >= 0.0f && gx < (float)g.nx && gy >= 0.0f && gy < (float)g.ny && gz >= 0.0f && gz < (float)g.nz)) return false;
   const int ix = (int)gx, iy = (int)gy, iz = (int)gz;
   index = (uint32_t)((iz * g.ny + iy) * g.nx + ix);
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------
+// voxel free space (include/rtuf.h, VOXEL FREE SPACE): the centre of a voxel, the optical_from_world inverse of a stream's
+// world_from_optical floats, and the free test.  The centre goes through point_transform and point_pixel above, as they
+// stand.  (tests/voxel_free_check.cpp against a numpy form, bit for bit.)
+// ---------------------------------------------------------------------------------------
+
+// c_r = o_r + ((float)i_r + 0.5f) * size with size = (float)voxel_size: one add (exact: i_r < 2048), one product, one add.
+RTUF_NUMERIC_HD float voxel_centre(int i, float o, float size)
+{
+  const float h = (float)i + 0.5f;
+  const float d = h * size;
+  return o + d;
+}
+
+// FREE iff z < Emin - m: one float subtraction, strict and ordered (a NaN on either side is not free).
+RTUF_NUMERIC_HD bool voxel_free_test(float z, float emin, float m) { return z < emin - m; }
+
+// optical_from_world of the 12 floats m (m[4 * c + r] = entry (r, c), r < 3) the insert uses, in point_transform's layout:
+// in double, a(r, c) the floats as doubles, every cofactor one p * q - r * s, det = (a00 C00 + a01 C01) + a02 C02,
+// R = adj / det with one division per entry, t'_r = -((R_r0 t_0 + R_r1 t_1) + R_r2 t_2), and only then each of the 12
+// results rounded to float.  false -- and out untouched -- when det is 0 or not finite or a result is not finite as a float.
+// Host only (once per rtuf_set_voxel_transforms): the includers compile with -ffp-contract=off.
+inline bool voxel_inverse_transform(const float* m, float* out)
+{
+  double a[3][3], t[3];
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) a[r][c] = (double)m[4 * c + r];
+    t[r] = (double)m[12 + r];
+  }
+  double C[3][3];      // C[i][j]: the cofactor of a(i, j)
+  C[0][0] = a[1][1] * a[2][2] - a[1][2] * a[2][1];
+  C[0][1] = a[1][2] * a[2][0] - a[1][0] * a[2][2];
+  C[0][2] = a[1][0] * a[2][1] - a[1][1] * a[2][0];
+  C[1][0] = a[0][2] * a[2][1] - a[0][1] * a[2][2];
+  C[1][1] = a[0][0] * a[2][2] - a[0][2] * a[2][0];
+  C[1][2] = a[0][1] * a[2][0] - a[0][0] * a[2][1];
+  C[2][0] = a[0][1] * a[1][2] - a[0][2] * a[1][1];
+  C[2][1] = a[0][2] * a[1][0] - a[0][0] * a[1][2];
+  C[2][2] = a[0][0] * a[1][1] - a[0][1] * a[1][0];
+  const double p0 = a[0][0] * C[0][0], p1 = a[0][1] * C[0][1], p2 = a[0][2] * C[0][2];
+  const double det = (p0 + p1) + p2;
+  if (!(std::isfinite(det) && det != 0.0)) return false;
+  float res[16];
+  for (int i = 0; i < 16; i++) res[i] = 0.0f;
+  for (int r = 0; r < 3; r++) {
+    double R[3];
+    for (int c = 0; c < 3; c++) R[c] = C[c][r] / det;      // (the adjugate is the cofactors' transpose)
+    const double q0 = R[0] * t[0], q1 = R[1] * t[1], q2 = R[2] * t[2];
+    const double tr = -((q0 + q1) + q2);
+    for (int c = 0; c < 3; c++) res[4 * c + r] = (float)R[c];
+    res[12 + r] = (float)tr;
+    for (int c = 0; c < 4; c++) if (!std::isfinite(res[4 * c + r])) return false;
+  }
+  for (int i = 0; i < 16; i++) out[i] = res[i];
   return true;
 }
 

@@ -600,6 +600,35 @@ class RealtimeURDFFilter:
         self._give_voxel_grid()
         return self._ctx.voxel_grid()
 
+    # ---- voxel free space (include/rtuf.h, VOXEL FREE SPACE) ----------------------------------
+    def voxelCarve(self, depth, projection_matrix, width, height, margin, radius_px=0):
+        """New, beyond the reference: marks the voxels of setVoxelGrid()'s grid that the camera sees THROUGH -- whose centre lies
+        more than `margin` metres in front of the smallest valid reading within radius_px pixels of its pixel -- with the
+        intrinsics cloud() would use.  The mask is not read and no model is posed.  depth: [H,W] float32 metres or uint16
+        millimetres, any width; projection_matrix is not read (the pinhole is getProjectionMatrix's).  Returns the summary [4]
+        uint32 (free, not free, not seen, n_voxels); None where filter() would have returned without a result."""
+        self._ensure_size(width, height)
+        if not self.renderers_:
+            return None
+        intr = getattr(self, "cloud_intrinsics_", None)
+        if intr is None:
+            raise RuntimeError("voxelCarve(): no intrinsics yet (getProjectionMatrix sets them)")
+        if getattr(self, "_cloud_intr_given_", None) != intr:      # (initGL clears it with every new context)
+            self._ctx.set_cloud_intrinsics(0, intr)
+            self._cloud_intr_given_ = intr
+        self._give_voxel_grid()
+        d = np.asarray(depth)
+        d = d.astype(np.uint16 if d.dtype == np.uint16 else np.float32, copy=False).reshape(1, height, width)
+        return self._ctx.voxel_carve_batch(d, margin, radius_px)[0]
+
+    def voxelFree(self):
+        """[ceil(nx * ny * nz / 32)] uint32: the free words of the grid as they stand.  Occupied wins over free; a voxel with
+        neither bit is unknown."""
+        if self._ctx is None:
+            raise RuntimeError("voxelFree(): no frame yet")
+        self._give_voxel_grid()
+        return self._ctx.voxel_free()
+
     # ---- scene planes (include/rtuf.h, SCENE PLANES) ------------------------------------------
     def learnScene(self, depth, projection_matrix, width, height, timestamp=None):
         """New, beyond the reference: lowers stream 0's scene plane to the readings of every pixel the robot filter keeps, for the

@@ -123,6 +123,7 @@ def build(tag):
     text("link padding on c3: padded mask-bits and cloud batches beside the dilated leg of the same run", ["README.md", "DESIGN.md 4"], "link_padding_rate_c3.txt", "the last line")
     text("point list batches on c3: points batches beside the render batch they are built on and beside render + torch ops", ["README.md", "DESIGN.md 4"], "points_rate_c3.txt", "the last line")
     text("voxel occupancy grids on c3: clear + insert cycles beside the mask-bits batch and beside compacted cloud + torch ops", ["README.md", "DESIGN.md 4"], "voxel_rate_c3.txt", "the last line")
+    text("voxel free space on c3: clear + carve cycles beside the clear + insert cycle and beside torch ops that give the same free words", ["README.md", "DESIGN.md 4"], "voxel_free_rate_c3.txt", "the last line")
     f = "scene_rate_c3.txt"
     if os.path.exists(os.path.join(PROFILES, f)):
         body =open(os.path.join(PROFILES, f)).read().splitlines()
