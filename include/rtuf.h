@@ -630,7 +630,8 @@ int rtuf_points_batch(rtuf_context *ctx, int n_streams, const float *const *poin
  * rtuf_voxel_clear zeroes bits and counts.  rtuf_voxel_grid_device hands out the device arrays (any of the three out-pointers
  * may be NULL; valid until the grid is replaced or freed), rtuf_get_voxel_grid copies them to the host (either may be NULL).
  * Errors, each of which writes nothing and changes no grid.  RTUF_ERR_INVALID: bad arguments (a NULL array, n, capacity, dims,
- * size or origin out of range), and the mask-bits calls' refusals with their texts (plane form).  RTUF_ERR_STATE: no grid, a
+ * size or origin out of range), and the mask-bits calls' refusals with their texts (plane form: among them a width that is
+ * not a multiple of 4, 32FC1 and 16UC1 alike; the list form and rtuf_voxel_carve_batch* take any width).  RTUF_ERR_STATE: no grid, a
  * context that is not finalized, a stream without cloud intrinsics (plane form), a count grid asked for -- counts_out, or the
  * d_counts out-pointer -- when the grid has none.
  * Out of scope: log-odds or decay, a threshold on counts, an asynchronous insert, merging

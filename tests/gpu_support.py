@@ -253,6 +253,31 @@ def soup_scene(seed, W, H, n=3):
     return OracleScene(wl, np.stack([S.sensor_depth(W, H, 0.37 * s + 0.1 * seed) for s in range(n)]))
 
 
+def edge_focal(W, H):
+    """soup_scene's focal length where W : H is at least 4 : 3; taken from the height where the frame is narrower than that."""
+    return 262.5 * max(W, 4.0 * H / 3.0) / 320.0
+
+
+@cached
+def edge_scene(seed, W, H, n=3):
+    """soup_scene for any frame from 1 x 1 to 2048 x 2048: the same geometry, poses, cameras and sensor planes from the same
+    draws in the same order, but the focal length follows the larger of W and 4 H / 3 (centred_projection scales it with W
+    alone: a 1 x 2048 soup_scene shows nine robot pixels)."""
+    rng = np.random.default_rng(seed)
+    geo = S.soup_geometry(rng, n_links=6, tris_per_link=40)
+    tfs = np.stack([np.stack(S.random_link_poses(rng, len(geo), near=bool(s & 1))) for s in range(n)])
+    cams = [S.random_camera(rng, small=True) for _ in range(n)]
+    wl = workload_of("edge%d_%dx%d" % (seed, W, H), W, H, geo, tfs, np.tile(centred_projection(W, H, edge_focal(W, H)), (n, 1)),
+                     np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
+    return OracleScene(wl, np.stack([S.sensor_depth(W, H, 0.37 * s + 0.1 * seed) for s in range(n)]))
+
+
+def edge_intrinsics(sc, slot):
+    """fx, fy, cx, cy of stream slot `slot` of an edge_scene: intrinsics() with the scene's own focal length."""
+    f = edge_focal(sc.W, sc.H)
+    return (f + slot, f - 0.5 * slot, (sc.W - 1) / 2.0 + 0.25 * slot, (sc.H - 1) / 2.0 - 0.5 * slot)
+
+
 @cached
 def border_scene(W=160, H=120):
     """Four bars, each crossing one image border (frustum half extents at z = 1: 0.61 x 0.46)."""

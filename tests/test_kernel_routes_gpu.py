@@ -12,6 +12,13 @@ without (stats()["cover_pass"] is asserted 1 and 0).  In this process the 36 til
 (RTUF_SMALL_LAUNCH=0 python tests/test_kernel_routes_gpu.py) the same cases take the 256-thread ones: the threshold is read
 once per process, so test_every_route_256_thread_kernels starts one.
 
+These are the routes as they stood before link padding, scene planes and point lists: the table has since got the Pad stage
+behind the tile kernel, the scene stage behind the compare stage and the Points tail, and neither cases() nor the `behind`
+set of test_the_cases_are_the_routes_of_the_table knows them.  Those routes are held by tests/test_link_padding_gpu.py (Pad),
+tests/test_scene_planes_gpu.py (the scene stage, in every mode) and tests/test_point_lists_gpu.py (Points), each against the
+oracle in the same way; tests/test_frame_sizes_gpu.py runs all of them, and the kinds of this module, at the smallest,
+thinnest and widest frames a context accepts, where this module has one frame of 160 x 120.
+
 One scene, soup_scene(1, 160, 120), three streams: 2.5 x 3.75 tiles of 64 x 32.  Every expectation comes from the CPU oracle's
 planes through tests/gpu_support.py and bench_support/*_check.py, never from the library; every comparison is for equality, of
 bit patterns where the output is a float."""
@@ -69,7 +76,8 @@ def case_id(case):
 
 def test_the_cases_are_the_routes_of_the_table():
     """The tile kernel's 22 variants are all met (with the cover code and without: the five batches), and so is every kernel
-    behind it with every tail."""
+    behind it with every tail -- of the table as it stood before link padding, scene planes and point lists (the module's
+    docstring names the modules that hold the Pad stage, the scene stage and the Points tail)."""
     variants, behind = set(), set()
     for kind, mod in cases():
         labels, thresh, u16 = mod.get("labels", False), mod.get("thresh", False), mod.get("u16", False)
