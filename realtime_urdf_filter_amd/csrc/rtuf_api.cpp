@@ -1147,46 +1147,40 @@ int rtuf_finalize_models(rtuf_context* c)
 
 // The setters of cameras / link matrices write into the staging set no batch in flight reads.  The first write after a
 // batch took the previous set carries over what this call does not overwrite (`whole` = it overwrites everything).
-static void begin_camera_write(rtuf_context* c, bool whole)
+template <typename T>
+static void begin_write(rtuf_context::StageRing& r, T* const* sets, size_t count, bool whole)
 {
-  auto& r = c->cam_ring;
   if (!r.carried) {
-    if (!whole) memcpy(c->ring_cams[r.write], c->ring_cams[r.live], sizeof(Camera) * (size_t)c->max_streams);
+    if (!whole) memcpy(sets[r.write], sets[r.live], sizeof(T) * count);
     r.carried = true;
   }
   r.written = true;
 }
-static void begin_link_write(rtuf_context* c, bool whole)
+static void begin_camera_write(rtuf_context* c, bool whole) { begin_write(c->cam_ring, c->ring_cams, (size_t)c->max_streams, whole); }
+static void begin_link_write(rtuf_context* c, bool whole) { begin_write(c->link_ring, c->ring_link_tf, 16 * (size_t)std::max(c->n_links, 1) * (size_t)c->max_streams, whole); }
+// The staging set that neither batch b, which reads `live`, nor a batch in flight beside it reads (idx_of: the set a batch
+// reads, or -1): of kMaxInflight + 1 sets one is always free.
+template <typename IdxOf>
+static int free_set(const rtuf_context* c, const rtuf_context::Batch& b, int live, IdxOf idx_of)
 {
-  auto& r = c->link_ring;
-  if (!r.carried) {
-    if (!whole) memcpy(c->ring_link_tf[r.write], c->ring_link_tf[r.live], sizeof(double) * 16 * (size_t)std::max(c->n_links, 1) * (size_t)c->max_streams);
-    r.carried = true;
-  }
-  r.written = true;
+  bool used[kMaxInflight + 1] = {};
+  used[live] = true;
+  for (const auto& o : c->batch) if (o.active && &o != &b && idx_of(o) >= 0) used[idx_of(o)] = true;
+  int i = 0;
+  while (i < kMaxInflight && used[i]) i++;
+  return i;
 }
 // A new batch takes the staged set of one array (if anything was staged since the last batch) and moves the setters on
-// to a set no batch in flight reads (kMaxInflight + 1 sets: one is always free).  Returns the set the batch reads.
+// to a set no batch in flight reads.  Returns the set the batch reads.
 template <typename IdxOf>
 static int take_staged(rtuf_context* c, rtuf_context::StageRing& r, const rtuf_context::Batch& b, IdxOf idx_of)
 {
-  if (r.written) {
-    r.live = r.write;
-    bool used[kMaxInflight + 1] = {};
-    used[r.live] = true;
-    for (const auto& o : c->batch) if (o.active && &o != &b) used[idx_of(o)] = true;
-    for (int i = 0; i <= kMaxInflight; i++) if (!used[i]) { r.write = i; break; }
-    r.written = false;
-    r.carried = false;
-  } else if (r.write == r.live) {
-    // nothing was staged since the last batch (or ever): the batch reads the live set, so the setters must move on to a
-    // set no batch reads -- a setter called while this batch is in flight would otherwise write into the pinned set its
-    // upload is still reading
-    bool used[kMaxInflight + 1] = {};
-    used[r.live] = true;
-    for (const auto& o : c->batch) if (o.active && &o != &b) used[idx_of(o)] = true;
-    for (int i = 0; i <= kMaxInflight; i++) if (!used[i]) { r.write = i; break; }
-    r.carried = false;
+  // (nothing staged since the last batch, or ever: the batch reads the live set, so the setters must move on all the same --
+  // a setter called while this batch is in flight would otherwise write into the pinned set its upload is still reading)
+  if (r.written || r.write == r.live) {
+    if (r.written) r.live = r.write;
+    r.write = free_set(c, b, r.live, idx_of);
+    r.written = r.carried = false;
   }
   return r.live;
 }
@@ -1641,13 +1635,276 @@ static int issue_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& 
   return RTUF_OK;
 }
 
-static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
+static bool aligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1u)) == 0u; }
+
+// ---- the steps of enqueue_batch, in the order it calls them (each is called from there and from nowhere else) ----
+// The slot takes its route, its lanes and its timing mode.  A re-run keeps what its first run took, but for its lanes:
+static void claim_lanes_and_timing(rtuf_context* c, rtuf_context::Batch& b, const Route& route, int n_groups, bool rerun)
+{
+  if (!rerun) {
+    b.route = route; b.dilation = route.post == Post::Dilate ? (int)c->params.silhouette_dilation_px : 0;
+    b.lanes_used = 0;      // (a batch that is not split takes one lane, the next such batch the other: below)
+    // mode 3 = mode 2 on every eighth batch only (each event costs ~5 us of stream time)
+    b.timing = c->timing == 3 ? ((c->timing_seq++ & 7u) == 0 ? 2 : 0) : c->timing;
+  }
+  // (a re-run after the launch group shrank may need every lane where the first run needed one)
+  if (n_groups > 1) for (int l = 0; l < std::min(c->n_lanes, n_groups); l++) b.lanes_used |= 1u << l;
+  else if (!rerun) { b.lanes_used = 1u << c->next_lane; c->next_lane = (c->next_lane + 1) % c->n_lanes; }
+  c->last_slot = (int)(&b - &c->batch[0]);
+}
+
+// The batch takes the staged poses -- the camera and link rings, every model's joint ring -- and only what the host changed
+// since the last batch crosses the bus, on `sp`, the stream of the pose stage (with on-device forward kinematics that is
+// just the joint positions).
+static int upload_staged_poses(rtuf_context* c, rtuf_context::Batch& b, int n, bool rerun, hipStream_t sp)
+{
+  const size_t L = (size_t)std::max(c->n_links, 1); const bool more = n > b.uploaded_streams;
+  // (a re-run after a bin regrowth finds this slot's device copies as its first run left them; its dirty flags may
+  // already belong to setter calls made since, for the batch that comes next)
+  if (!rerun) {
+    b.cam_idx = take_staged(c, c->cam_ring, b, [](const rtuf_context::Batch& o) { return o.cam_idx; });
+    b.link_idx = take_staged(c, c->link_ring, b, [](const rtuf_context::Batch& o) { return o.link_idx; });
+    c->h_cams = c->ring_cams[c->cam_ring.write]; c->h_link_tf = c->ring_link_tf[c->link_ring.write];
+    if (b.dirty_cams || more) HIP_TRY(c, hipMemcpyAsync(b.d_cams, c->ring_cams[b.cam_idx], sizeof(Camera) * n, hipMemcpyHostToDevice, sp));
+    if (b.dirty_link_tf || more) HIP_TRY(c, hipMemcpyAsync(b.d_link_tf, c->ring_link_tf[b.link_idx], sizeof(double) * 16 * L * n, hipMemcpyHostToDevice, sp));
+    b.dirty_cams = b.dirty_link_tf = false;
+  }
+  if (c->dirty_mask || n > c->mask_uploaded_streams) HIP_TRY(c, hipMemcpyAsync(c->d_model_mask, c->h_model_mask, sizeof(uint64_t) * n, hipMemcpyHostToDevice, sp));
+  c->dirty_mask = false;
+  b.uploaded_streams = std::max(b.uploaded_streams, n); c->mask_uploaded_streams = std::max(c->mask_uploaded_streams, n);
+  // on-device forward kinematics overwrites the link matrices (and camera) of the streams that use it
+  for (HostModel& m : c->models) {
+    Kinematics& k = m.kin;
+    if (!k.n_frames || !k.any_enabled) continue;
+    const size_t mi = (size_t)(&m - &c->models[0]);
+    if (b.q_idx.size() < c->models.size()) b.q_idx.resize(c->models.size(), 0);
+    if (!rerun) {
+      if (k.dirty_q) {                       // this batch takes the staged joint positions ...
+        k.q_live = k.q_write; k.q_carried = false; k.dirty_q = false;
+        // ... and later writes go to a buffer no batch in flight reads (kMaxInflight + 1 buffers: one is always free)
+        k.q_write = free_set(c, b, k.q_live, [mi](const rtuf_context::Batch& o) { return mi < o.q_idx.size() ? o.q_idx[mi] : -1; });
+      }
+      b.q_idx[mi] = k.q_live;
+    }
+    if (k.dirty_aux || n > k.aux_uploaded_streams) {
+      HIP_TRY(c, hipMemcpyAsync(k.d_root, k.h_root, sizeof(double) * 12 * (size_t)n, hipMemcpyHostToDevice, sp));
+      HIP_TRY(c, hipMemcpyAsync(k.d_enabled, k.h_enabled, (size_t)n, hipMemcpyHostToDevice, sp));
+    }
+    k.dirty_aux = false; k.aux_uploaded_streams = std::max(k.aux_uploaded_streams, n);
+  }
+  return RTUF_OK;
+}
+
+// What the argument blocks of one launch group are filled from: the batch, the group's streams, lane and counter block, and
+// the constants of the shading that every comparing kernel repeats.
+struct GroupFill {
+  const rtuf_context* c; const rtuf_context::Batch& b; const BatchRequest& r; const Route& route; const rtuf_context::Lane& ln;
+  Counters* counters; int base, size; size_t plane;      // the group's block, its streams [base, base + size) of the batch, pixels per plane
+  float sc_num, sc_off; int fast_div;
+};
+// the fields every block repeats
+extern "C++" {
+template <typename Args> static void set_group(Args& a, const GroupFill& f) { a.group_base = f.base; a.group_size = f.size; a.width = f.c->width; a.height = f.c->height; }
+template <typename Args> static void set_input(Args& a, const float* depth, const GroupFill& f) { a.depth = depth; a.io_u16 = f.r.u16 ? 1 : 0; }
+template <typename Args> static void set_shading(Args& a, const GroupFill& f)
+{
+  a.max_diff = f.c->params.depth_distance_threshold; a.replace_value = f.c->params.filter_replace_value; a.sc_num = f.sc_num; a.sc_off = f.sc_off; a.fast_div = f.fast_div;
+}
+// (the set-up and the tile kernel: the lane's bins)
+template <typename Args> static void set_bins(Args& a, const GroupFill& f)
+{
+  a.bins = f.ln.d_bins; a.bin_hdr = f.ln.d_bin_hdr; a.fbins = f.ln.d_fbins; a.fbin_count = f.ln.d_fbin_count; a.fcapacity = f.c->fcapacity; a.capacity = f.c->capacity;
+  a.big_list = f.ln.d_big_list; a.bg = f.b.d_bg; a.counters = f.counters; a.tiles_x = f.c->tiles_x; a.tiles_y = f.c->tiles_y; a.flags = f.c->params.flags;
+}
+// (the kernels that take the compare kernel's place: the outputs from the lane's z-surface)
+template <typename Args> static void set_post(Args& a, const GroupFill& f)
+{
+  set_group(a, f); set_input(a, f.r.depth, f); set_shading(a, f);
+  a.zsurface = f.ln.d_zsurface; a.masked = f.r.masked; a.mask = f.r.mask; a.bits = f.r.bits; a.counters = f.counters;
+}
+}  // extern "C++"
+
+static void fill_setup(SetupArgs& sa, const GroupFill& f)
+{
+  const rtuf_context* c = f.c;
+  set_group(sa, f); set_bins(sa, f);
+  sa.cverts = c->d_cverts; sa.ctris = c->d_ctris; sa.corder = c->d_corder; sa.chunks = c->d_chunks; sa.mvp = f.b.d_mvp; sa.model_mask = c->d_model_mask;
+  sa.clip_list = f.ln.d_clip_list; sa.clip_spill = f.ln.d_clip_spill; sa.big_capacity = c->big_capacity; sa.clip_capacity = c->clip_capacity;
+  sa.n_draws = c->n_draws; sa.bg_chunk = c->bg_chunk; sa.items = f.ln.d_items[c->last_slot]; sa.n_chunks = c->n_chunks;
+}
+static void fill_tile(TileArgs& ta, const GroupFill& f)
+{
+  const rtuf_context* c = f.c; const BatchRequest& r = f.r; const TileVariant& tv = f.route.tile;
+  set_group(ta, f); set_bins(ta, f); set_input(ta, r.depth, f); set_shading(ta, f);
+  ta.masked = r.masked; ta.mask = r.mask; ta.zsurface = f.ln.d_zsurface;
+  ta.z_near = c->params.near_plane; ta.z_far = c->params.far_plane; ta.key_shift = c->key_shift;
+  ta.bits = tv.out == TileOut::Bits ? r.bits : nullptr; ta.labels = r.labels;
+  ta.order_labels = tv.labels || tv.out == TileOut::Residual ? c->d_order_labels : nullptr;      // a label plane beside the outputs, or the rows of a residual table
+  if (f.route.post == Post::Pad) {
+    // link padding: the "label" of a winner is its link slot, and the plane is the lane's own, laid out like the z-surface
+    // (slot 0 = stream `base`) where the tile kernel indexes its label plane by batch stream: biased by the group's base
+    ta.order_labels = c->d_order_slot;
+    ta.labels = f.ln.d_slots - (ptrdiff_t)f.base * (ptrdiff_t)f.plane;
+  }
+  ta.order_thr = tv.thresh ? c->d_order_thr : nullptr;      // (allocated once, rewritten in place: a re-run finds the same table)
+  ta.virtual_out = r.virt; ta.empty_value = r.empty_value;
+  ta.resid_table = reinterpret_cast<unsigned long long*>(r.resid); ta.n_labels = r.n_labels;
+}
+static void fill_pad(PadArgs& pd, const GroupFill& f) { set_post(pd, f); pd.slots = f.ln.d_slots; pd.slot_pad = f.c->d_slot_pad; pd.focal = f.c->d_pad_focal; }
+static void fill_dilate(DilateArgs& da, const GroupFill& f) { set_post(da, f); da.radius = f.b.dilation; }
+// (no group fields: the compare kernel takes the group's planes as one run of pixels)
+static void fill_compare(CompareArgs& ca, const GroupFill& f)
+{
+  const size_t first = (size_t)f.base * f.plane * (f.r.u16 ? sizeof(uint16_t) : sizeof(float));      // the group's first plane, in bytes
+  set_input(ca, reinterpret_cast<const float*>(reinterpret_cast<const char*>(f.r.depth) + first), f); set_shading(ca, f);
+  ca.zsurface = f.ln.d_zsurface; ca.masked = reinterpret_cast<float*>(reinterpret_cast<char*>(f.r.masked) + first);
+  ca.mask = f.r.mask ? f.r.mask + (size_t)f.base * f.plane : nullptr; ca.n_pixels = (size_t)f.size * f.plane;
+  ca.z_near = f.c->params.near_plane; ca.z_far = f.c->params.far_plane;
+}
+static void fill_scene(SceneArgs& sc, const GroupFill& f)
+{
+  const rtuf_context* c = f.c; const BatchRequest& r = f.r; const bool planes_out = r.kind == Kind::Filter;
+  set_group(sc, f); set_input(sc, r.depth, f);
+  sc.scene = c->d_scene; sc.streams = c->d_scene_streams; sc.replace_value = c->params.filter_replace_value;
+  sc.masked = planes_out ? r.masked : nullptr; sc.mask = planes_out ? r.mask : nullptr; sc.bits = planes_out ? nullptr : r.bits;
+  // 16-byte accesses: every stream's plane (the planes form) or row (the bits form) starts on a 16-byte boundary
+  const size_t per_lane = r.u16 ? 8u : 4u;
+  sc.wide = aligned(r.depth, 16) && (planes_out ? f.plane % per_lane == 0 && aligned(r.masked, 16) && aligned(r.mask, 8) : (size_t)c->width % per_lane == 0) ? 1 : 0;
+}
+static void fill_cloud(CloudArgs& cl, const GroupFill& f)
+{
+  const BatchRequest& r = f.r; uint32_t* const rows = f.b.cl_rows; set_group(cl, f); set_input(cl, r.depth, f);
+  cl.bits = r.bits; cl.intr = f.c->d_cloud_intr; cl.points = r.points; cl.index = r.index; cl.counts = r.counts; cl.capacity = r.capacity;
+  cl.row_count = rows; cl.row_start = rows ? rows + (size_t)f.c->max_streams * f.c->height : nullptr;
+}
+static void fill_clearance(ClearanceArgs& cr, const GroupFill& f)
+{
+  const rtuf_context* c = f.c; const BatchRequest& r = f.r;
+  // (the spheres of labels below n_labels: the list is sorted by label)
+  int used = 0, slots = 0;
+  while (used < (int)c->clr_spheres.size() && (int)(c->clr_spheres[(size_t)used].label_slot & 0xffffu) < r.n_labels) used++;
+  while (slots < (int)c->clr_slot_label.size() && (int)c->clr_slot_label[(size_t)slots] < r.n_labels) slots++;
+  set_group(cr, f); set_input(cr, r.depth, f);
+  cr.bits = r.bits; cr.intr = c->d_cloud_intr; cr.spheres = c->d_clr_spheres; cr.slot_label = c->d_clr_slot_label;
+  cr.cams = f.b.d_cams; cr.link_tf = f.b.d_link_tf; cr.model_mask = c->d_model_mask; cr.posed = f.b.clr_posed;
+  cr.table = reinterpret_cast<unsigned long long*>(r.clr); cr.max_distance = r.max_distance;
+  cr.n_spheres = used; cr.n_slots = slots; cr.n_links = std::max(c->n_links, 1); cr.n_labels = r.n_labels;
+}
+static void fill_points(PointsArgs& pt, const GroupFill& f)
+{
+  const BatchRequest& r = f.r; set_group(pt, f);
+  pt.points = r.pt_points; pt.counts = r.pt_counts; pt.virt = r.virt; pt.intr = f.c->d_point_intr; pt.tf = f.c->d_point_tf;
+  pt.verdict = r.pt_verdict; pt.pixel = r.pt_pixel; pt.summary = r.pt_summary;
+  pt.capacity = r.capacity; pt.radius = r.pt_radius; pt.threshold = f.c->params.depth_distance_threshold;
+  pt.wide = (r.capacity & 3) == 0 && aligned(r.pt_points, 16) && aligned(r.pt_verdict, 4) && (!r.pt_pixel || aligned(r.pt_pixel, 16)) ? 1 : 0;
+}
+
+// Fills the plan of the batch in place, and writes nothing else: the forward kinematics of every model that has one, the pose
+// stage, and per launch group the argument blocks of the kernels its route has.  What no kernel of the route reads stays zero,
+// padding included (the plan is hashed byte-wise, and the captured graphs are found by that hash).
+static void build_plan(const rtuf_context* c, const rtuf_context::Batch& b, const Route& route, int n_groups, int per_group, int lane0, BatchPlan& plan)
 {
   const BatchRequest& r = b.rq;
-  const int n = r.n;
-  const float* d_depth = r.depth; float* d_masked = r.masked; uint8_t* d_mask = r.mask;
-  const bool io_u16 = r.u16;
-  const size_t esz = io_u16 ? sizeof(uint16_t) : sizeof(float);
+  const int n = r.n, L = std::max(c->n_links, 1);
+  plan.route = route;
+  for (const HostModel& m : c->models) {
+    const Kinematics& k = m.kin;
+    if (!k.n_frames || !k.any_enabled) continue;
+    FkArgs fa;
+    memset(&fa, 0, sizeof fa);               // (padding too: the plan is hashed byte-wise)
+    fa.parent = k.d_parent; fa.depth = k.d_depth; fa.max_depth = k.max_depth; fa.joint_type = k.d_type; fa.joint_origin = k.d_origin; fa.joint_axis = k.d_axis;
+    fa.link_frame = k.d_link_frame; fa.link_offset = k.d_link_offset; fa.q = k.h_q[b.q_idx[(size_t)(&m - &c->models[0])]]; fa.root_tf = k.d_root;
+    fa.enabled = k.d_enabled; fa.link_tf = b.d_link_tf; fa.cams = b.d_cams; fa.n_links_total = L; fa.camera_frame = k.camera_frame;
+    fa.n_streams = n; fa.n_frames = k.n_frames; fa.n_links_model = (int)m.links.size(); fa.link_base = m.link_base;
+    plan.fks.push_back(fa);
+  }
+  // to_linear_depth's constants exactly as the shader evaluates them (include/shaders/urdf_filter.frag:14-17), in float, and
+  // whether the kernels' per-pixel division by z - off may run as its eight-instruction core (div_core)
+  const float sc_num = shade_num(c->params.near_plane, c->params.far_plane), sc_off = shade_off(c->params.near_plane, c->params.far_plane);
+  const int fast_div = fast_div_admitted(sc_num, sc_off);
+  PoseArgs& pa = plan.pa;
+  memset(&pa, 0, sizeof pa);
+  pa.cams = b.d_cams; pa.link_tf = b.d_link_tf; pa.draws = c->d_draws; pa.mvp = b.d_mvp;
+  pa.bg = b.d_bg; pa.counters = b.d_counters; pa.n_counters = n_groups; pa.status = b.d_status;
+  pa.sc_num = sc_num; pa.sc_off = sc_off; pa.max_diff = c->params.depth_distance_threshold;
+  pa.n_streams = n; pa.n_draws = c->n_draws; pa.n_links = L; pa.z_far = c->params.far_plane; pa.width = c->width; pa.height = c->height;
+  for (int g = 0, base = 0; base < n; g++, base += per_group) {
+    plan.groups.emplace_back();
+    BatchPlan::Group& gr = plan.groups.back();
+    memset(static_cast<void*>(&gr), 0, sizeof gr);
+    gr.lane = n_groups == 1 ? lane0 : g % c->n_lanes;
+    const GroupFill f = {c, b, r, route, c->lane[gr.lane], b.d_counters + g, base, std::min(per_group, n - base), (size_t)c->width * c->height, sc_num, sc_off, fast_div};
+    fill_setup(gr.sa, f); fill_tile(gr.ta, f);
+    if (route.post == Post::Compare) fill_compare(gr.ca, f);
+    if (route.post == Post::Dilate) fill_dilate(gr.da, f);
+    if (route.post == Post::Pad) fill_pad(gr.pd, f);
+    if (route.scene) fill_scene(gr.sc, f);
+    if (route.tail == Tail::Cloud) fill_cloud(gr.cl, f);
+    if (route.tail == Tail::Clearance) fill_clearance(gr.cr, f);
+    if (route.tail == Tail::Points) fill_points(gr.pt, f);
+  }
+}
+
+// Launches the plan: kernel by kernel (issue_plan; the pose stage on `sp`), or -- use_graph -- as the replay of a hipGraph
+// captured once for these argument blocks on `st`, the stream of the batch's one lane.
+static int launch_plan(rtuf_context* c, rtuf_context::Batch& b, const BatchPlan& plan, bool use_graph, hipStream_t st, hipStream_t sp)
+{
+  b.setup_grid.assign(plan.groups.size(), 0xffffffffu);
+  // host-plane batches: the lanes' first kernels wait for the upload of the planes
+  if (b.rq.wait_upload)
+    for (int l = 0; l < c->n_lanes; l++)
+      if (b.lanes_used >> l & 1u) HIP_TRY(c, hipStreamWaitEvent(c->lane[l].stream, b.uploaded, 0));
+  if (!use_graph) { c->side_used_plain = true; return issue_plan(c, b, plan, sp, false); }
+  // Small batch: its ~8 launches, two event operations and the cross-stream wait cost the host more than the GPU
+  // spends on the kernels.  Capture them once per batch slot (pose stage forked onto the side stream inside the
+  // graph; the set-up grid is the worst case, so no list-length estimate is baked in) and replay with one call.
+  const uint64_t h = plan.hash();
+  hipGraphExec_t exec = nullptr;
+  for (auto& g : b.graphs) if (g.exec && g.hash == h) exec = g.exec;
+  // A capture that has to evict a LIVE entry of the slot's cache is what thrashing looks like (a caller that never repeats
+  // an argument set: fresh output buffers every frame); filling free entries -- the ring of staging buffers, the cover
+  // pass going on and off, a regrowth -- is not.  Judged over windows of 64 batches, so a burst long ago does not count.
+  if (exec) c->graph_hits++;
+  else { c->graph_misses++; if (b.graphs[b.graph_next].exec) c->graph_evictions++; }
+  if (((c->graph_hits + c->graph_misses) & 63u) == 0u) {
+    if (c->graph_evictions > 32) c->graphs_ok = false;       // more than half of the window's batches captured over a live entry
+    c->graph_evictions = 0;
+  }
+  if (!exec && c->graphs_ok) {
+    hipGraph_t graph = nullptr;
+    // (the side stream joins the capture below: it must not still carry plain launches of an earlier batch)
+    if (c->side_used_plain) { hipStreamSynchronize(c->side); c->side_used_plain = false; }
+    hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
+    if (e == hipSuccess) {
+      if (!c->fork_ev) hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming);
+      hipEventRecord(c->fork_ev, st);
+      hipStreamWaitEvent(c->side, c->fork_ev, 0);
+      const int rc = issue_plan(c, b, plan, c->side, true);
+      e = hipStreamEndCapture(st, &graph);
+      if (rc != RTUF_OK) e = hipErrorUnknown;
+    }
+    if (e == hipSuccess && graph) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    if (graph) hipGraphDestroy(graph);
+    if (e != hipSuccess || !exec) {
+      // no graphs on this runtime: fall back to plain launches for the life of the context
+      (void)hipGetLastError();
+      exec = nullptr; c->graphs_ok = false;
+    } else {
+      auto& slot = b.graphs[b.graph_next];
+      b.graph_next = (b.graph_next + 1) % rtuf_context::Batch::kGraphs;
+      if (slot.exec) hipGraphExecDestroy(slot.exec);       // (not in flight: a slot's batches are retired before it is reused)
+      slot.exec = exec; slot.hash = h;
+    }
+  }
+  if (!exec) return issue_plan(c, b, plan, st, false);       // (everything on the main stream, as the graph would have run it)
+  HIP_TRY(c, hipGraphLaunch(exec, st));
+  b.setup_grid.assign(plan.groups.size(), 0xffffffffu);          // worst-case grid: the work list always fits
+  return RTUF_OK;
+}
+
+static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
+{
+  const BatchRequest& r = b.rq; const int n = r.n;
   // Launch groups: as many as the lanes' bins ask for, alternating between the lanes; a batch that is not split takes one
   // lane, the next such batch the other.
   const int n_groups = groups_for(c, n);
@@ -1662,265 +1919,19 @@ static int enqueue_batch(rtuf_context* c, rtuf_context::Batch& b, bool rerun)
   const Route route = rerun ? b.route : route_of(route_facts(c, r));
   if (!route.ok() || !tile_variant_legal(route.tile))
     return c->fail(RTUF_ERR_STATE, "internal: no kernel route for a batch of kind %d (tile variant %d)", (int)r.kind, tile_variant_index(route.tile));
-  if (!rerun) {
-    b.route = route;
-    b.dilation = route.post == Post::Dilate ? (int)c->params.silhouette_dilation_px : 0;
-    b.lanes_used = 0;
-    if (n_groups == 1) { b.lanes_used = 1u << c->next_lane; c->next_lane = (c->next_lane + 1) % c->n_lanes; }
-    else for (int l = 0; l < std::min(c->n_lanes, n_groups); l++) b.lanes_used |= 1u << l;
-  } else if (n_groups > 1) {
-    // (a re-run after the launch group shrank may need every lane where the first run needed one)
-    for (int l = 0; l < std::min(c->n_lanes, n_groups); l++) b.lanes_used |= 1u << l;
-  }
+  claim_lanes_and_timing(c, b, route, n_groups, rerun);
   const int lane0 = __builtin_ctz(b.lanes_used);
   hipStream_t st = c->lane[lane0].stream;        // (graph replay: single-lane contexts only)
-  const size_t L = (size_t)std::max(c->n_links, 1);
-  const size_t plane = (size_t)c->width * c->height;
-  if (!rerun) {
-    // mode 3 = mode 2 on every eighth batch only (each event costs ~5 us of stream time)
-    b.timing = c->timing == 3 ? ((c->timing_seq++ & 7u) == 0 ? 2 : 0) : c->timing;
-  }
   const bool use_graph = c->graphs_ok && c->n_lanes == 1 && !b.timing && n <= kGraphMaxStreams && n_groups == 1;
   // the pose stage of this batch runs on the side stream, concurrent with the raster kernels of the batch before it
   // (graph replay: everything hangs off the main stream, the side stream is forked inside the graph)
   hipStream_t sp = use_graph ? st : c->side;
-  c->last_slot = (int)(&b - &c->batch[0]);
-  // only what the host changed since the last batch crosses the bus (with on-device forward
-  // kinematics that is just the joint positions below)
-  const bool more = n > b.uploaded_streams;
-  if (!rerun) {
-    b.cam_idx = take_staged(c, c->cam_ring, b, [](const rtuf_context::Batch& o) { return o.cam_idx; });
-    b.link_idx = take_staged(c, c->link_ring, b, [](const rtuf_context::Batch& o) { return o.link_idx; });
-    c->h_cams = c->ring_cams[c->cam_ring.write];
-    c->h_link_tf = c->ring_link_tf[c->link_ring.write];
-  }
-  // (a re-run after a bin regrowth finds this slot's device copies as its first run left them; its dirty flags may
-  // already belong to setter calls made since, for the batch that comes next)
-  if (!rerun) {
-    if (b.dirty_cams || more) HIP_TRY(c, hipMemcpyAsync(b.d_cams, c->ring_cams[b.cam_idx], sizeof(Camera) * n, hipMemcpyHostToDevice, sp));
-    if (b.dirty_link_tf || more) HIP_TRY(c, hipMemcpyAsync(b.d_link_tf, c->ring_link_tf[b.link_idx], sizeof(double) * 16 * L * n, hipMemcpyHostToDevice, sp));
-    b.dirty_cams = b.dirty_link_tf = false;
-  }
-  if (c->dirty_mask || n > c->mask_uploaded_streams) HIP_TRY(c, hipMemcpyAsync(c->d_model_mask, c->h_model_mask, sizeof(uint64_t) * n, hipMemcpyHostToDevice, sp));
-  c->dirty_mask = false;
-  b.uploaded_streams = std::max(b.uploaded_streams, n);
-  c->mask_uploaded_streams = std::max(c->mask_uploaded_streams, n);
+  { const int rc = upload_staged_poses(c, b, n, rerun, sp); if (rc != RTUF_OK) return rc; }
   BatchPlan plan;
-  plan.route = route;
-  const TileVariant& tv = route.tile;
-  // on-device forward kinematics overwrites the link matrices (and camera) of the streams that use it
-  for (HostModel& m : c->models) {
-    Kinematics& k = m.kin;
-    if (!k.n_frames || !k.any_enabled) continue;
-    const size_t mi = (size_t)(&m - &c->models[0]);
-    if (b.q_idx.size() < c->models.size()) b.q_idx.resize(c->models.size(), 0);
-    if (!rerun) {
-      if (k.dirty_q) {                       // this batch takes the staged joint positions ...
-        k.q_live = k.q_write; k.q_carried = false; k.dirty_q = false;
-        // ... and later writes go to a buffer no batch in flight reads (kMaxInflight + 1 buffers: one is always free)
-        bool used[kMaxInflight + 1] = {};
-        used[k.q_live] = true;
-        for (const auto& o : c->batch) if (o.active && &o != &b && mi < o.q_idx.size()) used[o.q_idx[mi]] = true;
-        for (int i = 0; i <= kMaxInflight; i++) if (!used[i]) { k.q_write = i; break; }
-      }
-      b.q_idx[mi] = k.q_live;
-    }
-    if (k.dirty_aux || n > k.aux_uploaded_streams) {
-      HIP_TRY(c, hipMemcpyAsync(k.d_root, k.h_root, sizeof(double) * 12 * (size_t)n, hipMemcpyHostToDevice, sp));
-      HIP_TRY(c, hipMemcpyAsync(k.d_enabled, k.h_enabled, (size_t)n, hipMemcpyHostToDevice, sp));
-    }
-    k.dirty_aux = false;
-    k.aux_uploaded_streams = std::max(k.aux_uploaded_streams, n);
-    FkArgs fa;
-    memset(&fa, 0, sizeof fa);               // (padding too: the plan is hashed byte-wise)
-    fa.parent = k.d_parent; fa.depth = k.d_depth; fa.max_depth = k.max_depth; fa.joint_type = k.d_type; fa.joint_origin = k.d_origin; fa.joint_axis = k.d_axis;
-    fa.link_frame = k.d_link_frame; fa.link_offset = k.d_link_offset; fa.q = k.h_q[b.q_idx[mi]]; fa.root_tf = k.d_root;
-    fa.enabled = k.d_enabled; fa.link_tf = b.d_link_tf; fa.cams = b.d_cams;
-    fa.n_streams = n; fa.n_frames = k.n_frames; fa.n_links_model = (int)m.links.size(); fa.link_base = m.link_base;
-    fa.n_links_total = (int)L; fa.camera_frame = k.camera_frame;
-    plan.fks.push_back(fa);
-  }
-  PoseArgs& pa = plan.pa;
-  memset(&pa, 0, sizeof pa);
-  pa.cams = b.d_cams; pa.link_tf = b.d_link_tf; pa.draws = c->d_draws; pa.mvp = b.d_mvp;
-  // to_linear_depth's constants exactly as the shader evaluates them (include/shaders/urdf_filter.frag:14-17), in float, and
-  // whether the kernels' per-pixel division by z - off may run as its eight-instruction core (div_core)
-  const float sc_num = shade_num(c->params.near_plane, c->params.far_plane), sc_off = shade_off(c->params.near_plane, c->params.far_plane);
-  const int fast_div = fast_div_admitted(sc_num, sc_off);
-  pa.bg = b.d_bg; pa.counters = b.d_counters; pa.n_counters = n_groups; pa.status = b.d_status;
-  pa.sc_num = sc_num; pa.sc_off = sc_off; pa.max_diff = c->params.depth_distance_threshold;
-  pa.n_streams = n; pa.n_draws = c->n_draws; pa.n_links = (int)L; pa.z_far = c->params.far_plane;
-  pa.width = c->width; pa.height = c->height;
-  for (int g = 0, base = 0; base < n; g++, base += per_group) {
-    const int gs = std::min(per_group, n - base);
-    plan.groups.emplace_back();
-    BatchPlan::Group& gr = plan.groups.back();
-    memset(&gr.sa, 0, sizeof gr.sa); memset(&gr.ta, 0, sizeof gr.ta); memset(&gr.ca, 0, sizeof gr.ca); memset(&gr.da, 0, sizeof gr.da); memset(&gr.pd, 0, sizeof gr.pd);
-    memset(&gr.cl, 0, sizeof gr.cl); memset(&gr.cr, 0, sizeof gr.cr); memset(&gr.sc, 0, sizeof gr.sc); memset(&gr.pt, 0, sizeof gr.pt);
-    gr.lane = n_groups == 1 ? lane0 : g % c->n_lanes;
-    const rtuf_context::Lane& ln = c->lane[gr.lane];
-    Counters* const d_counters = b.d_counters + g;
-    SetupArgs& sa = gr.sa;
-    sa.cverts = c->d_cverts; sa.ctris = c->d_ctris; sa.corder = c->d_corder; sa.chunks = c->d_chunks; sa.mvp = b.d_mvp;
-    sa.model_mask = c->d_model_mask; sa.bg = b.d_bg;
-    sa.bins = ln.d_bins; sa.bin_hdr = ln.d_bin_hdr; sa.fbins = ln.d_fbins; sa.fbin_count = ln.d_fbin_count; sa.fcapacity = c->fcapacity; sa.capacity = c->capacity;
-    sa.clip_list = ln.d_clip_list; sa.clip_spill = ln.d_clip_spill; sa.big_list = ln.d_big_list; sa.big_capacity = c->big_capacity; sa.counters = d_counters; sa.group_base = base; sa.group_size = gs;
-    sa.n_draws = c->n_draws; sa.width = c->width; sa.height = c->height; sa.tiles_x = c->tiles_x; sa.tiles_y = c->tiles_y;
-    sa.clip_capacity = c->clip_capacity; sa.bg_chunk = c->bg_chunk;
-    sa.items = ln.d_items[c->last_slot]; sa.n_chunks = c->n_chunks; sa.flags = c->params.flags;
-    TileArgs& ta = gr.ta;
-    ta.bins = ln.d_bins; ta.bin_hdr = ln.d_bin_hdr; ta.fbins = ln.d_fbins; ta.fbin_count = ln.d_fbin_count; ta.fcapacity = c->fcapacity; ta.capacity = c->capacity;
-    ta.depth = d_depth; ta.masked = d_masked; ta.mask = d_mask;
-    ta.zsurface = ln.d_zsurface; ta.bg = b.d_bg; ta.counters = d_counters;
-    ta.big_list = ln.d_big_list;
-    ta.group_base = base; ta.group_size = gs; ta.width = c->width; ta.height = c->height;
-    ta.tiles_x = c->tiles_x; ta.tiles_y = c->tiles_y; ta.flags = c->params.flags;
-    ta.z_near = c->params.near_plane; ta.z_far = c->params.far_plane;
-    ta.max_diff = c->params.depth_distance_threshold; ta.replace_value = c->params.filter_replace_value;
-    ta.sc_num = sc_num; ta.sc_off = sc_off;
-    ta.io_u16 = io_u16 ? 1 : 0;
-    ta.key_shift = c->key_shift;
-    ta.fast_div = fast_div;
-    ta.bits = tv.out == TileOut::Bits ? r.bits : nullptr;
-    ta.labels = r.labels;
-    ta.order_labels = tv.labels || tv.out == TileOut::Residual ? c->d_order_labels : nullptr;      // a label plane beside the outputs, or the rows of a residual table
-    if (route.post == Post::Pad) {
-      // link padding: the "label" of a winner is its link slot, and the plane is the lane's own, laid out like the z-surface
-      // (slot 0 = stream `base`) where the tile kernel indexes its label plane by batch stream: biased by the group's base
-      ta.order_labels = c->d_order_slot;
-      ta.labels = ln.d_slots - (ptrdiff_t)base * (ptrdiff_t)plane;
-      PadArgs& pd = gr.pd;
-      pd.depth = d_depth; pd.zsurface = ln.d_zsurface; pd.slots = ln.d_slots; pd.slot_pad = c->d_slot_pad; pd.focal = c->d_pad_focal;
-      pd.masked = d_masked; pd.mask = d_mask; pd.bits = r.bits; pd.counters = d_counters;
-      pd.group_base = base; pd.group_size = gs; pd.width = c->width; pd.height = c->height;
-      pd.max_diff = ta.max_diff; pd.replace_value = ta.replace_value; pd.sc_num = sc_num; pd.sc_off = sc_off;
-      pd.io_u16 = io_u16 ? 1 : 0; pd.fast_div = fast_div;
-    }
-    ta.order_thr = tv.thresh ? c->d_order_thr : nullptr;      // (allocated once, rewritten in place: a re-run finds the same table)
-    ta.virtual_out = r.virt; ta.empty_value = r.empty_value;
-    ta.resid_table = reinterpret_cast<unsigned long long*>(r.resid); ta.n_labels = r.n_labels;
-    if (route.post == Post::Dilate) {
-      DilateArgs& da = gr.da;
-      da.depth = d_depth; da.zsurface = ln.d_zsurface; da.masked = d_masked; da.mask = d_mask; da.bits = r.bits; da.counters = d_counters;
-      da.group_base = base; da.group_size = gs; da.width = c->width; da.height = c->height; da.radius = b.dilation;
-      da.max_diff = ta.max_diff; da.replace_value = ta.replace_value; da.sc_num = sc_num; da.sc_off = sc_off;
-      da.io_u16 = io_u16 ? 1 : 0; da.fast_div = fast_div;
-    }
-    if (route.scene) {
-      SceneArgs& sc = gr.sc;
-      const bool planes_out = r.kind == Kind::Filter;
-      sc.depth = d_depth; sc.scene = c->d_scene; sc.streams = c->d_scene_streams;
-      sc.masked = planes_out ? d_masked : nullptr; sc.mask = planes_out ? d_mask : nullptr; sc.bits = planes_out ? nullptr : r.bits;
-      sc.group_base = base; sc.group_size = gs; sc.width = c->width; sc.height = c->height;
-      sc.replace_value = c->params.filter_replace_value; sc.io_u16 = io_u16 ? 1 : 0;
-      // 16-byte accesses: every stream's plane (the planes form) or row (the bits form) starts on a 16-byte boundary
-      const size_t per_lane = io_u16 ? 8u : 4u;
-      auto aligned = [](const void* q, uintptr_t to) { return (reinterpret_cast<uintptr_t>(q) & (to - 1u)) == 0u; };
-      sc.wide = aligned(d_depth, 16) && (planes_out ? plane % per_lane == 0 && aligned(d_masked, 16) && aligned(d_mask, 8) : (size_t)c->width % per_lane == 0) ? 1 : 0;
-    }
-    if (route.tail == Tail::Cloud) {
-      CloudArgs& cl = gr.cl;
-      cl.depth = d_depth; cl.bits = r.bits; cl.intr = c->d_cloud_intr; cl.points = r.points; cl.index = r.index; cl.counts = r.counts;
-      cl.row_count = b.cl_rows; cl.row_start = b.cl_rows ? b.cl_rows + (size_t)c->max_streams * c->height : nullptr;
-      cl.group_base = base; cl.group_size = gs; cl.width = c->width; cl.height = c->height; cl.capacity = r.capacity; cl.io_u16 = io_u16 ? 1 : 0;
-    }
-    if (route.tail == Tail::Clearance) {
-      ClearanceArgs& cr = gr.cr;
-      // (the spheres of labels below n_labels: the list is sorted by label)
-      int used = 0, slots = 0;
-      while (used < (int)c->clr_spheres.size() && (int)(c->clr_spheres[(size_t)used].label_slot & 0xffffu) < r.n_labels) used++;
-      while (slots < (int)c->clr_slot_label.size() && (int)c->clr_slot_label[(size_t)slots] < r.n_labels) slots++;
-      cr.depth = d_depth; cr.bits = r.bits; cr.intr = c->d_cloud_intr; cr.spheres = c->d_clr_spheres; cr.slot_label = c->d_clr_slot_label;
-      cr.cams = b.d_cams; cr.link_tf = b.d_link_tf; cr.model_mask = c->d_model_mask; cr.posed = b.clr_posed;
-      cr.table = reinterpret_cast<unsigned long long*>(r.clr);
-      cr.n_spheres = used; cr.n_slots = slots; cr.n_links = (int)L; cr.n_labels = r.n_labels;
-      cr.group_base = base; cr.group_size = gs; cr.width = c->width; cr.height = c->height; cr.max_distance = r.max_distance; cr.io_u16 = io_u16 ? 1 : 0;
-    }
-    if (route.tail == Tail::Points) {
-      PointsArgs& pt = gr.pt;
-      pt.points = r.pt_points; pt.counts = r.pt_counts; pt.virt = r.virt; pt.intr = c->d_point_intr; pt.tf = c->d_point_tf;
-      pt.verdict = r.pt_verdict; pt.pixel = r.pt_pixel; pt.summary = r.pt_summary;
-      pt.group_base = base; pt.group_size = gs; pt.width = c->width; pt.height = c->height;
-      pt.capacity = r.capacity; pt.radius = r.pt_radius; pt.threshold = c->params.depth_distance_threshold;
-      auto aligned = [](const void* q, uintptr_t to) { return (reinterpret_cast<uintptr_t>(q) & (to - 1u)) == 0u; };
-      pt.wide = (r.capacity & 3) == 0 && aligned(r.pt_points, 16) && aligned(r.pt_verdict, 4) && (!r.pt_pixel || aligned(r.pt_pixel, 16)) ? 1 : 0;
-    }
-    if (route.post == Post::Compare) {
-      CompareArgs& ca = gr.ca;
-      ca.depth = reinterpret_cast<const float*>(reinterpret_cast<const char*>(d_depth) + (size_t)base * plane * esz); ca.zsurface = ln.d_zsurface;
-      ca.masked = reinterpret_cast<float*>(reinterpret_cast<char*>(d_masked) + (size_t)base * plane * esz);
-      ca.io_u16 = io_u16 ? 1 : 0; ca.mask = d_mask ? d_mask + (size_t)base * plane : nullptr;
-      ca.n_pixels = (size_t)gs * plane;
-      ca.z_near = ta.z_near; ca.z_far = ta.z_far; ca.max_diff = ta.max_diff; ca.replace_value = ta.replace_value;
-      ca.sc_num = sc_num; ca.sc_off = sc_off; ca.fast_div = fast_div;
-    }
-  }
-  b.n_groups = (int)plan.groups.size();          // (= n_groups: the loop makes ceil(n / per_group) groups, checked above)
-  b.setup_grid.assign(plan.groups.size(), 0xffffffffu);
+  build_plan(c, b, route, n_groups, per_group, lane0, plan);
+  b.n_groups = (int)plan.groups.size();          // (= n_groups: the plan has ceil(n / per_group) groups, checked above)
   if (may_write_zsurface(r)) c->last_lane = plan.groups.back().lane;
-  // host-plane batches: the lanes' first kernels wait for the upload of the planes
-  if (r.wait_upload)
-    for (int l = 0; l < c->n_lanes; l++)
-      if (b.lanes_used >> l & 1u) HIP_TRY(c, hipStreamWaitEvent(c->lane[l].stream, b.uploaded, 0));
-  bool launched = false;
-  if (use_graph) {
-    // Small batch: its ~8 launches, two event operations and the cross-stream wait cost the host more than the GPU
-    // spends on the kernels.  Capture them once per batch slot (pose stage forked onto the side stream inside the
-    // graph; the set-up grid is the worst case, so no list-length estimate is baked in) and replay with one call.
-    const uint64_t h = plan.hash();
-    hipGraphExec_t exec = nullptr;
-    for (auto& g : b.graphs) if (g.exec && g.hash == h) exec = g.exec;
-    // A capture that has to evict a LIVE entry of the slot's cache is what thrashing looks like (a caller that never repeats
-    // an argument set: fresh output buffers every frame); filling free entries -- the ring of staging buffers, the cover
-    // pass going on and off, a regrowth -- is not.  Judged over windows of 64 batches, so a burst long ago does not count.
-    if (exec) c->graph_hits++;
-    else {
-      c->graph_misses++;
-      if (b.graphs[b.graph_next].exec) c->graph_evictions++;
-    }
-    if (((c->graph_hits + c->graph_misses) & 63u) == 0u) {
-      if (c->graph_evictions > 32) c->graphs_ok = false;       // more than half of the window's batches captured over a live entry
-      c->graph_evictions = 0;
-    }
-    if (!exec && c->graphs_ok) {
-      hipGraph_t graph = nullptr;
-      // (the side stream joins the capture below: it must not still carry plain launches of an earlier batch)
-      if (c->side_used_plain) { hipStreamSynchronize(c->side); c->side_used_plain = false; }
-      hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
-      if (e == hipSuccess) {
-        if (!c->fork_ev) hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming);
-        hipEventRecord(c->fork_ev, st);
-        hipStreamWaitEvent(c->side, c->fork_ev, 0);
-        const int rc = issue_plan(c, b, plan, c->side, true);
-        e = hipStreamEndCapture(st, &graph);
-        if (rc != RTUF_OK) e = hipErrorUnknown;
-      }
-      if (e == hipSuccess && graph) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      if (graph) hipGraphDestroy(graph);
-      if (e != hipSuccess || !exec) {
-        // no graphs on this runtime: fall back to plain launches for the life of the context
-        (void)hipGetLastError();
-        exec = nullptr;
-        c->graphs_ok = false;
-      } else {
-        auto& slot = b.graphs[b.graph_next];
-        b.graph_next = (b.graph_next + 1) % rtuf_context::Batch::kGraphs;
-        if (slot.exec) hipGraphExecDestroy(slot.exec);       // (not in flight: a slot's batches are retired before it is reused)
-        slot.exec = exec;
-        slot.hash = h;
-      }
-    }
-    if (exec) {
-      HIP_TRY(c, hipGraphLaunch(exec, st));
-      b.setup_grid.assign(plan.groups.size(), 0xffffffffu);          // worst-case grid: the work list always fits
-      launched = true;
-    }
-  }
-  if (!launched) {
-    if (!use_graph) c->side_used_plain = true;
-    const int rc = issue_plan(c, b, plan, use_graph ? st : sp, false);
-    if (rc != RTUF_OK) return rc;
-  }
+  { const int rc = launch_plan(c, b, plan, use_graph, st, sp); if (rc != RTUF_OK) return rc; }
   for (int l = 0; l < c->n_lanes; l++)
     if (b.lanes_used >> l & 1u) HIP_TRY(c, hipEventRecord(b.done[l], c->lane[l].stream));
   HIP_TRY(c, hipGetLastError());
@@ -1975,6 +1986,171 @@ static int enqueue_download(rtuf_context* c, rtuf_context::Batch& b)
   return RTUF_OK;
 }
 
+// ---- the steps of retire_oldest ----
+// What the launch groups of a batch counted, summed over groups and shards, and which of the context's lists that outgrew.
+struct BatchTotals {
+  unsigned long long tris_binned = 0, bin_entries = 0, clip_count = 0, frags = 0, occluded = 0, raster_atomics = 0, drawn_pixels = 0, work_items = 0;
+  unsigned max_bin_fill = 0, max_fbin_fill = 0, clip_overflow = 0, uncovered = 0, max_big_fill = 0, cover_tiles = 0, exact_tiles = 0, zero_items = 0, max_items = 0;
+  bool list_over = false;                    // some group's set-up grid was sized too small for its work list
+  bool bin_over = false, big_over = false;   // (the clip list: clip_overflow)
+  bool overflowed() const { return bin_over || clip_overflow || list_over || big_over; }
+};
+static BatchTotals sum_counters(rtuf_context* c, const rtuf_context::Batch& b)
+{
+  BatchTotals k;
+#ifdef RTUF_LANECOUNT
+  for (int i = 0; i < kLaneLoops; i++) c->lane_slots[i] = c->lane_live[i] = 0;
+  for (int i = 0; i < kLaneRoleWords; i++) c->lane_roles[i] = 0;
+  for (int g = 0; g < b.n_groups; g++)
+    for (int sh = 0; sh < kCounterShards; sh++) {
+      for (int i = 0; i < kLaneLoops; i++) { c->lane_slots[i] += b.h_counters[g].shard[sh].lane_slots[i]; c->lane_live[i] += b.h_counters[g].shard[sh].lane_live[i]; }
+      for (int i = 0; i < kLaneRoleWords; i++) c->lane_roles[i] += b.h_counters[g].shard[sh].lane_roles[i];
+    }
+#endif
+  for (int g = 0; g < b.n_groups; g++) {
+    const Counters& cn = b.h_counters[g];
+    k.work_items += cn.work.n_items; k.max_items = std::max(k.max_items, cn.work.n_items);
+    k.list_over = k.list_over || cn.work.n_items > b.setup_grid[g];
+    for (int i = 0; i < kCounterShards; i++) {
+      const CounterShard& sh = cn.shard[i];
+      k.tris_binned += sh.tris_binned; k.bin_entries += sh.bin_entries; k.clip_count += sh.clip_count;
+      k.max_bin_fill = std::max(k.max_bin_fill, sh.max_bin_fill); k.clip_overflow |= sh.clip_overflow;
+      k.max_fbin_fill = std::max(k.max_fbin_fill, sh.max_fbin_fill); k.frags += sh.frags; k.uncovered |= sh.uncovered;
+      k.max_big_fill = std::max(k.max_big_fill, sh.max_big_fill); k.raster_atomics += sh.raster_atomics; k.drawn_pixels += sh.drawn_pixels;
+      k.occluded += sh.occluded; k.cover_tiles += sh.cover_tiles; k.exact_tiles += sh.exact_tiles; k.zero_items += sh.zero_items;
+    }
+  }
+  k.bin_over = k.max_bin_fill > c->capacity || k.max_fbin_fill > c->fcapacity; k.big_over = k.max_big_fill > c->big_capacity;
+  return k;
+}
+
+// The totals become rtuf_stats and the hints that size the next batches' set-up grids (first_run: of the batch being retired).
+static void publish_stats(rtuf_context* c, const rtuf_context::Batch& b, const BatchTotals& k, bool first_run)
+{
+  const int group_streams = (b.rq.n + b.n_groups - 1) / std::max(b.n_groups, 1);
+  c->items_hint = k.max_items;               // sizes the next batches' set-up grids (the longest list of this batch's groups ...
+  c->items_hint_streams = group_streams;     // ... of so many streams each)
+  c->group_items.resize((size_t)b.n_groups); c->group_streams.resize((size_t)b.n_groups);
+  for (int g = 0; g < b.n_groups; g++) {
+    c->group_items[(size_t)g] = b.h_counters[g].work.n_items;
+    c->group_streams[(size_t)g] = std::min(group_streams, b.rq.n - g * group_streams);
+  }
+  c->stats.triangles_submitted = (uint64_t)c->n_tris * (uint64_t)b.rq.n;
+  c->stats.triangles_binned = k.tris_binned; c->stats.bin_entries = k.bin_entries; c->stats.triangles_clipped = k.clip_count;
+  c->stats.max_bin_fill = k.max_bin_fill; c->stats.bin_capacity = c->capacity; c->stats.fragments_binned = k.frags; c->stats.max_fbin_fill = k.max_fbin_fill;
+  c->stats.occluded_entries = k.occluded; c->stats.cover_tiles = k.cover_tiles; c->stats.exact_tiles = k.exact_tiles;
+  c->stats.work_items = (uint32_t)std::min<unsigned long long>(k.work_items, 0xffffffffu); c->stats.zero_survivor_items = k.zero_items;
+  c->stats.raster_atomics = k.raster_atomics; c->stats.drawn_pixels = k.drawn_pixels;
+  c->stats.cover_pass = b.route.tile.cover ? 1u : 0u; c->stats.groups_last_batch = (uint32_t)b.n_groups;
+  if (k.list_over) c->stats.regrowths++;
+  // host mirror of the device status word (rtuf_batch_status_device): what the FIRST run of the batch being retired left there
+  if (first_run) {
+    c->stats.batch_status = (k.bin_over ? kStatusBinOverflow : 0u) | (k.clip_overflow ? kStatusClipOverflow : 0u) | (k.big_over ? kStatusBigOverflow : 0u) |
+                            (k.list_over ? kStatusGridShort : 0u) | (k.uncovered ? kStatusUncovered : 0u);
+    c->stats.batch_reruns = 0;
+  }
+}
+
+// the timing events of a timed batch become ms_* and sum_ms_*
+static void read_timing(rtuf_context* c, const rtuf_context::Batch& b)
+{
+  if (!b.timing || b.events.size() < (size_t)(kEvGroup0 + kEvPerGroup * b.n_groups)) return;
+  // per launch group E0 .. E4 (see issue_plan).  With several lanes the kernels of different groups overlap: the sums
+  // below add up per-launch durations, they are not wall time.
+  const bool behind = runs_behind_tile(b.route);      // ms_compare: whatever ran behind the tile kernel
+  auto el = [&](size_t i, size_t j) { float ms = 0; hipEventElapsedTime(&ms, b.events[i], b.events[j]); return ms; };
+  c->stats.ms_pose = c->stats.ms_setup = c->stats.ms_clip = c->stats.ms_raster = c->stats.ms_compare = c->stats.ms_total = 0;
+  for (int g = 0; g < b.n_groups; g++) {
+    const size_t e0 = kEvGroup0 + kEvPerGroup * (size_t)g;
+    if (b.timing == 1) c->stats.ms_setup += el(e0, e0 + 2);
+    else { c->stats.ms_setup += el(e0, e0 + 1); c->stats.ms_clip += el(e0 + 1, e0 + 2); }
+    c->stats.ms_raster += el(e0 + 2, e0 + 3); if (behind) c->stats.ms_compare += el(e0 + 3, e0 + 4);
+  }
+  if (b.timing == 1) {
+    c->stats.ms_pose = el(kEvStart, kEvPoseEnd);
+    for (int l = 0; l < c->n_lanes; l++)
+      if (b.lanes_used >> l & 1u) c->stats.ms_total = std::max(c->stats.ms_total, el(kEvStart, kEvLaneEnd + l));
+  }
+  c->acc_ms[0] += c->stats.ms_pose; c->acc_ms[1] += c->stats.ms_setup; c->acc_ms[2] += c->stats.ms_raster;
+  c->acc_ms[3] += c->stats.ms_compare; c->acc_ms[4] += c->stats.ms_total; c->acc_ms[5] += c->stats.ms_clip;
+  c->stats.timed_batches = ++c->acc_batches;
+  c->stats.sum_ms_pose = c->acc_ms[0]; c->stats.sum_ms_setup = c->acc_ms[1]; c->stats.sum_ms_raster = c->acc_ms[2];
+  c->stats.sum_ms_compare = c->acc_ms[3]; c->stats.sum_ms_total = c->acc_ms[4]; c->stats.sum_ms_clip = c->acc_ms[5];
+}
+
+// The clean exit: nothing overflowed, the batch is done and its slot free.
+static int retire_clean(rtuf_context* c, rtuf_context::Batch& b, const BatchTotals& k)
+{
+  if (b.host_io) HIP_TRY(c, hipEventSynchronize(b.downloaded));
+  read_timing(c, b);
+  if (b.route.tile.cover) {
+    if (k.cover_tiles) c->cover_idle = 0;
+    else if (++c->cover_idle >= 3) { c->cover_on = false; c->cover_sleep = 64; c->cover_idle = 2; }      // (idle = 2: one empty probe sends it back to sleep)
+  } else if (--c->cover_sleep <= 0) {
+    c->cover_on = true;
+  }
+  b.active = false; c->oldest = (c->oldest + 1) % kMaxInflight; c->pending--;      // the slot is free
+  if (b.rq.kind == Kind::Cloud && k.uncovered)
+    return c->fail(RTUF_ERR_STATE, "point cloud: a stream's background quad does not cover its whole image (non-standard projection), so the mask bits the cloud is "
+                                   "built on are undefined there; there is no cloud form for this camera (filter with the full-plane calls and convert the masked plane)");
+  if (b.rq.kind == Kind::Clearance && k.uncovered)
+    return c->fail(RTUF_ERR_STATE, "link clearance: a stream's background quad does not cover its whole image (non-standard projection), so the "
+                                   "mask bits the kept points are taken from are undefined there");
+  if (b.rq.kind == Kind::Bits && k.uncovered)
+    return c->fail(RTUF_ERR_STATE, "mask bits: a stream's background quad does not cover its whole image (non-standard projection), so "
+                                   "masked depth != select(bit, replace, sensor) there; use the full-plane calls for this camera");
+  return RTUF_OK;
+}
+
+// drops everything in flight (nothing of it can be run again) and hands the error on
+static int drop_in_flight(rtuf_context* c, int rc) { for (auto& o : c->batch) o.active = false; c->pending = 0; return rc; }
+
+// The overflow path: waits for the later batches too, enlarges what overflowed, and runs everything in flight again in order.
+static int regrow_and_rerun(rtuf_context* c, const BatchTotals& k)
+{
+  sync_lanes(c);
+  if (c->d2h) HIP_TRY(c, hipStreamSynchronize(c->d2h));
+  if (k.bin_over) { const int rc = grow_bins(c, k.max_bin_fill, k.max_fbin_fill); if (rc != RTUF_OK) return drop_in_flight(c, rc); }
+  if (k.clip_overflow) {
+    const uint32_t larger = c->clip_capacity * 4;
+    for (int l = 0; l < c->n_lanes; l++) {
+      int rc = regrow(c, c->lane[l].d_clip_list, (size_t)larger * kCounterShards * sizeof(ClipItem), "clip list");
+      if (rc == RTUF_OK && clip_spill_bytes(larger) != clip_spill_bytes(c->clip_capacity)) { rc = regrow(c, c->lane[l].d_clip_spill, clip_spill_bytes(larger), "clip spill area"); c->stats.regrowths--; }
+      if (rc != RTUF_OK) return drop_in_flight(c, rc);
+      if (l) c->stats.regrowths--;           // (one regrowth, however many lanes)
+    }
+    c->clip_capacity = larger;
+  }
+  if (k.big_over) {
+    // (half as much again as this run asked for: poses move, and a list that just fits overflows on the next batch)
+    uint32_t larger = c->big_capacity;
+    while (larger < k.max_big_fill + k.max_big_fill / 2) larger *= 2;
+    for (int l = 0; l < c->n_lanes; l++) {
+      const int rc = regrow(c, c->lane[l].d_big_list, (size_t)larger * kCounterShards * sizeof(BigRec), "many-tile list");
+      if (rc != RTUF_OK) return drop_in_flight(c, rc);
+      if (l) c->stats.regrowths--;
+    }
+    c->big_capacity = larger;
+  }
+  const size_t tiles = (size_t)c->tiles_x * c->tiles_y;
+  for (int l = 0; l < c->n_lanes; l++) {
+    // (the arrays were sized for the launch group the context started with: at least the present one)
+    launch_init_headers(c->lane[l].d_bin_hdr, (size_t)c->group * tiles, c->lane[l].stream);
+    HIP_TRY(c, hipMemsetAsync(c->lane[l].d_fbin_count, 0, (size_t)c->group * tiles * sizeof(uint32_t), c->lane[l].stream));
+  }
+  // (a grid that was too short: the re-run takes the worst-case grid, which no list can outgrow -- the estimate that failed
+  // once would size the same grid again)
+  c->force_worst_grid = k.list_over; c->stats.batch_reruns++;
+  int rc = RTUF_OK;
+  for (int i = 0; i < c->pending && rc == RTUF_OK; i++) {
+    rtuf_context::Batch& r = c->batch[(c->oldest + i) % kMaxInflight];
+    rc = enqueue_batch(c, r, true);
+    if (rc == RTUF_OK && r.host_io) rc = enqueue_download(c, r);
+  }
+  c->force_worst_grid = false;
+  return rc == RTUF_OK ? rc : drop_in_flight(c, rc);
+}
+
 // Retires the oldest batch in flight: waits for it, reads its counters, and if a bin or the clip list
 // overflowed, enlarges them and runs that batch and every later one again (their inputs are intact).
 static int retire_oldest(rtuf_context* c)
@@ -1984,177 +2160,35 @@ static int retire_oldest(rtuf_context* c)
     if (!c->pending || !b.active) { c->pending = 0; return RTUF_OK; }
     for (int l = 0; l < c->n_lanes; l++)
       if (b.lanes_used >> l & 1u) HIP_TRY(c, hipEventSynchronize(b.done[l]));
-    struct { unsigned long long tris_binned = 0, bin_entries = 0, clip_count = 0, frags = 0, occluded = 0, raster_atomics = 0, drawn_pixels = 0, work_items = 0;
-             unsigned max_bin_fill = 0, max_fbin_fill = 0, clip_overflow = 0, uncovered = 0, max_big_fill = 0, cover_tiles = 0, exact_tiles = 0, zero_items = 0,
-                      max_items = 0; } k;
-    bool list_over = false;                    // some group's set-up grid was sized too small for its work list
-    int group_streams = 0;
-#ifdef RTUF_LANECOUNT
-    for (int i = 0; i < kLaneLoops; i++) c->lane_slots[i] = c->lane_live[i] = 0;
-    for (int g = 0; g < b.n_groups; g++)
-      for (int sh = 0; sh < kCounterShards; sh++)
-        for (int i = 0; i < kLaneLoops; i++) { c->lane_slots[i] += b.h_counters[g].shard[sh].lane_slots[i]; c->lane_live[i] += b.h_counters[g].shard[sh].lane_live[i]; }
-    for (int i = 0; i < kLaneRoleWords; i++) c->lane_roles[i] = 0;
-    for (int g = 0; g < b.n_groups; g++)
-      for (int sh = 0; sh < kCounterShards; sh++)
-        for (int i = 0; i < kLaneRoleWords; i++) c->lane_roles[i] += b.h_counters[g].shard[sh].lane_roles[i];
-#endif
-    for (int g = 0; g < b.n_groups; g++) {
-      const Counters& cn = b.h_counters[g];
-      k.work_items += cn.work.n_items;
-      k.max_items = std::max(k.max_items, cn.work.n_items);
-      list_over = list_over || cn.work.n_items > b.setup_grid[g];
-      for (int i = 0; i < kCounterShards; i++) {
-        const CounterShard& sh = cn.shard[i];
-        k.tris_binned += sh.tris_binned; k.bin_entries += sh.bin_entries; k.clip_count += sh.clip_count;
-        k.max_bin_fill = std::max(k.max_bin_fill, sh.max_bin_fill); k.clip_overflow |= sh.clip_overflow;
-        k.max_fbin_fill = std::max(k.max_fbin_fill, sh.max_fbin_fill); k.frags += sh.frags; k.uncovered |= sh.uncovered;
-        k.max_big_fill = std::max(k.max_big_fill, sh.max_big_fill);
-        k.occluded += sh.occluded; k.cover_tiles += sh.cover_tiles; k.exact_tiles += sh.exact_tiles; k.zero_items += sh.zero_items;
-        k.raster_atomics += sh.raster_atomics; k.drawn_pixels += sh.drawn_pixels;
-      }
-    }
-    group_streams = (b.rq.n + b.n_groups - 1) / std::max(b.n_groups, 1);
-    c->items_hint = k.max_items;               // sizes the next batches' set-up grids (the longest list of this batch's groups ...
-    c->items_hint_streams = group_streams;     // ... of so many streams each)
-    c->group_items.resize((size_t)b.n_groups); c->group_streams.resize((size_t)b.n_groups);
-    for (int g = 0; g < b.n_groups; g++) {
-      c->group_items[(size_t)g] = b.h_counters[g].work.n_items;
-      c->group_streams[(size_t)g] = std::min(group_streams, b.rq.n - g * group_streams);
-    }
-    c->stats.triangles_submitted = (uint64_t)c->n_tris * (uint64_t)b.rq.n;
-    c->stats.triangles_binned = k.tris_binned;
-    c->stats.bin_entries = k.bin_entries;
-    c->stats.triangles_clipped = k.clip_count;
-    c->stats.max_bin_fill = k.max_bin_fill;
-    c->stats.bin_capacity = c->capacity;
-    c->stats.fragments_binned = k.frags;
-    c->stats.max_fbin_fill = k.max_fbin_fill;
-    c->stats.occluded_entries = k.occluded; c->stats.cover_tiles = k.cover_tiles; c->stats.exact_tiles = k.exact_tiles;
-    c->stats.work_items = (uint32_t)std::min<unsigned long long>(k.work_items, 0xffffffffu); c->stats.zero_survivor_items = k.zero_items;
-    c->stats.raster_atomics = k.raster_atomics; c->stats.drawn_pixels = k.drawn_pixels;
-    c->stats.cover_pass = b.route.tile.cover ? 1u : 0u;
-    c->stats.groups_last_batch = (uint32_t)b.n_groups;
-    const bool bin_over = k.max_bin_fill > c->capacity || k.max_fbin_fill > c->fcapacity;
-    const bool clip_over = k.clip_overflow != 0;
-    const bool big_over = k.max_big_fill > c->big_capacity;
-    if (list_over) c->stats.regrowths++;
-    // host mirror of the device status word (rtuf_batch_status_device): what the FIRST run of the batch being retired left there
-    if (attempt == 0) {
-      c->stats.batch_status = (bin_over ? kStatusBinOverflow : 0u) | (clip_over ? kStatusClipOverflow : 0u) | (big_over ? kStatusBigOverflow : 0u) |
-                              (list_over ? kStatusGridShort : 0u) | (k.uncovered ? kStatusUncovered : 0u);
-      c->stats.batch_reruns = 0;
-    }
-    if (!bin_over && !clip_over && !list_over && !big_over) {
-      if (b.host_io) HIP_TRY(c, hipEventSynchronize(b.downloaded));
-      if (b.timing && b.events.size() >= (size_t)(kEvGroup0 + kEvPerGroup * b.n_groups)) {
-        // per launch group E0 .. E4 (see issue_plan).  With several lanes the kernels of different groups overlap: the sums
-        // below add up per-launch durations, they are not wall time.
-        const bool behind = runs_behind_tile(b.route);      // ms_compare: whatever ran behind the tile kernel
-        auto el = [&](size_t i, size_t j) { float ms = 0; hipEventElapsedTime(&ms, b.events[i], b.events[j]); return ms; };
-        c->stats.ms_pose = c->stats.ms_setup = c->stats.ms_clip = c->stats.ms_raster = c->stats.ms_compare = c->stats.ms_total = 0;
-        for (int g = 0; g < b.n_groups; g++) {
-          const size_t e0 = kEvGroup0 + kEvPerGroup * (size_t)g;
-          if (b.timing == 1) {
-            c->stats.ms_setup += el(e0, e0 + 2);
-          } else {
-            c->stats.ms_setup += el(e0, e0 + 1);
-            c->stats.ms_clip += el(e0 + 1, e0 + 2);
-          }
-          c->stats.ms_raster += el(e0 + 2, e0 + 3);
-          if (behind) c->stats.ms_compare += el(e0 + 3, e0 + 4);
-        }
-        if (b.timing == 1) {
-          c->stats.ms_pose = el(kEvStart, kEvPoseEnd);
-          for (int l = 0; l < c->n_lanes; l++)
-            if (b.lanes_used >> l & 1u) c->stats.ms_total = std::max(c->stats.ms_total, el(kEvStart, kEvLaneEnd + l));
-        }
-        c->acc_ms[0] += c->stats.ms_pose; c->acc_ms[1] += c->stats.ms_setup; c->acc_ms[2] += c->stats.ms_raster;
-        c->acc_ms[3] += c->stats.ms_compare; c->acc_ms[4] += c->stats.ms_total; c->acc_ms[5] += c->stats.ms_clip;
-        c->acc_batches++;
-        c->stats.timed_batches = c->acc_batches;
-        c->stats.sum_ms_pose = c->acc_ms[0]; c->stats.sum_ms_setup = c->acc_ms[1]; c->stats.sum_ms_raster = c->acc_ms[2];
-        c->stats.sum_ms_compare = c->acc_ms[3]; c->stats.sum_ms_total = c->acc_ms[4]; c->stats.sum_ms_clip = c->acc_ms[5];
-      }
-      if (b.route.tile.cover) {
-        if (k.cover_tiles) c->cover_idle = 0;
-        else if (++c->cover_idle >= 3) { c->cover_on = false; c->cover_sleep = 64; c->cover_idle = 2; }      // (idle = 2: one empty probe sends it back to sleep)
-      } else if (--c->cover_sleep <= 0) {
-        c->cover_on = true;
-      }
-      b.active = false;
-      c->oldest = (c->oldest + 1) % kMaxInflight;
-      c->pending--;
-      if (b.rq.kind == Kind::Cloud && k.uncovered)
-        return c->fail(RTUF_ERR_STATE, "point cloud: a stream's background quad does not cover its whole image (non-standard projection), so the mask "
-                                       "bits the cloud is built on are undefined there; there is no cloud form for this camera (filter with the "
-                                       "full-plane calls and convert the masked plane)");
-      if (b.rq.kind == Kind::Clearance && k.uncovered)
-        return c->fail(RTUF_ERR_STATE, "link clearance: a stream's background quad does not cover its whole image (non-standard projection), so the "
-                                       "mask bits the kept points are taken from are undefined there");
-      if (b.rq.kind == Kind::Bits && k.uncovered)
-        return c->fail(RTUF_ERR_STATE, "mask bits: a stream's background quad does not cover its whole image (non-standard projection), so "
-                                       "masked depth != select(bit, replace, sensor) there; use the full-plane calls for this camera");
-      return RTUF_OK;
-    }
-    // overflow: wait for the later batches too, enlarge, and run everything in flight again in order
-    sync_lanes(c);
-    if (c->d2h) HIP_TRY(c, hipStreamSynchronize(c->d2h));
-    auto give_up = [&](int rc) { for (auto& o : c->batch) o.active = false; c->pending = 0; return rc; };
-    if (bin_over) { const int rc = grow_bins(c, k.max_bin_fill, k.max_fbin_fill); if (rc != RTUF_OK) return give_up(rc); }
-    if (clip_over) {
-      const uint32_t larger = c->clip_capacity * 4;
-      for (int l = 0; l < c->n_lanes; l++) {
-        int rc = regrow(c, c->lane[l].d_clip_list, (size_t)larger * kCounterShards * sizeof(ClipItem), "clip list");
-        if (rc == RTUF_OK && clip_spill_bytes(larger) != clip_spill_bytes(c->clip_capacity)) { rc = regrow(c, c->lane[l].d_clip_spill, clip_spill_bytes(larger), "clip spill area"); c->stats.regrowths--; }
-        if (rc != RTUF_OK) return give_up(rc);
-        if (l) c->stats.regrowths--;           // (one regrowth, however many lanes)
-      }
-      c->clip_capacity = larger;
-    }
-    if (big_over) {
-      // (half as much again as this run asked for: poses move, and a list that just fits overflows on the next batch)
-      uint32_t larger = c->big_capacity;
-      while (larger < k.max_big_fill + k.max_big_fill / 2) larger *= 2;
-      for (int l = 0; l < c->n_lanes; l++) {
-        const int rc = regrow(c, c->lane[l].d_big_list, (size_t)larger * kCounterShards * sizeof(BigRec), "many-tile list");
-        if (rc != RTUF_OK) return give_up(rc);
-        if (l) c->stats.regrowths--;
-      }
-      c->big_capacity = larger;
-    }
-    const size_t tiles = (size_t)c->tiles_x * c->tiles_y;
-    for (int l = 0; l < c->n_lanes; l++) {
-      // (the arrays were sized for the launch group the context started with: at least the present one)
-      launch_init_headers(c->lane[l].d_bin_hdr, (size_t)c->group * tiles, c->lane[l].stream);
-      HIP_TRY(c, hipMemsetAsync(c->lane[l].d_fbin_count, 0, (size_t)c->group * tiles * sizeof(uint32_t), c->lane[l].stream));
-    }
-    // (a grid that was too short: the re-run takes the worst-case grid, which no list can outgrow -- the estimate that failed
-    // once would size the same grid again)
-    c->force_worst_grid = list_over;
-    c->stats.batch_reruns++;
-    for (int i = 0; i < c->pending; i++) {
-      rtuf_context::Batch& r = c->batch[(c->oldest + i) % kMaxInflight];
-      int rc = enqueue_batch(c, r, true);
-      if (rc == RTUF_OK && r.host_io) rc = enqueue_download(c, r);
-      if (rc != RTUF_OK) { c->force_worst_grid = false; for (auto& o : c->batch) o.active = false; c->pending = 0; return rc; }
-    }
-    c->force_worst_grid = false;
+    const BatchTotals k = sum_counters(c, b);
+    publish_stats(c, b, k, attempt == 0);
+    if (!k.overflowed()) return retire_clean(c, b, k);
+    const int rc = regrow_and_rerun(c, k);
+    if (rc != RTUF_OK) return rc;
   }
-  for (auto& o : c->batch) o.active = false;
-  c->pending = 0;
-  return c->fail(RTUF_ERR_CAPACITY, "tile bins still overflow after regrowth");
+  return drop_in_flight(c, c->fail(RTUF_ERR_CAPACITY, "tile bins still overflow after regrowth"));
 }
 
 // ---- submission -----------------------------------------------------------------------
-// While link padding is in effect a margin in metres is projected with the stream's focal length: every stream of a batch needs
-// its intrinsics (no rule of the route: asked before anything is staged or enqueued).
-static int need_pad_intrinsics(rtuf_context* c, int n)
+// streams 0 .. n - 1 have their intrinsics (table: the one the caller's kernels read, d_cloud_intr or d_point_intr; the setter writes both)
+static int need_intrinsics(rtuf_context* c, int n, const void* table)
 {
-  for (int s = 0; c->pad_models > 0 && s < n; s++)
-    if (!c->d_cloud_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
+  for (int s = 0; s < n; s++)
+    if (!table || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
   return RTUF_OK;
 }
+
+// max_streams bits planes (rtuf_mask_bits_words each): what a buffer of the library's own holds that a mask-bits batch writes
+static size_t bits_planes_bytes(const rtuf_context* c) { return (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t); }
+static int ensure_bits_planes(rtuf_context* c, uint32_t*& p) { if (!p) HIP_TRY(c, dev_alloc(c, &p, bits_planes_bytes(c))); return RTUF_OK; }
+
+// The calls of their own (learning a scene, the voxel inserts and carves) and some setters run a kernel on lane 0 and wait.
+static int wait_lane0(rtuf_context* c) { HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream)); return RTUF_OK; }
+static int finish_on_lane0(rtuf_context* c) { const int rc = wait_lane0(c); if (rc == RTUF_OK) HIP_TRY(c, hipGetLastError()); return rc; }
+
+// While link padding is in effect a margin in metres is projected with the stream's focal length: every stream of a batch needs
+// its intrinsics (no rule of the route: asked before anything is staged or enqueued).
+static int need_pad_intrinsics(rtuf_context* c, int n) { return c->pad_models > 0 ? need_intrinsics(c, n, c->d_cloud_intr) : RTUF_OK; }
 
 static int check_u16_width(rtuf_context* c, bool u16) { return u16 && (c->width & 3) ? c->fail(RTUF_ERR_INVALID, "16UC1 path needs a width that is a multiple of 4") : RTUF_OK; }
 // What every batch call checks first: the models are final, n is in range and the arrays the call cannot do without are there
@@ -2195,18 +2229,13 @@ static int take_slot(rtuf_context* c, rtuf_context::Batch*& slot)
 // cloud batch gets the slot's own bits buffer and row scratch here, a clearance batch the bits buffer and its posed spheres.
 static int submit_batch(rtuf_context* c, rtuf_context::Batch& b, const BatchRequest& rq)
 {
-  if (rq.kind == Kind::Cloud) {
-    if (!b.cl_bits) HIP_TRY(c, dev_alloc(c, &b.cl_bits, (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
-    if (rq.capacity && !b.cl_rows) HIP_TRY(c, dev_alloc(c, &b.cl_rows, 2u * (size_t)c->max_streams * (size_t)c->height * sizeof(uint32_t)));
-  }
-  if (rq.kind == Kind::Clearance) {
-    if (!b.cl_bits) HIP_TRY(c, dev_alloc(c, &b.cl_bits, (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
-    if (b.clr_posed_have < c->clr_spheres.size()) {
-      dev_free(c, b.clr_posed);
-      b.clr_posed_have = 0;
-      HIP_TRY(c, dev_alloc(c, &b.clr_posed, (size_t)c->max_streams * c->clr_spheres.size() * sizeof(float4)));
-      b.clr_posed_have = c->clr_spheres.size();
-    }
+  if (rq.kind == Kind::Cloud || rq.kind == Kind::Clearance) { const int rc = ensure_bits_planes(c, b.cl_bits); if (rc != RTUF_OK) return rc; }
+  if (rq.kind == Kind::Cloud && rq.capacity && !b.cl_rows) HIP_TRY(c, dev_alloc(c, &b.cl_rows, 2u * (size_t)c->max_streams * (size_t)c->height * sizeof(uint32_t)));
+  if (rq.kind == Kind::Clearance && b.clr_posed_have < c->clr_spheres.size()) {
+    dev_free(c, b.clr_posed);
+    b.clr_posed_have = 0;
+    HIP_TRY(c, dev_alloc(c, &b.clr_posed, (size_t)c->max_streams * c->clr_spheres.size() * sizeof(float4)));
+    b.clr_posed_have = c->clr_spheres.size();
   }
   if (rq.kind == Kind::Points && !b.pt_plane)
     HIP_TRY(c, dev_alloc(c, &b.pt_plane, (size_t)c->max_streams * c->width * c->height * sizeof(float)));
@@ -2802,8 +2831,7 @@ static int ensure_scene(rtuf_context* c)
   HIP_TRY(c, dev_alloc(c, &c->d_scene, (size_t)c->max_streams * plane * sizeof(float)));
   HIP_TRY(c, hipMemcpy(c->d_scene_streams, c->scene_streams.data(), (size_t)c->max_streams * sizeof(SceneStream), hipMemcpyHostToDevice));
   launch_fill_f32(c->d_scene, (size_t)c->max_streams * plane, INFINITY, c->lane[0].stream);
-  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
-  return RTUF_OK;
+  return wait_lane0(c);
 }
 
 // (no batch in flight reads the table: every caller waited for them)
@@ -2874,8 +2902,7 @@ int rtuf_get_scene_planes_device(rtuf_context* c, int first, int n, float* d_out
   const size_t plane = (size_t)c->width * c->height;
   if (!c->d_scene) {
     launch_fill_f32(d_out, (size_t)n * plane, INFINITY, c->lane[0].stream);
-    HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
-    return RTUF_OK;
+    return wait_lane0(c);
   }
   HIP_TRY(c, hipMemcpy(d_out, c->d_scene + (size_t)first * plane, (size_t)n * plane * sizeof(float), hipMemcpyDeviceToDevice));
   return RTUF_OK;
@@ -2924,27 +2951,53 @@ int rtuf_clear_scene(rtuf_context* c, int first, int n)
     return RTUF_OK;
   }
   launch_fill_f32(c->d_scene + (size_t)first * plane, (size_t)n * plane, INFINITY, c->lane[0].stream);
-  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
+  { const int rc = wait_lane0(c); if (rc != RTUF_OK) return rc; }
   return upload_scene_streams(c);
 }
 
-// Learning.  The robot's bits come from a mask-bits batch like any other, but for its route (robot_only: never the scene) and
-// its output, the context's own buffer; rtuf_sync retires it, re-runs after an overflow included, before the planes are touched.
+// ---- what the calls of their own share (learning a scene, the voxel inserts and carves) ------------------------
+// Behind the call's own checks -- a refused call retires, allocates and copies nothing -- the host-plane forms retire what is in
+// flight and bring the caller's sensor planes up into a stage of the context's, allocated on first use: [max_streams][H][W]
+// floats and, summary, [max_streams][4] words behind them.
+static int stage_host_planes(rtuf_context* c, float*& stage, bool summary, int n, const void* const* depth_in, bool u16)
+{
+  for (int s = 0; s < n; s++) if (!depth_in[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
+  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  hipSetDevice(c->device);
+  const size_t plane = (size_t)c->width * c->height;
+  if (!stage) HIP_TRY(c, dev_alloc(c, &stage, (size_t)c->max_streams * (plane + (summary ? 4u : 0u)) * sizeof(float)));
+  return copy_planes(c, stage, const_cast<void* const*>(depth_in), n, plane * (u16 ? sizeof(uint16_t) : sizeof(float)), hipMemcpyHostToDevice, nullptr);
+}
+// the summary behind the planes of such a stage (nullptr: the caller wants none), and its way down
+static uint32_t* summary_behind(const rtuf_context* c, float* stage, const uint32_t* wanted) { return wanted ? reinterpret_cast<uint32_t*>(stage + (size_t)c->max_streams * c->width * c->height) : nullptr; }
+static int download_summary(rtuf_context* c, float* stage, int n, uint32_t* out)
+{
+  if (out) HIP_TRY(c, hipMemcpy(out, summary_behind(c, stage, out), (size_t)n * 4u * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RTUF_OK;
+}
+
+// The robot's mask bits of the call's planes: a mask-bits batch like any other but for its output, `bits` -- a buffer of the
+// context's, allocated on first use -- and, robot_only, its route (never the scene); rtuf_sync retires it, re-runs after an
+// overflow included, before anything reads the bits.  The caller has retired what was in flight.
+static int own_bits_pass(rtuf_context* c, uint32_t*& bits, int n, const void* d_depth, bool u16, bool robot_only)
+{
+  { const int rc = ensure_bits_planes(c, bits); if (rc != RTUF_OK) return rc; }
+  BatchRequest rq = bits_request(n, d_depth, bits, u16);
+  rq.robot_only = robot_only;
+  { const int rc = submit_device(c, rq); if (rc != RTUF_OK) return rc; }
+  return rtuf_sync(c);
+}
+
+// Learning: the robot's bits (own_bits_pass) are final before the planes are touched.
 static int learn_scene_device(rtuf_context* c, int n, const void* d_depth, bool u16)
 {
   { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
   { const int rc = ensure_scene(c); if (rc != RTUF_OK) return rc; }
-  if (!c->d_scene_bits) HIP_TRY(c, dev_alloc(c, &c->d_scene_bits, (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
-  BatchRequest rq = bits_request(n, d_depth, c->d_scene_bits, u16);
-  rq.robot_only = true;
-  { const int rc = submit_device(c, rq); if (rc != RTUF_OK) return rc; }
-  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
+  { const int rc = own_bits_pass(c, c->d_scene_bits, n, d_depth, u16, true); if (rc != RTUF_OK) return rc; }
   SceneLearnArgs la;
-  la.depth = static_cast<const float*>(d_depth); la.bits = c->d_scene_bits; la.scene = c->d_scene;
-  la.n_streams = n; la.width = c->width; la.height = c->height; la.io_u16 = u16 ? 1 : 0;
+  la.depth = static_cast<const float*>(d_depth); la.bits = c->d_scene_bits; la.scene = c->d_scene; la.n_streams = n; la.width = c->width; la.height = c->height; la.io_u16 = u16 ? 1 : 0;
   launch_scene_learn(la, c->lane[0].stream);
-  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
-  HIP_TRY(c, hipGetLastError());
+  { const int rc = finish_on_lane0(c); if (rc != RTUF_OK) return rc; }
   for (int s = 0; s < n; s++) c->scene_touched[(size_t)s] = 1;
   return RTUF_OK;
 }
@@ -2963,13 +3016,7 @@ static int learn_scene_kids(rtuf_context* c, int n, int rc)
 static int learn_scene_host(rtuf_context* c, int n, const void* const* depth_in, bool u16)
 {
   { const int rc = check_bits_call(c, n, depth_in, depth_in, u16); if (rc != RTUF_OK) return rc; }
-  for (int s = 0; s < n; s++) if (!depth_in[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
-  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
-  hipSetDevice(c->device);
-  const size_t plane = (size_t)c->width * c->height;
-  if (!c->d_scene_stage) HIP_TRY(c, dev_alloc(c, &c->d_scene_stage, (size_t)c->max_streams * plane * sizeof(float)));
-  { const int rc = copy_planes(c, c->d_scene_stage, const_cast<void* const*>(depth_in), n, plane * (u16 ? sizeof(uint16_t) : sizeof(float)), hipMemcpyHostToDevice, nullptr);
-    if (rc != RTUF_OK) return rc; }
+  { const int rc = stage_host_planes(c, c->d_scene_stage, false, n, depth_in, u16); if (rc != RTUF_OK) return rc; }
   return learn_scene_device(c, n, c->d_scene_stage, u16);
 }
 
@@ -3172,17 +3219,15 @@ static int check_cloud_call(rtuf_context* c, int n, const void* in, const void* 
   if (compact && (capacity < 1 || (long long)capacity > (long long)c->width * c->height))
     return c->fail(RTUF_ERR_INVALID, "capacity = %d: 1 .. width * height (%lld)", capacity, (long long)c->width * c->height);
   { const int rc = check_route(c, BatchRequest(Kind::Cloud, n, false)); if (rc != RTUF_OK) return rc; }      // (16UC1 or not: no refusal asks)
-  for (int s = 0; s < n; s++)
-    if (!c->d_cloud_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
-  return RTUF_OK;
+  return need_intrinsics(c, n, c->d_cloud_intr);
 }
 
 // device planes of the organized form: its kernel loads four sensor values at once (16 bytes of f32, 8 bytes of 16UC1) and stores 16-byte
 // vectors of points
 static int check_cloud_alignment(rtuf_context* c, const void* d_depth, const void* d_points, bool u16)
 {
-  if ((uintptr_t)d_points & 15u) return c->fail(RTUF_ERR_INVALID, "d_points must be 16-byte aligned");
-  if ((uintptr_t)d_depth & (u16 ? 7u : 15u)) return c->fail(RTUF_ERR_INVALID, "d_depth must be %d-byte aligned", u16 ? 8 : 16);
+  if (!aligned(d_points, 16)) return c->fail(RTUF_ERR_INVALID, "d_points must be 16-byte aligned");
+  if (!aligned(d_depth, u16 ? 8 : 16)) return c->fail(RTUF_ERR_INVALID, "d_depth must be %d-byte aligned", u16 ? 8 : 16);
   return RTUF_OK;
 }
 
@@ -3310,8 +3355,7 @@ static int check_points_call(rtuf_context* c, int n, bool have_args, long long c
   if (capacity < 1 || capacity > (long long)kMaxPointsCapacity) return c->fail(RTUF_ERR_INVALID, "capacity = %lld: 1 .. %d", capacity, kMaxPointsCapacity);
   if (radius < 0 || radius > kMaxPointsRadius) return c->fail(RTUF_ERR_INVALID, "radius_px = %d: 0 .. %d", radius, kMaxPointsRadius);
   { const int rc = check_route(c, BatchRequest(Kind::Points, n, false)); if (rc != RTUF_OK) return rc; }
-  for (int s = 0; s < n; s++)
-    if (!c->d_point_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
+  { const int rc = need_intrinsics(c, n, c->d_point_intr); if (rc != RTUF_OK) return rc; }
   return ensure_point_transforms(c);
 }
 
@@ -3353,12 +3397,7 @@ int rtuf_points_batch(rtuf_context* c, int n, const float* const* points_in, con
   const size_t o_points = 0, o_counts = o_points + up16((size_t)n * capacity * 3u * sizeof(float)), o_verdict = o_counts + up16((size_t)n * sizeof(uint32_t));
   const size_t o_pixel = o_verdict + up16((size_t)n * capacity), o_summary = o_pixel + up16(pixel_out ? (size_t)n * capacity * sizeof(uint32_t) : 0);
   const size_t bytes = o_summary + up16((size_t)n * 4u * sizeof(uint32_t));
-  if (c->pt_stage_bytes < bytes) {
-    dev_free(c, c->d_pt_stage);
-    c->pt_stage_bytes = 0;
-    HIP_TRY(c, dev_alloc(c, &c->d_pt_stage, bytes));
-    c->pt_stage_bytes = bytes;
-  }
+  { const int rc = ensure_staging(c, c->d_pt_stage, c->pt_stage_bytes, bytes, 1); if (rc != RTUF_OK) return rc; }
   char* const d = c->d_pt_stage;
   for (int s = 0; s < n; s++)
     if (counts[s]) HIP_TRY(c, hipMemcpy(d + o_points + (size_t)s * capacity * 3u * sizeof(float), points_in[s], (size_t)counts[s] * 3u * sizeof(float), hipMemcpyHostToDevice));
@@ -3405,9 +3444,7 @@ static int clear_voxel_grid(rtuf_context* c)
   launch_voxel_clear(c->d_vox_bits, (c->vox_words + 3u) & ~(size_t)3u, c->lane[0].stream);
   if (c->d_vox_counts) launch_voxel_clear(c->d_vox_counts, (c->vox_voxels + 3u) & ~(size_t)3u, c->lane[0].stream);
   if (c->d_vox_free) launch_voxel_clear(c->d_vox_free, (c->vox_words + 3u) & ~(size_t)3u, c->lane[0].stream);
-  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
-  HIP_TRY(c, hipGetLastError());
-  return RTUF_OK;
+  return finish_on_lane0(c);
 }
 
 int rtuf_set_voxel_grid(rtuf_context* c, const double* origin, double voxel_size, const int* dims, int with_counts)
@@ -3535,54 +3572,32 @@ static void voxel_grid_args(const rtuf_context* c, VoxelArgs& va, int n, uint32_
   va.grid_bits = c->d_vox_bits; va.grid_counts = c->d_vox_counts; va.world_tf = c->d_vox_tf;
   va.summary = d_summary; va.n_streams = n;
 }
-
-static int run_voxel_insert(rtuf_context* c, const VoxelArgs& va)
-{
-  launch_voxel_insert(va, c->lane[0].stream);
-  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
-  HIP_TRY(c, hipGetLastError());
-  return RTUF_OK;
-}
+static int run_voxel_insert(rtuf_context* c, const VoxelArgs& va) { launch_voxel_insert(va, c->lane[0].stream); return finish_on_lane0(c); }
 
 // what a plane insert checks before anything is retired or written: the mask-bits calls' conditions, the grid, the intrinsics
 static int check_voxel_call(rtuf_context* c, int n, const void* in, bool u16)
 {
   { const int rc = check_bits_call(c, n, in, in, u16); if (rc != RTUF_OK) return rc; }
   { const int rc = need_voxel_grid(c); if (rc != RTUF_OK) return rc; }
-  for (int s = 0; s < n; s++)
-    if (!c->d_cloud_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
-  return RTUF_OK;
+  return need_intrinsics(c, n, c->d_cloud_intr);
 }
 
 static int voxel_insert_device(rtuf_context* c, int n, const void* d_depth, uint32_t* d_summary, bool u16)
 {
   { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
-  hipSetDevice(c->device);
-  if (!c->d_vox_mask_bits) HIP_TRY(c, dev_alloc(c, &c->d_vox_mask_bits, (size_t)c->max_streams * rtuf_mask_bits_words(c->width, c->height) * sizeof(uint32_t)));
-  { const int rc = submit_device(c, bits_request(n, d_depth, c->d_vox_mask_bits, u16)); if (rc != RTUF_OK) return rc; }
-  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
-  VoxelArgs va{};
-  voxel_grid_args(c, va, n, d_summary);
+  { const int rc = own_bits_pass(c, c->d_vox_mask_bits, n, d_depth, u16, false); if (rc != RTUF_OK) return rc; }
+  VoxelArgs va{}; voxel_grid_args(c, va, n, d_summary);
   va.depth = static_cast<const float*>(d_depth); va.bits = c->d_vox_mask_bits; va.intr = c->d_cloud_intr;
-  va.width = c->width; va.height = c->height; va.io_u16 = u16 ? 1 : 0;
-  va.wide = (c->width & 3) == 0 && ((uintptr_t)d_depth & (u16 ? 7u : 15u)) == 0u ? 1 : 0;
+  va.width = c->width; va.height = c->height; va.io_u16 = u16 ? 1 : 0; va.wide = (c->width & 3) == 0 && aligned(d_depth, u16 ? 8 : 16) ? 1 : 0;
   return run_voxel_insert(c, va);
 }
 
 static int voxel_insert_host(rtuf_context* c, int n, const void* const* depth_in, uint32_t* summary_out, bool u16)
 {
   { const int rc = check_voxel_call(c, n, depth_in, u16); if (rc != RTUF_OK) return rc; }
-  for (int s = 0; s < n; s++) if (!depth_in[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
-  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
-  hipSetDevice(c->device);
-  const size_t plane = (size_t)c->width * c->height;
-  if (!c->d_vox_stage) HIP_TRY(c, dev_alloc(c, &c->d_vox_stage, (size_t)c->max_streams * (plane + 4u) * sizeof(float)));
-  uint32_t* const d_summary = reinterpret_cast<uint32_t*>(c->d_vox_stage + (size_t)c->max_streams * plane);
-  { const int rc = copy_planes(c, c->d_vox_stage, const_cast<void* const*>(depth_in), n, plane * (u16 ? sizeof(uint16_t) : sizeof(float)), hipMemcpyHostToDevice, nullptr);
-    if (rc != RTUF_OK) return rc; }
-  { const int rc = voxel_insert_device(c, n, c->d_vox_stage, summary_out ? d_summary : nullptr, u16); if (rc != RTUF_OK) return rc; }
-  if (summary_out) HIP_TRY(c, hipMemcpy(summary_out, d_summary, (size_t)n * 4u * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return RTUF_OK;
+  { const int rc = stage_host_planes(c, c->d_vox_stage, true, n, depth_in, u16); if (rc != RTUF_OK) return rc; }
+  { const int rc = voxel_insert_device(c, n, c->d_vox_stage, summary_behind(c, c->d_vox_stage, summary_out), u16); if (rc != RTUF_OK) return rc; }
+  return download_summary(c, c->d_vox_stage, n, summary_out);
 }
 
 int rtuf_voxel_insert_batch_device(rtuf_context* c, int n, const float* d_depth, uint32_t* d_summary)
@@ -3625,10 +3640,9 @@ int rtuf_voxel_insert_points_device(rtuf_context* c, int n, const float* d_point
   { const int rc = need_voxel_grid(c); if (rc != RTUF_OK) return rc; }
   { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }      // (the list may be the output of a batch in flight)
   hipSetDevice(c->device);
-  VoxelArgs va{};
-  voxel_grid_args(c, va, n, d_summary);
+  VoxelArgs va{}; voxel_grid_args(c, va, n, d_summary);
   va.points = d_points; va.counts = d_counts; va.verdict = d_verdict; va.point_tf = c->d_point_tf; va.capacity = capacity;
-  va.wide = ((uintptr_t)d_points & 15u) == 0u && ((uintptr_t)d_verdict & 3u) == 0u && (capacity & 3) == 0 ? 1 : 0;
+  va.wide = aligned(d_points, 16) && aligned(d_verdict, 4) && (capacity & 3) == 0 ? 1 : 0;
   return run_voxel_insert(c, va);
 }
 
@@ -3641,9 +3655,7 @@ static int ensure_voxel_free(rtuf_context* c)
   const size_t words = (c->vox_words + 3u) & ~(size_t)3u;
   HIP_TRY(c, dev_alloc(c, &c->d_vox_free, words * sizeof(uint32_t)));
   launch_voxel_clear(c->d_vox_free, words, c->lane[0].stream);
-  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
-  HIP_TRY(c, hipGetLastError());
-  return RTUF_OK;
+  return finish_on_lane0(c);
 }
 
 // what a carve checks before anything is retired or written
@@ -3657,9 +3669,7 @@ static int check_carve_call(rtuf_context* c, int n, const void* in, double margi
     if (!c->vox_inv_ok.empty() && !c->vox_inv_ok[(size_t)s])
       return c->fail(RTUF_ERR_INVALID, "stream %d: its voxel transform cannot be inverted (rtuf_set_voxel_transforms)", s);
   { const int rc = need_voxel_grid(c); if (rc != RTUF_OK) return rc; }
-  for (int s = 0; s < n; s++)
-    if (!c->d_point_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
-  return RTUF_OK;
+  return need_intrinsics(c, n, c->d_point_intr);
 }
 
 static int voxel_carve_device(rtuf_context* c, int n, const void* d_depth, double margin, int radius_px, uint32_t* d_summary, bool u16)
@@ -3678,25 +3688,15 @@ static int voxel_carve_device(rtuf_context* c, int n, const void* d_depth, doubl
   va.depth = static_cast<const float*>(d_depth); va.summary = d_summary; va.margin = (float)margin; va.radius = radius_px;
   va.width = c->width; va.height = c->height; va.io_u16 = u16 ? 1 : 0; va.n_streams = n;
   launch_voxel_carve(va, c->lane[0].stream);
-  HIP_TRY(c, hipStreamSynchronize(c->lane[0].stream));
-  HIP_TRY(c, hipGetLastError());
-  return RTUF_OK;
+  return finish_on_lane0(c);
 }
 
 static int voxel_carve_host(rtuf_context* c, int n, const void* const* depth_in, double margin, int radius_px, uint32_t* summary_out, bool u16)
 {
   { const int rc = check_carve_call(c, n, depth_in, margin, radius_px); if (rc != RTUF_OK) return rc; }
-  for (int s = 0; s < n; s++) if (!depth_in[s]) return c->fail(RTUF_ERR_INVALID, "null plane for stream %d", s);
-  { const int rc = rtuf_sync(c); if (rc != RTUF_OK) return rc; }
-  hipSetDevice(c->device);
-  const size_t plane = (size_t)c->width * c->height;
-  if (!c->d_vox_stage) HIP_TRY(c, dev_alloc(c, &c->d_vox_stage, (size_t)c->max_streams * (plane + 4u) * sizeof(float)));
-  uint32_t* const d_summary = reinterpret_cast<uint32_t*>(c->d_vox_stage + (size_t)c->max_streams * plane);
-  { const int rc = copy_planes(c, c->d_vox_stage, const_cast<void* const*>(depth_in), n, plane * (u16 ? sizeof(uint16_t) : sizeof(float)), hipMemcpyHostToDevice, nullptr);
-    if (rc != RTUF_OK) return rc; }
-  { const int rc = voxel_carve_device(c, n, c->d_vox_stage, margin, radius_px, summary_out ? d_summary : nullptr, u16); if (rc != RTUF_OK) return rc; }
-  if (summary_out) HIP_TRY(c, hipMemcpy(summary_out, d_summary, (size_t)n * 4u * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return RTUF_OK;
+  { const int rc = stage_host_planes(c, c->d_vox_stage, true, n, depth_in, u16); if (rc != RTUF_OK) return rc; }
+  { const int rc = voxel_carve_device(c, n, c->d_vox_stage, margin, radius_px, summary_behind(c, c->d_vox_stage, summary_out), u16); if (rc != RTUF_OK) return rc; }
+  return download_summary(c, c->d_vox_stage, n, summary_out);
 }
 
 int rtuf_voxel_carve_batch_device(rtuf_context* c, int n, const float* d_depth, double margin, int radius_px, uint32_t* d_summary)
@@ -3835,8 +3835,7 @@ static int check_clearance_call(rtuf_context* c, int n, const void* in, const vo
   if (n_labels < 1) return c->fail(RTUF_ERR_INVALID, "a clearance table needs at least one row per stream (n_labels=%d)", n_labels);
   if (!(max_distance > 0.0f)) return c->fail(RTUF_ERR_INVALID, "max_distance must be > 0 (+inf is allowed; got %g)", (double)max_distance);
   { const int rc = check_route(c, BatchRequest(Kind::Clearance, n, false)); if (rc != RTUF_OK) return rc; }      // (16UC1 or not: no refusal asks)
-  for (int s = 0; s < n; s++)
-    if (!c->d_cloud_intr || !c->cloud_intr_set[(size_t)s]) return c->fail(RTUF_ERR_STATE, "stream %d has no cloud intrinsics (rtuf_set_cloud_intrinsics)", s);
+  { const int rc = need_intrinsics(c, n, c->d_cloud_intr); if (rc != RTUF_OK) return rc; }
   return ensure_clearance_spheres(c);
 }
 

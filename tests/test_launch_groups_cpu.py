@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 
+import enqueue_steps as ES
 import launch_groups as LG
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -66,7 +67,7 @@ def test_the_library_takes_the_rule_from_the_shared_header():
     assert "static int groups_for(const rtuf_context* c, int n) { return rtuf::groups_for(n, c->group, c->n_lanes); }" in api
     assert "c->max_groups = rtuf::counter_blocks_for(c->max_streams, c->group, c->n_lanes);" in api
     assert "kSplitMin = " not in api and "c->n_lanes) * c->n_lanes" not in api
-    # the hard stop comes before the first change to the context or the batch slot
-    body = api.split("static int enqueue_batch(")[1]
-    stop = body.index("if (n_groups > c->max_groups)")
-    assert all(stop < body.index(m) for m in ("b.lanes_used = 0;", "c->next_lane", "c->timing_seq++", "c->last_slot =", "hipMemcpyAsync"))
+    # the hard stop comes before the first change to the context or the batch slot: before every step of enqueue_batch, and
+    # the changes stand in those steps (enqueue_steps.py)
+    assert ES.CHECKS[0] == "if (n_groups > c->max_groups)"
+    ES.assert_checks_precede_every_change(api)

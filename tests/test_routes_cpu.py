@@ -11,6 +11,8 @@ import subprocess
 
 import pytest
 
+import enqueue_steps as ES
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "realtime_urdf_filter_amd", "csrc")
 
@@ -79,7 +81,9 @@ def test_the_kernels_and_the_host_take_the_route_from_the_header():
     enqueue = _body(api, "static int enqueue_batch(")
     ask = enqueue.index("route_of(")
     assert "rerun ? b.route" in enqueue[:ask] and enqueue.index("if (!route.ok() || !tile_variant_legal(route.tile))\n    return c->fail(RTUF_ERR_STATE") > ask
-    assert all(ask < enqueue.index(m) for m in ("b.lanes_used = 0;", "c->next_lane", "c->timing_seq++", "c->last_slot =", "hipMemcpyAsync"))
+    # (before anything changes: the request and the refusal precede every step of enqueue_batch, where the changes stand)
+    assert ES.CHECKS[1:] == ("route_of(", "if (!route.ok() || !tile_variant_legal(route.tile))\n    return c->fail(RTUF_ERR_STATE")
+    ES.assert_checks_precede_every_change(api)
     # ... and keeps no second encoding of it: the plan's flags, the slot's saved pieces, the predicates the route replaced
     for gone in ("zroute", "b.cover_pass", "b.order_thr", "gr.compare", "gr.dilate", "gr.cloud", "gr.clearance", "takes_two_kernel",
                  "honours_dilation", "reads_thresholds", "fills_ms_compare", "enum class Kind"):
